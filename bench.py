@@ -1,10 +1,15 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark: MLUPS of the LBM time step on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--workload c5|c2|c3|c4|csf3d] [--size ...]
+    python bench.py --gpus N --steps K --warmup W [--workload c5|c2|c3|c4|csf3d] [--size ...] [--full] [--dump-outputs DIR]
 
 A "step" is one full lattice time step (stream + boundary planes + colour gradient / forces +
 collision + recolouring) over the whole synthetic domain.  MLUPS counts FLUID-node updates.
+
+A plain run sets up, warms up, times the K steps (checking afterwards that they conserved mass and stayed
+finite), writes the fields with --dump-outputs DIR and prints the line.  Everything else -- the
+secondary workloads and c5 legs, the CPU baselines, the stream-test ceiling, the live rocprofv3
+counter passes -- runs with --full only.
 
 Workloads (BASELINE.json configs):
   c5 (default)  D3Q19 colour gradient, 512^3 synthetic porous medium -- the configuration the
@@ -14,11 +19,20 @@ Workloads (BASELINE.json configs):
   c2            CSF colour-gradient D2Q9 MRT, 1024^2 capillary (configs[1]); N>1 = replicas.
   c3            explicit-forcing Shan-Chen D2Q9 MRT, 2048^2 porous (configs[2]); N>1 = replicas.
   c4            CSF colour gradient + D2Q5 tracer, 2048^2 porous (configs[3]); N>1 = replicas.
-At N=1 the c2, c3 and c4 figures are measured too and reported under "secondary" in the same line.
+With --full at N=1 the c2, c3 and c4 figures are measured too and reported under "secondary" in the same line.
 
 Prints ONE JSON line on rank 0 with `roofline` (dominant kernel, HBM bound, HIP-event timed on the
-stream the kernel runs on) and, at N=1, `cpu_baseline` (the C oracle -- a port of the reference
+stream the kernel runs on) and, with --full at N=1, `cpu_baseline` (the C oracle -- a port of the reference
 algorithm -- on this box's host cores, bounded sample; baseline only).
+
+--dump-outputs DIR: what the timed path computed in its last step, the fields a caller of the solver reads
+back, as DIR/<field>.npy in float64, written by rank 0.  At N > 1 the c5 and csf3d slabs are gathered into
+the whole lattice first, so the files do not depend on the slab cuts (which --gpus N measures and re-cuts);
+the c2 / c4 replicas are identical and rank 0 writes its own.  Where a field has more than DUMP_CELLS cells,
+every file holds the same fixed, seeded sample of DUMP_CELLS fluid cells of the whole lattice (at most six
+fields: 48 MiB in all).  The inputs depend on the arguments alone (fixed seed), so two builds compare output
+for output.  c3 is refused: its solver returns no field unless diagnostics, which change the timed kernel,
+were on while it stepped.
 """
 import argparse
 import json
@@ -34,6 +48,45 @@ sys.path.insert(0, ROOT)
 HBM_PEAK_GBS = 8000.0        # MI355X HBM3E spec peak (guides/MI355X_MICROARCH.md)
 B_ALG = {"c1": 288.0, "c2": 288.0, "c2p": 288.0, "c3": 288.0, "c4": 368.0, "c5": 608.0, "csf3d": 608.0}   # algorithmic bytes / lattice update
 SEED = 20260928
+DUMP_CELLS = 1 << 20         # --dump-outputs: cells per file (8 MiB), the sample of a larger lattice
+DUMP_MAX_FIELDS = 6          # ... and at most six files: 48 MiB in all, at any N
+
+
+def dump_sample(is_domain_global):
+    """flat indices (ascending) of the cells --dump-outputs writes: every cell of a lattice of at most DUMP_CELLS cells, else DUMP_CELLS
+    of its fluid cells (is_domain == 1) drawn with the fixed seed, or all of them where there are fewer -- a function of the whole lattice
+    alone"""
+    dom = np.asarray(is_domain_global).reshape(-1)
+    if dom.size <= DUMP_CELLS:
+        return None
+    fluid = np.flatnonzero(dom == 1)
+    if fluid.size <= DUMP_CELLS:
+        return fluid
+    return fluid[np.sort(np.random.default_rng(SEED).choice(fluid.size, DUMP_CELLS, replace=False))]
+
+
+def dump_outputs(path, fields, is_domain_global, rank=0, gather=None):
+    """--dump-outputs: `fields` (name -> callable returning the array the solver hands back) as path/<name>.npy in float64, by rank 0.
+    gather(local) -> the whole lattice's array on rank 0, None elsewhere (collective: every rank calls this function); without it the
+    array of rank 0 is the whole lattice and the other ranks write nothing."""
+    if len(fields) > DUMP_MAX_FIELDS:
+        raise ValueError("--dump-outputs: %d fields, at most %d" % (len(fields), DUMP_MAX_FIELDS))
+    if gather is None and rank != 0:
+        return
+    idx = dump_sample(is_domain_global) if rank == 0 else None
+    ncell = int(np.asarray(is_domain_global).size)
+    if rank == 0:
+        os.makedirs(path, exist_ok=True)
+    for name, get in fields.items():
+        a = get()
+        if gather is not None:
+            a = gather(a)
+        if rank != 0:
+            continue
+        a = np.asarray(a, dtype=np.float64).reshape(-1)
+        if a.size != ncell:
+            raise ValueError("--dump-outputs: field %s has %d values for %d cells" % (name, a.size, ncell))
+        np.save(os.path.join(path, name + ".npy"), a if idx is None else a[idx])
 
 
 def pmc_traffic(kernel, workload_tag):
@@ -225,6 +278,7 @@ class _CSF3DRanks:
         dom[0] = dom[1]; dom[-1] = dom[-2]
         rR, rB = c5_state(dom, 0, size[2], state)
         self.d = RK3DCSFDistributed(dom, dict(relax=relax, tauB=0.8), device=device)
+        self.dom = dom
         self.d.set_macro(rR, rB)
         self.num_fluid_nodes = int((dom == 1).sum())        # of the whole lattice
         self.step, self.sync, self.close, self.dominant_kernel = self.d.step, self.d.sync, self.d.close, "csf3d_collide_deep"
@@ -387,6 +441,9 @@ def main():
                     help="c5 relaxation: BASELINE.json names the MRT configuration; the shipped ini says 'SRT' with ';;MRT' beside it")
     ap.add_argument("--c5-state", default="initial", choices=sorted(C5_STATES),
                     help="c5 initial condition of the primary line (default: SURVEY 8d's); the other two run as secondary legs at N = 1")
+    ap.add_argument("--full", action="store_true", help="beside the headline: the stream-test ceiling, the CPU baselines, at N = 1 the secondary "
+                                                        "workloads and c5 legs, the live rocprofv3 counter passes (--no-* below switch them off one by one)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the fields the timed steps computed as DIR/<field>.npy (float64)")
     ap.add_argument("--no-c5-legs", action="store_true", help="N = 1: skip the secondary c5 legs (other states / other relaxation)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true")
@@ -394,6 +451,12 @@ def main():
                                                                    "(roofline.traffic then comes from the committed profile)")
     ap.add_argument("--no-calibration", action="store_true", help="N > 1: keep the equal-fluid-cells cuts (no measured re-cut of the slabs)")
     args = ap.parse_args()
+    if not args.full:
+        args.no_secondary = args.no_cpu_baseline = args.no_live_traffic = True
+    if args.steps is not None and args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
+    if args.dump_outputs and args.workload == "c3":
+        raise SystemExit("--dump-outputs: the c3 solver keeps no readable field unless its diagnostics change the timed kernel")
 
     import torch
     if args.gpus < 1:
@@ -470,7 +533,12 @@ def main():
             wall = time.perf_counter() - t0
             storage = slab.storage_info()
             slab.phase_field(diagnostics=True)
-            rho = slab.get("rhoR") + slab.get("rhoB")
+            rho_rb = {f: slab.get(f) for f in ("rhoR", "rhoB")}
+            rho = rho_rb["rhoR"] + rho_rb["rhoB"]
+            if args.dump_outputs:
+                dump_outputs(args.dump_outputs, {f: (lambda f=f: rho_rb[f] if f in rho_rb else slab.get(f)) for f in ("rhoR", "rhoB", "vx", "vy", "vz", "phi")},
+                             dom)
+            del rho_rb
             nfl_local, dom_kernel = slab.num_fluid_nodes, slab.dominant_kernel
             slab.close()
         else:
@@ -518,6 +586,8 @@ def main():
             dist.all_gather_object(per_rank, mine)
             d.observe()
             rho = d.slab.get("rhoR") + d.slab.get("rhoB")
+            if args.dump_outputs:
+                dump_outputs(args.dump_outputs, {f: (lambda f=f: d.slab.get(f)) for f in ("rhoR", "rhoB", "vx", "vy", "vz", "phi")}, dom, rank, d.gather)
             nfl_local, dom_kernel = d.slab.num_fluid_nodes, d.slab.dominant_kernel
             d.close()
         assert np.isfinite(rho).all(), "non-finite density after the timed run"
@@ -585,11 +655,11 @@ def main():
                                                ("profiles/pmc_traffic.json: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of tools/profile_round.sh over this "
                                                 "command on an MI355X box (committed; NOT measured in this run" + (
                                                     ": this process is itself under a profiler" if under_rocprof() else
-                                                    ": --no-live-traffic" if args.no_live_traffic else ": the live counter passes did not complete or do not apply") + ")") if traffic else None,
+                                                    ": a run without --full" if not args.full else ": --no-live-traffic" if args.no_live_traffic else ": the live counter passes did not complete or do not apply") + ")") if traffic else None,
                              "traffic_live": live, "traffic_committed_profile": committed,
                              "bytes_moved": moved,
                              "kernel": dom_kernel,
-                             "measured_stream_ceiling": measured_hbm(local_rank) if world == 1 else None,
+                             "measured_stream_ceiling": measured_hbm(local_rank) if world == 1 and args.full else None,
                              "note": None if world == 1 else "N>1: the kernel runs as boundary + interior launches on two "
                                      "streams beside the halo exchange; avg_launch_ms brackets the whole step, exchange included",
                              "avg_launch_ms": round(per_launch_ms, 5),
@@ -601,7 +671,7 @@ def main():
             if world == 1 and not args.no_live_traffic and dom_kernel == "rk3dq_fused":
                 def main_live(out=out, storage=storage, per_launch_ms=per_launch_ms, note=moved["note"]):
                     # the instance that runs every step but the first (template argument FIRST = false)
-                    lv = live_pmc_traffic("rk3dq_fused<false", ["--steps", "6", "--warmup", "2", "--no-cpu-baseline", "--no-secondary", "--no-live-traffic",
+                    lv = live_pmc_traffic("rk3dq_fused<false", ["--full", "--steps", "6", "--warmup", "2", "--no-cpu-baseline", "--no-secondary", "--no-live-traffic",
                                                                  "--relax", args.relax, "--c5-state", args.c5_state, "--size"] + [str(v) for v in size])
                     if not lv:
                         return
@@ -680,7 +750,7 @@ def main():
                            "bytes_moved": mv}
                     if not args.no_live_traffic and dk3 == "rk3dq_fused":
                         def leg_live(leg=leg, st3=st3, ms=md3 / nsteps):
-                            lv = live_pmc_traffic("rk3dq_fused<false", ["--steps", "6", "--warmup", "2", "--no-cpu-baseline", "--no-secondary", "--no-live-traffic",
+                            lv = live_pmc_traffic("rk3dq_fused<false", ["--full", "--steps", "6", "--warmup", "2", "--no-cpu-baseline", "--no-secondary", "--no-live-traffic",
                                                                          "--relax", relax, "--c5-state", state, "--size"] + [str(v) for v in size])
                             if not lv:
                                 return
@@ -726,7 +796,7 @@ def main():
                         def csf_live(leg=csf_leg, ms=mdc / kc):
                             # bytes the bulk's collision moves, counted in a child of this run (csf3d_collide_deep runs beside the full path's
                             # launches: its own time is not separable by events; the fraction below is over the step's time, all launches)
-                            lv = live_pmc_traffic("csf3d_collide_deep", ["--workload", "csf3d", "--steps", "6", "--warmup", "12", "--no-cpu-baseline", "--relax", args.relax,
+                            lv = live_pmc_traffic("csf3d_collide_deep", ["--full", "--workload", "csf3d", "--steps", "6", "--warmup", "12", "--no-cpu-baseline", "--relax", args.relax,
                                                                          "--size"] + [str(v) for v in size], calib="calib_shift19_b64")
                             if lv:
                                 leg["bulk_collision_counted"] = dict(lv, GBs_over_the_step=round(lv["traffic"] / (ms * 1e-3) / 1e9, 1),
@@ -780,6 +850,15 @@ def main():
         if mass is not None:
             m1 = mass()
             assert np.isfinite(m1) and abs(m1 - m0) / m0 < 1e-2, "mass drifted: the timed run did not do real work"
+        if args.dump_outputs:
+            if csf_ranks:       # the ranks' planes gathered into the whole lattice (u and phi of a slab would need its neighbours' planes)
+                dump_outputs(args.dump_outputs, {f: (lambda f=f: solver.d.get(f)) for f in ("rhoR", "rhoB")}, solver.dom, rank, solver.d.gather)
+            else:
+                names = ("rhoR", "rhoB", "rec_vx", "rec_vy") + (("rec_vz", "rec_phi") if wl == "csf3d" else ())
+                fields = {f: (lambda f=f: solver.get(f)) for f in names}
+                if wl == "c4":
+                    fields["tracer0"] = lambda: solver.get_tracer(0)
+                dump_outputs(args.dump_outputs, fields, solver.is_domain, rank)     # (N > 1: replicas of one lattice, rank 0 writes)
         if dist is not None:
             t = torch.tensor([wall], dtype=torch.float64, device="cuda" if dist.get_backend() == "nccl" else "cpu")
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -810,7 +889,7 @@ def main():
                              "frac": round(achieved / HBM_PEAK_GBS, 4),
                              "traffic": pmc_traffic(solver.dominant_kernel, "%s %s" % (wl, "x".join(str(v) for v in size))),
                              "traffic_source": "profiles/pmc_traffic.json (rocprofv3 counter passes of tools/profile_round.sh, committed; not measured in this run)",
-                             "measured_stream_ceiling": measured_hbm(local_rank),
+                             "measured_stream_ceiling": measured_hbm(local_rank) if args.full else None,
                              "kernel": solver.dominant_kernel, "avg_launch_ms": round(per_launch_ms, 6),
                              "algorithmic_bytes_per_launch": B_ALG[wl] * nfluid},
             }
@@ -828,7 +907,7 @@ def main():
                 out["roofline"].update(kernel="csf3d_collide_deep", achieved_is="B_alg (608 B) x fluid nodes / step time: NOT a bandwidth fraction -- the bulk path does not move "
                                        "608 B per cell; counted bytes below when this run could count them", frac_by_survey_balg=out["roofline"]["frac"])
                 lv = None if (args.no_live_traffic or world != 1) else live_pmc_traffic(
-                    "csf3d_collide_deep", ["--workload", "csf3d", "--steps", "6", "--warmup", "12", "--no-cpu-baseline", "--no-live-traffic", "--relax", args.relax,
+                    "csf3d_collide_deep", ["--full", "--workload", "csf3d", "--steps", "6", "--warmup", "12", "--no-cpu-baseline", "--no-live-traffic", "--relax", args.relax,
                                            "--c5-state", args.c5_state, "--size"] + [str(v) for v in size], calib="calib_shift19_b64")
                 if lv:
                     gbs = lv["traffic"] / (per_launch_ms * 1e-3) / 1e9

@@ -69,13 +69,13 @@ def main():
     global CAL
     CAL = calibration(fetch, write)
     collect(fetch, write, kernels, "")
-    # further passes of `bench.py --c5-state STATE --no-secondary`:  STATE fetch.txt write.txt  -> keys rk3dq_fused[STATE]
+    # further passes of `bench.py --full --c5-state STATE --no-secondary`:  STATE fetch.txt write.txt  -> keys rk3dq_fused[STATE]
     rest = sys.argv[3:]
     while len(rest) >= 3:
         collect(parse(rest[1], "FETCH_SIZE"), parse(rest[2], "WRITE_SIZE"), kernels, "" if rest[0] == "-" else "[%s]" % rest[0], only="rk3dq_fused")
         rest = rest[3:]
     print(json.dumps({"source": "rocprofv3 --kernel-trace --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) on "
-                                "`python bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-c5-legs` (and `--c5-state S --no-secondary` for the "
+                                "`python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-c5-legs` (and `--c5-state S --no-secondary` for the "
                                 "[S] entries), MI355X (tools/profile_round.sh)",
                       "correction": ("traffic = fetch_factor * FETCH_SIZE + write_factor * WRITE_SIZE (KB -> B), the factors measured in the same passes on "
                                      "calibration kernels of the lattice kernel's own access width (`calibration`; every kernel entry names the one it took)")

@@ -11,8 +11,8 @@ R=$(pwd)
 out=$R/gpurun_out/profiles_$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
-CMD="python $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-c5-legs"
-CMDX="python $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-secondary --c5-state mixed"
+CMD="python $R/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-c5-legs"
+CMDX="python $R/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-secondary --c5-state mixed"
 if [ -z "$SKIP_TRACE" ]; then
 rocprofv3 --kernel-trace --stats -d $R/gpurun_out/prof_trace -o x -- $CMD > $out/${tag}_bench_under_rocprof.json 2> $out/trace.log
 python $R/tools/rocprof_summary.py $(find $R/gpurun_out/prof_trace -name x_results.db | head -1) > $out/${tag}_bench_kernel_trace.txt
@@ -34,8 +34,8 @@ for set in "FETCH_SIZE" "WRITE_SIZE"; do
   python $R/tools/rocprof_summary.py $(find $R/gpurun_out/prof_mixed_$set -name x_results.db | head -1) --pmc > $out/${tag}_pmc_mixed_$set.txt
 done
 # the graded state and the SRT relaxation: their legs of the bench line get counted bytes too (no `counted_frac: null`)
-CMDG="python $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-secondary --c5-state graded"
-CMDS="python $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-secondary --relax SRT"
+CMDG="python $R/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-secondary --c5-state graded"
+CMDS="python $R/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-secondary --relax SRT"
 for set in "FETCH_SIZE" "WRITE_SIZE"; do
   rm -rf $R/gpurun_out/prof_graded_$set $R/gpurun_out/prof_srt_$set
   rocprofv3 --kernel-trace --pmc $set -d $R/gpurun_out/prof_graded_$set -o x -- $CMDG > /dev/null 2> $out/pmc_graded_$set.log
@@ -50,9 +50,9 @@ python tools/pmc_to_json.py $out/${tag}_pmc_FETCH_SIZE.txt $out/${tag}_pmc_WRITE
        graded $out/${tag}_pmc_graded_FETCH_SIZE.txt $out/${tag}_pmc_graded_WRITE_SIZE.txt \
        - $out/${tag}_pmc_srt_FETCH_SIZE.txt $out/${tag}_pmc_srt_WRITE_SIZE.txt > $out/pmc_traffic.json
 cp $out/pmc_traffic.json profiles/pmc_traffic.json      # (on the box: the bench runs below read it; copy it back by hand as well)
-python bench.py > $out/${tag}_bench_c5_n1.json 2> $out/bench.log
+python bench.py --full > $out/${tag}_bench_c5_n1.json 2> $out/bench.log
 if [ -z "$SKIP_LONG" ]; then
-python bench.py --steps 500 --warmup 50 --no-secondary --no-cpu-baseline > $out/${tag}_bench_c5_steps500.json 2>> $out/bench.log
+python bench.py --full --steps 500 --warmup 50 --no-secondary --no-cpu-baseline > $out/${tag}_bench_c5_steps500.json 2>> $out/bench.log
 python tools/dev/k3mixed.py 512 > $out/${tag}_k3mixed.log 2>&1
 python tools/slab_rank_cost.py 512 8 > $out/${tag}_slab_rank_cost_512_8.log 2>&1
 SLAB_CALIBRATE=2 python tools/slab_rank_cost.py 512 8 > $out/${tag}_slab_rank_cost_512_8_calibrated.log 2>&1
