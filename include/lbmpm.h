@@ -521,7 +521,9 @@ int64_t lbmpm_rk3d_device_bytes(const lbmpm_rk3d *ctx);
  * the five populations per colour that cross the face (after the collision; behind them a byte per fluid cell of two planes: whether the
  * cell's block handed on one colour alone, so that the bulk path -- see `variant` -- runs up to the faces).  lbmpm_rk3dcsf_stage runs a third of a step;
  * lbmpm_rk3dcsf_face_copy hands a message to a context of the same process, lbmpm_rk3dcsf_face_pack / _unpack go through a device buffer
- * the caller sends (RCCL / MPI / torch.distributed).  Bit-equal to the undivided lattice (tests/test_rk3d_csf_gpu.py).
+ * the caller sends (RCCL / MPI / torch.distributed), or -- opt-in, see the end of this block -- the library's own IPC / RCCL transport
+ * moves all three and lbmpm_rk3dcsf_step_slab runs whole steps behind one call.  Bit-equal to the undivided lattice (tests/test_rk3d_csf_gpu.py,
+ * tests/test_rk3d_csf_transport_gpu.py).
  * ---------------------------------------------------------------------------------- */
 typedef struct lbmpm_rk3dcsf_config {
     int64_t nx, ny, nz;        /* xDomain, yDomain, zDomain (incl. the ghost planes 0 and nz-1); nz >= 8 */
@@ -618,6 +620,54 @@ int64_t lbmpm_rk3dcsf_bulk_cells(lbmpm_rk3dcsf *ctx);
 int64_t lbmpm_rk3dcsf_steps_done(const lbmpm_rk3dcsf *ctx);
 int64_t lbmpm_rk3dcsf_device_bytes(const lbmpm_rk3dcsf *ctx);
 const char *lbmpm_rk3dcsf_dominant_kernel(const lbmpm_rk3dcsf *ctx);
+
+/* ---- 3-D CSF slabs: the three face messages over a transport INSIDE the library (the perturbation model's transports above, "Transport
+ * of the slab exchange": IPC landing areas filled by copy-engine transfers + stream value operations, or ncclSend / ncclRecv of a librccl
+ * opened at run time).  Opt-in: a context that never connects allocates nothing for it (device_bytes does not count the transport's
+ * landing area and send buffers either) and steps by lbmpm_rk3dcsf_stage as before.
+ * The slabs form a RING of two ranks or more: rank r's low neighbour is (r - 1) mod world, its high neighbour (r + 1) mod world.  With
+ * two ranks both faces talk to the same process: IPC maps that peer's handles once; RCCL posts send low, send high, receive high, receive
+ * low, so that between the one pair of ranks this rank's low-face message lands in the peer's high-face slot.  Every landing slot holds
+ * the largest of the three messages of its face; the sequence number counts messages (three per step).
+ *     IPC:  1. lbmpm_rk3dcsf_ipc_init(ctx, blob) (a blob of LBMPM_IPC_BLOB_BYTES: the landing area, the three message sizes expected
+ *              through either face, the slab's planes), 2. the caller moves every rank's blob to its two neighbours,
+ *           3. lbmpm_rk3dcsf_ipc_connect(ctx, blob_of_the_low_neighbour, blob_of_the_high_neighbour).  Refused with LBMPM_ERR_INVALID,
+ *              before anything is mapped: bytes that are not such a blob, a blob of a slab that is not the neighbour at that face (other
+ *              cuts), message sizes that differ from what this slab sends (other masks).  Blobs of the calling process connect by pointer.
+ *     RCCL: rank 0 lbmpm_rccl_unique_id, broadcast by the caller, then lbmpm_rk3dcsf_rccl_connect on every rank (collective).  The
+ *           caller compares the ranks' face_doubles / face_doubles_in before: ncclSend / ncclRecv cannot tell messages of other sizes.
+ * Undivided contexts (ghost_lo = ghost_hi = 0) are refused with LBMPM_ERR_INVALID.  Every rank makes the same sequence of exchanging calls
+ * (step_slab with the same step counts, transport_probe with the same rounds). */
+int lbmpm_rk3dcsf_ipc_init(lbmpm_rk3dcsf *ctx, void *blob_out);
+int lbmpm_rk3dcsf_ipc_connect(lbmpm_rk3dcsf *ctx, const void *blob_low, const void *blob_high);
+int lbmpm_rk3dcsf_rccl_connect(lbmpm_rk3dcsf *ctx, const void *id, int rank, int nranks, const char *librccl_path);
+/* drop the transport (synchronises the context's streams; closes the mapped handles / destroys the communicator, frees its buffers) */
+int lbmpm_rk3dcsf_transport_disconnect(lbmpm_rk3dcsf *ctx);
+/* LBMPM_TRANSPORT_* of the context; *value_ops (may be NULL): 1 when the IPC flags go through hipStreamWriteValue64 / WaitValue64 */
+int lbmpm_rk3dcsf_transport_kind(lbmpm_rk3dcsf *ctx, int *value_ops);
+/* set-up self-test: `rounds` x the three messages at the sizes of a step, patterned, each way through the send buffers and landing
+ * slots, enqueued on the context's stream and compared on the receiving GPU; the caller waits under a deadline and reads the number of
+ * doubles that arrived wrong (_probe_result synchronises the stream) */
+int lbmpm_rk3dcsf_transport_probe(lbmpm_rk3dcsf *ctx, int rounds);
+int lbmpm_rk3dcsf_transport_probe_result(lbmpm_rk3dcsf *ctx, int64_t *mismatches);
+/* IPC only: every wait of this context on an incoming message returns (the host writes the largest sequence number into its flags).
+ * The transport is unusable afterwards: step_slab and transport_probe return LBMPM_ERR_STATE and enqueue nothing until
+ * lbmpm_rk3dcsf_transport_disconnect and a fresh init + connect. */
+int lbmpm_rk3dcsf_ipc_release_waits(lbmpm_rk3dcsf *ctx);
+/* n whole steps of a connected slab behind ONE call, on the context's stream, no host synchronisation: stage 0 -> phi through both faces ->
+ * stage 1 -> n -> stage 2 -> the populations and flag bytes, each message packed, moved and unpacked straight from the landing slots; the
+ * bulk's collision runs on the second stream under the phi and n messages.  LBMPM_ERR_STATE without a connected transport, before
+ * set_macro / set_pdf, in the middle of a step begun with lbmpm_rk3dcsf_stage, after lbmpm_rk3dcsf_ipc_release_waits; LBMPM_ERR_TIMEOUT
+ * after the watchdog gave the transport up.  timed != 0: HIP events around every stage and message of (up to 256) steps. */
+int lbmpm_rk3dcsf_step_slab(lbmpm_rk3dcsf *ctx, int64_t nsteps, int timed);
+/* averages [ms] over the timed steps of the last step_slab: out[0..2] stages 0, 1, 2, out[3..5] the message after each (pack .. unpack,
+ * transfer and wait included), out[6] steps averaged.  Synchronises the context's streams. */
+int lbmpm_rk3dcsf_slab_timing(lbmpm_rk3dcsf *ctx, double *out);
+/* lbmpm_rk3dcsf_sync with the watchdog of lbmpm_rk3d_sync_deadline: every step_slab step ends by writing its number into a pinned host
+ * word, and the deadline counts from the last time that word moved.  When it passes: IPC -- the waits are released; RCCL -- the
+ * communicator is aborted; the transport is dead (later exchanges: LBMPM_ERR_TIMEOUT), the lattice state void (set_macro / set_pdf), and
+ * the call returns LBMPM_ERR_TIMEOUT. */
+int lbmpm_rk3dcsf_sync_deadline(lbmpm_rk3dcsf *ctx, double seconds);
 
 #ifdef __cplusplus
 }

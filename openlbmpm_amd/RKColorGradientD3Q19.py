@@ -16,7 +16,9 @@ continued from a checkpoint equals the uninterrupted one bit for bit, on any num
 
 [SurfaceTension] SurfaceTensionType = 'CSF' (the section of RKtwophasesetup2D.ini added to the 3-D file): the 2-D CSF loop carried to
 D3Q19 (openlbmpm_amd/rk3dcsf.py, lbmpm_rk3dcsf_*) instead of the perturbation loop -- surface tension, contact angle (wetting rule 2),
-DeltaValue, TauType from the ini; one GPU or one z-slab per rank (rk3dcsf.RK3DCSFDistributed: three face messages per step); records hold what the reference records (the lattice after the next step's boundary
+DeltaValue, TauType from the ini; one GPU or one z-slab per rank (rk3dcsf.RK3DCSFDistributed: three face messages per step, through
+torch.distributed from Python after every stage, or -- csf_transport = 'auto' | 'ipc' | 'rccl' -- over the library's own transports, one C
+call per run of steps); records hold what the reference records (the lattice after the next step's boundary
 planes, RKD2Q9.py:1382-1393); IsCycle and checkpoints as above (a checkpoint keeps the streamed populations and the last force).
 
 One process per GPU: when torch.distributed is initialised with world size > 1 the lattice is cut
@@ -41,7 +43,7 @@ GROUPS = (("FluidMacro", "MacroData"), ("FluidPDF", "MicroData"), ("FluidVelocit
 class _CSFSlab:
     """RK3DCSFSolver behind the calls this driver makes on a slab of the perturbation model"""
 
-    def __init__(self, dom, par, device, bulk_epsilon=0.0, distributed=False):
+    def __init__(self, dom, par, device, bulk_epsilon=0.0, distributed=False, transport=None):
         from .rk3dcsf import RK3DCSFSolver, RK3DCSFDistributed
         q = dict(sigma=par["sigma"], theta=par["theta"], wetting=par["wetting"], beta=par["beta"], delta=par["delta"], tauR=par["tauR"], tauB=par["tauB"],
                  tautype=par["tautype"], relax=par["relax"], inlet=par["inlet"], outlet=par["outlet"], velocityZR=par["velocityZR"],
@@ -49,7 +51,7 @@ class _CSFSlab:
                  bulk_epsilon=float(bulk_epsilon))
         # distributed: one slab per rank; set_* take the undivided arrays (a slab cuts its planes and the images of its neighbours' out of
         # them), get* return the rank's own planes
-        self.solver = RK3DCSFDistributed(dom, q, device=device) if distributed else RK3DCSFSolver(dom, q, device=device)
+        self.solver = RK3DCSFDistributed(dom, q, device=device, transport=transport) if distributed else RK3DCSFSolver(dom, q, device=device)
         self.step_single, self.sync, self.close = self.solver.step, self.solver.sync, self.solver.close
 
     num_fluid_nodes = property(lambda self: self.solver.num_fluid_nodes)
@@ -92,7 +94,8 @@ def duct(nx, ny, nz):
 
 class RKColorGradient3D:
     def __init__(self, pathIniFile, output_dir=None, domain=None, device=0, record_every=None, num_buffering_layers=10,
-                 structure_path=None, initial_dir=None, record_pdf=False, restart_from=None, checkpoint_every=0, csf_bulk_epsilon=0.0):
+                 structure_path=None, initial_dir=None, record_pdf=False, restart_from=None, checkpoint_every=0, csf_bulk_epsilon=0.0,
+                 csf_transport=None):
         self.pathIni = pathIniFile
         self.par = config.read_rk3d(pathIniFile)
         self.output_dir = output_dir or os.path.expanduser("~/LBMResults3D")       # main.py:28
@@ -104,6 +107,9 @@ class RKColorGradient3D:
         self.record_pdf = bool(record_pdf)          # /FluidPDF/FluidPDFRat<k>, ...Bat<k> [nz][ny][nx][19] with every record (38 doubles per cell)
         self.restart_from, self.checkpoint_every = restart_from, int(checkpoint_every)
         self.csf_bulk_epsilon = float(csf_bulk_epsilon)      # 3-D CSF only, opt-in (include/lbmpm.h: lbmpm_rk3dcsf_config.bulk_epsilon; 0 = exact)
+        # 3-D CSF under torchrun only, opt-in: None = the face messages through torch.distributed; 'auto' | 'ipc' | 'rccl' = over a transport
+        # inside the library, one C call per run of steps (rk3dcsf.RK3DCSFDistributed)
+        self.csf_transport = csf_transport
         self.gather_records = True
         self.records = 0
         self.physicalVX = self.physicalVY = self.physicalVZ = None
@@ -248,7 +254,7 @@ class RKColorGradient3D:
         whole_arrays = False          # distributed 3-D CSF: the slabs carry images of their neighbours' planes and cut them out of the undivided arrays
         if p["tension_type"] == "CSF":
             whole_arrays = self._distributed()
-            slab = sim = _CSFSlab(self.isDomain, p, self.device, self.csf_bulk_epsilon, distributed=whole_arrays)
+            slab = sim = _CSFSlab(self.isDomain, p, self.device, self.csf_bulk_epsilon, distributed=whole_arrays, transport=self.csf_transport)
             step, observe = slab.step_single, (lambda: None)
             self.z0, self.nzl = 0, self.zDomain
             if whole_arrays:

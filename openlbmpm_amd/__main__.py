@@ -4,6 +4,8 @@
     python -m openlbmpm_amd sc  <ini-dir> [--out DIR] [--steps N] [--device D]
     python -m openlbmpm_amd tr  <ini-dir> ...      colour gradient + tracers (RKtwophasesetup2D.ini + transportsetup.ini)
     python -m openlbmpm_amd rk3d <ini-dir> ...     D3Q19 colour gradient (RKtwophasesetup3D.ini); under torchrun: z-slabs, one per GPU
+        [--csf-transport auto|ipc|rccl]           SurfaceTensionType = 'CSF' under torchrun: the slabs' face messages over the library's
+                                                  own transports (default: through torch.distributed)
 """
 import argparse
 import sys
@@ -18,6 +20,8 @@ def main(argv=None):
     ap.add_argument("--out", default=None, help="result directory (default ~/LBMResults)")
     ap.add_argument("--steps", type=int, default=None, help="override the ini's number of time steps")
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--csf-transport", choices=["auto", "ipc", "rccl"], default=None,
+                    help="rk3d with SurfaceTensionType = 'CSF' under torchrun: move the slabs' face messages over the library's own transport")
     a = ap.parse_args(argv)
     t0 = time.time()
     if a.model == "rk":
@@ -41,7 +45,7 @@ def main(argv=None):
                 dist.init_process_group(backend="nccl", device_id=torch.device("cuda", device))
             else:                                                # "gloo": several ranks rehearsing on one GPU
                 dist.init_process_group(backend=os.environ["LBMPM_DIST_BACKEND"])
-        sim = RKColorGradient3D(a.ini_dir, output_dir=a.out, device=device)
+        sim = RKColorGradient3D(a.ini_dir, output_dir=a.out, device=device, csf_transport=a.csf_transport)
         if a.steps is not None:
             sim.timeSteps = a.steps
         path = sim.runRKColorGradient3D()

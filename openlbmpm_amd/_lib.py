@@ -191,6 +191,17 @@ _SIGNATURES = {
     "lbmpm_rk3dcsf_steps_done": (C.c_int64, [C.c_void_p]),
     "lbmpm_rk3dcsf_device_bytes": (C.c_int64, [C.c_void_p]),
     "lbmpm_rk3dcsf_dominant_kernel": (C.c_char_p, [C.c_void_p]),
+    "lbmpm_rk3dcsf_ipc_init": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "lbmpm_rk3dcsf_ipc_connect": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "lbmpm_rk3dcsf_rccl_connect": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_char_p]),
+    "lbmpm_rk3dcsf_transport_disconnect": (C.c_int, [C.c_void_p]),
+    "lbmpm_rk3dcsf_transport_kind": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    "lbmpm_rk3dcsf_transport_probe": (C.c_int, [C.c_void_p, C.c_int]),
+    "lbmpm_rk3dcsf_transport_probe_result": (C.c_int, [C.c_void_p, I64P]),
+    "lbmpm_rk3dcsf_ipc_release_waits": (C.c_int, [C.c_void_p]),
+    "lbmpm_rk3dcsf_step_slab": (C.c_int, [C.c_void_p, C.c_int64, C.c_int]),
+    "lbmpm_rk3dcsf_slab_timing": (C.c_int, [C.c_void_p, F64P]),
+    "lbmpm_rk3dcsf_sync_deadline": (C.c_int, [C.c_void_p, C.c_double]),
 }
 
 

@@ -2300,7 +2300,7 @@ extern "C" int lbmpm_rk3d_step_slab(lbmpm_rk3d *c, int64_t nsteps, int has_below
                 else if (exchange(user, 0) != 0) { set_error("lbmpm_rk3d_step_slab: the exchange callback failed"); return fail(LBMPM_ERR_STATE); }
                 rk3dq_face_unpack<<<fgrid, fblock, 0, c->stream>>>(q, c->fB, c->purB, from_below, from_above, has_below, has_above);
                 rk3dq_halo_phi<<<fgrid, fblock, 0, c->stream>>>(q, from_below, from_above, has_below, has_above);
-                slabtx::flag_store<<<1, 1, 0, c->stream>>>(c->beat_dev, (unsigned long long)(c->steps + 1));      // "the exchange of this step is through"
+                slabtx::launch_flag_store(c->stream, c->beat_dev, (unsigned long long)(c->steps + 1));      // "the exchange of this step is through"
                 if (ev[5]) SLAB_HIP_TRY(hipEventRecord(ev[5], c->stream));
                 SLAB_HIP_TRY(hipEventRecord(c->ev_dep, c->stream));
                 if (hipGetLastError() != hipSuccess) { set_error("lbmpm_rk3d_step_slab: kernel launch failed"); return fail(LBMPM_ERR_HIP); }
@@ -2364,7 +2364,7 @@ extern "C" int lbmpm_rk3d_step_slab(lbmpm_rk3d *c, int64_t nsteps, int has_below
             if (!(skip & 4)) {
                 rk3dq_face_unpack<<<fgrid, fblock, 0, c->stream>>>(q, c->fB, c->purB, from_below, from_above, has_below, has_above);
                 rk3dq_halo_phi<<<fgrid, fblock, 0, c->stream>>>(q, from_below, from_above, has_below, has_above);
-                slabtx::flag_store<<<1, 1, 0, c->stream>>>(c->beat_dev, (unsigned long long)(c->steps + 1));
+                slabtx::launch_flag_store(c->stream, c->beat_dev, (unsigned long long)(c->steps + 1));
             }
             if (hipGetLastError() != hipSuccess) { set_error("lbmpm_rk3d_step_slab: face kernel launch failed"); return fail(LBMPM_ERR_HIP); }
             if (ev[5]) SLAB_HIP_TRY(hipEventRecord(ev[5], c->stream));

@@ -32,6 +32,8 @@
 #include <cstdlib>
 #include <vector>
 
+#include "rk3d_transport.h"
+
 namespace {
 
 using lbmpm::set_error;
@@ -1026,6 +1028,16 @@ struct lbmpm_rk3dcsf {
     double *obs = nullptr;         // staging of the observe kernel: rho [2][N], u [3][N], phi [N] (the populations [2][N][19] come and go with the call)
     lbmpm::EventPool pool;
     size_t timed_steps = 0;
+    // slabs whose face messages travel over a transport inside the library (lbmpm_rk3dcsf_ipc_* / _rccl_connect, _step_slab): nothing of
+    // this is allocated before a connect
+    slabtx::Transport tx;
+    double *send_lo = nullptr, *send_hi = nullptr;      // the message through the low / high face, packed (the largest of the three kinds)
+    bool tx_released = false;                           // lbmpm_rk3dcsf_ipc_release_waits: the flags say "arrived" for every message to come
+    unsigned long long *probe_bad = nullptr;            // mismatch counter of lbmpm_rk3dcsf_transport_probe
+    unsigned long long *beat_host = nullptr, *beat_dev = nullptr;     // heartbeat of lbmpm_rk3dcsf_sync_deadline (pinned host word)
+    hipStream_t wd_stream = nullptr;                    // the watchdog's own copies
+    lbmpm::EventPool slab_pool;                         // lbmpm_rk3dcsf_step_slab(timed): 6 event pairs per step {stage, message} x 3
+    int64_t slab_timed_steps = 0;
 };
 
 namespace {
@@ -1135,6 +1147,12 @@ extern "C" void lbmpm_rk3dcsf_destroy(lbmpm_rk3dcsf *c)
     if (!c) return;
     (void)hipSetDevice(c->cfg.device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
+    if (c->stream2) (void)hipStreamSynchronize(c->stream2);
+    c->tx.disconnect();
+    for (void *q : {(void *)c->send_lo, (void *)c->send_hi, (void *)c->probe_bad}) if (q) (void)hipFree(q);
+    if (c->beat_host) (void)hipHostFree(c->beat_host);
+    if (c->wd_stream) (void)hipStreamDestroy(c->wd_stream);
+    c->slab_pool.destroy();
     void *ptrs[] = {c->wethome, c->rng, c->pfx, c->pure, c->deep_prev, c->bcblk, c->deep_now, c->work, c->tcnt, c->src, c->dom, c->meta, c->wetlist, c->cidx, c->cells, c->fA, c->fB, c->phi, c->G, c->nh, c->F, c->K, c->U, c->ns, c->obs};
     for (void *q : ptrs) if (q) (void)hipFree(q);
     c->pool.destroy();
@@ -1720,3 +1738,339 @@ extern "C" int64_t lbmpm_rk3dcsf_bulk_cells(lbmpm_rk3dcsf *c)
 extern "C" int64_t lbmpm_rk3dcsf_steps_done(const lbmpm_rk3dcsf *c) { return c ? c->steps : 0; }
 extern "C" int64_t lbmpm_rk3dcsf_device_bytes(const lbmpm_rk3dcsf *c) { return c ? c->bytes : 0; }
 extern "C" const char *lbmpm_rk3dcsf_dominant_kernel(const lbmpm_rk3dcsf *c) { (void)c; return "csf3d_collide"; }
+
+// ---- the three face messages over a transport inside the library (include/lbmpm.h, CSF block; rk3d_transport.h, shared with the
+// perturbation model's slabs)
+namespace {
+constexpr uint32_t CSF_BLOB_MAGIC = 0x4c424d43u;        // "LBMC" (the perturbation model's blobs: "LBMP")
+constexpr int STEP_MSGS[3] = {LBMPM_CSF_MSG_PHI, LBMPM_CSF_MSG_NORMAL, LBMPM_CSF_MSG_PDF};       // the message after stage 0, 1, 2
+const char *msg_name(int m) { return m == LBMPM_CSF_MSG_PHI ? "phi" : m == LBMPM_CSF_MSG_NORMAL ? "n" : "populations"; }
+
+// what a slab tells its two neighbours: the transport's blob, the three message sizes it expects through either face, its own planes
+struct CsfBlob {
+    slabtx::IpcBlob base;
+    uint64_t in_lo[3], in_hi[3];        // bytes of message LBMPM_CSF_MSG_* that come in through the low / high face
+    int32_t z0, z1, nzg, pad;           // own planes [z0, z1) of the undivided lattice of nzg planes
+};
+static_assert(sizeof(CsfBlob) <= LBMPM_IPC_BLOB_BYTES, "blob size is part of the ABI");
+
+size_t msg_bytes(const lbmpm_rk3dcsf *c, int msg, int face, bool in) { return 8 * (size_t)face_total(c, msg, face, in); }
+int own_z1(const lbmpm_rk3dcsf *c) { return (int)(c->cfg.slab_z0 + c->nz - c->cfg.ghost_lo - c->cfg.ghost_hi); }
+
+// the transport, its send buffers and its mapped handles given back (the context steps by stages again)
+void tx_drop(lbmpm_rk3dcsf *c)
+{
+    c->tx.disconnect();
+    for (double **q : {&c->send_lo, &c->send_hi}) { if (*q) (void)hipFree(*q); *q = nullptr; }
+    c->tx_released = false;
+}
+
+// landing slots for the largest message of each face, and the two send buffers
+int tx_shape(lbmpm_rk3dcsf *c, const char *who)
+{
+    if (!c->cfg.ghost_lo) { set_error("%s: the undivided lattice (ghost_lo = ghost_hi = 0) has no face messages", who); return LBMPM_ERR_INVALID; }
+    if (c->tx.kind != LBMPM_TRANSPORT_NONE) { set_error("%s: a transport is set up already: lbmpm_rk3dcsf_transport_disconnect first", who); return LBMPM_ERR_STATE; }
+    size_t out[2] = {8, 8}, in[2] = {8, 8};
+    for (int m = 0; m < 3; ++m)
+        for (int f = 0; f < 2; ++f) {
+            out[f] = out[f] > msg_bytes(c, m, f, false) ? out[f] : msg_bytes(c, m, f, false);
+            in[f] = in[f] > msg_bytes(c, m, f, true) ? in[f] : msg_bytes(c, m, f, true);
+        }
+    LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
+    int rc = c->tx.set_shape(c->cfg.device, true, true, out[1], out[0], in[0], in[1]);
+    if (rc == LBMPM_OK && (hipMalloc(reinterpret_cast<void **>(&c->send_lo), out[0]) != hipSuccess || hipMalloc(reinterpret_cast<void **>(&c->send_hi), out[1]) != hipSuccess)) {
+        (void)hipGetLastError();
+        set_error("%s: hipMalloc of the send buffers (%zu + %zu bytes) failed", who, out[0], out[1]);
+        rc = LBMPM_ERR_NOMEM;
+    }
+    if (rc != LBMPM_OK) tx_drop(c);
+    return rc;
+}
+
+// closes what ipc_connect opened before it failed: the context can connect again
+void ipc_unmap(lbmpm_rk3dcsf *c)
+{
+    for (int s = 0; s < 2; ++s) {
+        if (c->tx.mapped[s]) { (void)hipIpcCloseMemHandle(c->tx.peer_land[s]); (void)hipIpcCloseMemHandle(c->tx.peer_flags[s]); }
+        c->tx.peer_land[s] = nullptr; c->tx.peer_flags[s] = nullptr; c->tx.mapped[s] = false;
+    }
+}
+
+// one message kind through both faces, enqueued on the context's stream: pack -> transport -> unpack straight from the landing slots
+int tx_message(lbmpm_rk3dcsf *c, int msg)
+{
+    int rc = lbmpm_rk3dcsf_face_pack(c, msg, 0, c->send_lo);
+    if (rc == LBMPM_OK) rc = lbmpm_rk3dcsf_face_pack(c, msg, 1, c->send_hi);
+    const double *from_below = nullptr, *from_above = nullptr;
+    if (rc == LBMPM_OK) rc = c->tx.exchange(c->stream, c->send_hi, c->send_lo, msg_bytes(c, msg, 1, false), msg_bytes(c, msg, 0, false),
+                                            msg_bytes(c, msg, 0, true), msg_bytes(c, msg, 1, true), &from_below, &from_above);
+    if (rc == LBMPM_OK) rc = lbmpm_rk3dcsf_face_unpack(c, msg, 0, from_below);
+    if (rc == LBMPM_OK) rc = lbmpm_rk3dcsf_face_unpack(c, msg, 1, from_above);
+    return rc;
+}
+
+int tx_usable(lbmpm_rk3dcsf *c, const char *who)
+{
+    if (!c->tx.connected) { set_error("%s: no transport connected (lbmpm_rk3dcsf_ipc_connect / lbmpm_rk3dcsf_rccl_connect)", who); return LBMPM_ERR_STATE; }
+    if (c->tx.dead) { set_error("%s: the transport was given up by the watchdog (a neighbour did not answer): disconnect and set up the run again", who); return LBMPM_ERR_TIMEOUT; }
+    if (c->tx_released) { set_error("%s: the transport's waits were released (lbmpm_rk3dcsf_ipc_release_waits): disconnect and connect again", who); return LBMPM_ERR_STATE; }
+    return LBMPM_OK;
+}
+
+int release_waits(lbmpm_rk3dcsf *c)
+{
+    // from a private non-blocking stream: a copy on a stream that sits in the wait would never run
+    static const unsigned long long big[4] = {~0ull, ~0ull, ~0ull, ~0ull};
+    if (!c->wd_stream) LBMPM_HIP_TRY(hipStreamCreateWithFlags(&c->wd_stream, hipStreamNonBlocking));
+    LBMPM_HIP_TRY(hipMemcpyAsync(c->tx.flags, big, sizeof big, hipMemcpyHostToDevice, c->wd_stream));
+    LBMPM_HIP_TRY(hipStreamSynchronize(c->wd_stream));
+    c->tx_released = true;
+    return LBMPM_OK;
+}
+
+__global__ void csf3d_tx_fill(double *p, size_t n, double v) { const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; if (i < n) p[i] = v + (double)i; }
+__global__ void csf3d_tx_check(const double *p, size_t n, double v, unsigned long long *bad)
+{
+    const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i < n && p[i] != v + (double)i) atomicAdd(bad, 1ull);
+}
+}  // namespace
+
+extern "C" int lbmpm_rk3dcsf_ipc_init(lbmpm_rk3dcsf *c, void *blob_out)
+{
+    LBMPM_REQUIRE(c && blob_out, "lbmpm_rk3dcsf_ipc_init: null argument");
+    int rc = tx_shape(c, "lbmpm_rk3dcsf_ipc_init");
+    if (rc != LBMPM_OK) return rc;
+    CsfBlob b;
+    memset(&b, 0, sizeof b);
+    rc = c->tx.ipc_alloc(&b.base, CSF_BLOB_MAGIC);
+    if (rc != LBMPM_OK) { tx_drop(c); return rc; }
+    for (int m = 0; m < 3; ++m) { b.in_lo[m] = msg_bytes(c, m, 0, true); b.in_hi[m] = msg_bytes(c, m, 1, true); }
+    b.z0 = (int32_t)c->cfg.slab_z0; b.z1 = own_z1(c); b.nzg = c->nzg;
+    memset(blob_out, 0, LBMPM_IPC_BLOB_BYTES);
+    memcpy(blob_out, &b, sizeof b);
+    return LBMPM_OK;
+}
+
+extern "C" int lbmpm_rk3dcsf_ipc_connect(lbmpm_rk3dcsf *c, const void *blob_low, const void *blob_high)
+{
+    LBMPM_REQUIRE(c && blob_low && blob_high, "lbmpm_rk3dcsf_ipc_connect: null argument (a slab of the ring has a neighbour at either face)");
+    LBMPM_REQUIRE(c->cfg.ghost_lo, "lbmpm_rk3dcsf_ipc_connect: the undivided lattice (ghost_lo = ghost_hi = 0) has no face messages");
+    if (c->tx.kind != LBMPM_TRANSPORT_IPC || c->tx.connected) { set_error("lbmpm_rk3dcsf_ipc_connect: call lbmpm_rk3dcsf_ipc_init first (once)"); return LBMPM_ERR_STATE; }
+    CsfBlob b[2];
+    memcpy(&b[0], blob_low, sizeof b[0]);
+    memcpy(&b[1], blob_high, sizeof b[1]);
+    const int z0 = (int)c->cfg.slab_z0, z1 = own_z1(c), nzg = c->nzg;
+    // everything is compared before anything is mapped: a refused connect leaves the context as ipc_init made it
+    for (int side = 0; side < 2; ++side) {
+        const CsfBlob &n = b[side];
+        const char *where = side == 0 ? "low" : "high";
+        LBMPM_REQUIRE(n.base.magic == CSF_BLOB_MAGIC && n.base.version == slabtx::BLOB_VERSION,
+                      "lbmpm_rk3dcsf_ipc_connect: the %s neighbour's bytes are not a blob of lbmpm_rk3dcsf_ipc_init", where);
+        LBMPM_REQUIRE(n.nzg == nzg && n.nzg > 0 && (side == 0 ? n.z1 % nzg == z0 : n.z0 == z1 % nzg),
+                      "lbmpm_rk3dcsf_ipc_connect: the %s neighbour holds the planes [%d, %d) of %d -- not the slab next to this one's [%d, %d) of %d (other cuts)",
+                      where, (int)n.z0, (int)n.z1, (int)n.nzg, z0, z1, nzg);
+        for (int m = 0; m < 3; ++m) {
+            const uint64_t theirs = side == 0 ? n.in_hi[m] : n.in_lo[m], mine = msg_bytes(c, m, side, false);
+            LBMPM_REQUIRE(theirs == mine, "lbmpm_rk3dcsf_ipc_connect: the %s neighbour expects %llu bytes of %s through the shared face, this slab sends %llu (other masks)",
+                          where, (unsigned long long)theirs, msg_name(m), (unsigned long long)mine);
+        }
+    }
+    LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
+    int rc = c->tx.ipc_open(0, &b[0].base, c->tx.bytes_dn, CSF_BLOB_MAGIC);
+    if (rc == LBMPM_OK) {
+        if (!memcmp(&b[0].base, &b[1].base, sizeof b[0].base)) c->tx.ipc_share(1, 0);     // a ring of two: one peer, mapped once
+        else rc = c->tx.ipc_open(1, &b[1].base, c->tx.bytes_up, CSF_BLOB_MAGIC);
+    }
+    if (rc != LBMPM_OK) { ipc_unmap(c); return rc; }
+    c->tx.ring = true; c->tx.connected = true; c->tx.seq = 0;
+    return LBMPM_OK;
+}
+
+extern "C" int lbmpm_rk3dcsf_rccl_connect(lbmpm_rk3dcsf *c, const void *id, int rank, int nranks, const char *librccl_path)
+{
+    LBMPM_REQUIRE(c && id && nranks >= 2 && rank >= 0 && rank < nranks, "lbmpm_rk3dcsf_rccl_connect: bad argument (a ring of two ranks or more)");
+    int rc = tx_shape(c, "lbmpm_rk3dcsf_rccl_connect");
+    if (rc != LBMPM_OK) return rc;
+    rc = c->tx.rccl.open(librccl_path);
+    if (rc != LBMPM_OK) { tx_drop(c); return rc; }
+    slabtx::Rccl::UniqueId uid;
+    memcpy(&uid, id, sizeof uid);
+    const int e = c->tx.rccl.CommInitRank(&c->tx.comm, nranks, uid, rank);
+    if (e != 0) { set_error("ncclCommInitRank(rank %d of %d): %s", rank, nranks, c->tx.rccl.GetErrorString(e)); tx_drop(c); return LBMPM_ERR_HIP; }
+    c->tx.rank = rank; c->tx.nranks = nranks; c->tx.peer_up = (rank + 1) % nranks; c->tx.peer_dn = (rank + nranks - 1) % nranks;
+    c->tx.ring = true; c->tx.kind = LBMPM_TRANSPORT_RCCL; c->tx.connected = true; c->tx.seq = 0;
+    return LBMPM_OK;
+}
+
+extern "C" int lbmpm_rk3dcsf_transport_disconnect(lbmpm_rk3dcsf *c)
+{
+    LBMPM_REQUIRE(c, "null context");
+    LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
+    (void)hipStreamSynchronize(c->stream);
+    (void)hipStreamSynchronize(c->stream2);
+    tx_drop(c);
+    return LBMPM_OK;
+}
+
+extern "C" int lbmpm_rk3dcsf_transport_kind(lbmpm_rk3dcsf *c, int *value_ops)
+{
+    if (!c) return LBMPM_TRANSPORT_NONE;
+    if (value_ops) *value_ops = c->tx.kind == LBMPM_TRANSPORT_IPC && c->tx.value_ops ? 1 : 0;
+    return c->tx.connected ? c->tx.kind : LBMPM_TRANSPORT_NONE;
+}
+
+extern "C" int lbmpm_rk3dcsf_ipc_release_waits(lbmpm_rk3dcsf *c)
+{
+    LBMPM_REQUIRE(c && c->tx.kind == LBMPM_TRANSPORT_IPC && c->tx.flags, "lbmpm_rk3dcsf_ipc_release_waits: no IPC transport");
+    LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
+    return release_waits(c);
+}
+
+// `rounds` x the three message kinds, patterned, each way through the send buffers and landing slots at the sizes of a step, compared on
+// the receiving GPU behind the transport's waits; enqueued on the context's stream (the caller waits under a deadline)
+extern "C" int lbmpm_rk3dcsf_transport_probe(lbmpm_rk3dcsf *c, int rounds)
+{
+    LBMPM_REQUIRE(c && rounds >= 1, "lbmpm_rk3dcsf_transport_probe: bad argument");
+    { const int rc = tx_usable(c, "lbmpm_rk3dcsf_transport_probe"); if (rc != LBMPM_OK) return rc; }
+    LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
+    if (!c->probe_bad) LBMPM_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&c->probe_bad), sizeof(unsigned long long)));
+    LBMPM_HIP_TRY(hipMemsetAsync(c->probe_bad, 0, sizeof(unsigned long long), c->stream));
+    auto grid = [](size_t n) { return dim3((unsigned)((n + 255) / 256)); };
+    for (int r = 0; r < rounds; ++r)
+        for (int k = 0; k < 3; ++k) {
+            const int m = STEP_MSGS[k];
+            const size_t nu = msg_bytes(c, m, 1, false) / 8, nd = msg_bytes(c, m, 0, false) / 8, nb = msg_bytes(c, m, 0, true) / 8, na = msg_bytes(c, m, 1, true) / 8;
+            const double up = 1000. * (3 * r + k + 1) + 1., dn = -up;
+            if (nu) csf3d_tx_fill<<<grid(nu), 256, 0, c->stream>>>(c->send_hi, nu, up);
+            if (nd) csf3d_tx_fill<<<grid(nd), 256, 0, c->stream>>>(c->send_lo, nd, dn);
+            const double *fb = nullptr, *fa = nullptr;
+            const int rc = c->tx.exchange(c->stream, c->send_hi, c->send_lo, 8 * nu, 8 * nd, 8 * nb, 8 * na, &fb, &fa);
+            if (rc != LBMPM_OK) return rc;
+            if (nb) csf3d_tx_check<<<grid(nb), 256, 0, c->stream>>>(fb, nb, up, c->probe_bad);      // what the low neighbour sent up
+            if (na) csf3d_tx_check<<<grid(na), 256, 0, c->stream>>>(fa, na, dn, c->probe_bad);      // what the high neighbour sent down
+            LBMPM_HIP_TRY(hipGetLastError());
+        }
+    return LBMPM_OK;
+}
+
+extern "C" int lbmpm_rk3dcsf_transport_probe_result(lbmpm_rk3dcsf *c, int64_t *mismatches)
+{
+    LBMPM_REQUIRE(c && mismatches && c->probe_bad, "lbmpm_rk3dcsf_transport_probe_result: no probe was run");
+    LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
+    unsigned long long v = 0;
+    LBMPM_HIP_TRY(hipMemcpyAsync(&v, c->probe_bad, sizeof v, hipMemcpyDeviceToHost, c->stream));
+    LBMPM_HIP_TRY(hipStreamSynchronize(c->stream));
+    *mismatches = (int64_t)v;
+    return LBMPM_OK;
+}
+
+// n whole steps of a connected slab behind ONE call, enqueued on the context's stream without a host synchronisation:
+// stage 0 -> phi through both faces -> stage 1 -> n -> stage 2 -> populations + flag bytes -> heartbeat, the bulk's collision on the
+// second stream beside the first two messages (as lbmpm_rk3dcsf_stage places it)
+extern "C" int lbmpm_rk3dcsf_step_slab(lbmpm_rk3dcsf *c, int64_t nsteps, int timed)
+{
+    LBMPM_REQUIRE(c && nsteps >= 0, "lbmpm_rk3dcsf_step_slab: bad argument");
+    { const int rc = tx_usable(c, "lbmpm_rk3dcsf_step_slab"); if (rc != LBMPM_OK) return rc; }
+    if (!c->have_state) { set_error("lbmpm_rk3dcsf_step_slab before set_macro / set_pdf"); return LBMPM_ERR_STATE; }
+    if (c->next_stage != 0) { set_error("lbmpm_rk3dcsf_step_slab: stage %d of a step begun with lbmpm_rk3dcsf_stage is next", c->next_stage); return LBMPM_ERR_STATE; }
+    LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
+    if (!c->beat_host) {
+        LBMPM_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&c->beat_host), 64, hipHostMallocMapped));
+        *c->beat_host = 0ull;
+        LBMPM_HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void **>(&c->beat_dev), c->beat_host, 0));
+    }
+    const int64_t tsteps = timed ? (nsteps < 256 ? nsteps : 256) : 0;
+    if (timed) {
+        if (c->slab_pool.reserve((size_t)(6 * tsteps)) != LBMPM_OK) { set_error("hipEventCreate failed"); return LBMPM_ERR_HIP; }
+        c->slab_pool.reset();
+        c->slab_timed_steps = tsteps;
+    }
+    for (int64_t k = 0; k < nsteps; ++k) {
+        for (int st = 0; st < 3; ++st) {
+            hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+            if (k < tsteps) { c->slab_pool.take(&ev[0], &ev[1]); c->slab_pool.take(&ev[2], &ev[3]); }
+            if (ev[0]) LBMPM_HIP_TRY(hipEventRecord(ev[0], c->stream));
+            int rc = lbmpm_rk3dcsf_stage(c, st);
+            if (ev[1]) LBMPM_HIP_TRY(hipEventRecord(ev[1], c->stream));
+            if (ev[2]) LBMPM_HIP_TRY(hipEventRecord(ev[2], c->stream));
+            if (rc == LBMPM_OK) rc = tx_message(c, STEP_MSGS[st]);
+            if (rc != LBMPM_OK) return rc;           // (the state is void: set_macro / set_pdf before the next step)
+            if (ev[3]) LBMPM_HIP_TRY(hipEventRecord(ev[3], c->stream));
+        }
+        slabtx::launch_flag_store(c->stream, c->beat_dev, (unsigned long long)c->steps);     // "this step's messages are through"
+        LBMPM_HIP_TRY(hipGetLastError());
+    }
+    return LBMPM_OK;
+}
+
+// averages [ms] over the timed steps of the last step_slab(..., timed = 1): out[0..2] stage 0, 1, 2 (their launches on the context's
+// stream), out[3..5] the message after each (pack .. unpack, the transfer and the wait for the neighbours included), out[6] steps averaged
+extern "C" int lbmpm_rk3dcsf_slab_timing(lbmpm_rk3dcsf *c, double *out)
+{
+    LBMPM_REQUIRE(c && out, "lbmpm_rk3dcsf_slab_timing: null argument");
+    LBMPM_HIP_TRY(hipStreamSynchronize(c->stream));
+    LBMPM_HIP_TRY(hipStreamSynchronize(c->stream2));
+    for (int i = 0; i < 7; ++i) out[i] = 0.;
+    const int64_t n = c->slab_timed_steps;
+    if (n <= 0) return LBMPM_OK;
+    for (int64_t k = 0; k < n; ++k)
+        for (int st = 0; st < 3; ++st)
+            for (int w = 0; w < 2; ++w) {
+                const size_t e = (size_t)(12 * k + 4 * st + 2 * w);
+                float ms = 0.f;
+                LBMPM_HIP_TRY(hipEventElapsedTime(&ms, c->slab_pool.ev[e], c->slab_pool.ev[e + 1]));
+                out[3 * w + st] += ms;
+            }
+    for (int i = 0; i < 6; ++i) out[i] /= (double)n;
+    out[6] = (double)n;
+    return LBMPM_OK;
+}
+
+// lbmpm_rk3dcsf_sync with the watchdog of lbmpm_rk3d_sync_deadline: the deadline counts from the last step whose messages were through
+extern "C" int lbmpm_rk3dcsf_sync_deadline(lbmpm_rk3dcsf *c, double seconds)
+{
+    LBMPM_REQUIRE(c && seconds > 0., "lbmpm_rk3dcsf_sync_deadline: bad argument");
+    LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
+    struct timespec t0, t;
+    clock_gettime(CLOCK_MONOTONIC, &t0);
+    auto idle = [&]() -> int {          // 1 idle, 0 busy, -1 error
+        hipError_t e = hipStreamQuery(c->stream);
+        if (e == hipSuccess) e = hipStreamQuery(c->stream2);
+        if (e == hipSuccess) return 1;
+        if (e == hipErrorNotReady) { (void)hipGetLastError(); return 0; }
+        set_error("lbmpm_rk3dcsf_sync_deadline: %s", hipGetErrorString(e));
+        return -1;
+    };
+    volatile unsigned long long *beat = c->beat_host;
+    unsigned long long last = beat ? *beat : 0ull;
+    unsigned spins = 0;
+    for (;;) {
+        const int s = idle();
+        if (s == 1) return LBMPM_OK;
+        if (s < 0) return LBMPM_ERR_HIP;
+        clock_gettime(CLOCK_MONOTONIC, &t);
+        if (beat && *beat != last) { last = *beat; t0 = t; }
+        if ((double)(t.tv_sec - t0.tv_sec) + 1e-9 * (double)(t.tv_nsec - t0.tv_nsec) > seconds) break;
+        if (++spins > 2000) { struct timespec nap = {0, 200000}; nanosleep(&nap, nullptr); }
+    }
+    const int kind = c->tx.connected ? c->tx.kind : LBMPM_TRANSPORT_NONE;
+    if (kind == LBMPM_TRANSPORT_IPC) {
+        const int rc = release_waits(c);
+        if (rc != LBMPM_OK) return rc;
+    } else if (kind == LBMPM_TRANSPORT_RCCL) {
+        if (c->tx.comm && c->tx.rccl.CommAbort) { (void)c->tx.rccl.CommAbort(c->tx.comm); c->tx.comm = nullptr; }
+    }
+    if (kind != LBMPM_TRANSPORT_NONE) {
+        c->tx.dead = true;
+        (void)hipStreamSynchronize(c->stream);
+        (void)hipStreamSynchronize(c->stream2);
+        c->have_state = false;
+    }
+    set_error("lbmpm_rk3dcsf_sync_deadline: the slab's streams were busy and no step's messages came through for %.1f s -- %s (slab of the planes %d..%d of %d)", seconds,
+              kind == LBMPM_TRANSPORT_IPC ? "a neighbour's face message did not arrive; the waits were released, the lattice state is void" :
+              kind == LBMPM_TRANSPORT_RCCL ? "a neighbour did not answer; the communicator was aborted, the lattice state is void" :
+                                             "no in-library transport is connected: nothing was released",
+              (int)c->cfg.slab_z0, own_z1(c) - 1, c->nzg);
+    return LBMPM_ERR_TIMEOUT;
+}

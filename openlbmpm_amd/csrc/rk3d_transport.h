@@ -1,6 +1,8 @@
 // rk3d_transport.h -- the slab exchange's transports inside the library (include/lbmpm.h, "Transport of the slab exchange"):
 // IPC landing areas filled by copy-engine transfers and stream value operations, or ncclSend / ncclRecv of a librccl opened at run
-// time.  Included by rk3d.hip (host code only; the two one-lane kernels are the fallback of devices without stream value operations).
+// time.  Included by rk3d.hip (the perturbation model's slabs) and rk3d_csf.hip (the CSF model's slabs): host code only.  The two one-lane
+// kernels -- the fallback of devices without stream value operations, and the slab step's heartbeat -- live in rk3d_transport.hip, ONE
+// translation unit, and are launched through the two functions below.
 #include <dlfcn.h>
 #include <unistd.h>
 #include <time.h>
@@ -10,11 +12,9 @@ namespace slabtx {
 
 using lbmpm::set_error;
 
-__global__ void flag_store(unsigned long long *f, unsigned long long v) { __hip_atomic_store(f, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM); }
-__global__ void flag_wait(unsigned long long *f, unsigned long long v)
-{
-    while (__hip_atomic_load(f, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM) < v) __builtin_amdgcn_s_sleep(32);
-}
+// flag_store<<<1, 1, 0, st>>>(f, v) / flag_wait<<<1, 1, 0, st>>>(f, v) (rk3d_transport.hip); the caller checks hipGetLastError
+void launch_flag_store(hipStream_t st, unsigned long long *f, unsigned long long v);
+void launch_flag_wait(hipStream_t st, unsigned long long *f, unsigned long long v);
 
 // what a rank tells its neighbours (LBMPM_IPC_BLOB_BYTES)
 struct IpcBlob {
@@ -111,6 +111,8 @@ struct Transport {
     void *comm = nullptr;
     int rank = 0, nranks = 1;
     int peer_up = -1, peer_dn = -1;           // RCCL ranks of the neighbours (rank + 1, rank - 1; the self-test talks to itself)
+    bool ring = false;                        // the CSF model's ring of slabs: with two ranks both neighbours are ONE peer, whose messages
+                                              // pair with ours in the order posted -- send low, send high, receive high, receive low
 
     char *slot_ptr(char *base, int face, unsigned par) const { return base + ((size_t)face * 2 + par) * slot; }
     char *peer_slot_ptr(int side, int face, unsigned par) const { return peer_land[side] + ((size_t)face * 2 + par) * peer_slot[side]; }
@@ -141,7 +143,7 @@ struct Transport {
         return LBMPM_OK;
     }
 
-    int ipc_alloc(IpcBlob *blob)
+    int ipc_alloc(IpcBlob *blob, uint32_t magic = BLOB_MAGIC)
     {
         const int dev = device;
         const bool below = has_below, above = has_above;
@@ -155,7 +157,7 @@ struct Transport {
         (void)hipDeviceGetAttribute(&can, hipDeviceAttributeCanUseStreamWaitValue, dev);
         value_ops = can != 0 && !getenv("LBMPM_IPC_FLAG_KERNELS");      // (the variable forces the one-lane kernels: test coverage of the fallback)
         memset(blob, 0, sizeof *blob);
-        blob->magic = BLOB_MAGIC; blob->version = BLOB_VERSION; blob->pid = (int32_t)getpid(); blob->device = dev;
+        blob->magic = magic; blob->version = BLOB_VERSION; blob->pid = (int32_t)getpid(); blob->device = dev;
         blob->nonce = process_nonce();
         blob->slot_bytes = slot; blob->bytes_from_below = below ? bytes_from_below : 0; blob->bytes_from_above = above ? bytes_from_above : 0;
         blob->land_ptr = reinterpret_cast<uint64_t>(land); blob->flags_ptr = reinterpret_cast<uint64_t>(flags);
@@ -165,9 +167,12 @@ struct Transport {
         return LBMPM_OK;
     }
 
-    int ipc_open(int side, const IpcBlob *b, size_t my_bytes)
+    int ipc_open(int side, const IpcBlob *b, size_t my_bytes, uint32_t magic = BLOB_MAGIC)
     {
-        if (b->magic != BLOB_MAGIC || b->version != BLOB_VERSION) { set_error("lbmpm_rk3d_ipc_connect: not a blob of lbmpm_rk3d_ipc_init"); return LBMPM_ERR_INVALID; }
+        if (b->magic != magic || b->version != BLOB_VERSION) {
+            set_error("%s: not a blob of %s", magic == BLOB_MAGIC ? "lbmpm_rk3d_ipc_connect" : "lbmpm_rk3dcsf_ipc_connect", magic == BLOB_MAGIC ? "lbmpm_rk3d_ipc_init" : "lbmpm_rk3dcsf_ipc_init");
+            return LBMPM_ERR_INVALID;
+        }
         const uint64_t theirs = side == 0 ? b->bytes_from_above : b->bytes_from_below;     // the rank below receives "from above"
         if (theirs != my_bytes) {
             set_error("lbmpm_rk3d_ipc_connect: the rank %s expects %llu bytes per message, this rank sends %llu (different cuts or lattices)",
@@ -200,9 +205,24 @@ struct Transport {
         return LBMPM_OK;
     }
 
+    // both neighbours are one rank (a ring of two): side `to` uses the mapping of side `from` (a handle is opened once, closed once)
+    void ipc_share(int to, int from)
+    {
+        peer_land[to] = peer_land[from]; peer_flags[to] = peer_flags[from]; peer_slot[to] = peer_slot[from]; mapped[to] = false;
+    }
+
     // One message each way, enqueued on `st`: send_up -> the rank above, send_dn -> the rank below; *from_below / *from_above = where
     // this rank's incoming messages will have landed when the stream gets past the waits enqueued here.
     int exchange(hipStream_t st, const double *send_up, const double *send_dn, const double **from_below, const double **from_above)
+    {
+        return exchange(st, send_up, send_dn, bytes_up, bytes_dn, bytes_from_below, bytes_from_above, from_below, from_above);
+    }
+
+    // The same for one of several message kinds of different sizes (the CSF model: phi, n, populations after the three stages of a step;
+    // every size within the slots set_shape made).  The sequence number counts messages, whatever their kind: the two-parity argument
+    // holds as long as every exchange's waits are enqueued before the stream goes on to produce the next message.
+    int exchange(hipStream_t st, const double *send_up, const double *send_dn, size_t up, size_t dn, size_t in_below, size_t in_above,
+                 const double **from_below, const double **from_above)
     {
         if (!connected) { set_error("the slab's transport is not connected"); return LBMPM_ERR_STATE; }
         if (dead) { set_error("the slab's transport was given up by the watchdog (a neighbour did not answer): disconnect and set up the run again"); return LBMPM_ERR_TIMEOUT; }
@@ -211,16 +231,16 @@ struct Transport {
         if (kind == LBMPM_TRANSPORT_IPC) {
             *from_below = reinterpret_cast<const double *>(slot_ptr(land, 0, par));
             *from_above = reinterpret_cast<const double *>(slot_ptr(land, 1, par));
-            if (has_above) LBMPM_HIP_TRY(hipMemcpyAsync(peer_slot_ptr(1, 0, par), send_up, bytes_up, hipMemcpyDeviceToDevice, st));
-            if (has_below) LBMPM_HIP_TRY(hipMemcpyAsync(peer_slot_ptr(0, 1, par), send_dn, bytes_dn, hipMemcpyDeviceToDevice, st));
+            if (has_above) LBMPM_HIP_TRY(hipMemcpyAsync(peer_slot_ptr(1, 0, par), send_up, up, hipMemcpyDeviceToDevice, st));
+            if (has_below) LBMPM_HIP_TRY(hipMemcpyAsync(peer_slot_ptr(0, 1, par), send_dn, dn, hipMemcpyDeviceToDevice, st));
             auto post = [&](unsigned long long *f) -> hipError_t {
                 if (value_ops) return hipStreamWriteValue64(st, f, seq, 0);
-                flag_store<<<1, 1, 0, st>>>(f, seq);
+                launch_flag_store(st, f, seq);
                 return hipGetLastError();
             };
             auto await = [&](unsigned long long *f) -> hipError_t {
                 if (value_ops) return hipStreamWaitValue64(st, f, seq, hipStreamWaitValueGte, ~0ull);
-                flag_wait<<<1, 1, 0, st>>>(f, seq);
+                launch_flag_wait(st, f, seq);
                 return hipGetLastError();
             };
             if (has_above) LBMPM_HIP_TRY(post(peer_flags[1] + 0 * 2 + par));
@@ -233,10 +253,17 @@ struct Transport {
             *from_below = reinterpret_cast<const double *>(slot_ptr(land, 0, 0));
             *from_above = reinterpret_cast<const double *>(slot_ptr(land, 1, 0));
             int rc = rccl.GroupStart();
-            if (rc == 0 && has_above) rc = rccl.Send(send_up, bytes_up / 8, Rccl::kFloat64, peer_up, comm, st);
-            if (rc == 0 && has_above) rc = rccl.Recv(slot_ptr(land, 1, 0), bytes_from_above / 8, Rccl::kFloat64, peer_up, comm, st);
-            if (rc == 0 && has_below) rc = rccl.Send(send_dn, bytes_dn / 8, Rccl::kFloat64, peer_dn, comm, st);
-            if (rc == 0 && has_below) rc = rccl.Recv(slot_ptr(land, 0, 0), bytes_from_below / 8, Rccl::kFloat64, peer_dn, comm, st);
+            if (ring) {
+                if (rc == 0 && has_below) rc = rccl.Send(send_dn, dn / 8, Rccl::kFloat64, peer_dn, comm, st);
+                if (rc == 0 && has_above) rc = rccl.Send(send_up, up / 8, Rccl::kFloat64, peer_up, comm, st);
+                if (rc == 0 && has_above) rc = rccl.Recv(slot_ptr(land, 1, 0), in_above / 8, Rccl::kFloat64, peer_up, comm, st);
+                if (rc == 0 && has_below) rc = rccl.Recv(slot_ptr(land, 0, 0), in_below / 8, Rccl::kFloat64, peer_dn, comm, st);
+            } else {
+                if (rc == 0 && has_above) rc = rccl.Send(send_up, up / 8, Rccl::kFloat64, peer_up, comm, st);
+                if (rc == 0 && has_above) rc = rccl.Recv(slot_ptr(land, 1, 0), in_above / 8, Rccl::kFloat64, peer_up, comm, st);
+                if (rc == 0 && has_below) rc = rccl.Send(send_dn, dn / 8, Rccl::kFloat64, peer_dn, comm, st);
+                if (rc == 0 && has_below) rc = rccl.Recv(slot_ptr(land, 0, 0), in_below / 8, Rccl::kFloat64, peer_dn, comm, st);
+            }
             const int rc2 = rccl.GroupEnd();
             if (rc == 0) rc = rc2;
             if (rc != 0) { set_error("RCCL transport: %s", rccl.GetErrorString ? rccl.GetErrorString(rc) : "ncclSend / ncclRecv failed"); return LBMPM_ERR_HIP; }
@@ -260,7 +287,7 @@ struct Transport {
         if (land) (void)hipFree(land);
         if (flags) (void)hipFree(flags);
         land = nullptr; flags = nullptr;
-        kind = LBMPM_TRANSPORT_NONE; connected = false; seq = 0; dead = false;
+        kind = LBMPM_TRANSPORT_NONE; connected = false; seq = 0; dead = false; ring = false;
         (void)hipGetLastError();
     }
 };

@@ -1,0 +1,16 @@
+// rk3d_transport.hip -- the two one-lane kernels of the slab transports (rk3d_transport.h), in one translation unit: both slab models
+// (rk3d.hip, rk3d_csf.hip) include the transport, and a kernel defined in the header would be defined twice.
+#include "lbmpm_common.h"
+
+namespace slabtx {
+
+__global__ void flag_store(unsigned long long *f, unsigned long long v) { __hip_atomic_store(f, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM); }
+__global__ void flag_wait(unsigned long long *f, unsigned long long v)
+{
+    while (__hip_atomic_load(f, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM) < v) __builtin_amdgcn_s_sleep(32);
+}
+
+void launch_flag_store(hipStream_t st, unsigned long long *f, unsigned long long v) { flag_store<<<1, 1, 0, st>>>(f, v); }
+void launch_flag_wait(hipStream_t st, unsigned long long *f, unsigned long long v) { flag_wait<<<1, 1, 0, st>>>(f, v); }
+
+}  // namespace slabtx
