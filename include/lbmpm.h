@@ -621,6 +621,42 @@ int64_t lbmpm_rk3dcsf_steps_done(const lbmpm_rk3dcsf *ctx);
 int64_t lbmpm_rk3dcsf_device_bytes(const lbmpm_rk3dcsf *ctx);
 const char *lbmpm_rk3dcsf_dominant_kernel(const lbmpm_rk3dcsf *ctx);
 
+/* ---- D3Q7 tracers advected by the 3-D CSF flow: the tracer sub-step of the reference's coupled 2-D loop (Transport2DRK.py:1341-1418, the
+ * kernels listed at lbmpm_tracer_config) carried to three dimensions, one launch (tr3d_step) per time step after the flow's collision,
+ * with rho_R, u and the wetting-corrected colour gradient of that flow step.  Lattice: rest, +x, -x, +y, -y, +z, -z (the order of the
+ * populations below) with weights 0, 1/6 x 6; on a lattice uniform in y it is the reference's D2Q5 scheme with g0 + g(+y) + g(-y) as its rest
+ * population.  z is the flow axis (the 2-D model's y): free-flow outlet on plane 0, Inamuro inlet on plane nz-1.
+ * The flow itself is unchanged, and a context without tracers launches the kernels it launched before.
+ * NOT built: tracers on z-slabs (a context with ghost planes: LBMPM_ERR_UNSUPPORTED) and on the perturbation model (lbmpm_rk3d_*). */
+typedef struct lbmpm_tracer3d_config {
+    int32_t num_tracers;            /* [TransportParameters] NumberTracers, 1..4                                     */
+    double diffusion_x[4];          /* [TransportMRT] DiffusionX                                                     */
+    double diffusion_y[4];          /*                DiffusionY (across the flow; the 2-D model has no such axis)   */
+    double diffusion_z[4];          /*                DiffusionZ (along the flow: the 2-D model's DiffusionY)        */
+    double diffusion_xy, diffusion_yx;   /* off-diagonal entries of the diffusion tensor, the same for every tracer  */
+    double diffusion_xz, diffusion_zx;   /* (the 2-D model's DiffusionXY, DiffusionYX)                               */
+    double diffusion_yz, diffusion_zy;
+    double beta_interface[4];       /* [TransportParameters] BetaInterface                                           */
+    double criteria_rho;            /* criteriaFluidRho: the interface term acts where rhoR <= this                  */
+    double inlet_concentration[4];  /* [BoundaryCondition] ConcentrationInlet                                        */
+    int32_t dirichlet_inlet;        /* InletType 'Dirichlet' (Inamuro) on plane nz-1                                 */
+    int32_t free_outlet;            /* OutletType 'Freeflow': plane 0 copies plane 1                                 */
+    double reaction_rate;           /* [Reaction] ReactionRate: A + B -> C between tracers 0, 1, 2 (needs 3 tracers); 0 = none */
+    double diffusion_j[4];          /* rest weight J0' of the reaction source on THIS lattice: J0', (1 - J0') / 6 x 6.  The moving weights
+                                       must agree with the 2-D model's J0, (1 - J0) / 4 x 4: J0' = (3 J0 - 1) / 2, so J0 = 1/3 gives 0 */
+} lbmpm_tracer3d_config;
+/* before the first step; LBMPM_ERR_INVALID: more than 4 tracers, a reaction with a tracer count other than 3; LBMPM_ERR_STATE: after
+ * stepping; LBMPM_ERR_UNSUPPORTED: a slab */
+int lbmpm_rk3dcsf_tracer_configure(lbmpm_rk3dcsf *ctx, const lbmpm_tracer3d_config *cfg);
+/* dense [nz][ny][nx]; g_i = C w_i; before the first step */
+int lbmpm_rk3dcsf_tracer_set_concentration(lbmpm_rk3dcsf *ctx, int tracer, const double *conc);
+/* the concentration the reference records after the last completed step (streamed, inlet plane applied), dense [nz][ny][nx] */
+int lbmpm_rk3dcsf_tracer_get_concentration(lbmpm_rk3dcsf *ctx, int tracer, double *out);
+/* the populations behind it, [nz][ny][nx][7]; given back to a new context (with lbmpm_rk3dcsf_set_pdf of the flow) the run continues
+ * bit for bit */
+int lbmpm_rk3dcsf_tracer_get_pdf(lbmpm_rk3dcsf *ctx, int tracer, double *out);
+int lbmpm_rk3dcsf_tracer_set_pdf(lbmpm_rk3dcsf *ctx, int tracer, const double *pdf);
+
 /* ---- 3-D CSF slabs: the three face messages over a transport INSIDE the library (the perturbation model's transports above, "Transport
  * of the slab exchange": IPC landing areas filled by copy-engine transfers + stream value operations, or ncclSend / ncclRecv of a librccl
  * opened at run time).  Opt-in: a context that never connects allocates nothing for it (device_bytes does not count the transport's

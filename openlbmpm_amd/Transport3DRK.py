@@ -1,0 +1,134 @@
+"""Tracers carried by the 3-D colour-gradient CSF flow: class Transport3DRK(pathIniFile).runTransport3DMPMCRK().
+
+The reference couples tracers to its 2-D CSF loop only (RKCG2D/Transport2DRK.py; openlbmpm_amd/Transport2DRK.py is its counterpart
+here).  This is the same coupling on the D3Q19 CSF flow of RKColorGradientD3Q19.py with D3Q7 tracers (include/lbmpm.h,
+lbmpm_rk3dcsf_tracer_*): IniFiles/RKtwophasesetup3D.ini with [SurfaceTension] SurfaceTensionType = 'CSF' for the flow,
+transportsetup.ini (config.read_transport3d: the 2-D file's keys plus the z entries) for the tracers.  One GPU: tracers on z-slabs
+are not built, a run under torchrun is refused.
+
+Kept from the 2-D driver: the initial concentration rules with planes in the place of rows (tracer 0 = 1 below the top buffer planes
+for generated geometries, every tracer = 1 in the 10 top planes for voxel geometries; or initial_concentration=[nT][nz][ny][nx]),
+g_i = w_i C, one tracer sub-step inside every flow step after the wetting-corrected colour gradient, the record cadence, and
+`/TransportMacro/TracerConcType<k>in<record>` of ConcentrationResults.h5 beside the flow's SimulationResultsRK3D.h5.  As there, a
+record holds two views: the flow arrays at the START of step iStep, the concentrations AFTER the tracer update of that step; the
+record the 3-D driver writes after the last step holds the concentrations as they stand.  The inlet concentrations are the file's.
+checkpoint() / restart_from= carry the tracers' populations behind the flow's (41 + 7 per tracer doubles per cell): bit for bit.
+"""
+import numpy as np
+
+from . import config
+from .RKColorGradientD3Q19 import GROUPS, RKColorGradient3D, _CSFSlab
+from .results import RecordGuard, ResultFile
+
+
+class _CSFTracerSlab(_CSFSlab):
+    def configure(self, t):
+        n = t["num_tracers"]
+        self.num_tracers = n
+        self.solver.configure_tracers(num_tracers=n, diffusion_x=tuple(t["diffX"]), diffusion_y=tuple(t["diffY"]), diffusion_z=tuple(t["diffZ"]),
+                                      diffusion_xy=t["dXY"], diffusion_yx=t["dYX"], diffusion_xz=t["dXZ"], diffusion_zx=t["dZX"],
+                                      diffusion_yz=t["dYZ"], diffusion_zy=t["dZY"], beta_interface=t["beta"], criteria_rho=0.5,
+                                      inlet_concentration=tuple(t["inlet_conc"]), dirichlet_inlet=t["inlet_type"] == "Dirichlet",
+                                      free_outlet=t["outlet_type"] == "Freeflow", reaction_rate=t["reaction_rate"], diffusion_j=tuple(t["diffJ3"]))
+
+    def get_state(self):
+        st, info = _CSFSlab.get_state(self)
+        st = np.concatenate([st] + [self.solver.get_tracer_pdf(k) for k in range(self.num_tracers)], axis=-1)
+        return st, dict(info, doubles_per_cell=st.shape[-1])
+
+    def set_state(self, st, steps, post_collision):
+        st = np.asarray(st)
+        if st.shape[-1] != 41 + 7 * self.num_tracers:
+            raise config.ConfigError("restart_from: this checkpoint holds %d doubles per cell, the 3-D CSF model with %d tracers keeps %d (f_R, f_B, F, g)"
+                                     % (st.shape[-1], self.num_tracers, 41 + 7 * self.num_tracers))
+        _CSFSlab.set_state(self, st[..., :41], steps, post_collision)
+        for k in range(self.num_tracers):
+            self.solver.set_tracer_pdf(k, np.ascontiguousarray(st[..., 41 + 7 * k:48 + 7 * k]))
+
+
+class Transport3DRK(RKColorGradient3D):
+    def __init__(self, pathIniFile, initial_concentration=None, **kw):
+        RKColorGradient3D.__init__(self, pathIniFile, **kw)
+        self.tr = config.read_transport3d(pathIniFile)
+        self.numTracers = self.tr["num_tracers"]
+        self._initial_concentration = initial_concentration
+
+    def initializeTransportDomain(self):
+        fluid = self.isDomain == 1
+        nz = self.zDomain
+        if self._initial_concentration is not None:
+            conc = np.array(self._initial_concentration, dtype=np.float64)
+            if conc.shape != (self.numTracers,) + self.isDomain.shape:
+                raise config.ConfigError("initial_concentration has shape %s, %d tracers on the domain are %s" % (conc.shape, self.numTracers, (self.numTracers,) + self.isDomain.shape))
+            conc = conc * fluid
+        else:
+            planes = np.arange(nz)[:, None, None]
+            conc = np.zeros((self.numTracers,) + self.isDomain.shape)
+            if self._is_image:
+                conc[:, fluid & (planes >= nz - 10)] = 1.0
+            else:
+                conc[0, fluid & (planes <= nz - self.nbuf)] = 1.0
+        self.tracerConc = conc
+
+    def runTransport3DMPMCRK(self, progress=None):
+        p, t = self.par, self.tr
+        if p["tension_type"] != "CSF":
+            raise config.ConfigError("the tracers are coupled to the CSF colour-gradient flow: [SurfaceTension] SurfaceTensionType = 'CSF'")
+        if self._distributed():
+            raise config.ConfigError("tracers on z-slabs are not built: run the 3-D transport on one GPU")
+        self.initializeDomainBorder()
+        slab = _CSFTracerSlab(self.isDomain, p, self.device, self.csf_bulk_epsilon)
+        slab.configure(t)
+        self._slab, self._observe, self._gather = slab, (lambda: None), (lambda a: a)
+        self.z0, self.nzl = 0, self.zDomain
+        n, done = self.numTracers, 0
+        if self.restart_from:
+            done, self.records = self._load_checkpoint(slab, 0, self.zDomain)
+        else:
+            self.initializeDomainCondition(0, self.zDomain)
+            self._upload_initial_state(slab)
+            self.initializeTransportDomain()
+            for k in range(n):
+                slab.solver.set_concentration(k, self.tracerConc[k])
+        flow = ResultFile(self.output_dir, "SimulationResultsRK3D", GROUPS)
+        conc = ResultFile(self.output_dir, "ConcentrationResults", (("TransportMacro", "MacroData"),))
+        self.result_path, self.concentration_path = flow.path, conc.path
+        self._guard = RecordGuard("rk3d+tracers", slab.num_fluid_nodes, getattr(self, "nan_guard", "raise"))
+        tracer_guard = RecordGuard("tracers", slab.num_fluid_nodes, getattr(self, "nan_guard", "raise"))
+
+        def record_tracers(k, step):
+            self.tracerConc = np.array([slab.solver.get_concentration(i) for i in range(n)])
+            for i in range(n):
+                conc.write("TransportMacro", "TracerConcType%gin%g" % (i, k), self.tracerConc[i])
+            tracer_guard(k, step, {"tracer%d" % i: self.tracerConc[i] for i in range(n)}, {"tracer%d" % i: float(self.tracerConc[i].sum()) for i in range(n)})
+
+        def maybe_checkpoint():
+            if self.checkpoint_every > 0 and done % self.checkpoint_every == 0 and done < self.timeSteps:
+                slab.sync()
+                self.checkpoint_path = self.checkpoint()
+
+        while done < self.timeSteps:
+            self._step_now = done
+            if done % self.timeInterval == 0:
+                k = self.records
+                self._record(slab, flow)                # the flow at the start of step done + 1
+                slab.step_single(1)
+                done += 1
+                record_tracers(k, done)                 # the concentrations after the tracer update of that step
+                maybe_checkpoint()
+            m = min(self.timeInterval - done % self.timeInterval, self.timeSteps - done) if done % self.timeInterval else 0
+            if self.checkpoint_every > 0 and m:
+                m = min(m, self.checkpoint_every - done % self.checkpoint_every)
+            if m:
+                slab.step_single(m)
+                done += m
+                maybe_checkpoint()
+            if progress:
+                progress(done)
+        self._step_now = done
+        k = self.records
+        self._record(slab, flow)
+        record_tracers(k, done)
+        slab.sync()
+        self.solver = slab
+        return self.result_path, self.concentration_path

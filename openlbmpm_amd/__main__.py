@@ -3,6 +3,7 @@
     python -m openlbmpm_amd rk  <ini-dir> [--out DIR] [--steps N] [--device D]
     python -m openlbmpm_amd sc  <ini-dir> [--out DIR] [--steps N] [--device D]
     python -m openlbmpm_amd tr  <ini-dir> ...      colour gradient + tracers (RKtwophasesetup2D.ini + transportsetup.ini)
+    python -m openlbmpm_amd tr3d <ini-dir> ...     D3Q19 CSF colour gradient + D3Q7 tracers (RKtwophasesetup3D.ini + transportsetup.ini), one GPU
     python -m openlbmpm_amd rk3d <ini-dir> ...     D3Q19 colour gradient (RKtwophasesetup3D.ini); under torchrun: z-slabs, one per GPU
         [--csf-transport auto|ipc|rccl]           SurfaceTensionType = 'CSF' under torchrun: the slabs' face messages over the library's
                                                   own transports (default: through torch.distributed)
@@ -14,7 +15,7 @@ import time
 
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m openlbmpm_amd")
-    ap.add_argument("model", choices=["rk", "sc", "tr", "rk3d"], help="rk = colour gradient (RKtwophasesetup2D.ini); "
+    ap.add_argument("model", choices=["rk", "sc", "tr", "rk3d", "tr3d"], help="rk = colour gradient (RKtwophasesetup2D.ini); "
                                                        "sc = Shan-Chen / EFS (twophasesetup.ini + efs2D.ini|shanchen2D.ini)")
     ap.add_argument("ini_dir")
     ap.add_argument("--out", default=None, help="result directory (default ~/LBMResults)")
@@ -49,6 +50,13 @@ def main(argv=None):
         if a.steps is not None:
             sim.timeSteps = a.steps
         path = sim.runRKColorGradient3D()
+        steps, nodes = sim.timeSteps, sim.voidSpace
+    elif a.model == "tr3d":
+        from .Transport3DRK import Transport3DRK
+        sim = Transport3DRK(a.ini_dir, output_dir=a.out, device=a.device)
+        if a.steps is not None:
+            sim.timeSteps = a.steps
+        path = " and ".join(sim.runTransport3DMPMCRK())
         steps, nodes = sim.timeSteps, sim.voidSpace
     elif a.model == "tr":
         from .Transport2DRK import Transport2DRK

@@ -56,6 +56,16 @@ class TracerConfig(C.Structure):
                 ("reaction_rate", C.c_double), ("diffusion_j", C.c_double * 4)]
 
 
+class Tracer3DConfig(C.Structure):
+    # mirrors struct lbmpm_tracer3d_config (include/lbmpm.h)
+    _fields_ = [("num_tracers", C.c_int32), ("diffusion_x", C.c_double * 4), ("diffusion_y", C.c_double * 4), ("diffusion_z", C.c_double * 4),
+                ("diffusion_xy", C.c_double), ("diffusion_yx", C.c_double), ("diffusion_xz", C.c_double), ("diffusion_zx", C.c_double),
+                ("diffusion_yz", C.c_double), ("diffusion_zy", C.c_double), ("beta_interface", C.c_double * 4),
+                ("criteria_rho", C.c_double), ("inlet_concentration", C.c_double * 4),
+                ("dirichlet_inlet", C.c_int32), ("free_outlet", C.c_int32),
+                ("reaction_rate", C.c_double), ("diffusion_j", C.c_double * 4)]
+
+
 class SC2DConfig(C.Structure):
     # mirrors struct lbmpm_sc2d_config (include/lbmpm.h)
     _fields_ = [("nx", C.c_int64), ("ny", C.c_int64), ("model", C.c_int32), ("relaxation", C.c_int32),
@@ -191,6 +201,11 @@ _SIGNATURES = {
     "lbmpm_rk3dcsf_steps_done": (C.c_int64, [C.c_void_p]),
     "lbmpm_rk3dcsf_device_bytes": (C.c_int64, [C.c_void_p]),
     "lbmpm_rk3dcsf_dominant_kernel": (C.c_char_p, [C.c_void_p]),
+    "lbmpm_rk3dcsf_tracer_configure": (C.c_int, [C.c_void_p, C.POINTER(Tracer3DConfig)]),
+    "lbmpm_rk3dcsf_tracer_set_concentration": (C.c_int, [C.c_void_p, C.c_int, F64P]),
+    "lbmpm_rk3dcsf_tracer_get_concentration": (C.c_int, [C.c_void_p, C.c_int, F64P]),
+    "lbmpm_rk3dcsf_tracer_get_pdf": (C.c_int, [C.c_void_p, C.c_int, F64P]),
+    "lbmpm_rk3dcsf_tracer_set_pdf": (C.c_int, [C.c_void_p, C.c_int, F64P]),
     "lbmpm_rk3dcsf_ipc_init": (C.c_int, [C.c_void_p, C.c_void_p]),
     "lbmpm_rk3dcsf_ipc_connect": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "lbmpm_rk3dcsf_rccl_connect": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_char_p]),

@@ -303,3 +303,24 @@ def read_transport(ini_dir):
     p["dXY"] = c.floats("TransportMRT", "DiffusionXY", n)[0]
     p["dYX"] = c.floats("TransportMRT", "DiffusionYX", n)[0]
     return p
+
+
+def read_transport3d(ini_dir):
+    """transportsetup.ini for the D3Q7 tracers of the 3-D CSF flow: the keys of read_transport plus the z entries of [TransportMRT] --
+    DiffusionZ (per tracer), DiffusionXZ, DiffusionZX, DiffusionYZ, DiffusionZY.  A missing z entry defaults to the y entry of the 2-D
+    file (DiffusionZ <- DiffusionY, DiffusionXZ <- DiffusionXY, DiffusionZX <- DiffusionYX; DiffusionYZ, DiffusionZY <- 0), so a 2-D file
+    with DiffusionX = DiffusionY describes an isotropic 3-D case.  z is the flow axis: the inlet / outlet rules act on its end planes.
+    diffJ3 is the rest weight of the reaction source on the D3Q7 lattice: the moving weights must agree with the 2-D model's,
+    (1 - J0') / 6 = (1 - J0) / 4, so J0' = (3 J0 - 1) / 2 (the 2-D default J0 = 1/3 gives 0)."""
+    p = read_transport(ini_dir)
+    c = Ini(os.path.join(ini_dir, "transportsetup.ini"))
+    n = p["num_tracers"]
+    sec = c.cp["TransportMRT"] if "TransportMRT" in c.cp else {}
+    p["diffZ"] = c.floats("TransportMRT", "DiffusionZ", n) if "DiffusionZ" in sec else list(p["diffY"])
+
+    def first(key, default):
+        return c.floats("TransportMRT", key, n)[0] if key in sec else default
+    p["dXZ"], p["dZX"] = first("DiffusionXZ", p["dXY"]), first("DiffusionZX", p["dYX"])
+    p["dYZ"], p["dZY"] = first("DiffusionYZ", 0.0), first("DiffusionZY", 0.0)
+    p["diffJ3"] = [(3. * j - 1.) / 2. for j in p["diffJ"]]
+    return p

@@ -24,6 +24,7 @@
 //   csf3d_collide    pull + boundary planes again (bit-identical to the first pass), curvature from the neighbours' n, force,   }
 //                    collision, recolouring -> the other buffer                                   38 reads, 41 writes           }
 //   csf3d_collide_deep   the deep blocks: the present colour alone through a table of source cells 19 reads, 19 writes
+//   tr3d_step        tracers configured only (rk3d_tracer.h): the D3Q7 tracers' sub-step with rho_R, u (kept by the two collisions, TR) and G of this step
 // The curvature needs n one cell around and n needs phi one cell around that: two global dependencies per step, hence the two passes
 // over the populations where colours meet (136 doubles per cell and step).  Measured: DESIGN.md section 4.
 #include "lbmpm_common.h"
@@ -82,6 +83,7 @@ struct CsfDev {
     const uint32_t *work;        // [3][nblk + 1] lists of blocks in order, each followed by its length: L_TODO the blocks csf3d_phase / csf3d_gradient
                                  // have something to do in (not deep, or deep since this step), L_FULL the blocks that are not deep, L_DEEP those that are
     const uint32_t *src;         // [18][FS] number of the fluid cell x - e_i (the cell direction i is pulled from), SRC_WALL off a solid
+    double *trflow;              // [4][FS] tracers configured: rho_R, u of the step per fluid cell, for tr3d_step (rk3d_tracer.h); else null
 };
 
 struct Nb { unsigned xo[3], yo[3], zo[3]; };
@@ -459,11 +461,11 @@ __device__ __forceinline__ double tau_of(const CsfDev &p, double Phi, double rR,
 }
 
 // second half of the loop for one cell: curvature and force, collision with the Guo source, recolouring; stores the post-collision
-// populations (the next step pulls them).  DIAG: also keep u and K of the step.
+// populations (the next step pulls them).  DIAG: also keep u and K of the step.  TR: keep rho_R and u per fluid cell for the tracers.
 #ifndef CSF_MRT_WAVES
 #define CSF_MRT_WAVES 2
 #endif
-template <bool FIRST, bool MRT, bool DIAG>
+template <bool FIRST, bool MRT, bool DIAG, bool TR>
 __global__ __launch_bounds__(256, MRT ? CSF_MRT_WAVES : 3) void csf3d_collide(CsfDev p)
 {
     constexpr int CX[Q] = CSF_CX, CY[Q] = CSF_CY, CZ[Q] = CSF_CZ;
@@ -515,6 +517,7 @@ __global__ __launch_bounds__(256, MRT ? CSF_MRT_WAVES : 3) void csf3d_collide(Cs
     }
     if (!(deep && was_deep)) { p.F[n] = fx; p.F[p.NS + n] = fy; p.F[2 * p.NS + n] = fz; }
     if (DIAG) { p.K[n] = k; p.U[n] = vx; p.U[p.NS + n] = vy; p.U[2 * p.NS + n] = vz; }
+    if (TR) { p.trflow[j] = rR; p.trflow[p.FS + j] = vx; p.trflow[2 * p.FS + j] = vy; p.trflow[3 * p.FS + j] = vz; }
     const double tau = tau_of(p, phi, rR, rB);
     if (!MRT) {
 #pragma unroll
@@ -584,7 +587,7 @@ __global__ __launch_bounds__(256, MRT ? CSF_MRT_WAVES : 3) void csf3d_collide(Cs
 // (tests: variant 1 runs every block through csf3d_collide).  19 loads through the table of source cells (no lattice coordinates, no
 // meta words: the open planes are never deep), 19 stores; the absent colour is not read, and not written again once its zeros are in
 // place (a block deep since the step before: this buffer was written two steps ago, when the block held that colour alone already).
-template <bool MRT, bool DIAG>
+template <bool MRT, bool DIAG, bool TR>
 __global__ __launch_bounds__(256) void csf3d_collide_deep(CsfDev p)
 {
     constexpr int CX[Q] = CSF_CX, CY[Q] = CSF_CY, CZ[Q] = CSF_CZ, OPP[Q] = CSF_OPP;
@@ -618,6 +621,7 @@ __global__ __launch_bounds__(256) void csf3d_collide_deep(CsfDev p)
             const double phi = (rR - rB) / (rR + rB);
             if (!was_deep) { p.F[n] = 0.; p.F[p.NS + n] = 0.; p.F[2 * p.NS + n] = 0.; }
             if (DIAG) { p.K[n] = 0.; p.U[n] = vx; p.U[p.NS + n] = vy; p.U[2 * p.NS + n] = vz; }
+            if (TR) { p.trflow[j] = rR; p.trflow[p.FS + j] = vx; p.trflow[2 * p.FS + j] = vy; p.trflow[3 * p.FS + j] = vz; }
             const double tau = tau_of(p, phi, rR, rB);
             if (!MRT) {
 #pragma unroll
@@ -1003,6 +1007,8 @@ __global__ __launch_bounds__(256) void csf3d_import(CsfDev p, double *f, const d
     }
 }
 
+#include "rk3d_tracer.h"
+
 }  // namespace
 
 struct lbmpm_rk3dcsf {
@@ -1038,6 +1044,13 @@ struct lbmpm_rk3dcsf {
     hipStream_t wd_stream = nullptr;                    // the watchdog's own copies
     lbmpm::EventPool slab_pool;                         // lbmpm_rk3dcsf_step_slab(timed): 6 event pairs per step {stage, message} x 3
     int64_t slab_timed_steps = 0;
+    // tracers (lbmpm_rk3dcsf_tracer_*; rk3d_tracer.h): nothing of this is allocated before a configure
+    int ntr = 0;
+    bool tr_first = true;
+    lbmpm_tracer3d_config trcfg;
+    double *gA = nullptr, *gB = nullptr, *trflow = nullptr;      // [ntr][7][FS] x 2, [4][FS]
+    uint32_t *trsrc = nullptr;                                   // [6][FS] when the context has no table of source cells of its own
+    double trB[4][9];
 };
 
 namespace {
@@ -1071,11 +1084,44 @@ CsfDev make_dev(const lbmpm_rk3dcsf *c)
     for (int i = 0; i < 6; ++i) p.rate[i] = any ? c->cfg.mrt_rates[i] : own[i];
     p.eps = c->cfg.bulk_epsilon > 0. ? c->cfg.bulk_epsilon : 0x1p-51;
     p.nblk = c->nblk; p.skip = c->skip ? 1 : 0; p.pure = c->pure; p.deep_prev = c->deep_prev; p.bcblk = c->bcblk; p.rng = c->rng; p.pfx = c->pfx; p.deep_now = c->deep_now; p.work = c->work; p.src = c->src;
+    p.trflow = c->trflow;
     return p;
 }
 
 unsigned blocks_of(size_t n) { return (unsigned)((n + 255) / 256); }
 unsigned blocks8(size_t n) { return (blocks_of(n) + 7u) / 8u * 8u; }      // fluid_cell(): eight XCDs
+
+TrDev make_trdev(const lbmpm_rk3dcsf *c)
+{
+    TrDev t;
+    const lbmpm_tracer3d_config &k = c->trcfg;
+    t.nT = c->ntr; t.inlet = k.dirichlet_inlet != 0; t.outlet = k.free_outlet != 0; t.reaction = k.reaction_rate != 0.;
+    t.gin = c->gA; t.gout = c->gB; t.flow = c->trflow; t.src = c->src ? c->src : c->trsrc;
+    t.crit = k.criteria_rho; t.rate = k.reaction_rate;
+    for (int a = 0; a < 4; ++a) {
+        for (int b = 0; b < 9; ++b) t.B[a][b] = c->trB[a][b];
+        t.beta[a] = k.beta_interface[a]; t.cin[a] = k.inlet_concentration[a]; t.j0[a] = k.diffusion_j[a];
+    }
+    return t;
+}
+
+// one launch for all tracers over every fluid cell (g: blocks8 of the fluid cells); swaps the tracers' buffers
+int launch_tracers(lbmpm_rk3dcsf *c, const CsfDev &p, unsigned g)
+{
+    const TrDev t = make_trdev(c);
+#define TR3D_GO(NT) do { if (c->tr_first) tr3d_step<true, NT><<<g, 256, 0, c->stream>>>(p, t); else tr3d_step<false, NT><<<g, 256, 0, c->stream>>>(p, t); } while (0)
+    switch (c->ntr) {
+    case 1: TR3D_GO(1); break;
+    case 2: TR3D_GO(2); break;
+    case 3: TR3D_GO(3); break;
+    default: TR3D_GO(4); break;
+    }
+#undef TR3D_GO
+    LBMPM_HIP_TRY(hipGetLastError());
+    std::swap(c->gA, c->gB);
+    c->tr_first = false;
+    return LBMPM_OK;
+}
 
 // stages: bit 0 lists, bulk collision, phase field | bit 1 solid phi, gradient | bit 2 collision of the full path (7: a whole step)
 template <bool FIRST>
@@ -1089,7 +1135,7 @@ int launch_step(lbmpm_rk3dcsf *c, const CsfDev &p, hipEvent_t e0, hipEvent_t e1,
         csf3d_tile_count<1><<<nt, 1024, 0, c->stream>>>(p, c->deep_now, c->tcnt);
         csf3d_tile_rank<1><<<nt, 1024, 0, c->stream>>>(p, c->deep_now, c->tcnt, c->work);
     }
-    const bool mrt = c->cfg.relaxation == LBMPM_RELAX_MRT;
+    const bool mrt = c->cfg.relaxation == LBMPM_RELAX_MRT, tr = c->ntr > 0;
     const bool deep_launch = c->skip && !FIRST;      // (nothing is deep in the first step after a set_*)
     if (e0) LBMPM_HIP_TRY(hipEventRecord(e0, c->stream));
     if (deep_launch && (stages & 1)) {
@@ -1097,8 +1143,13 @@ int launch_step(lbmpm_rk3dcsf *c, const CsfDev &p, hipEvent_t e0, hipEvent_t e1,
         // second stream beside the four launches of the full path (small, latency-bound launches when most of the lattice is bulk)
         LBMPM_HIP_TRY(hipEventRecord(c->ev_lists, c->stream));
         LBMPM_HIP_TRY(hipStreamWaitEvent(c->stream2, c->ev_lists, 0));
-        if (mrt) { if (c->diag) csf3d_collide_deep<true, true><<<gw, 256, 0, c->stream2>>>(p); else csf3d_collide_deep<true, false><<<gw, 256, 0, c->stream2>>>(p); }
-        else { if (c->diag) csf3d_collide_deep<false, true><<<gw, 256, 0, c->stream2>>>(p); else csf3d_collide_deep<false, false><<<gw, 256, 0, c->stream2>>>(p); }
+        if (tr) {
+            if (mrt) { if (c->diag) csf3d_collide_deep<true, true, true><<<gw, 256, 0, c->stream2>>>(p); else csf3d_collide_deep<true, false, true><<<gw, 256, 0, c->stream2>>>(p); }
+            else { if (c->diag) csf3d_collide_deep<false, true, true><<<gw, 256, 0, c->stream2>>>(p); else csf3d_collide_deep<false, false, true><<<gw, 256, 0, c->stream2>>>(p); }
+        } else {
+            if (mrt) { if (c->diag) csf3d_collide_deep<true, true, false><<<gw, 256, 0, c->stream2>>>(p); else csf3d_collide_deep<true, false, false><<<gw, 256, 0, c->stream2>>>(p); }
+            else { if (c->diag) csf3d_collide_deep<false, true, false><<<gw, 256, 0, c->stream2>>>(p); else csf3d_collide_deep<false, false, false><<<gw, 256, 0, c->stream2>>>(p); }
+        }
         LBMPM_HIP_TRY(hipEventRecord(c->ev_deep, c->stream2));
     }
     if (stages & 1) csf3d_phase<FIRST><<<gw, 256, 0, c->stream>>>(p);
@@ -1107,9 +1158,16 @@ int launch_step(lbmpm_rk3dcsf *c, const CsfDev &p, hipEvent_t e0, hipEvent_t e1,
         csf3d_gradient<<<gw, 256, 0, c->stream>>>(p);
     }
     if (stages & 4) {
-        if (mrt) { if (c->diag) csf3d_collide<FIRST, true, true><<<gw, 256, 0, c->stream>>>(p); else csf3d_collide<FIRST, true, false><<<gw, 256, 0, c->stream>>>(p); }
-        else { if (c->diag) csf3d_collide<FIRST, false, true><<<gw, 256, 0, c->stream>>>(p); else csf3d_collide<FIRST, false, false><<<gw, 256, 0, c->stream>>>(p); }
+        if (tr) {
+            if (mrt) { if (c->diag) csf3d_collide<FIRST, true, true, true><<<gw, 256, 0, c->stream>>>(p); else csf3d_collide<FIRST, true, false, true><<<gw, 256, 0, c->stream>>>(p); }
+            else { if (c->diag) csf3d_collide<FIRST, false, true, true><<<gw, 256, 0, c->stream>>>(p); else csf3d_collide<FIRST, false, false, true><<<gw, 256, 0, c->stream>>>(p); }
+        } else {
+            if (mrt) { if (c->diag) csf3d_collide<FIRST, true, true, false><<<gw, 256, 0, c->stream>>>(p); else csf3d_collide<FIRST, true, false, false><<<gw, 256, 0, c->stream>>>(p); }
+            else { if (c->diag) csf3d_collide<FIRST, false, true, false><<<gw, 256, 0, c->stream>>>(p); else csf3d_collide<FIRST, false, false, false><<<gw, 256, 0, c->stream>>>(p); }
+        }
         if (deep_launch) LBMPM_HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_deep, 0));
+        // the tracers' sub-step of this flow step: rho_R, u as both collisions left them, G of csf3d_gradient (rk3d_tracer.h)
+        if (tr) { const int rc = launch_tracers(c, p, g); if (rc != LBMPM_OK) return rc; }
     }
     if (e1) LBMPM_HIP_TRY(hipEventRecord(e1, c->stream));
     LBMPM_HIP_TRY(hipGetLastError());
@@ -1153,7 +1211,7 @@ extern "C" void lbmpm_rk3dcsf_destroy(lbmpm_rk3dcsf *c)
     if (c->beat_host) (void)hipHostFree(c->beat_host);
     if (c->wd_stream) (void)hipStreamDestroy(c->wd_stream);
     c->slab_pool.destroy();
-    void *ptrs[] = {c->wethome, c->rng, c->pfx, c->pure, c->deep_prev, c->bcblk, c->deep_now, c->work, c->tcnt, c->src, c->dom, c->meta, c->wetlist, c->cidx, c->cells, c->fA, c->fB, c->phi, c->G, c->nh, c->F, c->K, c->U, c->ns, c->obs};
+    void *ptrs[] = {c->gA, c->gB, c->trflow, c->trsrc, c->wethome, c->rng, c->pfx, c->pure, c->deep_prev, c->bcblk, c->deep_now, c->work, c->tcnt, c->src, c->dom, c->meta, c->wetlist, c->cidx, c->cells, c->fA, c->fB, c->phi, c->G, c->nh, c->F, c->K, c->U, c->ns, c->obs};
     for (void *q : ptrs) if (q) (void)hipFree(q);
     c->pool.destroy();
     if (c->ev_lists) (void)hipEventDestroy(c->ev_lists);
@@ -2073,4 +2131,134 @@ extern "C" int lbmpm_rk3dcsf_sync_deadline(lbmpm_rk3dcsf *c, double seconds)
                                              "no in-library transport is connected: nothing was released",
               (int)c->cfg.slab_z0, own_z1(c) - 1, c->nzg);
     return LBMPM_ERR_TIMEOUT;
+}
+
+// ---- D3Q7 tracers advected by the CSF flow (include/lbmpm.h, end of the CSF block; kernels: rk3d_tracer.h)
+namespace {
+// I - S^-1 with S = 1/2 I + 3 D (the flux block of Transport2DRK.py:313-347 on three axes); false when S is singular
+bool tracer_flux_matrix(const double D[9], double B[9])
+{
+    double S[9];
+    for (int a = 0; a < 9; ++a) S[a] = 3. * D[a] + (a % 4 == 0 ? 0.5 : 0.);
+    const double det = S[0] * (S[4] * S[8] - S[5] * S[7]) - S[1] * (S[3] * S[8] - S[5] * S[6]) + S[2] * (S[3] * S[7] - S[4] * S[6]);
+    if (!(fabs(det) > 1.0e-300)) return false;
+    const double R[9] = {(S[4] * S[8] - S[5] * S[7]) / det, (S[2] * S[7] - S[1] * S[8]) / det, (S[1] * S[5] - S[2] * S[4]) / det,
+                         (S[5] * S[6] - S[3] * S[8]) / det, (S[0] * S[8] - S[2] * S[6]) / det, (S[2] * S[3] - S[0] * S[5]) / det,
+                         (S[3] * S[7] - S[4] * S[6]) / det, (S[1] * S[6] - S[0] * S[7]) / det, (S[0] * S[4] - S[1] * S[3]) / det};
+    for (int a = 0; a < 9; ++a) B[a] = (a % 4 == 0 ? 1. : 0.) - R[a];
+    return true;
+}
+int tracer_ready(const lbmpm_rk3dcsf *c, int tracer, const char *who)
+{
+    if (!c->ntr) { set_error("%s before lbmpm_rk3dcsf_tracer_configure", who); return LBMPM_ERR_STATE; }
+    if (tracer < 0 || tracer >= c->ntr) { set_error("%s: tracer %d of %d", who, tracer, c->ntr); return LBMPM_ERR_INVALID; }
+    return LBMPM_OK;
+}
+}  // namespace
+
+extern "C" int lbmpm_rk3dcsf_tracer_configure(lbmpm_rk3dcsf *c, const lbmpm_tracer3d_config *k)
+{
+    LBMPM_REQUIRE(c && k, "lbmpm_rk3dcsf_tracer_configure: null argument");
+    if (c->cfg.ghost_lo || c->cfg.ghost_hi) {
+        set_error("lbmpm_rk3dcsf_tracer_configure: tracers on z-slabs are not built (a context with ghost planes; the slabs' face messages carry no tracer populations): "
+                  "run the tracers on the undivided lattice");
+        return LBMPM_ERR_UNSUPPORTED;
+    }
+    LBMPM_REQUIRE(k->num_tracers >= 1 && k->num_tracers <= 4, "lbmpm_rk3dcsf_tracer_configure: NumberTracers %d, 1 .. 4 are built", (int)k->num_tracers);
+    LBMPM_REQUIRE(k->reaction_rate == 0. || k->num_tracers == 3, "lbmpm_rk3dcsf_tracer_configure: the reaction A + B -> C couples exactly three tracers, not %d", (int)k->num_tracers);
+    if (c->steps > 0 || !c->first) { set_error("lbmpm_rk3dcsf_tracer_configure after stepping: configure the tracers before the first step"); return LBMPM_ERR_STATE; }
+    if (c->ntr) { set_error("lbmpm_rk3dcsf_tracer_configure: the tracers of this context are configured already"); return LBMPM_ERR_STATE; }
+    double B[4][9];
+    for (int t = 0; t < k->num_tracers; ++t) {
+        const double D[9] = {k->diffusion_x[t], k->diffusion_xy, k->diffusion_xz, k->diffusion_yx, k->diffusion_y[t], k->diffusion_yz, k->diffusion_zx, k->diffusion_zy, k->diffusion_z[t]};
+        LBMPM_REQUIRE(tracer_flux_matrix(D, B[t]), "lbmpm_rk3dcsf_tracer_configure: 1/2 I + 3 D of tracer %d is singular", t);
+    }
+    LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
+    const size_t per = (size_t)k->num_tracers * TQ * c->FS;
+    const int64_t bytes_before = c->bytes;
+    int rc = dev_alloc(c, &c->gA, per);
+    if (rc == LBMPM_OK) rc = dev_alloc(c, &c->gB, per);
+    if (rc == LBMPM_OK) rc = dev_alloc(c, &c->trflow, 4 * c->FS);
+    if (rc == LBMPM_OK && !c->src) rc = dev_alloc(c, &c->trsrc, 6 * c->FS);
+    if (rc != LBMPM_OK) {                        // all or nothing: a later configure starts from scratch
+        for (double **q : {&c->gA, &c->gB, &c->trflow}) if (*q) { (void)hipFree(*q); *q = nullptr; }
+        if (c->trsrc) { (void)hipFree(c->trsrc); c->trsrc = nullptr; }
+        c->bytes = bytes_before;
+        return rc;
+    }
+    LBMPM_HIP_TRY(hipMemsetAsync(c->gA, 0, per * sizeof(double), c->stream));
+    LBMPM_HIP_TRY(hipMemsetAsync(c->gB, 0, per * sizeof(double), c->stream));
+    LBMPM_HIP_TRY(hipMemsetAsync(c->trflow, 0, 4 * c->FS * sizeof(double), c->stream));
+    if (c->trsrc) {
+        tr3d_setup_src<<<blocks_of((size_t)c->nfluid), 256, 0, c->stream>>>(make_dev(c), c->trsrc);
+        LBMPM_HIP_TRY(hipGetLastError());
+    }
+    LBMPM_HIP_TRY(hipStreamSynchronize(c->stream));
+    c->trcfg = *k;
+    for (int t = 0; t < 4; ++t) for (int a = 0; a < 9; ++a) c->trB[t][a] = t < k->num_tracers ? B[t][a] : 0.;
+    c->ntr = k->num_tracers;
+    c->tr_first = true;
+    return LBMPM_OK;
+}
+
+static int tracer_import(lbmpm_rk3dcsf *c, int tracer, const double *conc, const double *pdf, const char *who)
+{
+    { const int rc = tracer_ready(c, tracer, who); if (rc) return rc; }
+    LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
+    const size_t count = conc ? c->N : c->N * TQ;
+    double *st = nullptr;
+    LBMPM_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&st), count * sizeof(double)));
+    int rc = upload(c, st, conc ? conc : pdf, count);
+    if (rc == LBMPM_OK) {
+        tr3d_import<<<blocks_of(c->N), 256, 0, c->stream>>>(make_dev(c), c->gA + (size_t)tracer * TQ * c->FS, conc ? st : nullptr, conc ? nullptr : st);
+        if (hipGetLastError() != hipSuccess) { set_error("tr3d_import did not launch"); rc = LBMPM_ERR_HIP; }
+    }
+    (void)hipStreamSynchronize(c->stream);
+    (void)hipFree(st);
+    return rc;
+}
+
+extern "C" int lbmpm_rk3dcsf_tracer_set_concentration(lbmpm_rk3dcsf *c, int tracer, const double *conc)
+{
+    LBMPM_REQUIRE(c && conc, "lbmpm_rk3dcsf_tracer_set_concentration: null argument");
+    if (c->ntr && !c->tr_first) { set_error("lbmpm_rk3dcsf_tracer_set_concentration after stepping: the tracers' state is given before the first step"); return LBMPM_ERR_STATE; }
+    return tracer_import(c, tracer, conc, nullptr, "lbmpm_rk3dcsf_tracer_set_concentration");
+}
+
+extern "C" int lbmpm_rk3dcsf_tracer_set_pdf(lbmpm_rk3dcsf *c, int tracer, const double *pdf)
+{
+    LBMPM_REQUIRE(c && pdf, "lbmpm_rk3dcsf_tracer_set_pdf: null argument");
+    if (c->ntr && !c->tr_first) { set_error("lbmpm_rk3dcsf_tracer_set_pdf after stepping: the tracers' state is given before the first step"); return LBMPM_ERR_STATE; }
+    return tracer_import(c, tracer, nullptr, pdf, "lbmpm_rk3dcsf_tracer_set_pdf");
+}
+
+static int tracer_observe(lbmpm_rk3dcsf *c, int tracer, double *conc, double *pdf, const char *who)
+{
+    { const int rc = tracer_ready(c, tracer, who); if (rc) return rc; }
+    LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
+    double *st = nullptr;                        // [N] + [N][7], for the length of the call
+    LBMPM_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&st), c->N * (pdf ? 1 + TQ : 1) * sizeof(double)));
+    const CsfDev p = make_dev(c);
+    const TrDev t = make_trdev(c);
+    if (c->tr_first) tr3d_observe<true><<<blocks_of(c->N), 256, 0, c->stream>>>(p, t, tracer, pdf ? st + c->N : nullptr, st);
+    else tr3d_observe<false><<<blocks_of(c->N), 256, 0, c->stream>>>(p, t, tracer, pdf ? st + c->N : nullptr, st);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess && conc) e = hipMemcpy(conc, st, c->N * sizeof(double), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && pdf) e = hipMemcpy(pdf, st + c->N, c->N * TQ * sizeof(double), hipMemcpyDeviceToHost);
+    (void)hipFree(st);
+    if (e != hipSuccess) { set_error("%s failed: %s", who, hipGetErrorString(e)); return LBMPM_ERR_HIP; }
+    return LBMPM_OK;
+}
+
+extern "C" int lbmpm_rk3dcsf_tracer_get_concentration(lbmpm_rk3dcsf *c, int tracer, double *out)
+{
+    LBMPM_REQUIRE(c && out, "lbmpm_rk3dcsf_tracer_get_concentration: null argument");
+    return tracer_observe(c, tracer, out, nullptr, "lbmpm_rk3dcsf_tracer_get_concentration");
+}
+
+extern "C" int lbmpm_rk3dcsf_tracer_get_pdf(lbmpm_rk3dcsf *c, int tracer, double *out)
+{
+    LBMPM_REQUIRE(c && out, "lbmpm_rk3dcsf_tracer_get_pdf: null argument");
+    return tracer_observe(c, tracer, nullptr, out, "lbmpm_rk3dcsf_tracer_get_pdf");
 }

@@ -206,6 +206,64 @@ class RK3DCSFSolver:
         check(self._L.lbmpm_rk3dcsf_slab_timing(self._h, out), "lbmpm_rk3dcsf_slab_timing")
         return dict(stage_ms=list(out[0:3]), message_ms=list(out[3:6]), messages=["phi", "normal", "populations"], steps=int(out[6]))
 
+    # ---- D3Q7 tracers advected by the flow (lbmpm_rk3dcsf_tracer_*; undivided lattices only)
+    def configure_tracers(self, num_tracers=1, diffusion_x=1. / 6., diffusion_y=None, diffusion_z=None, diffusion_xy=0., diffusion_yx=0.,
+                          diffusion_xz=0., diffusion_zx=0., diffusion_yz=0., diffusion_zy=0., beta_interface=0., criteria_rho=0.5,
+                          inlet_concentration=0., dirichlet_inlet=False, free_outlet=False, reaction_rate=0., diffusion_j=0.):
+        """Before the first step.  Per-tracer entries are a number or a sequence of num_tracers numbers; diffusion_y, diffusion_z default
+        to diffusion_x.  diffusion_j is the rest weight J0' of the reaction source on the D3Q7 lattice ((3 J0 - 1) / 2 of the 2-D file's J0:
+        config.read_transport3d maps it).  The tracer sub-step runs after the flow's collision with rho_R, u and G of that flow step."""
+        from ._lib import Tracer3DConfig
+        nT = int(num_tracers)
+        cfg = Tracer3DConfig()
+        cfg.num_tracers = nT
+
+        def per(v, what):
+            a = np.broadcast_to(np.asarray(v, dtype=np.float64), (max(min(nT, 4), 1),)) if np.ndim(v) == 0 else np.asarray(v, dtype=np.float64)
+            if a.shape[0] < min(nT, 4):
+                raise ValueError("%s: %d entries for %d tracers" % (what, a.shape[0], nT))
+            return a
+        dy = diffusion_x if diffusion_y is None else diffusion_y
+        dz = diffusion_x if diffusion_z is None else diffusion_z
+        for name, v in (("diffusion_x", diffusion_x), ("diffusion_y", dy), ("diffusion_z", dz), ("beta_interface", beta_interface),
+                        ("inlet_concentration", inlet_concentration), ("diffusion_j", diffusion_j)):
+            a = per(v, name)
+            for t in range(min(nT, 4)):
+                getattr(cfg, name)[t] = float(a[t])
+        cfg.diffusion_xy, cfg.diffusion_yx, cfg.diffusion_xz = float(diffusion_xy), float(diffusion_yx), float(diffusion_xz)
+        cfg.diffusion_zx, cfg.diffusion_yz, cfg.diffusion_zy = float(diffusion_zx), float(diffusion_yz), float(diffusion_zy)
+        cfg.criteria_rho = float(criteria_rho)
+        cfg.dirichlet_inlet, cfg.free_outlet = int(bool(dirichlet_inlet)), int(bool(free_outlet))
+        cfg.reaction_rate = float(reaction_rate)
+        check(self._L.lbmpm_rk3dcsf_tracer_configure(self._h, C.byref(cfg)), "lbmpm_rk3dcsf_tracer_configure")
+        self.num_tracers = nT
+
+    def set_concentration(self, t, conc):
+        """dense [nz][ny][nx]; g_i = C w_i; before the first step"""
+        self._keep = []
+        ptr = self._ptr(conc, self.shape, "concentration")
+        check(self._L.lbmpm_rk3dcsf_tracer_set_concentration(self._h, int(t), ptr), "lbmpm_rk3dcsf_tracer_set_concentration")
+        self._keep = []
+
+    def get_concentration(self, t):
+        """the concentration the reference records after the last completed step, [nz][ny][nx] (zeros off the fluid)"""
+        out = np.empty(self.shape, dtype=np.float64)
+        check(self._L.lbmpm_rk3dcsf_tracer_get_concentration(self._h, int(t), out.ctypes.data_as(F64P)), "lbmpm_rk3dcsf_tracer_get_concentration")
+        return out
+
+    def get_tracer_pdf(self, t):
+        """the populations behind get_concentration, [nz][ny][nx][7] in the order rest, +x, -x, +y, -y, +z, -z"""
+        out = np.empty(self.shape + (7,), dtype=np.float64)
+        check(self._L.lbmpm_rk3dcsf_tracer_get_pdf(self._h, int(t), out.ctypes.data_as(F64P)), "lbmpm_rk3dcsf_tracer_get_pdf")
+        return out
+
+    def set_tracer_pdf(self, t, g):
+        """the restart: populations as get_tracer_pdf returns them, together with set_pdf of the flow"""
+        self._keep = []
+        ptr = self._ptr(g, self.shape + (7,), "tracer populations")
+        check(self._L.lbmpm_rk3dcsf_tracer_set_pdf(self._h, int(t), ptr), "lbmpm_rk3dcsf_tracer_set_pdf")
+        self._keep = []
+
     def get(self, name):
         out = np.empty(self.shape + ((19,) if name in _PDF_FIELDS else ()), dtype=np.float64)
         check(self._L.lbmpm_rk3dcsf_get_field(self._h, FIELDS[name], out.ctypes.data_as(F64P)), "get_field(%s)" % name)
@@ -302,6 +360,12 @@ class RK3DCSFCluster:
         for s, g in zip(self.slabs, self.geo):
             s.set_pdf(g.cut(np.asarray(fR)), g.cut(np.asarray(fB)), None if force is None else tuple(g.cut(np.asarray(c)) for c in force))
 
+    def configure_tracers(self, *args, **kwargs):
+        """tracers on z-slabs are not built: the face messages carry no tracer populations"""
+        raise _lib.LbmpmError("tracers on z-slabs are not built (%s): run them on RK3DCSFSolver, the undivided lattice" % type(self).__name__, _lib.ERR_UNSUPPORTED)
+
+    set_concentration = get_concentration = get_tracer_pdf = set_tracer_pdf = configure_tracers
+
     def _exchange(self, msg):
         n = len(self.slabs)
         for k in range(n):                         # a ring: the last slab's high face is the first slab's low face
@@ -396,6 +460,12 @@ class RK3DCSFDistributed:
         self.deadline_s = float(os.environ.get("LBMPM_SLAB_DEADLINE_S", "120"))      # the watchdog of sync() in library mode
         if self.world > 1 and want != "torch":
             self._connect(want)
+
+    def configure_tracers(self, *args, **kwargs):
+        """tracers on z-slabs are not built: the face messages carry no tracer populations"""
+        raise _lib.LbmpmError("tracers on z-slabs are not built (%s): run them on RK3DCSFSolver, the undivided lattice" % type(self).__name__, _lib.ERR_UNSUPPORTED)
+
+    set_concentration = get_concentration = get_tracer_pdf = set_tracer_pdf = configure_tracers
 
     def _agree(self, ok):
         """True when every rank says ok (a collective on host objects: works on every backend)"""

@@ -1,0 +1,327 @@
+"""D3Q7 tracers advected by the 3-D CSF flow on the GPU (lbmpm_rk3dcsf_tracer_*, csrc/rk3d_tracer.h) through the C ABI.
+
+* against the CPU restatement tests/tr3d_ref.py (pinned by reduction to the 2-D oracle, tests/test_tr3d_ref.py) on fully 3-D lattices:
+  concentration and populations, 1e-10 field-relative -- the tolerance tests/test_rk3d_csf_gpu.py holds the 3-D flow to;
+* the reduction itself through the HIP kernels: a y-uniform lattice against the 2-D oracle composition (1e-9);
+* the bulk skip stays exact, the flow is untouched, the restart is bit for bit, the tracer is conserved, a Gaussian blob spreads as 2 D t;
+* the refusals."""
+import numpy as np
+import pytest
+
+from helpers import rel_err
+from tr3d_ref import Coupled3DRef, project_g
+
+pytestmark = pytest.mark.gpu
+
+TOL = 1e-10          # (measured over the 20 cases and 200 steps: 6e-15 at worst)
+CRISP = 2.0 ** -51           # the library's "one colour alone" rule, which the flow oracle can follow (tests/test_rk3d_csf_gpu.py)
+
+
+def solver(dom, par, **kw):
+    from openlbmpm_amd.rk3dcsf import RK3DCSFSolver
+    return RK3DCSFSolver(dom, par, **kw)
+
+
+def tracer_case(nT, reaction=True, **over):
+    """(keyword arguments of RK3DCSFSolver.configure_tracers, the same case for tests/tr3d_ref.py)"""
+    dx, dy, dz = (1. / 6., 0.1, 0.2, 0.15)[:nT], (0.12, 0.1, 0.15, 0.2)[:nT], (0.2, 0.08, 0.1, 0.12)[:nT]
+    k = dict(num_tracers=nT, diffusion_x=dx, diffusion_y=dy, diffusion_z=dz, diffusion_xy=0.01, diffusion_yx=-0.02, diffusion_xz=0.03, diffusion_zx=0.015,
+             diffusion_yz=-0.01, diffusion_zy=0.02, beta_interface=(1.0, 0.5, 0.0, 0.8)[:nT], criteria_rho=0.5, inlet_concentration=(0.8, 0.4, 0.0, 0.2)[:nT],
+             dirichlet_inlet=True, free_outlet=True, reaction_rate=0.03 if (nT == 3 and reaction) else 0.0, diffusion_j=(0.0, 0.25, 0.1, 0.0)[:nT])
+    k.update(over)
+    r = dict(diffX=k["diffusion_x"], diffY=k["diffusion_y"], diffZ=k["diffusion_z"], dXY=k["diffusion_xy"], dYX=k["diffusion_yx"], dXZ=k["diffusion_xz"],
+             dZX=k["diffusion_zx"], dYZ=k["diffusion_yz"], dZY=k["diffusion_zy"], beta=k["beta_interface"], crit=k["criteria_rho"],
+             inlet_conc=k["inlet_concentration"], free_outlet=k["free_outlet"], dirichlet_inlet=k["dirichlet_inlet"], reaction_rate=k["reaction_rate"],
+             diffJ=k["diffusion_j"])
+    return k, r
+
+
+def concentrations(dom, nT):
+    nz, ny, nx = dom.shape
+    zz, yy, xx = np.mgrid[0:nz, 0:ny, 0:nx]
+    return np.array([(0.5 + 0.3 * np.sin(2 * np.pi * (xx + 2 * k) / nx) * np.cos(2 * np.pi * (yy + k) / ny) * np.cos(2 * np.pi * (zz + 3 * k) / nz)) * (dom == 1)
+                     for k in range(nT)])
+
+
+def obstacle_box():
+    """a box with an obstacle with wetting walls and a slanted wall piece (the sample without symmetry of the flow's tests)"""
+    from test_oracle_rk3d_csf import blob3
+    return blob3()
+
+
+def porous_box():
+    from openlbmpm_amd.geometry import porous_spheres, initial_densities_rk3d
+    dom = porous_spheres(32, 20, 36, porosity=0.7, rmin=3.0, rmax=6.0, seed=7, nbuf=5)
+    dom[0] = dom[1]; dom[-1] = dom[-2]
+    rR, rB = initial_densities_rk3d(dom, 12)
+    return dom, rR, rB
+
+
+def odd_nx_box():
+    from test_oracle_rk3d_csf import blob3
+    return blob3(nx=17, ny=10, nz=24)
+
+
+LATTICES = {"obstacle": obstacle_box, "porous": porous_box, "odd nx": odd_nx_box}
+FLOWS = {
+    "SRT": dict(relax="SRT"), "MRT": dict(relax="MRT"),
+    "SRT tau type 1": dict(relax="SRT", tautype=1, tauB=0.65), "MRT tau type 1": dict(relax="MRT", tautype=1, tauB=0.7),
+    "SRT pressure inlet": dict(relax="SRT", inlet="Dirichlet"), "MRT pressure inlet": dict(relax="MRT", inlet="Dirichlet"),
+}
+CASES = [("obstacle", f, n) for f in sorted(FLOWS) for n in (1, 3)] + [(l, f, n) for l in ("porous", "odd nx") for f in ("SRT", "MRT") for n in (1, 3)]
+STEPS = 200
+
+
+def compare_tracers(s, o, fl, nT, what):
+    worst = 0.0
+    for k in range(nT):
+        c, g = s.get_concentration(k), s.get_tracer_pdf(k)
+        assert np.all(c[~fl] == 0.0) and np.all(g[~fl] == 0.0)
+        ec = rel_err(c[fl], o.C[k][fl])
+        eg = rel_err(np.moveaxis(g, -1, 0)[:, fl], o.g[k][:, fl])
+        print("%s: tracer %d concentration %.3e populations %.3e" % (what, k, ec, eg))
+        assert ec < TOL and eg < TOL, (what, k, ec, eg)
+        worst = max(worst, ec, eg)
+    return worst
+
+
+@pytest.mark.parametrize("lattice,flow,nT", CASES)
+def test_against_the_restatement(lattice, flow, nT):
+    dom, rR, rB = LATTICES[lattice]()
+    par = dict(theta=50.0, tauB=0.8, velocityZR=0.0, velocityZB=-1.0e-2, sigma=0.05); par.update(FLOWS[flow])
+    kw, ref = tracer_case(nT)
+    c0 = concentrations(dom, nT)
+    s = solver(dom, par)
+    s.configure_tracers(**kw)
+    s.set_macro(rR, rB)
+    for k in range(nT):
+        s.set_concentration(k, c0[k])
+    o = Coupled3DRef(dom, rR, rB, c0, dict(par, crisp=CRISP), ref)
+    fl = dom == 1
+    phi0 = s.get("rec_phi")
+    for n in (1, 2, STEPS):
+        s.step(n - s.steps_done); o.run(n - o.steps)
+        compare_tracers(s, o, fl, nT, "%s, %s, %d tracers, step %d" % (lattice, flow, nT, n))
+    assert np.max(np.abs(s.get("rec_phi") - phi0)) > 0.5          # the interface has moved
+    assert all(np.max(np.abs(o.C[k] - c0[k])) > 1e-2 for k in range(nT))
+    s.close()
+
+
+@pytest.mark.parametrize("name", ["one tracer", "three tracers with the reaction", "anisotropic D with off-diagonals", "free outlet and Dirichlet inlet"])
+def test_reduces_to_the_2d_oracle_through_the_kernels(name):
+    """a lattice uniform in y against the 2-D composition rk_csf_step_a -> tr_substep -> rk_csf_step_b of tests/test_tr3d_ref.py"""
+    import test_tr3d_ref as R
+    ny = 4
+    dom2, o2, o3 = R.setup(name, ny=ny)
+    t = o3.tr.t
+    nT = o3.tr.nT
+    s = solver(R.extrude(dom2, ny), {k: v for k, v in o3.flow.p.items() if k != "crisp"})
+    s.configure_tracers(num_tracers=nT, diffusion_x=t["diffX"], diffusion_y=t["diffY"], diffusion_z=t["diffZ"], diffusion_xz=t["dXZ"], diffusion_zx=t["dZX"],
+                        beta_interface=t["beta"], criteria_rho=t["crit"], inlet_concentration=t["inlet_conc"], dirichlet_inlet=t["dirichlet_inlet"],
+                        free_outlet=t["free_outlet"], reaction_rate=t["reaction_rate"], diffusion_j=t["diffJ"] or 0.0)
+    f = o3.flow
+    s.set_macro(f.field("rhoR"), f.field("rhoB"))
+    for k in range(nT):
+        s.set_concentration(k, o3.C[k])
+    fl = dom2 == 1
+    worst = 0.0
+    for n in range(1, R.STEPS + 1):
+        R.step2(o2)
+        if n in (1, 2, 3, 10, 30, R.STEPS):
+            s.step(n - s.steps_done)
+            for k in range(nT):
+                c, g = s.get_concentration(k), np.moveaxis(s.get_tracer_pdf(k), -1, 0)
+                assert np.max(np.abs(c - c[:, :1, :])) <= 1e-12 * np.max(np.abs(c))
+                worst = max(worst, rel_err(c[:, 0, :][fl], R.dense2(o2, o2.C[k])[fl]), rel_err(project_g(g)[fl], R.dense2(o2, o2.g[k])[fl]))
+    print("%s: worst field-relative difference from the 2-D oracle %.3e" % (name, worst))
+    assert worst < 1e-9, (name, worst)
+    s.close()
+
+
+def front_in_a_duct():
+    from openlbmpm_amd.RKColorGradientD3Q19 import duct
+    dom = duct(34, 30, 120)
+    dom[40:60, 8:20, 10:24] = 0                       # an obstacle with wetting walls inside the red bulk
+    zz = np.mgrid[0:120, 0:30, 0:34][0]
+    fl = dom == 1
+    return dom, np.where(fl & (zz < 84), 1.0, 0.0), np.where(fl & (zz >= 84), 1.0, 0.0)
+
+
+FLOW_FIELDS = ("fR", "fB", "rhoR", "rhoB", "phi", "Gx", "Gy", "Gz", "Fx", "Fy", "Fz", "rec_vz", "rec_phi")
+
+
+@pytest.mark.parametrize("relax", ["MRT", "SRT"])
+def test_the_bulk_skip_stays_exact_with_tracers(relax):
+    """the deep blocks' collision hands rho_R and u to the tracers like the full path's, and G is an exact zero there: variant 0 against the
+    run that sends every cell through the full path (variant 1), bit for bit, flow and concentrations, while a front moves"""
+    dom, rR, rB = front_in_a_duct()
+    par = dict(relax=relax, theta=60.0, tauB=0.8, velocityZR=0.0, velocityZB=-4.0e-3, sigma=0.05)
+    kw, _ = tracer_case(3)
+    c0 = concentrations(dom, 3)
+    a = solver(dom, par); b = solver(dom, dict(par, variant=1))
+    for s in (a, b):
+        s.configure_tracers(**kw); s.set_macro(rR, rB)
+        for k in range(3):
+            s.set_concentration(k, c0[k])
+    seen = []
+    for n in (1, 2, 3, 40, 41, 120):
+        a.step(n - a.steps_done); b.step(n - b.steps_done)
+        seen.append(a.bulk_cells)
+        assert b.bulk_cells == 0
+        for f in FLOW_FIELDS:
+            assert np.array_equal(a.get(f), b.get(f)), (n, f)
+        for k in range(3):
+            assert np.array_equal(a.get_concentration(k), b.get_concentration(k)), (n, k)
+            assert np.array_equal(a.get_tracer_pdf(k), b.get_tracer_pdf(k)), (n, k)
+    assert seen[1] > 0.3 * a.num_fluid_nodes and len(set(seen[1:])) > 1, seen
+    a.close(); b.close()
+
+
+@pytest.mark.parametrize("relax,variant", [("MRT", 0), ("SRT", 0), ("MRT", 1)])
+def test_the_flow_is_untouched(relax, variant):
+    dom, rR, rB = front_in_a_duct()
+    par = dict(relax=relax, theta=60.0, tauB=0.8, velocityZR=0.0, velocityZB=-4.0e-3, sigma=0.05, variant=variant)
+    kw, _ = tracer_case(2)
+    a = solver(dom, par); b = solver(dom, par)
+    a.configure_tracers(**kw)
+    c0 = concentrations(dom, 2)
+    for s in (a, b):
+        s.set_macro(rR, rB)
+    for k in range(2):
+        a.set_concentration(k, c0[k])
+    assert a.device_bytes > b.device_bytes + 2 * 2 * 7 * 8 * a.num_fluid_nodes       # lbmpm_rk3dcsf_device_bytes counts the tracers' buffers
+    for n in (1, 2, 50):
+        a.step(n - a.steps_done); b.step(n - b.steps_done)
+        for f in FLOW_FIELDS:
+            assert np.array_equal(a.get(f), b.get(f)), (n, f)
+    assert a.bulk_cells == b.bulk_cells
+    a.close(); b.close()
+
+
+def test_restart_bit_for_bit():
+    dom, rR, rB = front_in_a_duct()
+    par = dict(relax="MRT", theta=60.0, tauB=0.8, velocityZR=0.0, velocityZB=-4.0e-3, sigma=0.05)
+    kw, _ = tracer_case(3)
+    c0 = concentrations(dom, 3)
+    a = solver(dom, par)
+    a.configure_tracers(**kw); a.set_macro(rR, rB)
+    for k in range(3):
+        a.set_concentration(k, c0[k])
+    a.step(45)
+    c = solver(dom, par)
+    c.configure_tracers(**kw)
+    c.set_pdf(a.get("fR"), a.get("fB"), force=(a.get("Fx"), a.get("Fy"), a.get("Fz")))
+    for k in range(3):
+        c.set_tracer_pdf(k, a.get_tracer_pdf(k))
+    for k in range(3):
+        assert np.array_equal(a.get_concentration(k), c.get_concentration(k))
+    a.step(30); c.step(30)
+    for f in ("fR", "fB", "phi", "Fz"):
+        assert np.array_equal(a.get(f), c.get(f)), f
+    for k in range(3):
+        assert np.array_equal(a.get_tracer_pdf(k), c.get_tracer_pdf(k)), k
+        assert np.array_equal(a.get_concentration(k), c.get_concentration(k)), k
+    a.close(); c.close()
+
+
+@pytest.mark.parametrize("reaction", [False, True])
+def test_conservation(reaction):
+    """no open plane for the tracers (the lattice wraps z as it wraps x and y; walls bounce back): the collision keeps sum_i g_i, the
+    interface term adds cos(e_i, n) over opposite pairs, the streaming moves populations -- sum C over the fluid cells is constant to
+    rounding.  The reaction takes k C_0 C_1 from tracers 0 and 1 and gives it to tracer 2: sum (C_0 - C_1) and sum (C_0 + C_2) stay."""
+    dom, rR, rB = porous_box()
+    par = dict(relax="MRT", theta=50.0, tauB=0.8, velocityZR=0.0, velocityZB=-3.0e-3, sigma=0.05)
+    kw, _ = tracer_case(3, reaction=reaction, dirichlet_inlet=False, free_outlet=False)
+    c0 = concentrations(dom, 3)
+    s = solver(dom, par)
+    s.configure_tracers(**kw); s.set_macro(rR, rB)
+    for k in range(3):
+        s.set_concentration(k, c0[k])
+    total = lambda: np.array([float(np.sum(s.get_concentration(k))) for k in range(3)])
+    t0 = total()
+    s.step(300)
+    t1 = total()
+    print("conservation (reaction %s): totals %s -> %s" % (reaction, t0, t1))
+    # 300 steps of ~ 1e4 cells in double precision: sums of O(1e4) terms each carrying 1e-16 per step
+    if not reaction:
+        assert np.all(np.abs(t1 - t0) < 1e-11 * np.abs(t0)), (t0, t1)
+    else:
+        assert abs((t1[0] - t1[1]) - (t0[0] - t0[1])) < 1e-11 * abs(t0[0]) and abs((t1[0] + t1[2]) - (t0[0] + t0[2])) < 1e-11 * abs(t0[0] + t0[2]), (t0, t1)
+        assert t0[0] - t1[0] > 1e-3 * t0[0]          # the reaction did consume A
+    s.close()
+
+
+def test_a_gaussian_blob_spreads_as_2_d_t():
+    """A Gaussian blob in a uniform single-phase flow along z (all fluid, red alone, plug flow set from the start): its variance grows as
+    2 D t per axis with an anisotropic D, its centre moves with the flow.  Slopes between steps 100 and 300.  Measured on the MI355X:
+    d var / dt off 2 D by 3e-6 (x), 4.5e-4 (y), 3.0e-4 (z), the drift equal to the flow to six digits; the bound is the 2-D test's 0.3 %."""
+    nx, ny, nz = 64, 64, 160
+    dom = np.ones((nz, ny, nx), dtype=np.uint8)
+    U = -0.01
+    D = (0.04, 0.08, 0.12)
+    par = dict(relax="MRT", velocityZR=U, velocityZB=0.0, densityRL=1.0, densityBL=0.0, sigma=0.0)
+    s = solver(dom, par)
+    s.configure_tracers(num_tracers=1, diffusion_x=D[0], diffusion_y=D[1], diffusion_z=D[2], beta_interface=0.0)
+    one = np.ones(dom.shape)
+    s.set_macro(one, 0.0 * one, vz=U * one)
+    zz, yy, xx = np.mgrid[0:nz, 0:ny, 0:nx].astype(np.float64)
+    c0 = (31.5, 31.5, 90.0)
+    s.set_concentration(0, np.exp(-((xx - c0[0]) ** 2 + (yy - c0[1]) ** 2 + (zz - c0[2]) ** 2) / (2. * 16.)))
+
+    def moments():
+        c = s.get_concentration(0)
+        m = c.sum()
+        out = []
+        for a in (xx, yy, zz):
+            mu = (c * a).sum() / m
+            out.append((mu, (c * (a - mu) ** 2).sum() / m))
+        return m, out
+    s.step(100); m1, a1 = moments()
+    s.step(200); m2, a2 = moments()
+    assert abs(m2 - m1) < 1e-10 * m1
+    for ax in range(3):
+        slope = (a2[ax][1] - a1[ax][1]) / 200.
+        err = abs(slope - 2. * D[ax]) / (2. * D[ax])
+        print("axis %d: d var / dt = %.6f, 2 D = %.6f, relative error %.3e" % (ax, slope, 2. * D[ax], err))
+        assert err < 3e-3, (ax, slope)
+    drift = (a2[2][0] - a1[2][0]) / 200.
+    print("drift along z %.6f, flow %.6f" % (drift, U))
+    assert abs(drift - U) < 3e-3 * abs(U)
+    s.close()
+
+
+def test_refusals():
+    from openlbmpm_amd._lib import LbmpmError, ERR_UNSUPPORTED, ERR_INVALID, ERR_STATE
+    from openlbmpm_amd.rk3dcsf import RK3DCSFCluster
+    dom, rR, rB = obstacle_box()
+    s = solver(dom, None)
+    with pytest.raises(LbmpmError) as e:
+        s.get_concentration(0)
+    assert e.value.status == ERR_STATE and "tracer_configure" in str(e.value)
+    with pytest.raises(LbmpmError) as e:
+        s.configure_tracers(num_tracers=5)
+    assert e.value.status == ERR_INVALID and "1 .. 4" in str(e.value)
+    with pytest.raises(LbmpmError) as e:
+        s.configure_tracers(num_tracers=2, reaction_rate=0.1)
+    assert e.value.status == ERR_INVALID and "three tracers" in str(e.value)
+    s.set_macro(rR, rB)
+    s.step(1)
+    with pytest.raises(LbmpmError) as e:
+        s.configure_tracers(num_tracers=1)
+    assert e.value.status == ERR_STATE and "before the first step" in str(e.value)
+    s.close()
+    s = solver(dom, None)
+    s.configure_tracers(num_tracers=1)
+    with pytest.raises(LbmpmError) as e:
+        s.set_concentration(1, rR)
+    assert e.value.status == ERR_INVALID
+    s.close()
+    big = np.concatenate([dom, dom[::-1]], axis=0)
+    cl = RK3DCSFCluster(big, None, nslabs=2)
+    with pytest.raises(LbmpmError) as e:
+        cl.slabs[0].configure_tracers(num_tracers=1)       # a context with ghost planes
+    assert e.value.status == ERR_UNSUPPORTED and "slabs" in str(e.value)
+    with pytest.raises(LbmpmError) as e:
+        cl.configure_tracers(num_tracers=1)
+    assert e.value.status == ERR_UNSUPPORTED and "slabs" in str(e.value)
+    cl.close()
