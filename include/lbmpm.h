@@ -594,7 +594,9 @@ int lbmpm_rk3dcsf_step(lbmpm_rk3dcsf *ctx, int64_t nsteps);          /* undivide
  * LBMPM_CSF_MSG_PHI after stage 0, LBMPM_CSF_MSG_NORMAL after stage 1, LBMPM_CSF_MSG_PDF after stage 2.  face: 0 = low z, 1 = high z. */
 enum { LBMPM_CSF_MSG_PDF = 0, LBMPM_CSF_MSG_PHI = 1, LBMPM_CSF_MSG_NORMAL = 2 };
 int lbmpm_rk3dcsf_stage(lbmpm_rk3dcsf *ctx, int stage);
-/* doubles of a message through that face (0 for the undivided lattice); the two sides of a face must agree (same mask on both) */
+/* doubles of a message through that face (0 for the undivided lattice); the two sides of a face must agree (same mask on both, and the
+ * same number of tracers: LBMPM_CSF_MSG_PDF = ten flow populations per fluid cell of the sender's edge plane, then one D3Q7 population per
+ * tracer and such cell (lbmpm_rk3dcsf_tracer_configure_slab; none without tracers), then the flag bytes of two planes) */
 int64_t lbmpm_rk3dcsf_face_doubles(const lbmpm_rk3dcsf *ctx, int msg, int face);
 /* ... of the message that comes in through that face (the populations travel for the fluid cells of the sender's edge plane only: the
  * plane this context holds an image of, not the one it sends) */
@@ -627,7 +629,12 @@ const char *lbmpm_rk3dcsf_dominant_kernel(const lbmpm_rk3dcsf *ctx);
  * populations below) with weights 0, 1/6 x 6; on a lattice uniform in y it is the reference's D2Q5 scheme with g0 + g(+y) + g(-y) as its rest
  * population.  z is the flow axis (the 2-D model's y): free-flow outlet on plane 0, Inamuro inlet on plane nz-1.
  * The flow itself is unchanged, and a context without tracers launches the kernels it launched before.
- * NOT built: tracers on z-slabs (a context with ghost planes: LBMPM_ERR_UNSUPPORTED) and on the perturbation model (lbmpm_rk3d_*). */
+ * On z-slabs (a context with ghost planes; lbmpm_rk3dcsf_tracer_configure_slab): of all a cell's tracer sub-step reads, one population per
+ * tracer comes from beyond a z-face -- direction +z out of the first ghost plane below, -z out of the one above.  It travels inside
+ * LBMPM_CSF_MSG_PDF behind the ten flow populations: a step keeps its three messages per face, face_doubles(LBMPM_CSF_MSG_PDF, face) grows
+ * by num_tracers x the fluid cells of that plane, the other two messages do not change.  Outlet and inlet are planes 0 and global_nz - 1
+ * of the undivided lattice; the slabs compute what the undivided lattice computes, bit for bit.
+ * NOT built: tracers on the perturbation model (lbmpm_rk3d_*). */
 typedef struct lbmpm_tracer3d_config {
     int32_t num_tracers;            /* [TransportParameters] NumberTracers, 1..4                                     */
     double diffusion_x[4];          /* [TransportMRT] DiffusionX                                                     */
@@ -646,9 +653,17 @@ typedef struct lbmpm_tracer3d_config {
                                        must agree with the 2-D model's J0, (1 - J0) / 4 x 4: J0' = (3 J0 - 1) / 2, so J0 = 1/3 gives 0 */
 } lbmpm_tracer3d_config;
 /* before the first step; LBMPM_ERR_INVALID: more than 4 tracers, a reaction with a tracer count other than 3; LBMPM_ERR_STATE: after
- * stepping; LBMPM_ERR_UNSUPPORTED: a slab */
+ * stepping; LBMPM_ERR_UNSUPPORTED: a slab (lbmpm_rk3dcsf_tracer_configure_slab) */
 int lbmpm_rk3dcsf_tracer_configure(lbmpm_rk3dcsf *ctx, const lbmpm_tracer3d_config *cfg);
-/* dense [nz][ny][nx]; g_i = C w_i; before the first step */
+/* the same for a context with ghost planes.  A call of its own because it changes the size of a message the neighbours must agree on:
+ * call it with the same configuration on EVERY slab of the ring, before lbmpm_rk3dcsf_ipc_init / _rccl_connect (they size the landing
+ * slots and the blob's message sizes) -- a caller who moves LBMPM_CSF_MSG_PDF through buffers of their own sizes them by face_doubles
+ * afterwards.  LBMPM_ERR_INVALID also on an undivided context; LBMPM_ERR_STATE also once a transport is set up.  lbmpm_rk3dcsf_face_copy
+ * and lbmpm_rk3dcsf_ipc_connect refuse neighbours whose tracer counts differ (LBMPM_ERR_INVALID, nothing copied or mapped). */
+int lbmpm_rk3dcsf_tracer_configure_slab(lbmpm_rk3dcsf *ctx, const lbmpm_tracer3d_config *cfg);
+/* The four calls below take / return the context's lattice [nz][ny][nx]: on a slab with its ghost planes, like set_macro / get_field
+ * (ghost planes given: cut from the undivided array, wrapping around its ends; returned: not meaningful, drop them).
+ * dense [nz][ny][nx]; g_i = C w_i; before the first step */
 int lbmpm_rk3dcsf_tracer_set_concentration(lbmpm_rk3dcsf *ctx, int tracer, const double *conc);
 /* the concentration the reference records after the last completed step (streamed, inlet plane applied), dense [nz][ny][nx] */
 int lbmpm_rk3dcsf_tracer_get_concentration(lbmpm_rk3dcsf *ctx, int tracer, double *out);

@@ -43,7 +43,7 @@ GROUPS = (("FluidMacro", "MacroData"), ("FluidPDF", "MicroData"), ("FluidVelocit
 class _CSFSlab:
     """RK3DCSFSolver behind the calls this driver makes on a slab of the perturbation model"""
 
-    def __init__(self, dom, par, device, bulk_epsilon=0.0, distributed=False, transport=None):
+    def __init__(self, dom, par, device, bulk_epsilon=0.0, distributed=False, transport=None, tracers=None):
         from .rk3dcsf import RK3DCSFSolver, RK3DCSFDistributed
         q = dict(sigma=par["sigma"], theta=par["theta"], wetting=par["wetting"], beta=par["beta"], delta=par["delta"], tauR=par["tauR"], tauB=par["tauB"],
                  tautype=par["tautype"], relax=par["relax"], inlet=par["inlet"], outlet=par["outlet"], velocityZR=par["velocityZR"],
@@ -51,7 +51,10 @@ class _CSFSlab:
                  bulk_epsilon=float(bulk_epsilon))
         # distributed: one slab per rank; set_* take the undivided arrays (a slab cuts its planes and the images of its neighbours' out of
         # them), get* return the rank's own planes
-        self.solver = RK3DCSFDistributed(dom, q, device=device, transport=transport) if distributed else RK3DCSFSolver(dom, q, device=device)
+        # tracers (Transport3DRK): the keyword arguments of RK3DCSFSolver.configure_tracers, given at construction -- on slabs they are
+        # part of the population message, which is sized before the transport connects
+        more = {} if tracers is None else dict(tracers=tracers)
+        self.solver = RK3DCSFDistributed(dom, q, device=device, transport=transport, **more) if distributed else RK3DCSFSolver(dom, q, device=device, **more)
         self.step_single, self.sync, self.close = self.solver.step, self.solver.sync, self.solver.close
 
     num_fluid_nodes = property(lambda self: self.solver.num_fluid_nodes)

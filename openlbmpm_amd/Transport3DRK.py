@@ -3,8 +3,10 @@
 The reference couples tracers to its 2-D CSF loop only (RKCG2D/Transport2DRK.py; openlbmpm_amd/Transport2DRK.py is its counterpart
 here).  This is the same coupling on the D3Q19 CSF flow of RKColorGradientD3Q19.py with D3Q7 tracers (include/lbmpm.h,
 lbmpm_rk3dcsf_tracer_*): IniFiles/RKtwophasesetup3D.ini with [SurfaceTension] SurfaceTensionType = 'CSF' for the flow,
-transportsetup.ini (config.read_transport3d: the 2-D file's keys plus the z entries) for the tracers.  One GPU: tracers on z-slabs
-are not built, a run under torchrun is refused.
+transportsetup.ini (config.read_transport3d: the 2-D file's keys plus the z entries) for the tracers.  One GPU, or one z-slab per rank
+under torchrun like the flow's driver (rk3dcsf.RK3DCSFDistributed; csf_transport honoured): the tracers' populations that cross a cut
+ride the flow's population message, rank 0 writes ONE SimulationResultsRK3D.h5 and ONE ConcentrationResults.h5 with the stacked planes,
+the records' verdicts are collective, and a checkpoint (the undivided state, stacked on rank 0) restarts on any number of ranks.
 
 Kept from the 2-D driver: the initial concentration rules with planes in the place of rows (tracer 0 = 1 below the top buffer planes
 for generated geometries, every tracer = 1 in the 10 top planes for voxel geometries; or initial_concentration=[nT][nz][ny][nx]),
@@ -22,14 +24,15 @@ from .results import RecordGuard, ResultFile
 
 
 class _CSFTracerSlab(_CSFSlab):
-    def configure(self, t):
+    def __init__(self, dom, par, t, device, bulk_epsilon=0.0, distributed=False, transport=None):
         n = t["num_tracers"]
         self.num_tracers = n
-        self.solver.configure_tracers(num_tracers=n, diffusion_x=tuple(t["diffX"]), diffusion_y=tuple(t["diffY"]), diffusion_z=tuple(t["diffZ"]),
-                                      diffusion_xy=t["dXY"], diffusion_yx=t["dYX"], diffusion_xz=t["dXZ"], diffusion_zx=t["dZX"],
-                                      diffusion_yz=t["dYZ"], diffusion_zy=t["dZY"], beta_interface=t["beta"], criteria_rho=0.5,
-                                      inlet_concentration=tuple(t["inlet_conc"]), dirichlet_inlet=t["inlet_type"] == "Dirichlet",
-                                      free_outlet=t["outlet_type"] == "Freeflow", reaction_rate=t["reaction_rate"], diffusion_j=tuple(t["diffJ3"]))
+        tracers = dict(num_tracers=n, diffusion_x=tuple(t["diffX"]), diffusion_y=tuple(t["diffY"]), diffusion_z=tuple(t["diffZ"]),
+                       diffusion_xy=t["dXY"], diffusion_yx=t["dYX"], diffusion_xz=t["dXZ"], diffusion_zx=t["dZX"],
+                       diffusion_yz=t["dYZ"], diffusion_zy=t["dZY"], beta_interface=t["beta"], criteria_rho=0.5,
+                       inlet_concentration=tuple(t["inlet_conc"]), dirichlet_inlet=t["inlet_type"] == "Dirichlet",
+                       free_outlet=t["outlet_type"] == "Freeflow", reaction_rate=t["reaction_rate"], diffusion_j=tuple(t["diffJ3"]))
+        _CSFSlab.__init__(self, dom, par, device, bulk_epsilon, distributed=distributed, transport=transport, tracers=tracers)
 
     def get_state(self):
         st, info = _CSFSlab.get_state(self)
@@ -74,13 +77,18 @@ class Transport3DRK(RKColorGradient3D):
         p, t = self.par, self.tr
         if p["tension_type"] != "CSF":
             raise config.ConfigError("the tracers are coupled to the CSF colour-gradient flow: [SurfaceTension] SurfaceTensionType = 'CSF'")
-        if self._distributed():
-            raise config.ConfigError("tracers on z-slabs are not built: run the 3-D transport on one GPU")
         self.initializeDomainBorder()
-        slab = _CSFTracerSlab(self.isDomain, p, self.device, self.csf_bulk_epsilon)
-        slab.configure(t)
+        # distributed: one slab per rank; set_* take the undivided arrays, get* return the rank's own planes, rank 0 writes what it gathers
+        shared = self._distributed()
+        slab = _CSFTracerSlab(self.isDomain, p, t, self.device, self.csf_bulk_epsilon, distributed=shared, transport=self.csf_transport)
         self._slab, self._observe, self._gather = slab, (lambda: None), (lambda a: a)
         self.z0, self.nzl = 0, self.zDomain
+        rank = 0
+        if shared:
+            import torch.distributed as dist
+            rank = dist.get_rank()
+            self.z0, self.nzl = slab.solver.z0, slab.solver.nzl
+            self._gather = slab.solver.gather
         n, done = self.numTracers, 0
         if self.restart_from:
             done, self.records = self._load_checkpoint(slab, 0, self.zDomain)
@@ -90,16 +98,19 @@ class Transport3DRK(RKColorGradient3D):
             self.initializeTransportDomain()
             for k in range(n):
                 slab.solver.set_concentration(k, self.tracerConc[k])
-        flow = ResultFile(self.output_dir, "SimulationResultsRK3D", GROUPS)
-        conc = ResultFile(self.output_dir, "ConcentrationResults", (("TransportMacro", "MacroData"),))
-        self.result_path, self.concentration_path = flow.path, conc.path
-        self._guard = RecordGuard("rk3d+tracers", slab.num_fluid_nodes, getattr(self, "nan_guard", "raise"))
-        tracer_guard = RecordGuard("tracers", slab.num_fluid_nodes, getattr(self, "nan_guard", "raise"))
+        flow = ResultFile(self.output_dir, "SimulationResultsRK3D", GROUPS) if rank == 0 else None
+        conc = ResultFile(self.output_dir, "ConcentrationResults", (("TransportMacro", "MacroData"),)) if rank == 0 else None
+        self.result_path, self.concentration_path = (flow.path, conc.path) if rank == 0 else (None, None)
+        # distributed: every rank checks its own planes, the verdict is collective (all ranks raise together, none is left in an exchange)
+        self._guard = RecordGuard("rk3d+tracers", slab.num_fluid_nodes, getattr(self, "nan_guard", "raise"), collective=shared, device=self.device)
+        tracer_guard = RecordGuard("tracers", slab.num_fluid_nodes, getattr(self, "nan_guard", "raise"), collective=shared, device=self.device)
 
         def record_tracers(k, step):
-            self.tracerConc = np.array([slab.solver.get_concentration(i) for i in range(n)])
+            self.tracerConc = np.array([slab.solver.get_concentration(i) for i in range(n)])      # (distributed: this rank's planes)
             for i in range(n):
-                conc.write("TransportMacro", "TracerConcType%gin%g" % (i, k), self.tracerConc[i])
+                whole = self._gather(self.tracerConc[i])
+                if conc is not None and whole is not None:
+                    conc.write("TransportMacro", "TracerConcType%gin%g" % (i, k), whole)
             tracer_guard(k, step, {"tracer%d" % i: self.tracerConc[i] for i in range(n)}, {"tracer%d" % i: float(self.tracerConc[i].sum()) for i in range(n)})
 
         def maybe_checkpoint():

@@ -3,14 +3,31 @@
     python -m openlbmpm_amd rk  <ini-dir> [--out DIR] [--steps N] [--device D]
     python -m openlbmpm_amd sc  <ini-dir> [--out DIR] [--steps N] [--device D]
     python -m openlbmpm_amd tr  <ini-dir> ...      colour gradient + tracers (RKtwophasesetup2D.ini + transportsetup.ini)
-    python -m openlbmpm_amd tr3d <ini-dir> ...     D3Q19 CSF colour gradient + D3Q7 tracers (RKtwophasesetup3D.ini + transportsetup.ini), one GPU
+    python -m openlbmpm_amd tr3d <ini-dir> ...     D3Q19 CSF colour gradient + D3Q7 tracers (RKtwophasesetup3D.ini + transportsetup.ini); under torchrun: z-slabs
     python -m openlbmpm_amd rk3d <ini-dir> ...     D3Q19 colour gradient (RKtwophasesetup3D.ini); under torchrun: z-slabs, one per GPU
-        [--csf-transport auto|ipc|rccl]           SurfaceTensionType = 'CSF' under torchrun: the slabs' face messages over the library's
+        [--csf-transport auto|ipc|rccl]           rk3d with SurfaceTensionType = 'CSF' and tr3d under torchrun: the slabs' face messages over the library's
                                                   own transports (default: through torch.distributed)
 """
 import argparse
 import sys
 import time
+
+
+def _rank_device(device):
+    """launched by torchrun: one rank per GPU, the process group of LBMPM_DIST_BACKEND (nccl; gloo: several ranks rehearsing on one GPU)"""
+    import os
+    if int(os.environ.get("WORLD_SIZE", "1")) <= 1:
+        return device
+    import torch
+    import torch.distributed as dist
+    device = int(os.environ.get("LOCAL_RANK", "0")) % torch.cuda.device_count()
+    torch.cuda.set_device(device)
+    os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+    if os.environ.get("LBMPM_DIST_BACKEND", "nccl") == "nccl":
+        dist.init_process_group(backend="nccl", device_id=torch.device("cuda", device))
+    else:
+        dist.init_process_group(backend=os.environ["LBMPM_DIST_BACKEND"])
+    return device
 
 
 def main(argv=None):
@@ -22,7 +39,7 @@ def main(argv=None):
     ap.add_argument("--steps", type=int, default=None, help="override the ini's number of time steps")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--csf-transport", choices=["auto", "ipc", "rccl"], default=None,
-                    help="rk3d with SurfaceTensionType = 'CSF' under torchrun: move the slabs' face messages over the library's own transport")
+                    help="rk3d with SurfaceTensionType = 'CSF', tr3d; under torchrun: move the slabs' face messages over the library's own transport")
     a = ap.parse_args(argv)
     t0 = time.time()
     if a.model == "rk":
@@ -33,19 +50,8 @@ def main(argv=None):
         path = sim.runRKColorGradient2D()
         steps, nodes = sim.timeSteps, sim.voidSpace
     elif a.model == "rk3d":
-        import os
         from .RKColorGradientD3Q19 import RKColorGradient3D
-        device = a.device
-        if int(os.environ.get("WORLD_SIZE", "1")) > 1:          # launched by torchrun: one rank per GPU
-            import torch
-            import torch.distributed as dist
-            device = int(os.environ.get("LOCAL_RANK", "0")) % torch.cuda.device_count()
-            torch.cuda.set_device(device)
-            os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-            if os.environ.get("LBMPM_DIST_BACKEND", "nccl") == "nccl":
-                dist.init_process_group(backend="nccl", device_id=torch.device("cuda", device))
-            else:                                                # "gloo": several ranks rehearsing on one GPU
-                dist.init_process_group(backend=os.environ["LBMPM_DIST_BACKEND"])
+        device = _rank_device(a.device)
         sim = RKColorGradient3D(a.ini_dir, output_dir=a.out, device=device, csf_transport=a.csf_transport)
         if a.steps is not None:
             sim.timeSteps = a.steps
@@ -53,10 +59,10 @@ def main(argv=None):
         steps, nodes = sim.timeSteps, sim.voidSpace
     elif a.model == "tr3d":
         from .Transport3DRK import Transport3DRK
-        sim = Transport3DRK(a.ini_dir, output_dir=a.out, device=a.device)
+        sim = Transport3DRK(a.ini_dir, output_dir=a.out, device=_rank_device(a.device), csf_transport=a.csf_transport)
         if a.steps is not None:
             sim.timeSteps = a.steps
-        path = " and ".join(sim.runTransport3DMPMCRK())
+        path = " and ".join(str(f) for f in sim.runTransport3DMPMCRK())        # (under torchrun rank 0 writes both files)
         steps, nodes = sim.timeSteps, sim.voidSpace
     elif a.model == "tr":
         from .Transport2DRK import Transport2DRK

@@ -202,6 +202,7 @@ _SIGNATURES = {
     "lbmpm_rk3dcsf_device_bytes": (C.c_int64, [C.c_void_p]),
     "lbmpm_rk3dcsf_dominant_kernel": (C.c_char_p, [C.c_void_p]),
     "lbmpm_rk3dcsf_tracer_configure": (C.c_int, [C.c_void_p, C.POINTER(Tracer3DConfig)]),
+    "lbmpm_rk3dcsf_tracer_configure_slab": (C.c_int, [C.c_void_p, C.POINTER(Tracer3DConfig)]),
     "lbmpm_rk3dcsf_tracer_set_concentration": (C.c_int, [C.c_void_p, C.c_int, F64P]),
     "lbmpm_rk3dcsf_tracer_get_concentration": (C.c_int, [C.c_void_p, C.c_int, F64P]),
     "lbmpm_rk3dcsf_tracer_get_pdf": (C.c_int, [C.c_void_p, C.c_int, F64P]),

@@ -679,7 +679,8 @@ __global__ __launch_bounds__(256) void csf3d_face_flags(const uint8_t *flags, co
 }
 
 // the runs of a face message in one launch (blockIdx.y = the run)
-struct RunSet { const double *src[10]; double *dst[10]; unsigned count[10]; };
+constexpr int MAX_RUNS = 14;        // ten of the flow + one per tracer
+struct RunSet { const double *src[MAX_RUNS]; double *dst[MAX_RUNS]; unsigned count[MAX_RUNS]; };
 __global__ __launch_bounds__(256) void csf3d_copy_runs(RunSet r)
 {
     const unsigned k = blockIdx.y, n = r.count[k];
@@ -1109,13 +1110,11 @@ TrDev make_trdev(const lbmpm_rk3dcsf *c)
 int launch_tracers(lbmpm_rk3dcsf *c, const CsfDev &p, unsigned g)
 {
     const TrDev t = make_trdev(c);
-#define TR3D_GO(NT) do { if (c->tr_first) tr3d_step<true, NT><<<g, 256, 0, c->stream>>>(p, t); else tr3d_step<false, NT><<<g, 256, 0, c->stream>>>(p, t); } while (0)
-    switch (c->ntr) {
-    case 1: TR3D_GO(1); break;
-    case 2: TR3D_GO(2); break;
-    case 3: TR3D_GO(3); break;
-    default: TR3D_GO(4); break;
-    }
+    // (SLAB: a context with ghost planes; the undivided lattice keeps the instance without the ghost and global-plane tests)
+#define TR3D_GO(NT, SLAB) do { if (c->tr_first) tr3d_step<true, NT, SLAB><<<g, 256, 0, c->stream>>>(p, t); else tr3d_step<false, NT, SLAB><<<g, 256, 0, c->stream>>>(p, t); } while (0)
+#define TR3D_NT(SLAB) switch (c->ntr) { case 1: TR3D_GO(1, SLAB); break; case 2: TR3D_GO(2, SLAB); break; case 3: TR3D_GO(3, SLAB); break; default: TR3D_GO(4, SLAB); break; }
+    if (c->cfg.ghost_lo || c->cfg.ghost_hi) { TR3D_NT(true) } else { TR3D_NT(false) }
+#undef TR3D_NT
 #undef TR3D_GO
     LBMPM_HIP_TRY(hipGetLastError());
     std::swap(c->gA, c->gB);
@@ -1502,7 +1501,7 @@ namespace {
 // A face message as runs of doubles inside the context's arrays: what this context SENDS through `face` (recv = false: its edge planes)
 // or where what comes through `face` lands (recv = true: its ghost planes).  The two sides list their runs in the same order.
 struct Run { double *ptr; size_t count; };
-int face_runs(lbmpm_rk3dcsf *c, int msg, int face, bool recv, Run runs[10])
+int face_runs(lbmpm_rk3dcsf *c, int msg, int face, bool recv, Run runs[MAX_RUNS])
 {
     const int g = face == 0 ? c->cfg.ghost_lo : c->cfg.ghost_hi;
     if (g == 0) return 0;
@@ -1516,7 +1515,10 @@ int face_runs(lbmpm_rk3dcsf *c, int msg, int face, bool recv, Run runs[10])
         const size_t first = c->pfirst[(size_t)z], count = c->pfirst[(size_t)z + 1] - first;
         for (int col = 0; col < 2; ++col)
             for (int a = 0; a < 5; ++a) runs[col * 5 + a] = Run{c->fA + ((size_t)col * Q + (size_t)dir[a]) * c->FS + first, count};
-        return 10;
+        // behind them, per tracer, the one D3Q7 population that crosses the face (-z: 6, +z: 5), as tr3d_step has just written it: out of /
+        // into the buffer the next tr3d_step reads (launch_tracers has swapped it when stage 2 returns)
+        for (int t = 0; t < c->ntr; ++t) runs[10 + t] = Run{c->gA + ((size_t)t * TQ + (size_t)dir[0]) * c->FS + first, count};
+        return 10 + c->ntr;
     }
     return 0;                                    // (phi and n: cell_msg)
 }
@@ -1527,7 +1529,7 @@ int copy_runs(const Run *from, const Run *to, const double *buf_in, double *buf_
     RunSet r;
     unsigned most = 0;
     size_t off = 0;
-    for (int k = 0; k < 10; ++k) {
+    for (int k = 0; k < MAX_RUNS; ++k) {
         r.count[k] = k < n ? (unsigned)shape[k].count : 0u;
         r.src[k] = k < n ? (from ? from[k].ptr : buf_in + off) : nullptr;
         r.dst[k] = k < n ? (to ? to[k].ptr : buf_out + off) : nullptr;
@@ -1592,7 +1594,7 @@ static int64_t face_total(const lbmpm_rk3dcsf *c, int msg, int face, bool recv)
         const CellMsg m = cell_msg(c, msg, face, recv);
         return (int64_t)m.ncomp * m.count;
     }
-    Run runs[10];
+    Run runs[MAX_RUNS];
     const int n = face_runs(const_cast<lbmpm_rk3dcsf *>(c), msg, face, recv, runs);
     int64_t t = 0;
     for (int k = 0; k < n; ++k) t += (int64_t)runs[k].count;
@@ -1608,7 +1610,7 @@ extern "C" int lbmpm_rk3dcsf_face_pack(lbmpm_rk3dcsf *c, int msg, int face, doub
     LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
     if ((face == 0 ? c->cfg.ghost_lo : c->cfg.ghost_hi) == 0) return LBMPM_OK;
     if (msg != LBMPM_CSF_MSG_PDF) { const CellMsg m = cell_msg(c, msg, face, false); return copy_cells(&m, c, nullptr, nullptr, nullptr, buf, c->stream); }
-    Run runs[10];
+    Run runs[MAX_RUNS];
     const int n = face_runs(c, msg, face, false, runs);
     { const int rc = copy_runs(runs, nullptr, nullptr, buf, runs, n, c->stream); if (rc) return rc; }
     for (int k = 0; k < n; ++k) buf += runs[k].count;
@@ -1627,7 +1629,7 @@ extern "C" int lbmpm_rk3dcsf_face_unpack(lbmpm_rk3dcsf *c, int msg, int face, co
     LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
     if ((face == 0 ? c->cfg.ghost_lo : c->cfg.ghost_hi) == 0) return LBMPM_OK;
     if (msg != LBMPM_CSF_MSG_PDF) { const CellMsg m = cell_msg(c, msg, face, true); return copy_cells(nullptr, nullptr, &m, c, buf, nullptr, c->stream); }
-    Run runs[10];
+    Run runs[MAX_RUNS];
     const int n = face_runs(c, msg, face, true, runs);
     { const int rc = copy_runs(nullptr, runs, buf, nullptr, runs, n, c->stream); if (rc) return rc; }
     for (int k = 0; k < n; ++k) buf += runs[k].count;
@@ -1643,13 +1645,14 @@ extern "C" int lbmpm_rk3dcsf_face_unpack(lbmpm_rk3dcsf *c, int msg, int face, co
 extern "C" int lbmpm_rk3dcsf_face_copy(lbmpm_rk3dcsf *src, int src_face, lbmpm_rk3dcsf *dst, int msg)
 {
     LBMPM_REQUIRE(src && dst && src != dst && msg_ok(msg, src_face), "lbmpm_rk3dcsf_face_copy: bad argument");
-    Run out[10], in[10];
+    Run out[MAX_RUNS], in[MAX_RUNS];
     int n = 0;
     CellMsg cm_out{}, cm_in{};
     if ((src_face == 0 ? src->cfg.ghost_lo : src->cfg.ghost_hi) == 0 || (src_face == 0 ? dst->cfg.ghost_hi : dst->cfg.ghost_lo) == 0) {
         set_error("lbmpm_rk3dcsf_face_copy: the two contexts do not share that face"); return LBMPM_ERR_INVALID;
     }
     if (msg == LBMPM_CSF_MSG_PDF) {
+        if (src->ntr != dst->ntr) { set_error("lbmpm_rk3dcsf_face_copy: the two contexts carry %d and %d tracers (lbmpm_rk3dcsf_tracer_configure_slab on every slab of the ring)", src->ntr, dst->ntr); return LBMPM_ERR_INVALID; }
         n = face_runs(src, msg, src_face, false, out);
         const int m = face_runs(dst, msg, 1 - src_face, true, in);
         if (n == 0 || n != m) { set_error("lbmpm_rk3dcsf_face_copy: the two contexts do not share that face"); return LBMPM_ERR_INVALID; }
@@ -1808,7 +1811,7 @@ const char *msg_name(int m) { return m == LBMPM_CSF_MSG_PHI ? "phi" : m == LBMPM
 struct CsfBlob {
     slabtx::IpcBlob base;
     uint64_t in_lo[3], in_hi[3];        // bytes of message LBMPM_CSF_MSG_* that come in through the low / high face
-    int32_t z0, z1, nzg, pad;           // own planes [z0, z1) of the undivided lattice of nzg planes
+    int32_t z0, z1, nzg, ntr;           // own planes [z0, z1) of the undivided lattice of nzg planes; its tracers (their runs are part of MSG_PDF)
 };
 static_assert(sizeof(CsfBlob) <= LBMPM_IPC_BLOB_BYTES, "blob size is part of the ABI");
 
@@ -1904,7 +1907,7 @@ extern "C" int lbmpm_rk3dcsf_ipc_init(lbmpm_rk3dcsf *c, void *blob_out)
     rc = c->tx.ipc_alloc(&b.base, CSF_BLOB_MAGIC);
     if (rc != LBMPM_OK) { tx_drop(c); return rc; }
     for (int m = 0; m < 3; ++m) { b.in_lo[m] = msg_bytes(c, m, 0, true); b.in_hi[m] = msg_bytes(c, m, 1, true); }
-    b.z0 = (int32_t)c->cfg.slab_z0; b.z1 = own_z1(c); b.nzg = c->nzg;
+    b.z0 = (int32_t)c->cfg.slab_z0; b.z1 = own_z1(c); b.nzg = c->nzg; b.ntr = c->ntr;
     memset(blob_out, 0, LBMPM_IPC_BLOB_BYTES);
     memcpy(blob_out, &b, sizeof b);
     return LBMPM_OK;
@@ -1928,6 +1931,8 @@ extern "C" int lbmpm_rk3dcsf_ipc_connect(lbmpm_rk3dcsf *c, const void *blob_low,
         LBMPM_REQUIRE(n.nzg == nzg && n.nzg > 0 && (side == 0 ? n.z1 % nzg == z0 : n.z0 == z1 % nzg),
                       "lbmpm_rk3dcsf_ipc_connect: the %s neighbour holds the planes [%d, %d) of %d -- not the slab next to this one's [%d, %d) of %d (other cuts)",
                       where, (int)n.z0, (int)n.z1, (int)n.nzg, z0, z1, nzg);
+        LBMPM_REQUIRE(n.ntr == c->ntr, "lbmpm_rk3dcsf_ipc_connect: the %s neighbour carries %d tracers, this slab %d (lbmpm_rk3dcsf_tracer_configure_slab on every slab of the ring, before ipc_init)",
+                      where, (int)n.ntr, c->ntr);
         for (int m = 0; m < 3; ++m) {
             const uint64_t theirs = side == 0 ? n.in_hi[m] : n.in_lo[m], mine = msg_bytes(c, m, side, false);
             LBMPM_REQUIRE(theirs == mine, "lbmpm_rk3dcsf_ipc_connect: the %s neighbour expects %llu bytes of %s through the shared face, this slab sends %llu (other masks)",
@@ -2156,22 +2161,41 @@ int tracer_ready(const lbmpm_rk3dcsf *c, int tracer, const char *who)
 }
 }  // namespace
 
+static int tracer_configure(lbmpm_rk3dcsf *c, const lbmpm_tracer3d_config *k, const char *who);
+
 extern "C" int lbmpm_rk3dcsf_tracer_configure(lbmpm_rk3dcsf *c, const lbmpm_tracer3d_config *k)
 {
     LBMPM_REQUIRE(c && k, "lbmpm_rk3dcsf_tracer_configure: null argument");
     if (c->cfg.ghost_lo || c->cfg.ghost_hi) {
-        set_error("lbmpm_rk3dcsf_tracer_configure: tracers on z-slabs are not built (a context with ghost planes; the slabs' face messages carry no tracer populations): "
-                  "run the tracers on the undivided lattice");
+        set_error("lbmpm_rk3dcsf_tracer_configure: tracers on z-slabs (a context with ghost planes) change the size of LBMPM_CSF_MSG_PDF, which the neighbouring slabs "
+                  "must agree on: lbmpm_rk3dcsf_tracer_configure_slab, on every slab of the ring before a transport is set up");
         return LBMPM_ERR_UNSUPPORTED;
     }
-    LBMPM_REQUIRE(k->num_tracers >= 1 && k->num_tracers <= 4, "lbmpm_rk3dcsf_tracer_configure: NumberTracers %d, 1 .. 4 are built", (int)k->num_tracers);
-    LBMPM_REQUIRE(k->reaction_rate == 0. || k->num_tracers == 3, "lbmpm_rk3dcsf_tracer_configure: the reaction A + B -> C couples exactly three tracers, not %d", (int)k->num_tracers);
-    if (c->steps > 0 || !c->first) { set_error("lbmpm_rk3dcsf_tracer_configure after stepping: configure the tracers before the first step"); return LBMPM_ERR_STATE; }
-    if (c->ntr) { set_error("lbmpm_rk3dcsf_tracer_configure: the tracers of this context are configured already"); return LBMPM_ERR_STATE; }
+    return tracer_configure(c, k, "lbmpm_rk3dcsf_tracer_configure");
+}
+
+extern "C" int lbmpm_rk3dcsf_tracer_configure_slab(lbmpm_rk3dcsf *c, const lbmpm_tracer3d_config *k)
+{
+    LBMPM_REQUIRE(c && k, "lbmpm_rk3dcsf_tracer_configure_slab: null argument");
+    LBMPM_REQUIRE(c->cfg.ghost_lo || c->cfg.ghost_hi, "lbmpm_rk3dcsf_tracer_configure_slab: the undivided lattice (ghost_lo = ghost_hi = 0) has no face messages: lbmpm_rk3dcsf_tracer_configure");
+    if (c->tx.kind != LBMPM_TRANSPORT_NONE) {    // (landing slots, send buffers and the blob's message sizes hold the sizes without tracers)
+        set_error("lbmpm_rk3dcsf_tracer_configure_slab: a transport is set up already (lbmpm_rk3dcsf_ipc_init / _rccl_connect sized it for the messages without tracers): configure first");
+        return LBMPM_ERR_STATE;
+    }
+    if (c->next_stage != 0) { set_error("lbmpm_rk3dcsf_tracer_configure_slab after stepping: configure the tracers before the first step"); return LBMPM_ERR_STATE; }
+    return tracer_configure(c, k, "lbmpm_rk3dcsf_tracer_configure_slab");
+}
+
+static int tracer_configure(lbmpm_rk3dcsf *c, const lbmpm_tracer3d_config *k, const char *who)
+{
+    LBMPM_REQUIRE(k->num_tracers >= 1 && k->num_tracers <= 4, "%s: NumberTracers %d, 1 .. 4 are built", who, (int)k->num_tracers);
+    LBMPM_REQUIRE(k->reaction_rate == 0. || k->num_tracers == 3, "%s: the reaction A + B -> C couples exactly three tracers, not %d", who, (int)k->num_tracers);
+    if (c->steps > 0 || !c->first) { set_error("%s after stepping: configure the tracers before the first step", who); return LBMPM_ERR_STATE; }
+    if (c->ntr) { set_error("%s: the tracers of this context are configured already", who); return LBMPM_ERR_STATE; }
     double B[4][9];
     for (int t = 0; t < k->num_tracers; ++t) {
         const double D[9] = {k->diffusion_x[t], k->diffusion_xy, k->diffusion_xz, k->diffusion_yx, k->diffusion_y[t], k->diffusion_yz, k->diffusion_zx, k->diffusion_zy, k->diffusion_z[t]};
-        LBMPM_REQUIRE(tracer_flux_matrix(D, B[t]), "lbmpm_rk3dcsf_tracer_configure: 1/2 I + 3 D of tracer %d is singular", t);
+        LBMPM_REQUIRE(tracer_flux_matrix(D, B[t]), "%s: 1/2 I + 3 D of tracer %d is singular", who, t);
     }
     LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
     const size_t per = (size_t)k->num_tracers * TQ * c->FS;

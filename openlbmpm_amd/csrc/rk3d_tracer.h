@@ -17,6 +17,10 @@
 //   concentration  T:78-90
 // Stored: the post-collision populations, SoA [tracer][7][FS] over fluid cells like the flow's planes, two buffers.  tr3d_step pulls
 // (streaming + inlet + concentration: the end of sub-step k - 1) and collides with rhoR, u, G of flow step k (the start of sub-step k).
+// Slabs (a context with ghost planes, SLAB): the outlet and the inlet are planes of the UNDIVIDED lattice (z + zoff), the ghost planes'
+// cells are received, not computed.  Of all a cell pulls, one population per tracer comes from beyond a z-face: direction 5 (+z) out of
+// the first ghost plane below, 6 (-z) out of the one above (tr3d_setup_src / csf3d_setup_src number the ghost cell, SRC_WALL where it is
+// solid: half-way bounce-back across a cut).  Those runs travel inside LBMPM_CSF_MSG_PDF (face_runs in rk3d_csf.hip).
 // rhoR and u of the step are what csf3d_collide / csf3d_collide_deep<TR = true> leave in `flow` [4][FS]; G is the flow's own array
 // (zeros in the deep blocks).  14 doubles per tracer + 7 (rhoR, u, G) + 6 source numbers read, + the 4 doubles the collision wrote.
 
@@ -68,7 +72,7 @@ __device__ __forceinline__ void tr_sources(const CsfDev &p, const TrDev &t, unsi
     for (int i = 1; i < TQ; ++i) s[i] = FIRST ? js : t.src[(size_t)(i - 1) * p.FS + js];
 }
 
-template <bool FIRST, int NT>
+template <bool FIRST, int NT, bool SLAB>
 __global__ __launch_bounds__(256) void tr3d_step(CsfDev p, TrDev t)
 {
     constexpr int CX[Q] = CSF_CX, CY[Q] = CSF_CY, CZ[Q] = CSF_CZ;
@@ -76,9 +80,11 @@ __global__ __launch_bounds__(256) void tr3d_step(CsfDev p, TrDev t)
     if (j >= p.NF) return;
     const unsigned n = p.cells[j], pl = (unsigned)p.nx * (unsigned)p.ny;
     const unsigned z = n / pl;
+    if (SLAB && ((int)z < p.glo || (int)z >= p.nz - p.ghi)) return;   // (an image of the neighbour's cell: its populations arrive with the face message)
+    const int zg = SLAB ? (int)z + p.zoff : (int)z, nzg = SLAB ? p.nzg : p.nz;        // the plane of the undivided lattice
     unsigned js = j, ns = n;
-    if (t.outlet && z == 0u) { ns = n + pl; js = p.cidx[ns]; }       // T:461-478: plane 0 holds what plane 1's cell computes (same mask)
-    const bool top = z == (unsigned)p.nz - 1u;
+    if (t.outlet && zg == 0) { ns = n + pl; js = p.cidx[ns]; }       // T:461-478: plane 0 holds what plane 1's cell computes (same mask)
+    const bool top = zg == nzg - 1;
     unsigned s[TQ];
     tr_sources<FIRST>(p, t, js, s);
     double g[NT][TQ], C[NT];
@@ -136,7 +142,7 @@ __global__ __launch_bounds__(256) void tr3d_observe(CsfDev p, TrDev t, int tr, d
         const unsigned j = p.cidx[n], pl = (unsigned)p.nx * (unsigned)p.ny;
         unsigned s[TQ];
         tr_sources<FIRST>(p, t, j, s);
-        tr_pull<FIRST>(p, t, tr, j, s, n / pl == (unsigned)p.nz - 1u, g);
+        tr_pull<FIRST>(p, t, tr, j, s, (int)(n / pl) + p.zoff == p.nzg - 1, g);      // (the inlet plane of the undivided lattice)
         c = tr_sum(g);
     }
     if (out_g) {

@@ -24,11 +24,44 @@ def _f64(a):
     return np.ascontiguousarray(a, dtype=np.float64)
 
 
+def tracer_config(num_tracers=1, diffusion_x=1. / 6., diffusion_y=None, diffusion_z=None, diffusion_xy=0., diffusion_yx=0.,
+                  diffusion_xz=0., diffusion_zx=0., diffusion_yz=0., diffusion_zy=0., beta_interface=0., criteria_rho=0.5,
+                  inlet_concentration=0., dirichlet_inlet=False, free_outlet=False, reaction_rate=0., diffusion_j=0.):
+    """the lbmpm_tracer3d_config of RK3DCSFSolver.configure_tracers(...) and of RK3DCSFSolver(..., tracers=dict(...)).  Per-tracer entries
+    are a number or a sequence of num_tracers numbers; diffusion_y, diffusion_z default to diffusion_x"""
+    from ._lib import Tracer3DConfig
+    nT = int(num_tracers)
+    cfg = Tracer3DConfig()
+    cfg.num_tracers = nT
+
+    def per(v, what):
+        a = np.broadcast_to(np.asarray(v, dtype=np.float64), (max(min(nT, 4), 1),)) if np.ndim(v) == 0 else np.asarray(v, dtype=np.float64)
+        if a.shape[0] < min(nT, 4):
+            raise ValueError("%s: %d entries for %d tracers" % (what, a.shape[0], nT))
+        return a
+    dy = diffusion_x if diffusion_y is None else diffusion_y
+    dz = diffusion_x if diffusion_z is None else diffusion_z
+    for name, v in (("diffusion_x", diffusion_x), ("diffusion_y", dy), ("diffusion_z", dz), ("beta_interface", beta_interface),
+                    ("inlet_concentration", inlet_concentration), ("diffusion_j", diffusion_j)):
+        a = per(v, name)
+        for t in range(min(nT, 4)):
+            getattr(cfg, name)[t] = float(a[t])
+    cfg.diffusion_xy, cfg.diffusion_yx, cfg.diffusion_xz = float(diffusion_xy), float(diffusion_yx), float(diffusion_xz)
+    cfg.diffusion_zx, cfg.diffusion_yz, cfg.diffusion_zy = float(diffusion_zx), float(diffusion_yz), float(diffusion_zy)
+    cfg.criteria_rho = float(criteria_rho)
+    cfg.dirichlet_inlet, cfg.free_outlet = int(bool(dirichlet_inlet)), int(bool(free_outlet))
+    cfg.reaction_rate = float(reaction_rate)
+    return cfg
+
+
 class RK3DCSFSolver:
-    def __init__(self, is_domain, params=None, device=0, diagnostics=False, slab=None):
+    def __init__(self, is_domain, params=None, device=0, diagnostics=False, slab=None, tracers=None):
         """slab = (z0, global_nz): this lattice is a slab of an undivided lattice of global_nz planes -- its planes 2 .. nz-3 are the planes
         z0 .. of that lattice, its two planes at either end images of the neighbouring slabs' edge planes (cut from the undivided lattice,
-        wrapping around its ends, like the rest)"""
+        wrapping around its ends, like the rest).
+        tracers = dict(<the keyword arguments of configure_tracers>): the D3Q7 tracers, configured at construction.  On a slab this is the
+        only way to them (lbmpm_rk3dcsf_tracer_configure_slab): their populations travel inside the population message, so every slab of
+        the ring is given the same dict, before a transport is connected."""
         L = _lib.lib()
         p = dict(DEFAULT_PARAMS)
         p.update(params or {})
@@ -76,6 +109,13 @@ class RK3DCSFSolver:
         self._L = L
         if diagnostics:
             self.enable_diagnostics(True)
+        if tracers is not None:
+            cfg = tracer_config(**tracers)
+            if slab:
+                check(L.lbmpm_rk3dcsf_tracer_configure_slab(self._h, C.byref(cfg)), "lbmpm_rk3dcsf_tracer_configure_slab")
+            else:
+                check(L.lbmpm_rk3dcsf_tracer_configure(self._h, C.byref(cfg)), "lbmpm_rk3dcsf_tracer_configure")
+            self.num_tracers = int(cfg.num_tracers)
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
@@ -206,40 +246,17 @@ class RK3DCSFSolver:
         check(self._L.lbmpm_rk3dcsf_slab_timing(self._h, out), "lbmpm_rk3dcsf_slab_timing")
         return dict(stage_ms=list(out[0:3]), message_ms=list(out[3:6]), messages=["phi", "normal", "populations"], steps=int(out[6]))
 
-    # ---- D3Q7 tracers advected by the flow (lbmpm_rk3dcsf_tracer_*; undivided lattices only)
-    def configure_tracers(self, num_tracers=1, diffusion_x=1. / 6., diffusion_y=None, diffusion_z=None, diffusion_xy=0., diffusion_yx=0.,
-                          diffusion_xz=0., diffusion_zx=0., diffusion_yz=0., diffusion_zy=0., beta_interface=0., criteria_rho=0.5,
-                          inlet_concentration=0., dirichlet_inlet=False, free_outlet=False, reaction_rate=0., diffusion_j=0.):
-        """Before the first step.  Per-tracer entries are a number or a sequence of num_tracers numbers; diffusion_y, diffusion_z default
-        to diffusion_x.  diffusion_j is the rest weight J0' of the reaction source on the D3Q7 lattice ((3 J0 - 1) / 2 of the 2-D file's J0:
+    # ---- D3Q7 tracers advected by the flow (lbmpm_rk3dcsf_tracer_*)
+    def configure_tracers(self, *args, **kwargs):
+        """Before the first step, on the undivided lattice (a slab takes them at construction: tracers=); the keyword arguments of
+        tracer_config().  diffusion_j is the rest weight J0' of the reaction source on the D3Q7 lattice ((3 J0 - 1) / 2 of the 2-D file's J0:
         config.read_transport3d maps it).  The tracer sub-step runs after the flow's collision with rho_R, u and G of that flow step."""
-        from ._lib import Tracer3DConfig
-        nT = int(num_tracers)
-        cfg = Tracer3DConfig()
-        cfg.num_tracers = nT
-
-        def per(v, what):
-            a = np.broadcast_to(np.asarray(v, dtype=np.float64), (max(min(nT, 4), 1),)) if np.ndim(v) == 0 else np.asarray(v, dtype=np.float64)
-            if a.shape[0] < min(nT, 4):
-                raise ValueError("%s: %d entries for %d tracers" % (what, a.shape[0], nT))
-            return a
-        dy = diffusion_x if diffusion_y is None else diffusion_y
-        dz = diffusion_x if diffusion_z is None else diffusion_z
-        for name, v in (("diffusion_x", diffusion_x), ("diffusion_y", dy), ("diffusion_z", dz), ("beta_interface", beta_interface),
-                        ("inlet_concentration", inlet_concentration), ("diffusion_j", diffusion_j)):
-            a = per(v, name)
-            for t in range(min(nT, 4)):
-                getattr(cfg, name)[t] = float(a[t])
-        cfg.diffusion_xy, cfg.diffusion_yx, cfg.diffusion_xz = float(diffusion_xy), float(diffusion_yx), float(diffusion_xz)
-        cfg.diffusion_zx, cfg.diffusion_yz, cfg.diffusion_zy = float(diffusion_zx), float(diffusion_yz), float(diffusion_zy)
-        cfg.criteria_rho = float(criteria_rho)
-        cfg.dirichlet_inlet, cfg.free_outlet = int(bool(dirichlet_inlet)), int(bool(free_outlet))
-        cfg.reaction_rate = float(reaction_rate)
+        cfg = tracer_config(*args, **kwargs)
         check(self._L.lbmpm_rk3dcsf_tracer_configure(self._h, C.byref(cfg)), "lbmpm_rk3dcsf_tracer_configure")
-        self.num_tracers = nT
+        self.num_tracers = int(cfg.num_tracers)
 
     def set_concentration(self, t, conc):
-        """dense [nz][ny][nx]; g_i = C w_i; before the first step"""
+        """dense [nz][ny][nx] (a slab: with its ghost planes, like set_macro); g_i = C w_i; before the first step"""
         self._keep = []
         ptr = self._ptr(conc, self.shape, "concentration")
         check(self._L.lbmpm_rk3dcsf_tracer_set_concentration(self._h, int(t), ptr), "lbmpm_rk3dcsf_tracer_set_concentration")
@@ -332,12 +349,17 @@ class _SlabGeometry:
         return a[self.ghost[0]:a.shape[0] - self.ghost[1]]
 
 
+_TRACERS_AT_CONSTRUCTION = ("tracers on z-slabs are part of the slabs' population message, which is sized when the ring is set up: "
+                            "give them to %s at construction (tracers=dict(...)), not afterwards")
+
+
 class RK3DCSFCluster:
     """The 3-D CSF model cut into slabs along z, every slab a context of its own (devices[k]; all on one GPU: a rehearsal of the
     decomposition, bit-equal to the undivided lattice).  One time step = three stages with a face message after each: phi (two planes),
     n (one plane), the populations crossing the face (lbmpm_rk3dcsf_stage / _face_copy)."""
 
-    def __init__(self, is_domain, params=None, nslabs=2, devices=None, cuts=None, diagnostics=False):
+    def __init__(self, is_domain, params=None, nslabs=2, devices=None, cuts=None, diagnostics=False, tracers=None):
+        """tracers = dict(<the keyword arguments of RK3DCSFSolver.configure_tracers>): D3Q7 tracers on every slab"""
         dom = np.ascontiguousarray(is_domain, dtype=np.uint8)
         self.shape = dom.shape
         self.nz, self.ny, self.nx = dom.shape
@@ -345,8 +367,9 @@ class RK3DCSFCluster:
         n = len(self.cuts) - 1
         devices = list(devices) if devices is not None else [0] * n
         self.geo = [_SlabGeometry(self.nz, self.cuts[k], self.cuts[k + 1]) for k in range(n)]
-        self.slabs = [RK3DCSFSolver(g.cut(dom), params, device=devices[k], diagnostics=diagnostics, slab=g.slab) for k, g in enumerate(self.geo)]
+        self.slabs = [RK3DCSFSolver(g.cut(dom), params, device=devices[k], diagnostics=diagnostics, slab=g.slab, tracers=tracers) for k, g in enumerate(self.geo)]
         self.params = self.slabs[0].params
+        self.num_tracers = getattr(self.slabs[0], "num_tracers", 0)
 
     def close(self):
         for s in self.slabs:
@@ -361,10 +384,23 @@ class RK3DCSFCluster:
             s.set_pdf(g.cut(np.asarray(fR)), g.cut(np.asarray(fB)), None if force is None else tuple(g.cut(np.asarray(c)) for c in force))
 
     def configure_tracers(self, *args, **kwargs):
-        """tracers on z-slabs are not built: the face messages carry no tracer populations"""
-        raise _lib.LbmpmError("tracers on z-slabs are not built (%s): run them on RK3DCSFSolver, the undivided lattice" % type(self).__name__, _lib.ERR_UNSUPPORTED)
+        """refused: on slabs the tracers change the size of the population message, so they are given at construction (tracers=)"""
+        raise _lib.LbmpmError(_TRACERS_AT_CONSTRUCTION % type(self).__name__, _lib.ERR_UNSUPPORTED)
 
-    set_concentration = get_concentration = get_tracer_pdf = set_tracer_pdf = configure_tracers
+    def set_concentration(self, t, conc):
+        """the undivided array [nz][ny][nx]; every slab takes its planes (and the images of its neighbours')"""
+        for s, g in zip(self.slabs, self.geo):
+            s.set_concentration(t, g.cut(np.asarray(conc, dtype=np.float64)))
+
+    def set_tracer_pdf(self, t, pdf):
+        for s, g in zip(self.slabs, self.geo):
+            s.set_tracer_pdf(t, g.cut(np.asarray(pdf, dtype=np.float64)))
+
+    def get_concentration(self, t):
+        return np.concatenate([g.own(s.get_concentration(t)) for s, g in zip(self.slabs, self.geo)], axis=0)
+
+    def get_tracer_pdf(self, t):
+        return np.concatenate([g.own(s.get_tracer_pdf(t)) for s, g in zip(self.slabs, self.geo)], axis=0)
 
     def _exchange(self, msg):
         n = len(self.slabs)
@@ -405,12 +441,14 @@ class RK3DCSFCluster:
 class RK3DCSFDistributed:
     """One slab of the 3-D CSF model per rank of torch.distributed (launch: one process per GPU).  The face messages travel as device
     tensors under the nccl (= RCCL) backend and through host memory under gloo; three per step and face (phi, n, populations: 2 + 3 +
-    10 doubles per cell of a plane), batched per stage.  Opt-in (transport='ipc' | 'rccl' | 'auto'): the messages travel over a transport
+    10 doubles per cell of a plane, + 1 per tracer), batched per stage.  Opt-in (transport='ipc' | 'rccl' | 'auto'): the messages travel over a transport
     inside the library instead, and a call to step() is one lbmpm_rk3dcsf_step_slab -- no Python and no host synchronisation between the
     stages; torch.distributed then only carries the set-up (blobs, unique id, agreement)."""
 
-    def __init__(self, is_domain, params=None, device=0, cuts=None, diagnostics=False, slab_factory=None, transport=None):
-        """slab_factory: tests/test_slab_cpu.py puts a host stand-in with the library's stage / face calls in the solver's place (attribute
+    def __init__(self, is_domain, params=None, device=0, cuts=None, diagnostics=False, slab_factory=None, transport=None, tracers=None):
+        """tracers = dict(<the keyword arguments of RK3DCSFSolver.configure_tracers>), the same on every rank: D3Q7 tracers, one more
+        double per tracer and fluid cell of a plane in the population message (configured before the transport connects).
+        slab_factory: tests/test_slab_cpu.py puts a host stand-in with the library's stage / face calls in the solver's place (attribute
         on_host: its buffers are host tensors) to run this class's orchestration under gloo without a GPU.
         transport: None or 'torch' (default) -- the messages through torch.distributed, from Python, after every stage; 'ipc' | 'rccl' --
         that in-library transport, which must connect and pass its probe on every rank, else RuntimeError on every rank; 'auto' -- ipc
@@ -429,8 +467,10 @@ class RK3DCSFDistributed:
             raise ValueError("one slab per rank: %d cuts for %d ranks" % (len(self.cuts) - 1, self.world))
         self.geo = _SlabGeometry(self.nz, self.cuts[self.rank], self.cuts[self.rank + 1])
         self.z0, self.nzl = self.geo.z0, self.geo.z1 - self.geo.z0
-        self.slab = (slab_factory or RK3DCSFSolver)(self.geo.cut(dom), params, device=device, diagnostics=diagnostics, slab=self.geo.slab)
+        more = {} if tracers is None else dict(tracers=tracers)
+        self.slab = (slab_factory or RK3DCSFSolver)(self.geo.cut(dom), params, device=device, diagnostics=diagnostics, slab=self.geo.slab, **more)
         self.params = self.slab.params
+        self.num_tracers = 0 if tracers is None else int(dict(tracers).get("num_tracers", 1))
         self._on_device = dist.get_backend() == "nccl"
         dev = self._dev = torch.device("cpu") if getattr(slab_factory, "on_host", False) else torch.device("cuda", int(device))
         self._t_stage, self._t_msg, self._t_count = [0.0] * 3, [0.0] * 3, [0] * 3
@@ -442,7 +482,7 @@ class RK3DCSFDistributed:
                     self._buf[(msg, face)] = (torch.empty(n, dtype=torch.float64, device=dev), torch.empty(m, dtype=torch.float64, device=dev))
         # every rank cuts its slab out of the same undivided lattice
         import zlib
-        mine = torch.tensor([zlib.crc32(dom.tobytes())] + list(dom.shape) + self.cuts, dtype=torch.int64)
+        mine = torch.tensor([zlib.crc32(dom.tobytes())] + list(dom.shape) + self.cuts + [self.num_tracers], dtype=torch.int64)
         every = [torch.zeros_like(mine) for _ in range(self.world)]
         if self._on_device:
             every = [t.to(dev) for t in every]
@@ -450,7 +490,7 @@ class RK3DCSFDistributed:
         dist.all_gather(every, mine)
         for r in range(self.world):
             if not bool((every[r] == mine).all()):
-                raise ValueError("rank %d holds another lattice or other cuts than rank %d" % (r, self.rank))
+                raise ValueError("rank %d holds another lattice, other cuts or another number of tracers than rank %d" % (r, self.rank))
         want = "torch" if transport is None else transport
         if want not in ("torch", "auto", "ipc", "rccl"):
             raise ValueError("transport must be None, 'torch', 'auto', 'ipc' or 'rccl'")
@@ -462,10 +502,22 @@ class RK3DCSFDistributed:
             self._connect(want)
 
     def configure_tracers(self, *args, **kwargs):
-        """tracers on z-slabs are not built: the face messages carry no tracer populations"""
-        raise _lib.LbmpmError("tracers on z-slabs are not built (%s): run them on RK3DCSFSolver, the undivided lattice" % type(self).__name__, _lib.ERR_UNSUPPORTED)
+        """refused: on slabs the tracers change the size of the population message, so they are given at construction (tracers=)"""
+        raise _lib.LbmpmError(_TRACERS_AT_CONSTRUCTION % type(self).__name__, _lib.ERR_UNSUPPORTED)
 
-    set_concentration = get_concentration = get_tracer_pdf = set_tracer_pdf = configure_tracers
+    def set_concentration(self, t, conc):
+        """the undivided array [nz][ny][nx]; every rank takes its planes (and the images of its neighbours')"""
+        self.slab.set_concentration(t, self.geo.cut(np.asarray(conc, dtype=np.float64)))
+
+    def set_tracer_pdf(self, t, pdf):
+        self.slab.set_tracer_pdf(t, self.geo.cut(np.asarray(pdf, dtype=np.float64)))
+
+    def get_concentration(self, t):
+        """this rank's own planes (gather() stacks them on rank 0)"""
+        return np.ascontiguousarray(self.geo.own(self.slab.get_concentration(t)))
+
+    def get_tracer_pdf(self, t):
+        return np.ascontiguousarray(self.geo.own(self.slab.get_tracer_pdf(t)))
 
     def _agree(self, ok):
         """True when every rank says ok (a collective on host objects: works on every backend)"""
