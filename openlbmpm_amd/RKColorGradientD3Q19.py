@@ -56,6 +56,7 @@ class _CSFSlab:
         more = {} if tracers is None else dict(tracers=tracers)
         self.solver = RK3DCSFDistributed(dom, q, device=device, transport=transport, **more) if distributed else RK3DCSFSolver(dom, q, device=device, **more)
         self.step_single, self.sync, self.close = self.solver.step, self.solver.sync, self.solver.close
+        self.base_steps = 0          # the steps a restored checkpoint had behind it (set_pdf starts the solver's own counter again)
 
     num_fluid_nodes = property(lambda self: self.solver.num_fluid_nodes)
     dominant_kernel = property(lambda self: self.solver.dominant_kernel)
@@ -78,13 +79,14 @@ class _CSFSlab:
     def get_state(self):
         s = self.solver
         st = np.concatenate([s.get("fR"), s.get("fB")] + [s.get(c)[..., None] for c in ("Fx", "Fy", "Fz")], axis=-1)
-        return st, dict(doubles_per_cell=41, steps=s.steps_done, post_collision=False)
+        return st, dict(doubles_per_cell=41, steps=self.base_steps + s.steps_done, post_collision=False)
 
     def set_state(self, st, steps, post_collision):
         st = np.asarray(st)
         if st.shape[-1] != 41:
             raise config.ConfigError("restart_from: this checkpoint is not one of the 3-D CSF model (41 doubles per cell: f_R, f_B, F)")
         self.solver.set_pdf(st[..., :19], st[..., 19:38], force=tuple(np.ascontiguousarray(st[..., 38 + a]) for a in range(3)))
+        self.base_steps = int(steps)
 
 
 def duct(nx, ny, nz):

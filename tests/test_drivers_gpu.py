@@ -670,6 +670,41 @@ def test_rk3d_driver_runs_the_csf_loop(tmp_path, relax):
         assert np.array_equal(res2[key], res[key]), key
 
 
+def test_rk3d_csf_checkpoint_of_a_restarted_run_continues_bit_for_bit(tmp_path):
+    """two generations of checkpoints of the 3-D CSF model: a run restarted from a checkpoint writes one of its own, and the run restarted
+    from THAT one performs exactly the remaining steps and ends where the uninterrupted run ends -- the second checkpoint holds the absolute
+    step count, not the steps since the first restart"""
+    from ini_fixtures import write_rk3d_csf
+    from openlbmpm_amd.RKColorGradientD3Q19 import RKColorGradient3D
+    from openlbmpm_amd.results import load_results, read_planes
+    write_rk3d_csf(str(tmp_path), nx=14, ny=12, nz=40, steps=40, relax="MRT", sigma=0.05, theta=60.0)
+    run = lambda name, **kw: RKColorGradient3D(str(tmp_path), output_dir=str(tmp_path / name), record_every=10, **kw)
+    whole = run("whole")
+    ref = load_results(whole.runRKColorGradient3D())
+    assert whole.records == 5 and whole.solver.solver.steps_done == 40
+    first = run("first", checkpoint_every=12)
+    first.timeSteps = 20                                  # one checkpoint, after 12 steps
+    first.runRKColorGradient3D()
+    assert [int(v) for v in read_planes(first.checkpoint_path, "/Checkpoint/Info")][:3] == [41, 12, 0]
+    second = run("second", checkpoint_every=12, restart_from=first.checkpoint_path)
+    second.timeSteps = 30                                 # steps 13 .. 30, one checkpoint after step 24
+    got2 = load_results(second.runRKColorGradient3D())
+    assert second.solver.solver.steps_done == 18
+    info = [int(v) for v in read_planes(second.checkpoint_path, "/Checkpoint/Info")]
+    assert info[1] == 24 and info[6] == 3, info           # the absolute step count; records 0, 1, 2 written before it
+    last = run("last", restart_from=second.checkpoint_path)
+    got = load_results(last.runRKColorGradient3D())
+    assert last.solver.solver.steps_done == 40 - 24       # exactly the remaining steps
+    assert last.records == whole.records == 5
+    names = ("/FluidMacro/FluidDensityRin%d", "/FluidMacro/FluidDensityBin%d", "/FluidVelocity/FluidVelocityXAt%d", "/FluidVelocity/FluidVelocityZAt%d")
+    assert sorted(k for k in got if k.startswith("/FluidMacro/FluidDensityRin")) == ["/FluidMacro/FluidDensityRin3", "/FluidMacro/FluidDensityRin4"]
+    for k, res in ((2, got2), (3, got), (4, got)):
+        for name in names:
+            assert np.array_equal(res[name % k], ref[name % k]), (name, k)
+    (st_a, info_a), (st_b, info_b) = whole.solver.get_state(), last.solver.get_state()
+    assert info_a["steps"] == info_b["steps"] == 40 and np.array_equal(st_a, st_b)
+
+
 def test_rk3d_csf_cycle_restart_from_the_last_record(tmp_path):
     """the same [CyclesSetup] IsCycle = 'yes' branch with SurfaceTensionType = 'CSF': the record LastStep's densities and velocity, the top 20
     planes refilled with blue, populations = their equilibria (RKD2Q9.py:492-508 in 3-D) -- against the CSF oracle started from those fields"""

@@ -126,3 +126,42 @@ def test_checkpoint_and_restart_continue_bit_for_bit(tmp_path):
             assert np.array_equal(rb[key], ra[key]), key
     st_a, st_b = a.solver.get_state()[0], b.solver.get_state()[0]
     assert st_a.shape[-1] == 41 + 14 and np.array_equal(st_a, st_b)
+
+
+@pytest.mark.gpu
+def test_a_checkpoint_of_a_restarted_run_continues_bit_for_bit(tmp_path):
+    """two generations: the checkpoint a restarted run writes holds the absolute step count, and the run restarted from it performs exactly
+    the remaining steps, writes the uninterrupted run's records under their indices and ends in its state"""
+    from openlbmpm_amd.Transport3DRK import Transport3DRK
+    from openlbmpm_amd.results import load_results, read_planes
+    write_ini(tmp_path, nx=14, ny=12, nz=40, steps=40, relax="MRT", sigma=0.05, theta=60.0)
+    run = lambda name, **kw: Transport3DRK(str(tmp_path), output_dir=str(tmp_path / name), record_every=10, **kw)
+
+    def results(sim):
+        flow, conc = sim.runTransport3DMPMCRK()
+        out = dict(load_results(flow)); out.update(load_results(conc))
+        return out
+    whole = run("whole")
+    ref = results(whole)
+    assert whole.records == 5 and whole.solver.solver.steps_done == 40
+    first = run("first", checkpoint_every=12)
+    first.timeSteps = 20                                  # one checkpoint, after 12 steps
+    results(first)
+    assert [int(v) for v in read_planes(first.checkpoint_path, "/Checkpoint/Info")][:3] == [41 + 14, 12, 0]
+    second = run("second", checkpoint_every=12, restart_from=first.checkpoint_path)
+    second.timeSteps = 30                                 # steps 13 .. 30, one checkpoint after step 24
+    got2 = results(second)
+    assert second.solver.solver.steps_done == 18
+    info = [int(v) for v in read_planes(second.checkpoint_path, "/Checkpoint/Info")]
+    assert info[1] == 24 and info[6] == 3, info           # the absolute step count; records 0, 1, 2 written before it
+    last = run("last", restart_from=second.checkpoint_path)
+    got = results(last)
+    assert last.solver.solver.steps_done == 40 - 24       # exactly the remaining steps
+    assert last.records == whole.records == 5
+    names = ("/FluidMacro/FluidDensityRin%d", "/FluidVelocity/FluidVelocityZAt%d", "/TransportMacro/TracerConcType0in%d", "/TransportMacro/TracerConcType1in%d")
+    assert sorted(k for k in got if k.startswith("/TransportMacro/TracerConcType0in")) == ["/TransportMacro/TracerConcType0in3", "/TransportMacro/TracerConcType0in4"]
+    for k, res in ((2, got2), (3, got), (4, got)):
+        for name in names:
+            assert np.array_equal(res[name % k], ref[name % k]), (name, k)
+    (st_a, info_a), (st_b, info_b) = whole.solver.get_state(), last.solver.get_state()
+    assert info_a["steps"] == info_b["steps"] == 40 and st_a.shape[-1] == 41 + 14 and np.array_equal(st_a, st_b)
