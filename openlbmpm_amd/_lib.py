@@ -287,3 +287,65 @@ def check(rc, what=""):
     if rc != 0:
         msg = lib().lbmpm_last_error().decode("utf-8", "replace")
         raise LbmpmError("%s failed (status %d): %s" % (what or "lbmpm call", rc, msg), status=rc)
+
+
+class SlabTransportCalls:
+    """The calls of a slab's in-library transport (include/lbmpm.h: LBMPM_TRANSPORT_*), the same for both 3-D models but for the C
+    prefix.  A class that inherits this has the library in _L, its context in _h, and sets the two names below."""
+    _C_PREFIX = None            # "lbmpm_rk3d" | "lbmpm_rk3dcsf"
+    _NO_TRANSPORT = None        # what `transport` says when none is connected
+
+    def _tx(self, name, *args):
+        name = "%s_%s" % (self._C_PREFIX, name)
+        check(getattr(self._L, name)(self._h, *args), name)
+
+    def ipc_init(self):
+        """allocate this slab's landing area; returns the bytes its neighbours need (lbmpm_*_ipc_init)"""
+        blob = C.create_string_buffer(IPC_BLOB_BYTES)
+        self._tx("ipc_init", blob)
+        return blob.raw
+
+    def ipc_connect(self, blob_below, blob_above):
+        """map the neighbours' landing areas (their ipc_init bytes; None where the slab has no neighbour; in a ring of two the same)"""
+        keep = [C.create_string_buffer(bytes(b), IPC_BLOB_BYTES) if b is not None else None for b in (blob_below, blob_above)]
+        self._tx("ipc_connect", keep[0], keep[1])
+
+    @staticmethod
+    def rccl_unique_id(librccl_path=None):
+        idb = C.create_string_buffer(RCCL_ID_BYTES)
+        check(lib().lbmpm_rccl_unique_id(idb, librccl_path.encode() if librccl_path else None), "lbmpm_rccl_unique_id")
+        return idb.raw
+
+    def rccl_connect(self, unique_id, rank, nranks, librccl_path=None):
+        """collective over the ranks of the run: ncclCommInitRank inside the library"""
+        idb = C.create_string_buffer(unique_id, RCCL_ID_BYTES)
+        self._tx("rccl_connect", idb, int(rank), int(nranks), librccl_path.encode() if librccl_path else None)
+
+    def transport_disconnect(self):
+        self._tx("transport_disconnect")
+
+    @property
+    def transport(self):
+        """_NO_TRANSPORT (none connected), 'ipc (...)' with how the flags travel, or 'rccl'"""
+        v = C.c_int(0)
+        k = getattr(self._L, self._C_PREFIX + "_transport_kind")(self._h, C.byref(v))
+        return {0: self._NO_TRANSPORT, 1: "ipc (copy engine + %s)" % ("stream value operations" if v.value else "one-lane flag kernels"), 2: "rccl"}[k]
+
+    def transport_probe(self, rounds=6):
+        self._tx("transport_probe", int(rounds))
+
+    def transport_probe_result(self):
+        v = C.c_int64(-1)
+        self._tx("transport_probe_result", C.byref(v))
+        return int(v.value)
+
+    def ipc_release_waits(self):
+        self._tx("ipc_release_waits")
+
+    def sync(self, deadline_s=None):
+        """wait for the slab's streams; with deadline_s the library's watchdog (lbmpm_*_sync_deadline): LbmpmError with status
+        LBMPM_ERR_TIMEOUT (-6) when a connected slab's neighbour stops answering -- the transport is given up, the state is void"""
+        if deadline_s is None:
+            self._tx("sync")
+        else:
+            self._tx("sync_deadline", float(deadline_s))

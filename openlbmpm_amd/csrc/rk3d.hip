@@ -1194,8 +1194,7 @@ struct lbmpm_rk3d {
     unsigned long long *trace = nullptr;      // dev tool, see RK3Dev
     unsigned *slotq = nullptr;                // tile counters of the rk3dq_fused launches (launch_q23); null: tiles by block index
     unsigned slot_launches = 0;
-    unsigned long long *probe_bad = nullptr;    // mismatch counter of lbmpm_rk3d_transport_probe
-    slabtx::Transport tx;            // the exchange's transport when the library drives it itself (lbmpm_rk3d_ipc_* / lbmpm_rk3d_rccl_connect)
+    slabtx::Transport tx{"lbmpm_rk3d", slabtx::BLOB_MAGIC};      // the exchange's transport when the library drives it itself (lbmpm_rk3d_ipc_* / lbmpm_rk3d_rccl_connect)
     bool halo_valid = false;         // q23 slabs: the halo planes (populations, records, flags, phase field) belong to the current state
     int dbg = 0;
     int nseg = 0;
@@ -1220,8 +1219,6 @@ struct lbmpm_rk3d {
     int64_t slab_timed_steps = 0;
     // steady-state watchdog (lbmpm_rk3d_sync_deadline): a word in pinned host memory that the exchange chain of every slab step writes
     // its step number into -- the host's evidence of progress -- and a private stream for the watchdog's own copies
-    unsigned long long *beat_host = nullptr, *beat_dev = nullptr;
-    hipStream_t wd_stream = nullptr;
     int64_t observed_at = -1;        // value of `steps` when lbmpm_rk3d_phase_field(ctx, 1) last filled phi / diag for all owned planes
     lbmpm::EventPool pool;
 };
@@ -1485,10 +1482,7 @@ extern "C" void lbmpm_rk3d_destroy(lbmpm_rk3d *c)
     (void)hipSetDevice(c->cfg.device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->aux) (void)hipStreamSynchronize(c->aux);
-    c->tx.disconnect();
-    if (c->probe_bad) (void)hipFree(c->probe_bad);
-    if (c->beat_host) (void)hipHostFree(c->beat_host);
-    if (c->wd_stream) (void)hipStreamDestroy(c->wd_stream);
+    c->tx.destroy();
     for (void *ptr : {(void *)c->seg, (void *)c->seg2, (void *)c->pstart, (void *)c->flags, (void *)c->solidnbr, (void *)c->fA, (void *)c->fB, (void *)c->purA, (void *)c->purB, (void *)c->trace, (void *)c->slotq, (void *)c->phi, (void *)c->diag,
                       (void *)c->send_up, (void *)c->send_dn, (void *)c->recv_below, (void *)c->recv_above})
         if (ptr) (void)hipFree(ptr);
@@ -1984,7 +1978,7 @@ extern "C" int lbmpm_rk3d_ipc_connect(lbmpm_rk3d *c, const void *blob_below, con
     int rc = LBMPM_OK;
     if (blob_below) { memcpy(&b, blob_below, sizeof b); rc = c->tx.ipc_open(0, &b, c->tx.bytes_dn); }
     if (rc == LBMPM_OK && blob_above) { memcpy(&b, blob_above, sizeof b); rc = c->tx.ipc_open(1, &b, c->tx.bytes_up); }
-    if (rc != LBMPM_OK) return rc;
+    if (rc != LBMPM_OK) { c->tx.unmap(); return rc; }       // (a retried connect maps the neighbours afresh)
     c->tx.connected = true;
     c->halo_valid = false;
     return LBMPM_OK;
@@ -2014,15 +2008,8 @@ extern "C" int lbmpm_rk3d_rccl_connect(lbmpm_rk3d *c, const void *id, int rank, 
         c->tx.disconnect();           // (the landing area of tx_shape: every error path behind it gives it back)
         return LBMPM_ERR_INVALID;
     }
-    rc = c->tx.rccl.open(librccl_path);
+    rc = c->tx.rccl_connect(id, rank, nranks, librccl_path, false);
     if (rc != LBMPM_OK) { c->tx.disconnect(); return rc; }
-    slabtx::Rccl::UniqueId uid;
-    memcpy(&uid, id, sizeof uid);
-    if (hipSetDevice(c->cfg.device) != hipSuccess) { set_error("hipSetDevice(%d) failed", c->cfg.device); c->tx.disconnect(); return LBMPM_ERR_HIP; }
-    const int e = c->tx.rccl.CommInitRank(&c->tx.comm, nranks, uid, rank);
-    if (e != 0) { set_error("ncclCommInitRank(rank %d of %d): %s", rank, nranks, c->tx.rccl.GetErrorString(e)); c->tx.disconnect(); return LBMPM_ERR_HIP; }
-    c->tx.rank = rank; c->tx.nranks = nranks; c->tx.peer_up = rank + 1; c->tx.peer_dn = rank - 1;
-    c->tx.kind = LBMPM_TRANSPORT_RCCL; c->tx.connected = true; c->tx.seq = 0;
     c->halo_valid = false;
     return LBMPM_OK;
 }
@@ -2038,72 +2025,41 @@ extern "C" int lbmpm_rk3d_transport_disconnect(lbmpm_rk3d *c)
     return LBMPM_OK;
 }
 
-extern "C" int lbmpm_rk3d_transport_kind(lbmpm_rk3d *c, int *value_ops)
-{
-    if (!c) return LBMPM_TRANSPORT_NONE;
-    if (value_ops) *value_ops = c->tx.kind == LBMPM_TRANSPORT_IPC && c->tx.value_ops ? 1 : 0;
-    return c->tx.connected ? c->tx.kind : LBMPM_TRANSPORT_NONE;
-}
+extern "C" int lbmpm_rk3d_transport_kind(lbmpm_rk3d *c, int *value_ops) { return c ? c->tx.kind_for_caller(value_ops) : LBMPM_TRANSPORT_NONE; }
 
-static int release_ipc_waits(lbmpm_rk3d *c);
 extern "C" int lbmpm_rk3d_ipc_release_waits(lbmpm_rk3d *c)
 {
-    LBMPM_REQUIRE(c && c->tx.kind == LBMPM_TRANSPORT_IPC && c->tx.flags, "lbmpm_rk3d_ipc_release_waits: no IPC transport");
+    LBMPM_REQUIRE(c, "null context");
     LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
-    return release_ipc_waits(c);
+    return c->tx.ipc_release_waits();
 }
 
-namespace { __global__ void tx_fill(double *p, size_t n, double v) { const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; if (i < n) p[i] = v + (double)i; } }
-namespace { __global__ void tx_check(const double *p, size_t n, double v, unsigned long long *bad)
-{
-    const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
-    if (i < n && p[i] != v + (double)i) atomicAdd(bad, 1ull);
-} }
-
-// Probe of the CONNECTED transport between the real neighbours, enqueued on the context's stream (the caller polls the stream under a
-// deadline, then reads the verdict): `rounds` patterned messages each way -- both slot parities several times over, so that a reader
-// that served a landing slot from a stale cache line would be caught -- written into the (still unused) send buffers, exchanged,
-// and compared on the receiving side by a kernel launched behind the transport's waits.  Call before set_density.
+// `rounds` patterned messages each way (slabtx::Transport::probe_round) -- both slot parities several times over, so that a reader
+// that served a landing slot from a stale cache line would be caught.  Call before set_density.
 extern "C" int lbmpm_rk3d_transport_probe(lbmpm_rk3d *c, int rounds)
 {
     LBMPM_REQUIRE(c && c->tx.connected && rounds >= 1, "lbmpm_rk3d_transport_probe: no transport connected");
     LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
-    if (!c->probe_bad) LBMPM_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&c->probe_bad), sizeof(unsigned long long)));
-    LBMPM_HIP_TRY(hipMemsetAsync(c->probe_bad, 0, sizeof(unsigned long long), c->stream));
-    const size_t nu = c->tx.bytes_up / 8, nd = c->tx.bytes_dn / 8, nb = c->tx.bytes_from_below / 8, na = c->tx.bytes_from_above / 8;
-    auto grid = [](size_t n) { return dim3((unsigned)((n + 255) / 256)); };
-    for (int r = 1; r <= rounds; ++r) {
-        const double up = 1000. * r + 1., dn = -(1000. * r + 1.);
-        if (c->tx.has_above) tx_fill<<<grid(nu), dim3(256), 0, c->stream>>>(c->send_up, nu, up);
-        if (c->tx.has_below) tx_fill<<<grid(nd), dim3(256), 0, c->stream>>>(c->send_dn, nd, dn);
-        const double *fb = nullptr, *fa = nullptr;
-        const int rc = c->tx.exchange(c->stream, c->send_up, c->send_dn, &fb, &fa);
-        if (rc != LBMPM_OK) return rc;
-        if (c->tx.has_below) tx_check<<<grid(nb), dim3(256), 0, c->stream>>>(fb, nb, up, c->probe_bad);       // what the rank below sent up
-        if (c->tx.has_above) tx_check<<<grid(na), dim3(256), 0, c->stream>>>(fa, na, dn, c->probe_bad);       // what the rank above sent down
-        LBMPM_HIP_TRY(hipGetLastError());
-    }
-    c->halo_valid = false;
-    return LBMPM_OK;
+    int rc = c->tx.probe_begin(c->stream);
+    const size_t nu = c->tx.has_above ? c->tx.bytes_up / 8 : 0, nd = c->tx.has_below ? c->tx.bytes_dn / 8 : 0;
+    const size_t nb = c->tx.has_below ? c->tx.bytes_from_below / 8 : 0, na = c->tx.has_above ? c->tx.bytes_from_above / 8 : 0;
+    for (int r = 1; r <= rounds && rc == LBMPM_OK; ++r) rc = c->tx.probe_round(c->stream, c->send_up, c->send_dn, nu, nd, nb, na, 1000. * r + 1.);
+    if (rc == LBMPM_OK) c->halo_valid = false;
+    return rc;
 }
 
-// verdict of the last probe: doubles that arrived different from what the neighbour sent (synchronises the context's stream)
 extern "C" int lbmpm_rk3d_transport_probe_result(lbmpm_rk3d *c, int64_t *mismatches)
 {
-    LBMPM_REQUIRE(c && mismatches && c->probe_bad, "lbmpm_rk3d_transport_probe_result: no probe was run");
+    LBMPM_REQUIRE(c, "null context");
     LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
-    unsigned long long v = 0;
-    LBMPM_HIP_TRY(hipMemcpyAsync(&v, c->probe_bad, sizeof v, hipMemcpyDeviceToHost, c->stream));
-    LBMPM_HIP_TRY(hipStreamSynchronize(c->stream));
-    *mismatches = (int64_t)v;
-    return LBMPM_OK;
+    return c->tx.probe_result(c->stream, mismatches);
 }
 
 extern "C" int lbmpm_transport_selftest(int kind, int device, int64_t bytes, const char *librccl_path)
 {
     LBMPM_REQUIRE((kind == LBMPM_TRANSPORT_IPC || kind == LBMPM_TRANSPORT_RCCL) && bytes >= 8 && bytes % 8 == 0, "lbmpm_transport_selftest: bad argument");
     LBMPM_HIP_TRY(hipSetDevice(device));
-    slabtx::Transport t;
+    slabtx::Transport t{"lbmpm_rk3d", slabtx::BLOB_MAGIC};      // (a transport of no model: it borrows the perturbation model's identity)
     const size_t n = (size_t)bytes / 8;
     double *up = nullptr, *dn = nullptr;
     hipStream_t st = nullptr;
@@ -2120,7 +2076,7 @@ extern "C" int lbmpm_transport_selftest(int kind, int device, int64_t bytes, con
         if (rc != LBMPM_OK) return done(rc);
         t.connected = true;
     } else {
-        rc = t.rccl.open(librccl_path);
+        rc = t.rccl.open(librccl_path);         // (not rccl_connect: a communicator of one rank that is its own neighbour both ways)
         if (rc != LBMPM_OK) return done(rc);
         slabtx::Rccl::UniqueId id;
         int e = t.rccl.GetUniqueId(&id);
@@ -2130,8 +2086,8 @@ extern "C" int lbmpm_transport_selftest(int kind, int device, int64_t bytes, con
     }
     std::vector<double> got(n);
     for (int round = 1; round <= 3; ++round) {          // three messages: both parities of the IPC slots, and the first one again
-        tx_fill<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st>>>(up, n, 1000. * round);
-        tx_fill<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st>>>(dn, n, -1000. * round);
+        slabtx::launch_probe_fill(st, up, n, 1000. * round);
+        slabtx::launch_probe_fill(st, dn, n, -1000. * round);
         const double *fb = nullptr, *fa = nullptr;
         rc = t.exchange(st, up, dn, &fb, &fa);
         if (rc != LBMPM_OK) return done(rc);
@@ -2213,11 +2169,7 @@ extern "C" int lbmpm_rk3d_step_slab(lbmpm_rk3d *c, int64_t nsteps, int has_below
         };
         // every error exit of this block goes through fail(): the lattice launches live on the second stream (advisor, round 5)
 #define SLAB_HIP_TRY(expr) do { const hipError_t e_ = (expr); if (e_ != hipSuccess) { set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); return fail(LBMPM_ERR_HIP); } } while (0)
-        if (!c->beat_host) {
-            SLAB_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&c->beat_host), 64, hipHostMallocMapped));
-            *c->beat_host = 0ull;
-            SLAB_HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void **>(&c->beat_dev), c->beat_host, 0));
-        }
+        SLAB_HIP_TRY(c->tx.beat_ready());
         if (!c->halo_valid) {
             int rc;
             if (own_tx) rc = lbmpm_rk3d_halo_exchange(c);
@@ -2300,7 +2252,7 @@ extern "C" int lbmpm_rk3d_step_slab(lbmpm_rk3d *c, int64_t nsteps, int has_below
                 else if (exchange(user, 0) != 0) { set_error("lbmpm_rk3d_step_slab: the exchange callback failed"); return fail(LBMPM_ERR_STATE); }
                 rk3dq_face_unpack<<<fgrid, fblock, 0, c->stream>>>(q, c->fB, c->purB, from_below, from_above, has_below, has_above);
                 rk3dq_halo_phi<<<fgrid, fblock, 0, c->stream>>>(q, from_below, from_above, has_below, has_above);
-                slabtx::launch_flag_store(c->stream, c->beat_dev, (unsigned long long)(c->steps + 1));      // "the exchange of this step is through"
+                c->tx.beat(c->stream, (unsigned long long)(c->steps + 1));      // "the exchange of this step is through"
                 if (ev[5]) SLAB_HIP_TRY(hipEventRecord(ev[5], c->stream));
                 SLAB_HIP_TRY(hipEventRecord(c->ev_dep, c->stream));
                 if (hipGetLastError() != hipSuccess) { set_error("lbmpm_rk3d_step_slab: kernel launch failed"); return fail(LBMPM_ERR_HIP); }
@@ -2364,7 +2316,7 @@ extern "C" int lbmpm_rk3d_step_slab(lbmpm_rk3d *c, int64_t nsteps, int has_below
             if (!(skip & 4)) {
                 rk3dq_face_unpack<<<fgrid, fblock, 0, c->stream>>>(q, c->fB, c->purB, from_below, from_above, has_below, has_above);
                 rk3dq_halo_phi<<<fgrid, fblock, 0, c->stream>>>(q, from_below, from_above, has_below, has_above);
-                slabtx::launch_flag_store(c->stream, c->beat_dev, (unsigned long long)(c->steps + 1));
+                c->tx.beat(c->stream, (unsigned long long)(c->steps + 1));
             }
             if (hipGetLastError() != hipSuccess) { set_error("lbmpm_rk3d_step_slab: face kernel launch failed"); return fail(LBMPM_ERR_HIP); }
             if (ev[5]) SLAB_HIP_TRY(hipEventRecord(ev[5], c->stream));
@@ -2491,71 +2443,22 @@ extern "C" int lbmpm_rk3d_sync(lbmpm_rk3d *c)
     return LBMPM_OK;
 }
 
-// The steady-state watchdog (include/lbmpm.h): host-side polling, so that a stream stuck in hipStreamWaitValue64 / flag_wait / an
-// ncclRecv on a neighbour that died does not hang this process for good.
-static int release_ipc_waits(lbmpm_rk3d *c)
-{
-    // from a private non-blocking stream: a copy on the legacy null stream would queue behind the very wait it is to release when the
-    // context runs on a blocking stream (advisor, round 5)
-    static const unsigned long long big[4] = {~0ull, ~0ull, ~0ull, ~0ull};
-    if (!c->wd_stream) LBMPM_HIP_TRY(hipStreamCreateWithFlags(&c->wd_stream, hipStreamNonBlocking));
-    LBMPM_HIP_TRY(hipMemcpyAsync(c->tx.flags, big, sizeof big, hipMemcpyHostToDevice, c->wd_stream));
-    LBMPM_HIP_TRY(hipStreamSynchronize(c->wd_stream));
-    return LBMPM_OK;
-}
-
+// The steady-state watchdog (include/lbmpm.h; slabtx::Transport::sync_deadline): the heartbeat is the step number that every slab step's
+// exchange chain writes (lbmpm_rk3d_step_slab)
 extern "C" int lbmpm_rk3d_sync_deadline(lbmpm_rk3d *c, double seconds)
 {
     LBMPM_REQUIRE(c && seconds > 0., "lbmpm_rk3d_sync_deadline: bad argument");
     LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
-    struct timespec t0, t;
-    clock_gettime(CLOCK_MONOTONIC, &t0);
-    auto idle = [&]() -> int {          // 1 idle, 0 busy, -1 error
-        hipError_t e = hipStreamQuery(c->stream);
-        if (e == hipSuccess && c->aux) e = hipStreamQuery(c->aux);
-        if (e == hipSuccess) return 1;
-        if (e == hipErrorNotReady) { (void)hipGetLastError(); return 0; }
-        set_error("lbmpm_rk3d_sync_deadline: %s", hipGetErrorString(e));
-        return -1;
-    };
-    // The deadline counts from the last PROGRESS, not from the call: every slab step's exchange chain ends by writing its step number
-    // into a pinned host word (lbmpm_rk3d_step_slab); while that word moves, the neighbours answer and the queued steps drain, however
-    // many there are and however slow a neighbour is (advisor, round 5: an absolute deadline voided healthy long queues).
-    volatile unsigned long long *beat = c->beat_host;
-    unsigned long long last = beat ? *beat : 0ull;
-    unsigned spins = 0;
-    for (;;) {
-        const int s = idle();
-        if (s == 1) return LBMPM_OK;
-        if (s < 0) return LBMPM_ERR_HIP;
-        clock_gettime(CLOCK_MONOTONIC, &t);
-        if (beat && *beat != last) { last = *beat; t0 = t; }
-        if ((double)(t.tv_sec - t0.tv_sec) + 1e-9 * (double)(t.tv_nsec - t0.tv_nsec) > seconds) break;
-        if (++spins > 2000) { struct timespec nap = {0, 200000}; nanosleep(&nap, nullptr); }       // busy for the first moments, then 0.2 ms naps
-    }
-    const int kind = c->tx.connected ? c->tx.kind : LBMPM_TRANSPORT_NONE;
-    if (kind == LBMPM_TRANSPORT_IPC) {
-        const int rc = release_ipc_waits(c);       // every wait of this context returns
-        if (rc != LBMPM_OK) return rc;
-        c->tx.dead = true;
-        (void)hipStreamSynchronize(c->stream);
-        if (c->aux) (void)hipStreamSynchronize(c->aux);
-    } else if (kind == LBMPM_TRANSPORT_RCCL) {
-        c->tx.dead = true;
-        if (c->tx.comm && c->tx.rccl.CommAbort) { (void)c->tx.rccl.CommAbort(c->tx.comm); c->tx.comm = nullptr; }
-        (void)hipStreamSynchronize(c->stream);
-        if (c->aux) (void)hipStreamSynchronize(c->aux);
-    }
-    if (kind != LBMPM_TRANSPORT_NONE) {      // (nothing released: the work is still running, the step protocol's flags stay what they are)
+    char where[96];
+    snprintf(where, sizeof where, "rank with planes %d..%d of %d", (int)c->cfg.z_offset, (int)(c->cfg.z_offset + c->cfg.nz_local) - 1, (int)c->cfg.nz_global);
+    const hipStream_t streams[2] = {c->stream, c->aux};
+    int gave_up = LBMPM_TRANSPORT_NONE;
+    const int rc = c->tx.sync_deadline(streams, c->aux ? 2 : 1, seconds, where, &gave_up);
+    if (rc == LBMPM_ERR_TIMEOUT && gave_up != LBMPM_TRANSPORT_NONE) {      // (nothing released: the step protocol's flags stay what they are)
         c->halo_valid = false;
         c->interior_pending = false;
     }
-    set_error("lbmpm_rk3d_sync_deadline: the slab's streams were busy and no face exchange completed for %.1f s -- %s (rank with planes %d..%d of %d)", seconds,
-              kind == LBMPM_TRANSPORT_IPC ? "a neighbour's face message did not arrive; the waits were released, the lattice state is void" :
-              kind == LBMPM_TRANSPORT_RCCL ? "a neighbour did not answer; the communicator was aborted, the lattice state is void" :
-                                             "no in-library transport is connected: nothing was released",
-              c->cfg.z_offset, c->cfg.z_offset + c->cfg.nz_local - 1, c->cfg.nz_global);
-    return LBMPM_ERR_TIMEOUT;
+    return rc;
 }
 
 extern "C" int lbmpm_rk3d_buffer(lbmpm_rk3d *c, int which, void **ptr, int64_t *bytes)

@@ -1037,12 +1037,9 @@ struct lbmpm_rk3dcsf {
     size_t timed_steps = 0;
     // slabs whose face messages travel over a transport inside the library (lbmpm_rk3dcsf_ipc_* / _rccl_connect, _step_slab): nothing of
     // this is allocated before a connect
-    slabtx::Transport tx;
+    slabtx::Transport tx{"lbmpm_rk3dcsf", slabtx::BLOB_MAGIC_CSF};
     double *send_lo = nullptr, *send_hi = nullptr;      // the message through the low / high face, packed (the largest of the three kinds)
     bool tx_released = false;                           // lbmpm_rk3dcsf_ipc_release_waits: the flags say "arrived" for every message to come
-    unsigned long long *probe_bad = nullptr;            // mismatch counter of lbmpm_rk3dcsf_transport_probe
-    unsigned long long *beat_host = nullptr, *beat_dev = nullptr;     // heartbeat of lbmpm_rk3dcsf_sync_deadline (pinned host word)
-    hipStream_t wd_stream = nullptr;                    // the watchdog's own copies
     lbmpm::EventPool slab_pool;                         // lbmpm_rk3dcsf_step_slab(timed): 6 event pairs per step {stage, message} x 3
     int64_t slab_timed_steps = 0;
     // tracers (lbmpm_rk3dcsf_tracer_*; rk3d_tracer.h): nothing of this is allocated before a configure
@@ -1205,10 +1202,8 @@ extern "C" void lbmpm_rk3dcsf_destroy(lbmpm_rk3dcsf *c)
     (void)hipSetDevice(c->cfg.device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->stream2) (void)hipStreamSynchronize(c->stream2);
-    c->tx.disconnect();
-    for (void *q : {(void *)c->send_lo, (void *)c->send_hi, (void *)c->probe_bad}) if (q) (void)hipFree(q);
-    if (c->beat_host) (void)hipHostFree(c->beat_host);
-    if (c->wd_stream) (void)hipStreamDestroy(c->wd_stream);
+    c->tx.destroy();
+    for (void *q : {(void *)c->send_lo, (void *)c->send_hi}) if (q) (void)hipFree(q);
     c->slab_pool.destroy();
     void *ptrs[] = {c->gA, c->gB, c->trflow, c->trsrc, c->wethome, c->rng, c->pfx, c->pure, c->deep_prev, c->bcblk, c->deep_now, c->work, c->tcnt, c->src, c->dom, c->meta, c->wetlist, c->cidx, c->cells, c->fA, c->fB, c->phi, c->G, c->nh, c->F, c->K, c->U, c->ns, c->obs};
     for (void *q : ptrs) if (q) (void)hipFree(q);
@@ -1803,7 +1798,6 @@ extern "C" const char *lbmpm_rk3dcsf_dominant_kernel(const lbmpm_rk3dcsf *c) { (
 // ---- the three face messages over a transport inside the library (include/lbmpm.h, CSF block; rk3d_transport.h, shared with the
 // perturbation model's slabs)
 namespace {
-constexpr uint32_t CSF_BLOB_MAGIC = 0x4c424d43u;        // "LBMC" (the perturbation model's blobs: "LBMP")
 constexpr int STEP_MSGS[3] = {LBMPM_CSF_MSG_PHI, LBMPM_CSF_MSG_NORMAL, LBMPM_CSF_MSG_PDF};       // the message after stage 0, 1, 2
 const char *msg_name(int m) { return m == LBMPM_CSF_MSG_PHI ? "phi" : m == LBMPM_CSF_MSG_NORMAL ? "n" : "populations"; }
 
@@ -1848,15 +1842,6 @@ int tx_shape(lbmpm_rk3dcsf *c, const char *who)
     return rc;
 }
 
-// closes what ipc_connect opened before it failed: the context can connect again
-void ipc_unmap(lbmpm_rk3dcsf *c)
-{
-    for (int s = 0; s < 2; ++s) {
-        if (c->tx.mapped[s]) { (void)hipIpcCloseMemHandle(c->tx.peer_land[s]); (void)hipIpcCloseMemHandle(c->tx.peer_flags[s]); }
-        c->tx.peer_land[s] = nullptr; c->tx.peer_flags[s] = nullptr; c->tx.mapped[s] = false;
-    }
-}
-
 // one message kind through both faces, enqueued on the context's stream: pack -> transport -> unpack straight from the landing slots
 int tx_message(lbmpm_rk3dcsf *c, int msg)
 {
@@ -1878,23 +1863,6 @@ int tx_usable(lbmpm_rk3dcsf *c, const char *who)
     return LBMPM_OK;
 }
 
-int release_waits(lbmpm_rk3dcsf *c)
-{
-    // from a private non-blocking stream: a copy on a stream that sits in the wait would never run
-    static const unsigned long long big[4] = {~0ull, ~0ull, ~0ull, ~0ull};
-    if (!c->wd_stream) LBMPM_HIP_TRY(hipStreamCreateWithFlags(&c->wd_stream, hipStreamNonBlocking));
-    LBMPM_HIP_TRY(hipMemcpyAsync(c->tx.flags, big, sizeof big, hipMemcpyHostToDevice, c->wd_stream));
-    LBMPM_HIP_TRY(hipStreamSynchronize(c->wd_stream));
-    c->tx_released = true;
-    return LBMPM_OK;
-}
-
-__global__ void csf3d_tx_fill(double *p, size_t n, double v) { const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; if (i < n) p[i] = v + (double)i; }
-__global__ void csf3d_tx_check(const double *p, size_t n, double v, unsigned long long *bad)
-{
-    const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
-    if (i < n && p[i] != v + (double)i) atomicAdd(bad, 1ull);
-}
 }  // namespace
 
 extern "C" int lbmpm_rk3dcsf_ipc_init(lbmpm_rk3dcsf *c, void *blob_out)
@@ -1904,7 +1872,7 @@ extern "C" int lbmpm_rk3dcsf_ipc_init(lbmpm_rk3dcsf *c, void *blob_out)
     if (rc != LBMPM_OK) return rc;
     CsfBlob b;
     memset(&b, 0, sizeof b);
-    rc = c->tx.ipc_alloc(&b.base, CSF_BLOB_MAGIC);
+    rc = c->tx.ipc_alloc(&b.base);
     if (rc != LBMPM_OK) { tx_drop(c); return rc; }
     for (int m = 0; m < 3; ++m) { b.in_lo[m] = msg_bytes(c, m, 0, true); b.in_hi[m] = msg_bytes(c, m, 1, true); }
     b.z0 = (int32_t)c->cfg.slab_z0; b.z1 = own_z1(c); b.nzg = c->nzg; b.ntr = c->ntr;
@@ -1926,7 +1894,7 @@ extern "C" int lbmpm_rk3dcsf_ipc_connect(lbmpm_rk3dcsf *c, const void *blob_low,
     for (int side = 0; side < 2; ++side) {
         const CsfBlob &n = b[side];
         const char *where = side == 0 ? "low" : "high";
-        LBMPM_REQUIRE(n.base.magic == CSF_BLOB_MAGIC && n.base.version == slabtx::BLOB_VERSION,
+        LBMPM_REQUIRE(n.base.magic == c->tx.magic && n.base.version == slabtx::BLOB_VERSION,
                       "lbmpm_rk3dcsf_ipc_connect: the %s neighbour's bytes are not a blob of lbmpm_rk3dcsf_ipc_init", where);
         LBMPM_REQUIRE(n.nzg == nzg && n.nzg > 0 && (side == 0 ? n.z1 % nzg == z0 : n.z0 == z1 % nzg),
                       "lbmpm_rk3dcsf_ipc_connect: the %s neighbour holds the planes [%d, %d) of %d -- not the slab next to this one's [%d, %d) of %d (other cuts)",
@@ -1940,12 +1908,12 @@ extern "C" int lbmpm_rk3dcsf_ipc_connect(lbmpm_rk3dcsf *c, const void *blob_low,
         }
     }
     LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
-    int rc = c->tx.ipc_open(0, &b[0].base, c->tx.bytes_dn, CSF_BLOB_MAGIC);
+    int rc = c->tx.ipc_open(0, &b[0].base, c->tx.bytes_dn);
     if (rc == LBMPM_OK) {
         if (!memcmp(&b[0].base, &b[1].base, sizeof b[0].base)) c->tx.ipc_share(1, 0);     // a ring of two: one peer, mapped once
-        else rc = c->tx.ipc_open(1, &b[1].base, c->tx.bytes_up, CSF_BLOB_MAGIC);
+        else rc = c->tx.ipc_open(1, &b[1].base, c->tx.bytes_up);
     }
-    if (rc != LBMPM_OK) { ipc_unmap(c); return rc; }
+    if (rc != LBMPM_OK) { c->tx.unmap(); return rc; }       // (the context can connect again)
     c->tx.ring = true; c->tx.connected = true; c->tx.seq = 0;
     return LBMPM_OK;
 }
@@ -1955,15 +1923,9 @@ extern "C" int lbmpm_rk3dcsf_rccl_connect(lbmpm_rk3dcsf *c, const void *id, int 
     LBMPM_REQUIRE(c && id && nranks >= 2 && rank >= 0 && rank < nranks, "lbmpm_rk3dcsf_rccl_connect: bad argument (a ring of two ranks or more)");
     int rc = tx_shape(c, "lbmpm_rk3dcsf_rccl_connect");
     if (rc != LBMPM_OK) return rc;
-    rc = c->tx.rccl.open(librccl_path);
-    if (rc != LBMPM_OK) { tx_drop(c); return rc; }
-    slabtx::Rccl::UniqueId uid;
-    memcpy(&uid, id, sizeof uid);
-    const int e = c->tx.rccl.CommInitRank(&c->tx.comm, nranks, uid, rank);
-    if (e != 0) { set_error("ncclCommInitRank(rank %d of %d): %s", rank, nranks, c->tx.rccl.GetErrorString(e)); tx_drop(c); return LBMPM_ERR_HIP; }
-    c->tx.rank = rank; c->tx.nranks = nranks; c->tx.peer_up = (rank + 1) % nranks; c->tx.peer_dn = (rank + nranks - 1) % nranks;
-    c->tx.ring = true; c->tx.kind = LBMPM_TRANSPORT_RCCL; c->tx.connected = true; c->tx.seq = 0;
-    return LBMPM_OK;
+    rc = c->tx.rccl_connect(id, rank, nranks, librccl_path, true);
+    if (rc != LBMPM_OK) tx_drop(c);
+    return rc;
 }
 
 extern "C" int lbmpm_rk3dcsf_transport_disconnect(lbmpm_rk3dcsf *c)
@@ -1976,18 +1938,15 @@ extern "C" int lbmpm_rk3dcsf_transport_disconnect(lbmpm_rk3dcsf *c)
     return LBMPM_OK;
 }
 
-extern "C" int lbmpm_rk3dcsf_transport_kind(lbmpm_rk3dcsf *c, int *value_ops)
-{
-    if (!c) return LBMPM_TRANSPORT_NONE;
-    if (value_ops) *value_ops = c->tx.kind == LBMPM_TRANSPORT_IPC && c->tx.value_ops ? 1 : 0;
-    return c->tx.connected ? c->tx.kind : LBMPM_TRANSPORT_NONE;
-}
+extern "C" int lbmpm_rk3dcsf_transport_kind(lbmpm_rk3dcsf *c, int *value_ops) { return c ? c->tx.kind_for_caller(value_ops) : LBMPM_TRANSPORT_NONE; }
 
 extern "C" int lbmpm_rk3dcsf_ipc_release_waits(lbmpm_rk3dcsf *c)
 {
-    LBMPM_REQUIRE(c && c->tx.kind == LBMPM_TRANSPORT_IPC && c->tx.flags, "lbmpm_rk3dcsf_ipc_release_waits: no IPC transport");
+    LBMPM_REQUIRE(c, "null context");
     LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
-    return release_waits(c);
+    const int rc = c->tx.ipc_release_waits();
+    if (rc == LBMPM_OK) c->tx_released = true;
+    return rc;
 }
 
 // `rounds` x the three message kinds, patterned, each way through the send buffers and landing slots at the sizes of a step, compared on
@@ -1997,35 +1956,21 @@ extern "C" int lbmpm_rk3dcsf_transport_probe(lbmpm_rk3dcsf *c, int rounds)
     LBMPM_REQUIRE(c && rounds >= 1, "lbmpm_rk3dcsf_transport_probe: bad argument");
     { const int rc = tx_usable(c, "lbmpm_rk3dcsf_transport_probe"); if (rc != LBMPM_OK) return rc; }
     LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
-    if (!c->probe_bad) LBMPM_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&c->probe_bad), sizeof(unsigned long long)));
-    LBMPM_HIP_TRY(hipMemsetAsync(c->probe_bad, 0, sizeof(unsigned long long), c->stream));
-    auto grid = [](size_t n) { return dim3((unsigned)((n + 255) / 256)); };
+    int rc = c->tx.probe_begin(c->stream);
     for (int r = 0; r < rounds; ++r)
-        for (int k = 0; k < 3; ++k) {
+        for (int k = 0; k < 3 && rc == LBMPM_OK; ++k) {
             const int m = STEP_MSGS[k];
-            const size_t nu = msg_bytes(c, m, 1, false) / 8, nd = msg_bytes(c, m, 0, false) / 8, nb = msg_bytes(c, m, 0, true) / 8, na = msg_bytes(c, m, 1, true) / 8;
-            const double up = 1000. * (3 * r + k + 1) + 1., dn = -up;
-            if (nu) csf3d_tx_fill<<<grid(nu), 256, 0, c->stream>>>(c->send_hi, nu, up);
-            if (nd) csf3d_tx_fill<<<grid(nd), 256, 0, c->stream>>>(c->send_lo, nd, dn);
-            const double *fb = nullptr, *fa = nullptr;
-            const int rc = c->tx.exchange(c->stream, c->send_hi, c->send_lo, 8 * nu, 8 * nd, 8 * nb, 8 * na, &fb, &fa);
-            if (rc != LBMPM_OK) return rc;
-            if (nb) csf3d_tx_check<<<grid(nb), 256, 0, c->stream>>>(fb, nb, up, c->probe_bad);      // what the low neighbour sent up
-            if (na) csf3d_tx_check<<<grid(na), 256, 0, c->stream>>>(fa, na, dn, c->probe_bad);      // what the high neighbour sent down
-            LBMPM_HIP_TRY(hipGetLastError());
+            rc = c->tx.probe_round(c->stream, c->send_hi, c->send_lo, msg_bytes(c, m, 1, false) / 8, msg_bytes(c, m, 0, false) / 8,
+                                   msg_bytes(c, m, 0, true) / 8, msg_bytes(c, m, 1, true) / 8, 1000. * (3 * r + k + 1) + 1.);
         }
-    return LBMPM_OK;
+    return rc;
 }
 
 extern "C" int lbmpm_rk3dcsf_transport_probe_result(lbmpm_rk3dcsf *c, int64_t *mismatches)
 {
-    LBMPM_REQUIRE(c && mismatches && c->probe_bad, "lbmpm_rk3dcsf_transport_probe_result: no probe was run");
+    LBMPM_REQUIRE(c, "null context");
     LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
-    unsigned long long v = 0;
-    LBMPM_HIP_TRY(hipMemcpyAsync(&v, c->probe_bad, sizeof v, hipMemcpyDeviceToHost, c->stream));
-    LBMPM_HIP_TRY(hipStreamSynchronize(c->stream));
-    *mismatches = (int64_t)v;
-    return LBMPM_OK;
+    return c->tx.probe_result(c->stream, mismatches);
 }
 
 // n whole steps of a connected slab behind ONE call, enqueued on the context's stream without a host synchronisation:
@@ -2038,11 +1983,7 @@ extern "C" int lbmpm_rk3dcsf_step_slab(lbmpm_rk3dcsf *c, int64_t nsteps, int tim
     if (!c->have_state) { set_error("lbmpm_rk3dcsf_step_slab before set_macro / set_pdf"); return LBMPM_ERR_STATE; }
     if (c->next_stage != 0) { set_error("lbmpm_rk3dcsf_step_slab: stage %d of a step begun with lbmpm_rk3dcsf_stage is next", c->next_stage); return LBMPM_ERR_STATE; }
     LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
-    if (!c->beat_host) {
-        LBMPM_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&c->beat_host), 64, hipHostMallocMapped));
-        *c->beat_host = 0ull;
-        LBMPM_HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void **>(&c->beat_dev), c->beat_host, 0));
-    }
+    LBMPM_HIP_TRY(c->tx.beat_ready());
     const int64_t tsteps = timed ? (nsteps < 256 ? nsteps : 256) : 0;
     if (timed) {
         if (c->slab_pool.reserve((size_t)(6 * tsteps)) != LBMPM_OK) { set_error("hipEventCreate failed"); return LBMPM_ERR_HIP; }
@@ -2061,7 +2002,7 @@ extern "C" int lbmpm_rk3dcsf_step_slab(lbmpm_rk3dcsf *c, int64_t nsteps, int tim
             if (rc != LBMPM_OK) return rc;           // (the state is void: set_macro / set_pdf before the next step)
             if (ev[3]) LBMPM_HIP_TRY(hipEventRecord(ev[3], c->stream));
         }
-        slabtx::launch_flag_store(c->stream, c->beat_dev, (unsigned long long)c->steps);     // "this step's messages are through"
+        c->tx.beat(c->stream, (unsigned long long)c->steps);     // "this step's messages are through"
         LBMPM_HIP_TRY(hipGetLastError());
     }
     return LBMPM_OK;
@@ -2095,47 +2036,16 @@ extern "C" int lbmpm_rk3dcsf_sync_deadline(lbmpm_rk3dcsf *c, double seconds)
 {
     LBMPM_REQUIRE(c && seconds > 0., "lbmpm_rk3dcsf_sync_deadline: bad argument");
     LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
-    struct timespec t0, t;
-    clock_gettime(CLOCK_MONOTONIC, &t0);
-    auto idle = [&]() -> int {          // 1 idle, 0 busy, -1 error
-        hipError_t e = hipStreamQuery(c->stream);
-        if (e == hipSuccess) e = hipStreamQuery(c->stream2);
-        if (e == hipSuccess) return 1;
-        if (e == hipErrorNotReady) { (void)hipGetLastError(); return 0; }
-        set_error("lbmpm_rk3dcsf_sync_deadline: %s", hipGetErrorString(e));
-        return -1;
-    };
-    volatile unsigned long long *beat = c->beat_host;
-    unsigned long long last = beat ? *beat : 0ull;
-    unsigned spins = 0;
-    for (;;) {
-        const int s = idle();
-        if (s == 1) return LBMPM_OK;
-        if (s < 0) return LBMPM_ERR_HIP;
-        clock_gettime(CLOCK_MONOTONIC, &t);
-        if (beat && *beat != last) { last = *beat; t0 = t; }
-        if ((double)(t.tv_sec - t0.tv_sec) + 1e-9 * (double)(t.tv_nsec - t0.tv_nsec) > seconds) break;
-        if (++spins > 2000) { struct timespec nap = {0, 200000}; nanosleep(&nap, nullptr); }
-    }
-    const int kind = c->tx.connected ? c->tx.kind : LBMPM_TRANSPORT_NONE;
-    if (kind == LBMPM_TRANSPORT_IPC) {
-        const int rc = release_waits(c);
-        if (rc != LBMPM_OK) return rc;
-    } else if (kind == LBMPM_TRANSPORT_RCCL) {
-        if (c->tx.comm && c->tx.rccl.CommAbort) { (void)c->tx.rccl.CommAbort(c->tx.comm); c->tx.comm = nullptr; }
-    }
-    if (kind != LBMPM_TRANSPORT_NONE) {
-        c->tx.dead = true;
-        (void)hipStreamSynchronize(c->stream);
-        (void)hipStreamSynchronize(c->stream2);
+    char where[96];
+    snprintf(where, sizeof where, "slab of the planes %d..%d of %d", (int)c->cfg.slab_z0, own_z1(c) - 1, c->nzg);
+    const hipStream_t streams[2] = {c->stream, c->stream2};
+    int gave_up = LBMPM_TRANSPORT_NONE;
+    const int rc = c->tx.sync_deadline(streams, 2, seconds, where, &gave_up);
+    if (rc == LBMPM_ERR_TIMEOUT && gave_up != LBMPM_TRANSPORT_NONE) {
         c->have_state = false;
+        if (gave_up == LBMPM_TRANSPORT_IPC) c->tx_released = true;
     }
-    set_error("lbmpm_rk3dcsf_sync_deadline: the slab's streams were busy and no step's messages came through for %.1f s -- %s (slab of the planes %d..%d of %d)", seconds,
-              kind == LBMPM_TRANSPORT_IPC ? "a neighbour's face message did not arrive; the waits were released, the lattice state is void" :
-              kind == LBMPM_TRANSPORT_RCCL ? "a neighbour did not answer; the communicator was aborted, the lattice state is void" :
-                                             "no in-library transport is connected: nothing was released",
-              (int)c->cfg.slab_z0, own_z1(c) - 1, c->nzg);
-    return LBMPM_ERR_TIMEOUT;
+    return rc;
 }
 
 // ---- D3Q7 tracers advected by the CSF flow (include/lbmpm.h, end of the CSF block; kernels: rk3d_tracer.h)

@@ -1,8 +1,16 @@
 // rk3d_transport.h -- the slab exchange's transports inside the library (include/lbmpm.h, "Transport of the slab exchange"):
 // IPC landing areas filled by copy-engine transfers and stream value operations, or ncclSend / ncclRecv of a librccl opened at run
-// time.  Included by rk3d.hip (the perturbation model's slabs) and rk3d_csf.hip (the CSF model's slabs): host code only.  The two one-lane
-// kernels -- the fallback of devices without stream value operations, and the slab step's heartbeat -- live in rk3d_transport.hip, ONE
-// translation unit, and are launched through the two functions below.
+// time.  Included by rk3d.hip (the perturbation model's slabs) and rk3d_csf.hip (the CSF model's slabs): host code only.  What both
+// models share lives here, once:
+//   * the blob, its check and the mapping of the neighbours' landing areas (ipc_alloc / ipc_open / ipc_share / unmap), under the
+//     identity -- API prefix of the error messages and blob magic -- the owning context gives its Transport once;
+//   * the communicator of the RCCL transport, for the chain or the ring of slabs (rccl_connect);
+//   * the per-step exchange (exchange) and the heartbeat its steps write (beat_ready / beat);
+//   * the probe of a connected transport (probe_begin / probe_round / probe_result);
+//   * the watchdog (release_waits / ipc_release_waits / sync_deadline) and the clean-up (disconnect / destroy).
+// The model files keep their argument checks, their message sizes and loops, and what a failure voids of their own state.  The
+// kernels -- two one-lane ones (the fallback of devices without stream value operations, and the heartbeat) and the probe's pair --
+// live in rk3d_transport.hip, ONE translation unit, and are launched through the functions below.
 #include <dlfcn.h>
 #include <unistd.h>
 #include <time.h>
@@ -15,6 +23,9 @@ using lbmpm::set_error;
 // flag_store<<<1, 1, 0, st>>>(f, v) / flag_wait<<<1, 1, 0, st>>>(f, v) (rk3d_transport.hip); the caller checks hipGetLastError
 void launch_flag_store(hipStream_t st, unsigned long long *f, unsigned long long v);
 void launch_flag_wait(hipStream_t st, unsigned long long *f, unsigned long long v);
+// the probe's pattern p[i] = v + i written / compared (mismatches counted in *bad), n doubles; n > 0
+void launch_probe_fill(hipStream_t st, double *p, size_t n, double v);
+void launch_probe_check(hipStream_t st, const double *p, size_t n, double v, unsigned long long *bad);
 
 // what a rank tells its neighbours (LBMPM_IPC_BLOB_BYTES)
 struct IpcBlob {
@@ -28,7 +39,8 @@ struct IpcBlob {
                                           // containers or pid namespaces of one node commonly share a pid, e.g. 1)
 };
 static_assert(sizeof(IpcBlob) <= LBMPM_IPC_BLOB_BYTES, "blob size is part of the ABI");
-constexpr uint32_t BLOB_MAGIC = 0x4c424d50u;     // "LBMP"
+constexpr uint32_t BLOB_MAGIC = 0x4c424d50u;     // "LBMP": the perturbation model's blobs
+constexpr uint32_t BLOB_MAGIC_CSF = 0x4c424d43u; // "LBMC": the CSF model's (a CsfBlob around the IpcBlob)
 constexpr uint32_t BLOB_VERSION = 2;
 
 // one random 64-bit value per process (from /dev/urandom; pid, clock and an address as the fallback)
@@ -88,6 +100,9 @@ struct Rccl {
 };
 
 struct Transport {
+    // ---- identity, given once where the owner is made: Transport tx{"lbmpm_rk3d", BLOB_MAGIC}
+    const char *api = nullptr;                // the owner's API prefix: every error message names the caller's own functions
+    uint32_t magic = 0;                       // of the owner's blobs
     int kind = LBMPM_TRANSPORT_NONE;
     int device = 0;
     bool has_below = false, has_above = false;
@@ -105,7 +120,11 @@ struct Transport {
     bool mapped[2] = {false, false};          // peer_* came from hipIpcOpenMemHandle (to be closed)
     bool value_ops = false;
     bool connected = false;
-    bool dead = false;                        // the steady-state watchdog gave up on a neighbour (lbmpm_rk3d_sync_deadline)
+    bool dead = false;                        // the steady-state watchdog gave up on a neighbour (sync_deadline)
+    // ---- watchdog and probe (kept over disconnect, freed by destroy)
+    hipStream_t wd_stream = nullptr;          // the watchdog's own copies
+    unsigned long long *beat_host = nullptr, *beat_dev = nullptr;     // heartbeat: a pinned host word the slab steps write their number into
+    unsigned long long *probe_bad = nullptr;  // mismatch counter of the probe
     // ---- RCCL
     Rccl rccl;
     void *comm = nullptr;
@@ -119,7 +138,7 @@ struct Transport {
 
     int set_shape(int dev, bool below, bool above, size_t up, size_t dn, size_t from_below, size_t from_above)
     {
-        if (kind != LBMPM_TRANSPORT_NONE) { set_error("a transport is connected already: lbmpm_rk3d_transport_disconnect first"); return LBMPM_ERR_STATE; }
+        if (kind != LBMPM_TRANSPORT_NONE) { set_error("a transport is connected already: %s_transport_disconnect first", api); return LBMPM_ERR_STATE; }
         device = dev; has_below = below; has_above = above; bytes_up = up; bytes_dn = dn; bytes_from_below = from_below; bytes_from_above = from_above;
         const size_t m = from_below > from_above ? from_below : from_above;
         slot = (m + 4095) / 4096 * 4096;
@@ -143,7 +162,7 @@ struct Transport {
         return LBMPM_OK;
     }
 
-    int ipc_alloc(IpcBlob *blob, uint32_t magic = BLOB_MAGIC)
+    int ipc_alloc(IpcBlob *blob)
     {
         const int dev = device;
         const bool below = has_below, above = has_above;
@@ -167,19 +186,16 @@ struct Transport {
         return LBMPM_OK;
     }
 
-    int ipc_open(int side, const IpcBlob *b, size_t my_bytes, uint32_t magic = BLOB_MAGIC)
+    int ipc_open(int side, const IpcBlob *b, size_t my_bytes)
     {
-        if (b->magic != magic || b->version != BLOB_VERSION) {
-            set_error("%s: not a blob of %s", magic == BLOB_MAGIC ? "lbmpm_rk3d_ipc_connect" : "lbmpm_rk3dcsf_ipc_connect", magic == BLOB_MAGIC ? "lbmpm_rk3d_ipc_init" : "lbmpm_rk3dcsf_ipc_init");
-            return LBMPM_ERR_INVALID;
-        }
+        if (b->magic != magic || b->version != BLOB_VERSION) { set_error("%s_ipc_connect: not a blob of %s_ipc_init", api, api); return LBMPM_ERR_INVALID; }
         const uint64_t theirs = side == 0 ? b->bytes_from_above : b->bytes_from_below;     // the rank below receives "from above"
         if (theirs != my_bytes) {
-            set_error("lbmpm_rk3d_ipc_connect: the rank %s expects %llu bytes per message, this rank sends %llu (different cuts or lattices)",
+            set_error("%s_ipc_connect: the rank %s expects %llu bytes per message, this rank sends %llu (different cuts or lattices)", api,
                       side == 0 ? "below" : "above", (unsigned long long)theirs, (unsigned long long)my_bytes);
             return LBMPM_ERR_INVALID;
         }
-        if (b->slot_bytes < my_bytes) { set_error("lbmpm_rk3d_ipc_connect: the neighbour's slots are smaller than the message"); return LBMPM_ERR_INVALID; }
+        if (b->slot_bytes < my_bytes) { set_error("%s_ipc_connect: the neighbour's slots are smaller than the message", api); return LBMPM_ERR_INVALID; }
         peer_slot[side] = (size_t)b->slot_bytes;
         if (b->pid == (int32_t)getpid() && b->nonce == process_nonce()) {      // a slab of this very process: plain pointers (peer access if it lives on another GPU)
             if (b->device != device) {
@@ -209,6 +225,39 @@ struct Transport {
     void ipc_share(int to, int from)
     {
         peer_land[to] = peer_land[from]; peer_flags[to] = peer_flags[from]; peer_slot[to] = peer_slot[from]; mapped[to] = false;
+    }
+
+    // closes what ipc_open mapped (a connect that failed half way can be tried again; disconnect)
+    void unmap()
+    {
+        for (int s = 0; s < 2; ++s) {
+            if (mapped[s]) { (void)hipIpcCloseMemHandle(peer_land[s]); (void)hipIpcCloseMemHandle(peer_flags[s]); }
+            peer_land[s] = nullptr; peer_flags[s] = nullptr; mapped[s] = false;
+        }
+    }
+
+    // librccl opened, ncclCommInitRank (a blocking collective over the nranks ranks), the neighbours' ranks: rank -+ 1 in the chain of
+    // slabs, modulo nranks in the ring.  After set_shape; a failure leaves the clean-up (disconnect) to the caller.
+    int rccl_connect(const void *id, int rank_, int nranks_, const char *librccl_path, bool ring_)
+    {
+        const int rc = rccl.open(librccl_path);
+        if (rc != LBMPM_OK) return rc;
+        Rccl::UniqueId uid;
+        memcpy(&uid, id, sizeof uid);
+        if (hipSetDevice(device) != hipSuccess) { set_error("hipSetDevice(%d) failed", device); return LBMPM_ERR_HIP; }
+        const int e = rccl.CommInitRank(&comm, nranks_, uid, rank_);
+        if (e != 0) { set_error("ncclCommInitRank(rank %d of %d): %s", rank_, nranks_, rccl.GetErrorString(e)); return LBMPM_ERR_HIP; }
+        rank = rank_; nranks = nranks_; ring = ring_;
+        peer_up = ring ? (rank + 1) % nranks : rank + 1; peer_dn = ring ? (rank + nranks - 1) % nranks : rank - 1;
+        kind = LBMPM_TRANSPORT_RCCL; connected = true; seq = 0;
+        return LBMPM_OK;
+    }
+
+    // what lbmpm_*_transport_kind answers
+    int kind_for_caller(int *value_ops_out) const
+    {
+        if (value_ops_out) *value_ops_out = kind == LBMPM_TRANSPORT_IPC && value_ops ? 1 : 0;
+        return connected ? kind : LBMPM_TRANSPORT_NONE;
     }
 
     // One message each way, enqueued on `st`: send_up -> the rank above, send_dn -> the rank below; *from_below / *from_above = where
@@ -273,12 +322,113 @@ struct Transport {
         return LBMPM_ERR_STATE;
     }
 
+    // ---- the heartbeat: every slab step's exchange chain ends by writing its step number into a pinned host word (sync_deadline reads it)
+    hipError_t beat_ready()
+    {
+        if (beat_dev) return hipSuccess;
+        if (!beat_host) {
+            const hipError_t e = hipHostMalloc(reinterpret_cast<void **>(&beat_host), 64, hipHostMallocMapped);
+            if (e != hipSuccess) { beat_host = nullptr; return e; }
+            *beat_host = 0ull;
+        }
+        return hipHostGetDevicePointer(reinterpret_cast<void **>(&beat_dev), beat_host, 0);
+    }
+    void beat(hipStream_t st, unsigned long long v) { launch_flag_store(st, beat_dev, v); }      // after beat_ready; the caller checks hipGetLastError
+
+    // ---- Probe of the CONNECTED transport between the real neighbours, enqueued on `st` (the caller polls the stream under a deadline,
+    // then reads the verdict): probe_begin, then rounds of one patterned message each way -- written into the (still unused) send
+    // buffers, exchanged, and compared on the receiving side by a kernel launched behind the transport's waits.
+    int probe_begin(hipStream_t st)
+    {
+        if (!probe_bad) LBMPM_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&probe_bad), sizeof(unsigned long long)));
+        LBMPM_HIP_TRY(hipMemsetAsync(probe_bad, 0, sizeof(unsigned long long), st));
+        return LBMPM_OK;
+    }
+    // nu / nd doubles go up / down as value + i / -value + i, nb / na doubles arrive from below / above (0: no message that way)
+    int probe_round(hipStream_t st, double *send_up, double *send_dn, size_t nu, size_t nd, size_t nb, size_t na, double value)
+    {
+        if (nu) launch_probe_fill(st, send_up, nu, value);
+        if (nd) launch_probe_fill(st, send_dn, nd, -value);
+        const double *fb = nullptr, *fa = nullptr;
+        const int rc = exchange(st, send_up, send_dn, 8 * nu, 8 * nd, 8 * nb, 8 * na, &fb, &fa);
+        if (rc != LBMPM_OK) return rc;
+        if (nb) launch_probe_check(st, fb, nb, value, probe_bad);        // what the rank below sent up
+        if (na) launch_probe_check(st, fa, na, -value, probe_bad);       // what the rank above sent down
+        LBMPM_HIP_TRY(hipGetLastError());
+        return LBMPM_OK;
+    }
+    // verdict of the last probe: doubles that arrived different from what the neighbour sent (synchronises `st`)
+    int probe_result(hipStream_t st, int64_t *mismatches)
+    {
+        if (!mismatches || !probe_bad) { set_error("%s_transport_probe_result: no probe was run", api); return LBMPM_ERR_INVALID; }
+        unsigned long long v = 0;
+        LBMPM_HIP_TRY(hipMemcpyAsync(&v, probe_bad, sizeof v, hipMemcpyDeviceToHost, st));
+        LBMPM_HIP_TRY(hipStreamSynchronize(st));
+        *mismatches = (int64_t)v;
+        return LBMPM_OK;
+    }
+
+    // ---- The steady-state watchdog (include/lbmpm.h): host-side polling, so that a stream stuck in hipStreamWaitValue64 / flag_wait / an
+    // ncclRecv on a neighbour that died does not hang this process for good.
+    // every IPC wait of this slab returns: the flags say "arrived" for every message to come
+    int release_waits()
+    {
+        // from a private non-blocking stream: a copy on the legacy null stream would queue behind the very wait it is to release when the
+        // context runs on a blocking stream, and one on a stream that sits in the wait would never run
+        static const unsigned long long big[4] = {~0ull, ~0ull, ~0ull, ~0ull};
+        if (!wd_stream) LBMPM_HIP_TRY(hipStreamCreateWithFlags(&wd_stream, hipStreamNonBlocking));
+        LBMPM_HIP_TRY(hipMemcpyAsync(flags, big, sizeof big, hipMemcpyHostToDevice, wd_stream));
+        LBMPM_HIP_TRY(hipStreamSynchronize(wd_stream));
+        return LBMPM_OK;
+    }
+    int ipc_release_waits()         // lbmpm_*_ipc_release_waits
+    {
+        if (kind != LBMPM_TRANSPORT_IPC || !flags) { set_error("%s_ipc_release_waits: no IPC transport", api); return LBMPM_ERR_INVALID; }
+        return release_waits();
+    }
+
+    // Waits until the n (1 or 2) streams are idle -> LBMPM_OK, or until no heartbeat came for `seconds` -> LBMPM_ERR_TIMEOUT.  The
+    // deadline counts from the last PROGRESS, not from the call: while the heartbeat word moves, the neighbours answer and the queued
+    // steps drain, however many there are and however slow a neighbour is (an absolute deadline voided healthy long queues).  On a
+    // time-out the connected transport is given up -- IPC: the waits released, RCCL: the communicator aborted; dead, the streams
+    // synchronised -- and *gave_up names its kind; LBMPM_TRANSPORT_NONE: nothing was released, the work is still running and the
+    // caller's state stays what it is.  Else the caller voids its state.  `where`: the slab's planes, the tail of the message.
+    int sync_deadline(const hipStream_t *streams, int n, double seconds, const char *where, int *gave_up)
+    {
+        struct timespec t0, t;
+        clock_gettime(CLOCK_MONOTONIC, &t0);
+        volatile unsigned long long *hb = beat_host;
+        unsigned long long last = hb ? *hb : 0ull;
+        for (unsigned spins = 0;;) {
+            hipError_t e = hipSuccess;
+            for (int i = 0; i < n && e == hipSuccess; ++i) e = hipStreamQuery(streams[i]);
+            if (e == hipSuccess) return LBMPM_OK;
+            if (e != hipErrorNotReady) { set_error("%s_sync_deadline: %s", api, hipGetErrorString(e)); return LBMPM_ERR_HIP; }
+            (void)hipGetLastError();
+            clock_gettime(CLOCK_MONOTONIC, &t);
+            if (hb && *hb != last) { last = *hb; t0 = t; }
+            if ((double)(t.tv_sec - t0.tv_sec) + 1e-9 * (double)(t.tv_nsec - t0.tv_nsec) > seconds) break;
+            if (++spins > 2000) { struct timespec nap = {0, 200000}; nanosleep(&nap, nullptr); }       // busy for the first moments, then 0.2 ms naps
+        }
+        *gave_up = connected ? kind : LBMPM_TRANSPORT_NONE;
+        if (*gave_up == LBMPM_TRANSPORT_IPC) {
+            const int rc = release_waits();
+            if (rc != LBMPM_OK) return rc;
+        } else if (*gave_up == LBMPM_TRANSPORT_RCCL && comm && rccl.CommAbort) { (void)rccl.CommAbort(comm); comm = nullptr; }
+        if (*gave_up != LBMPM_TRANSPORT_NONE) {
+            dead = true;
+            for (int i = 0; i < n; ++i) (void)hipStreamSynchronize(streams[i]);
+        }
+        set_error("%s_sync_deadline: the slab's streams were busy and no step's face messages came through for %.1f s -- %s (%s)", api, seconds,
+                  *gave_up == LBMPM_TRANSPORT_IPC ? "a neighbour's face message did not arrive; the waits were released, the lattice state is void" :
+                  *gave_up == LBMPM_TRANSPORT_RCCL ? "a neighbour did not answer; the communicator was aborted, the lattice state is void" :
+                                                     "no in-library transport is connected: nothing was released", where);
+        return LBMPM_ERR_TIMEOUT;
+    }
+
     void disconnect()
     {
-        for (int s = 0; s < 2; ++s) {
-            if (mapped[s]) { (void)hipIpcCloseMemHandle(peer_land[s]); (void)hipIpcCloseMemHandle(peer_flags[s]); }
-            peer_land[s] = nullptr; peer_flags[s] = nullptr; mapped[s] = false;
-        }
+        unmap();
         if (comm) {         // dead: a peer is known not to answer (the watchdog fired) -- ncclCommDestroy would wait for it
             if (dead && rccl.CommAbort) (void)rccl.CommAbort(comm); else if (!dead) (void)rccl.CommDestroy(comm);
             comm = nullptr;
@@ -289,6 +439,16 @@ struct Transport {
         land = nullptr; flags = nullptr;
         kind = LBMPM_TRANSPORT_NONE; connected = false; seq = 0; dead = false; ring = false;
         (void)hipGetLastError();
+    }
+
+    // the end of the owning context: the transport and what outlives a disconnect
+    void destroy()
+    {
+        disconnect();
+        if (probe_bad) (void)hipFree(probe_bad);
+        if (beat_host) (void)hipHostFree(beat_host);
+        if (wd_stream) (void)hipStreamDestroy(wd_stream);
+        probe_bad = nullptr; beat_host = beat_dev = nullptr; wd_stream = nullptr;
     }
 };
 

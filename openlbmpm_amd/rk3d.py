@@ -6,8 +6,9 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import F64P, U8P, RK3DConfig, check
-from .slab import partition_z, partition_z_balanced, neighbour_exchange, local_exchange, DeviceBuffer
+from ._lib import F64P, U8P, RK3DConfig, SlabTransportCalls, check
+from .slab import partition_z, partition_z_balanced, neighbour_exchange, local_exchange, connect_in_library, DeviceBuffer
+from .slab import _torch_librccl        # noqa: F401 -- its earlier home: importable from here as before
 
 FIELDS = dict(phi=0, rhoR=1, rhoB=2, vx=3, vy=4, vz=5)
 BUF = dict(f_send_up=0, f_send_down=1, f_recv_below=2, f_recv_above=3,
@@ -21,8 +22,10 @@ DEFAULT_PARAMS = dict(AkR=7.0e-3, AkB=7.0e-3, beta=1.0, tauR=1.0, tauB=1.0, Soli
                       outlet="Dirichlet")                                    # BoundaryTypeOutlet 'Convective': planes 0 .. 2 copy plane 3
 
 
-class RK3DSlab:
-    """One slab: planes [z0, z0+nzl) of a global [nz, ny, nx] lattice."""
+class RK3DSlab(SlabTransportCalls):
+    """One slab: planes [z0, z0+nzl) of a global [nz, ny, nx] lattice.  The exchange's transport inside the library (ipc_init ..
+    sync(deadline_s)): SlabTransportCalls; `transport` says 'callback' when none is connected -- the caller's exchange function."""
+    _C_PREFIX, _NO_TRANSPORT = "lbmpm_rk3d", "callback"
 
     def __init__(self, is_domain_global, z0, nzl, params=None, device=0):
         L = _lib.lib()
@@ -181,53 +184,8 @@ class RK3DSlab:
             raise err[0]
         check(rc, "lbmpm_rk3d_step_slab")
 
-    # ---- the exchange's transport inside the library (include/lbmpm.h: LBMPM_TRANSPORT_*)
-    def ipc_init(self):
-        """allocate this slab's landing area; returns the bytes its neighbours need (lbmpm_rk3d_ipc_init)"""
-        blob = C.create_string_buffer(_lib.IPC_BLOB_BYTES)
-        check(self._L.lbmpm_rk3d_ipc_init(self._h, blob), "lbmpm_rk3d_ipc_init")
-        return blob.raw
-
-    def ipc_connect(self, blob_below, blob_above):
-        """map the neighbours' landing areas (their ipc_init bytes; None where the slab has no neighbour)"""
-        keep = [C.create_string_buffer(b, _lib.IPC_BLOB_BYTES) if b is not None else None for b in (blob_below, blob_above)]
-        check(self._L.lbmpm_rk3d_ipc_connect(self._h, keep[0], keep[1]), "lbmpm_rk3d_ipc_connect")
-
-    @staticmethod
-    def rccl_unique_id(librccl_path=None):
-        idb = C.create_string_buffer(_lib.RCCL_ID_BYTES)
-        check(_lib.lib().lbmpm_rccl_unique_id(idb, librccl_path.encode() if librccl_path else None), "lbmpm_rccl_unique_id")
-        return idb.raw
-
-    def rccl_connect(self, unique_id, rank, nranks, librccl_path=None):
-        """collective over the ranks of the run: ncclCommInitRank inside the library"""
-        idb = C.create_string_buffer(unique_id, _lib.RCCL_ID_BYTES)
-        check(self._L.lbmpm_rk3d_rccl_connect(self._h, idb, int(rank), int(nranks), librccl_path.encode() if librccl_path else None),
-              "lbmpm_rk3d_rccl_connect")
-
-    def transport_disconnect(self):
-        check(self._L.lbmpm_rk3d_transport_disconnect(self._h), "lbmpm_rk3d_transport_disconnect")
-
-    @property
-    def transport(self):
-        """'callback' (none connected: the caller's exchange function), 'ipc' or 'rccl'; with ipc also how the flags travel"""
-        v = C.c_int(0)
-        k = self._L.lbmpm_rk3d_transport_kind(self._h, C.byref(v))
-        return {0: "callback", 1: "ipc (copy engine + %s)" % ("stream value operations" if v.value else "one-lane flag kernels"), 2: "rccl"}[k]
-
     def halo_exchange(self):
         check(self._L.lbmpm_rk3d_halo_exchange(self._h), "lbmpm_rk3d_halo_exchange")
-
-    def transport_probe(self, rounds=6):
-        check(self._L.lbmpm_rk3d_transport_probe(self._h, int(rounds)), "lbmpm_rk3d_transport_probe")
-
-    def transport_probe_result(self):
-        v = C.c_int64(-1)
-        check(self._L.lbmpm_rk3d_transport_probe_result(self._h, C.byref(v)), "lbmpm_rk3d_transport_probe_result")
-        return int(v.value)
-
-    def ipc_release_waits(self):
-        check(self._L.lbmpm_rk3d_ipc_release_waits(self._h), "lbmpm_rk3d_ipc_release_waits")
 
     def slab_timing(self):
         """dict of average ms over the timed steps of the last step_slab(..., timed=True)"""
@@ -242,14 +200,6 @@ class RK3DSlab:
         a, b = C.c_double(0), C.c_double(0)
         check(self._L.lbmpm_rk3d_step_timed(self._h, int(n), C.byref(a), C.byref(b)), "step_timed")
         return a.value, b.value
-
-    def sync(self, deadline_s=None):
-        """wait for the slab's streams; with deadline_s the library's watchdog (lbmpm_rk3d_sync_deadline): LbmpmError with status
-        LBMPM_ERR_TIMEOUT (-6) when a neighbour's face message does not arrive in time -- the waits are released, the state is void"""
-        if deadline_s is None:
-            check(self._L.lbmpm_rk3d_sync(self._h), "sync")
-        else:
-            check(self._L.lbmpm_rk3d_sync_deadline(self._h, float(deadline_s)), "lbmpm_rk3d_sync_deadline")
 
     def get(self, name):
         out = np.empty((self.nzl, self.ny, self.nx), dtype=np.float64)
@@ -292,17 +242,6 @@ class RK3DSlab:
         """True for the q23 storage: one face message per step carries populations, records, row flags and the class sums the
         neighbour needs for the phase field of its halo plane (csrc/rk3dq.h); it is needed before the first step too"""
         return self.dominant_kernel == "rk3dq_fused"
-
-
-def _torch_librccl():
-    """the librccl that ships inside the torch wheel (the one torch.distributed's nccl backend uses), or None: the system's"""
-    import os
-    try:
-        import torch
-        p = os.path.join(os.path.dirname(torch.__file__), "lib", "librccl.so")
-        return p if os.path.exists(p) else None
-    except ImportError:
-        return None
 
 
 class RK3DCluster:
@@ -434,78 +373,12 @@ class RK3DDistributed:
             else:
                 self._connect(want)
 
-    def _agree(self, ok):
-        """True when every rank says ok (MIN over the group; a collective on host objects: works on every backend)"""
-        import torch.distributed as dist
-        got = [None] * self.world
-        dist.all_gather_object(got, bool(ok), group=self.group)
-        return all(got)
-
     def _connect(self, want):
-        """Connect the in-library transport; every rank takes the same decision (a transport that works on some ranks only is dropped
-        by all).  Each candidate is tried with a self-test under a deadline: patterned face messages each way; a stuck wait (IPC) is
-        released by the host, a stuck communicator (RCCL) aborted -- a hang must not stop the job before it has begun.  Every candidate's
-        verdict goes to self.transport_log."""
-        import torch.distributed as dist
-        s, err = self.slab, None
-        for kind in (("ipc", "rccl") if want == "auto" and dist.get_backend(self.group) == "nccl" else (("ipc",) if want in ("auto", "ipc") else ("rccl",))):
-            # every rank goes through the same collectives in the same order, whatever fails on it: a rank that skipped one would pair
-            # its next collective with its neighbours' current one
-            ok, err = True, None
-            if kind == "ipc":
-                try:
-                    mine = s.ipc_init()
-                except Exception as e:      # noqa: BLE001
-                    mine, ok, err = None, False, e
-                blobs = [None] * self.world
-                dist.all_gather_object(blobs, mine, group=self.group)
-                if ok and all(b is not None for b in blobs):
-                    try:
-                        s.ipc_connect(blobs[self.rank - 1] if self.rank > 0 else None, blobs[self.rank + 1] if self.rank + 1 < self.world else None)
-                    except Exception as e:  # noqa: BLE001
-                        ok, err = False, e
-                elif ok:
-                    ok, err = False, "ipc_init failed on rank(s) %s" % [r for r, b in enumerate(blobs) if b is None]
-            else:
-                box = [None]
-                if self.rank == 0:
-                    try:
-                        box = [s.rccl_unique_id(_torch_librccl())]
-                    except Exception as e:  # noqa: BLE001
-                        err = e
-                dist.broadcast_object_list(box, src=dist.get_global_rank(self.group, 0) if self.group is not None else 0, group=self.group)
-                ok = box[0] is not None
-                if not ok and err is None:
-                    err = "rank 0 could not make a unique id"
-                # ipc_open compares the neighbours' message sizes; ncclSend / ncclRecv would silently pair messages of different
-                # lengths (different cuts or lattices on two ranks): compare them here, before the blocking collective
-                sizes = [None] * self.world
-                dist.all_gather_object(sizes, self._face_bytes(), group=self.group)
-                for r in range(self.world - 1):
-                    if sizes[r]["up"] != sizes[r + 1]["from_below"] or sizes[r + 1]["down"] != sizes[r]["from_above"]:
-                        ok, err = False, "ranks %d and %d disagree on the size of the face message across their cut (%s vs %s)" % (r, r + 1, sizes[r], sizes[r + 1])
-                if self._agree(ok):         # ncclCommInitRank is a blocking collective: enter it only if every rank will
-                    try:
-                        s.rccl_connect(box[0], self.rank, self.world, _torch_librccl())
-                    except Exception as e:  # noqa: BLE001
-                        ok, err = False, e
-                else:
-                    ok = False
-            connected = self._agree(ok)
-            tested, why = (self._self_test(kind) if connected else (False, "not tried"))
-            if connected and tested:
-                self.transport_log.append(dict(transport=kind, ok=True, why="connected; probe of 6 patterned messages each way compared equal on every rank"))
-                self.transport_note = "in-library "
-                return
-            try:
-                s.transport_disconnect()
-            except Exception:               # noqa: BLE001
-                pass
-            reason = ("connect: %s" % err) if err else ("another rank could not connect" if not connected else "self-test: %s" % why)
-            self.transport_log.append(dict(transport=kind, ok=False, why=str(reason)))
-            self.transport_note = "%s did not connect on every rank (%s); " % (kind, reason)
-            if want != "auto":
-                raise RuntimeError("transport %r could not be connected on every rank: %s" % (kind, reason))
+        """Connect the in-library transport along the chain of slabs (slab.connect_in_library: every rank takes the same decision, every
+        candidate is probed under a deadline and leaves its verdict in self.transport_log)"""
+        kind, why_not = connect_in_library(self.slab, self.rank, self.world, self.group, want, False, self._face_bytes, self.transport_log,
+                                           enqueue=lambda: self._torch.cuda.stream(self.stream), messages="6")
+        self.transport_note = "in-library " if kind else why_not + "; "
 
     def _face_bytes(self):
         """sizes of this rank's four face messages (bytes; 0 where it has no neighbour), from its halo buffers"""
@@ -515,29 +388,6 @@ class RK3DDistributed:
             b = self.slab.buffer(name) if there else None
             out[key] = int(b.numel() * b.element_size()) if b is not None else 0
         return out
-
-    def _self_test(self, kind, deadline_s=20.0):
-        """six patterned messages each way between the real neighbours through the new transport (lbmpm_rk3d_transport_probe: every
-        landing slot three times, compared on the receiving GPU), under a deadline for EITHER transport: the library's watchdog
-        releases a stuck IPC wait / aborts a stuck communicator.  -> (every rank passed, this rank's verdict as text)"""
-        s = self.slab
-        try:
-            with self._torch.cuda.stream(self.stream):
-                s.transport_probe(6)
-        except Exception as e:              # noqa: BLE001 -- this rank could not even enqueue: tell the others (same collective)
-            self._agree(False)
-            return False, "could not enqueue the probe: %s" % e
-        why = "ok"
-        try:
-            s.sync(deadline_s=deadline_s)
-            bad = s.transport_probe_result()
-            mine = bad == 0
-            if not mine:
-                why = "%d doubles arrived wrong" % bad
-        except Exception as e:              # noqa: BLE001 -- the watchdog fired (or the stream failed)
-            mine, why = False, str(e)
-        every = self._agree(mine)
-        return every, (why if not mine else ("ok here, failed on another rank" if not every else "ok"))
 
     @property
     def transport(self):

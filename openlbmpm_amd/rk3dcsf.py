@@ -8,7 +8,8 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import F64P, U8P, RK3DCSFConfig, check
+from ._lib import F64P, U8P, RK3DCSFConfig, SlabTransportCalls, check
+from .slab import connect_in_library
 
 FIELDS = dict(fR=0, fB=1, rhoR=2, rhoB=3, vx=4, vy=5, vz=6, phi=7, Gx=8, Gy=9, Gz=10, Fx=11, Fy=12, Fz=13, K=14, nsx=15, nsy=16, nsz=17,
               kind=18, rec_fR=30, rec_fB=31, rec_rhoR=32, rec_rhoB=33, rec_vx=34, rec_vy=35, rec_vz=36, rec_phi=37)
@@ -54,7 +55,9 @@ def tracer_config(num_tracers=1, diffusion_x=1. / 6., diffusion_y=None, diffusio
     return cfg
 
 
-class RK3DCSFSolver:
+class RK3DCSFSolver(SlabTransportCalls):
+    _C_PREFIX, _NO_TRANSPORT = "lbmpm_rk3dcsf", "none"
+
     def __init__(self, is_domain, params=None, device=0, diagnostics=False, slab=None, tracers=None):
         """slab = (z0, global_nz): this lattice is a slab of an undivided lattice of global_nz planes -- its planes 2 .. nz-3 are the planes
         z0 .. of that lattice, its two planes at either end images of the neighbouring slabs' edge planes (cut from the undivided lattice,
@@ -183,59 +186,8 @@ class RK3DCSFSolver:
         check(self._L.lbmpm_rk3dcsf_step_timed(self._h, int(nsteps), C.byref(a), C.byref(b)), "lbmpm_rk3dcsf_step_timed")
         return a.value, b.value
 
-    def sync(self, deadline_s=None):
-        """wait for the solver's streams; with deadline_s the library's watchdog (lbmpm_rk3dcsf_sync_deadline): LbmpmError with status
-        LBMPM_ERR_TIMEOUT (-6) when a connected slab's neighbour stops answering -- the transport is given up, the state is void"""
-        if deadline_s is None:
-            check(self._L.lbmpm_rk3dcsf_sync(self._h), "lbmpm_rk3dcsf_sync")
-        else:
-            check(self._L.lbmpm_rk3dcsf_sync_deadline(self._h, float(deadline_s)), "lbmpm_rk3dcsf_sync_deadline")
-
-    # ---- a slab's face messages over a transport inside the library (include/lbmpm.h, CSF block; the slabs form a ring)
-    def ipc_init(self):
-        """allocate this slab's landing area; returns the bytes its two neighbours need (lbmpm_rk3dcsf_ipc_init)"""
-        blob = C.create_string_buffer(_lib.IPC_BLOB_BYTES)
-        check(self._L.lbmpm_rk3dcsf_ipc_init(self._h, blob), "lbmpm_rk3dcsf_ipc_init")
-        return blob.raw
-
-    def ipc_connect(self, blob_low, blob_high):
-        """map the landing areas of the neighbours at the low and the high face (their ipc_init bytes; with two ranks the same)"""
-        keep = [C.create_string_buffer(bytes(b), _lib.IPC_BLOB_BYTES) for b in (blob_low, blob_high)]
-        check(self._L.lbmpm_rk3dcsf_ipc_connect(self._h, keep[0], keep[1]), "lbmpm_rk3dcsf_ipc_connect")
-
-    @staticmethod
-    def rccl_unique_id(librccl_path=None):
-        idb = C.create_string_buffer(_lib.RCCL_ID_BYTES)
-        check(_lib.lib().lbmpm_rccl_unique_id(idb, librccl_path.encode() if librccl_path else None), "lbmpm_rccl_unique_id")
-        return idb.raw
-
-    def rccl_connect(self, unique_id, rank, nranks, librccl_path=None):
-        """collective over the ranks of the ring: ncclCommInitRank inside the library"""
-        idb = C.create_string_buffer(unique_id, _lib.RCCL_ID_BYTES)
-        check(self._L.lbmpm_rk3dcsf_rccl_connect(self._h, idb, int(rank), int(nranks), librccl_path.encode() if librccl_path else None),
-              "lbmpm_rk3dcsf_rccl_connect")
-
-    def transport_disconnect(self):
-        check(self._L.lbmpm_rk3dcsf_transport_disconnect(self._h), "lbmpm_rk3dcsf_transport_disconnect")
-
-    @property
-    def transport(self):
-        """'none' (the slab steps by stage(), the caller moves the messages), 'ipc (...)' or 'rccl'"""
-        v = C.c_int(0)
-        k = self._L.lbmpm_rk3dcsf_transport_kind(self._h, C.byref(v))
-        return {0: "none", 1: "ipc (copy engine + %s)" % ("stream value operations" if v.value else "one-lane flag kernels"), 2: "rccl"}[k]
-
-    def transport_probe(self, rounds=6):
-        check(self._L.lbmpm_rk3dcsf_transport_probe(self._h, int(rounds)), "lbmpm_rk3dcsf_transport_probe")
-
-    def transport_probe_result(self):
-        v = C.c_int64(-1)
-        check(self._L.lbmpm_rk3dcsf_transport_probe_result(self._h, C.byref(v)), "lbmpm_rk3dcsf_transport_probe_result")
-        return int(v.value)
-
-    def ipc_release_waits(self):
-        check(self._L.lbmpm_rk3dcsf_ipc_release_waits(self._h), "lbmpm_rk3dcsf_ipc_release_waits")
-
+    # ---- a slab's face messages over a transport inside the library (the slabs form a ring): ipc_init .. sync(deadline_s) are
+    # _lib.SlabTransportCalls; `transport` says 'none' while the slab steps by stage() and the caller moves the messages
     def step_slab(self, nsteps=1, timed=False):
         """nsteps whole steps of a connected slab behind one C call: stages and face messages enqueued, the host not blocked"""
         check(self._L.lbmpm_rk3dcsf_step_slab(self._h, int(nsteps), int(bool(timed))), "lbmpm_rk3dcsf_step_slab")
@@ -519,12 +471,6 @@ class RK3DCSFDistributed:
     def get_tracer_pdf(self, t):
         return np.ascontiguousarray(self.geo.own(self.slab.get_tracer_pdf(t)))
 
-    def _agree(self, ok):
-        """True when every rank says ok (a collective on host objects: works on every backend)"""
-        got = [None] * self.world
-        self._dist.all_gather_object(got, bool(ok))
-        return all(got)
-
     def _face_sizes(self):
         """doubles of the three messages (LBMPM_CSF_MSG_* order) this slab sends / expects through either face"""
         s = self.slab
@@ -532,90 +478,13 @@ class RK3DCSFDistributed:
                     from_below=[s.face_doubles_in(m, 0) for m in range(3)], from_above=[s.face_doubles_in(m, 1) for m in range(3)])
 
     def _connect(self, want):
-        """Connect the in-library transport with the set-up of RK3DDistributed._connect: every rank goes through the same collectives in
-        the same order whatever fails on it, a candidate that fails on one rank is dropped by all, and each one is probed under a deadline
-        before it is kept.  The ring: the low neighbour is rank - 1, the high one rank + 1 (mod world; with two ranks the same)."""
-        dist, s = self._dist, self.slab
+        """Connect the in-library transport around the ring of slabs -- the low neighbour is rank - 1, the high one rank + 1 (mod world;
+        with two ranks the same) -- by slab.connect_in_library: every rank takes the same decision, every candidate is probed under a
+        deadline and leaves its verdict in self.transport_log"""
         if self._dev.type == "cuda":
             self._torch.cuda.set_device(self._dev)       # (collectives of the nccl backend run on the current device)
-        lo, hi = (self.rank - 1) % self.world, (self.rank + 1) % self.world
-        for kind in (("ipc", "rccl") if want == "auto" and dist.get_backend() == "nccl" else (("ipc",) if want in ("auto", "ipc") else ("rccl",))):
-            ok, err = True, None
-            if kind == "ipc":
-                try:
-                    mine = s.ipc_init()
-                except Exception as e:      # noqa: BLE001
-                    mine, ok, err = None, False, e
-                blobs = [None] * self.world
-                dist.all_gather_object(blobs, mine)
-                if ok and all(b is not None for b in blobs):
-                    try:
-                        s.ipc_connect(blobs[lo], blobs[hi])
-                    except Exception as e:  # noqa: BLE001
-                        ok, err = False, e
-                elif ok:
-                    ok, err = False, "ipc_init failed on rank(s) %s" % [r for r, b in enumerate(blobs) if b is None]
-            else:
-                from .rk3d import _torch_librccl
-                box = [None]
-                if self.rank == 0:
-                    try:
-                        box = [s.rccl_unique_id(_torch_librccl())]
-                    except Exception as e:  # noqa: BLE001
-                        err = e
-                dist.broadcast_object_list(box, src=0)
-                ok = box[0] is not None
-                if not ok and err is None:
-                    err = "rank 0 could not make a unique id"
-                # ncclSend / ncclRecv would pair messages of different lengths: compare them before the blocking collective
-                sizes = [None] * self.world
-                dist.all_gather_object(sizes, self._face_sizes())
-                for r in range(self.world):
-                    h = (r + 1) % self.world
-                    if sizes[r]["up"] != sizes[h]["from_below"] or sizes[h]["down"] != sizes[r]["from_above"]:
-                        ok, err = False, "ranks %d and %d disagree on the sizes of the face messages across their cut (%s vs %s)" % (r, h, sizes[r], sizes[h])
-                if self._agree(ok):         # ncclCommInitRank is a blocking collective: enter it only if every rank will
-                    try:
-                        s.rccl_connect(box[0], self.rank, self.world, _torch_librccl())
-                    except Exception as e:  # noqa: BLE001
-                        ok, err = False, e
-                else:
-                    ok = False
-            connected = self._agree(ok)
-            tested, why = self._self_test() if connected else (False, "not tried")
-            if connected and tested:
-                self.transport_log.append(dict(transport=kind, ok=True, why="connected; probe of 6 x 3 patterned messages each way compared equal on every rank"))
-                self._library = True
-                return
-            try:
-                s.transport_disconnect()
-            except Exception:               # noqa: BLE001
-                pass
-            reason = ("connect: %s" % err) if err else ("another rank could not connect" if not connected else "self-test: %s" % why)
-            self.transport_log.append(dict(transport=kind, ok=False, why=str(reason)))
-            if want != "auto":
-                raise RuntimeError("transport %r could not be connected on every rank: %s" % (kind, reason))
-
-    def _self_test(self, deadline_s=20.0):
-        """six rounds of the three patterned messages each way between the real neighbours (lbmpm_rk3dcsf_transport_probe), waited for
-        under the library's watchdog -> (every rank passed, this rank's verdict as text)"""
-        s = self.slab
-        try:
-            s.transport_probe(6)
-        except Exception as e:              # noqa: BLE001 -- this rank could not even enqueue: tell the others (same collective)
-            self._agree(False)
-            return False, "could not enqueue the probe: %s" % e
-        why = "ok"
-        try:
-            s.sync(deadline_s=deadline_s)
-            bad = s.transport_probe_result()
-            mine = bad == 0
-            if not mine:
-                why = "%d doubles arrived wrong" % bad
-        except Exception as e:              # noqa: BLE001 -- the watchdog fired (or the stream failed)
-            mine, why = False, str(e)
-        every = self._agree(mine)
-        return every, (why if not mine else ("ok here, failed on another rank" if not every else "ok"))
+        self._library = connect_in_library(self.slab, self.rank, self.world, None, want, True, self._face_sizes, self.transport_log,
+                                           messages="6 x 3")[0] is not None
 
     @property
     def transport(self):

@@ -119,6 +119,127 @@ def gather_planes(local, parts, rank, world, group=None, device=None):
     return out
 
 
+def _torch_librccl():
+    """the librccl that ships inside the torch wheel (the one torch.distributed's nccl backend uses), or None: the system's"""
+    import os
+    try:
+        import torch
+        p = os.path.join(os.path.dirname(torch.__file__), "lib", "librccl.so")
+        return p if os.path.exists(p) else None
+    except ImportError:
+        return None
+
+
+def slab_neighbours(rank, world, ring):
+    """(rank below, rank above) of a slab: None at the two ends of a chain, wrapping in a ring (with two ranks both are the same rank)"""
+    if ring:
+        return (rank - 1) % world, (rank + 1) % world
+    return (rank - 1 if rank > 0 else None), (rank + 1 if rank + 1 < world else None)
+
+
+def slab_pairs(world, ring):
+    """[(lower, upper)] ranks on the two sides of every cut: world - 1 cuts in a chain, world in a ring"""
+    return [(r, (r + 1) % world) for r in range(world if ring else world - 1)]
+
+
+def connect_in_library(slab, rank, world, group, want, ring, face_sizes, log, enqueue=None, messages="6", deadline_s=20.0):
+    """Connect the in-library transport of `slab` (the SlabTransportCalls of _lib.py) between the ranks of `group`, a chain or a ring of
+    slabs; the one set-up of both 3-D models.  want: 'auto' (ipc, then rccl under the nccl backend) | 'ipc' | 'rccl'.  Every rank takes
+    the same decision (a transport that works on some ranks only is dropped by all).  Each candidate is probed under a deadline:
+    patterned face messages each way between the real neighbours, compared on the receiving GPU; the library's watchdog releases a
+    stuck IPC wait and aborts a stuck communicator -- a hang must not stop the job before it has begun.
+    face_sizes() -> this rank's dict(up, down, from_below, from_above) of message sizes; enqueue() -> the context manager under which
+    the probe is enqueued (None: none needed); messages: how many patterned messages the probe sends each way, for the log.
+    Every candidate's verdict is appended to `log` as dict(transport, ok, why).  Returns (kind, reason): the kind that connected and
+    None, or None and "<last candidate> did not connect on every rank (<why>)".  A named transport that fails raises RuntimeError
+    (on every rank) instead."""
+    import contextlib
+    import torch.distributed as dist
+
+    def agree(ok):
+        """True when every rank says ok (a collective on host objects: works on every backend)"""
+        got = [None] * world
+        dist.all_gather_object(got, bool(ok), group=group)
+        return all(got)
+
+    lo, hi = slab_neighbours(rank, world, ring)
+    for kind in (("ipc", "rccl") if want == "auto" and dist.get_backend(group) == "nccl" else (("ipc",) if want in ("auto", "ipc") else ("rccl",))):
+        # every rank goes through the same collectives in the same order, whatever fails on it: a rank that skipped one would pair
+        # its next collective with its neighbours' current one
+        ok, err = True, None
+        if kind == "ipc":
+            try:
+                mine = slab.ipc_init()
+            except Exception as e:      # noqa: BLE001
+                mine, ok, err = None, False, e
+            blobs = [None] * world
+            dist.all_gather_object(blobs, mine, group=group)
+            if ok and all(b is not None for b in blobs):
+                try:
+                    slab.ipc_connect(*[None if r is None else blobs[r] for r in (lo, hi)])
+                except Exception as e:  # noqa: BLE001
+                    ok, err = False, e
+            elif ok:
+                ok, err = False, "ipc_init failed on rank(s) %s" % [r for r, b in enumerate(blobs) if b is None]
+        else:
+            box = [None]
+            if rank == 0:
+                try:
+                    box = [slab.rccl_unique_id(_torch_librccl())]
+                except Exception as e:  # noqa: BLE001
+                    err = e
+            dist.broadcast_object_list(box, src=dist.get_global_rank(group, 0) if group is not None else 0, group=group)
+            ok = box[0] is not None
+            if not ok and err is None:
+                err = "rank 0 could not make a unique id"
+            # ipc_open compares the neighbours' message sizes; ncclSend / ncclRecv would silently pair messages of different
+            # lengths (different cuts or lattices on two ranks): compare them here, before the blocking collective
+            sizes = [None] * world
+            dist.all_gather_object(sizes, face_sizes(), group=group)
+            for r, h in slab_pairs(world, ring):
+                if sizes[r]["up"] != sizes[h]["from_below"] or sizes[h]["down"] != sizes[r]["from_above"]:
+                    ok, err = False, "ranks %d and %d disagree on the sizes of the face messages across their cut (%s vs %s)" % (r, h, sizes[r], sizes[h])
+            if agree(ok):               # ncclCommInitRank is a blocking collective: enter it only if every rank will
+                try:
+                    slab.rccl_connect(box[0], rank, world, _torch_librccl())
+                except Exception as e:  # noqa: BLE001
+                    ok, err = False, e
+            else:
+                ok = False
+        connected = agree(ok)
+        tested, why = False, "not tried"
+        if connected:
+            try:
+                with (enqueue() if enqueue is not None else contextlib.nullcontext()):
+                    slab.transport_probe(6)
+                mine, why = True, "ok"
+            except Exception as e:      # noqa: BLE001 -- this rank could not even enqueue: it tells the others in the same collective
+                mine, why = False, "could not enqueue the probe: %s" % e
+            if mine:
+                try:
+                    slab.sync(deadline_s=deadline_s)
+                    bad = slab.transport_probe_result()
+                    if bad:
+                        mine, why = False, "%d doubles arrived wrong" % bad
+                except Exception as e:  # noqa: BLE001 -- the watchdog fired (or the stream failed)
+                    mine, why = False, str(e)
+            tested = agree(mine)
+            if mine and not tested:
+                why = "ok here, failed on another rank"
+        if connected and tested:
+            log.append(dict(transport=kind, ok=True, why="connected; probe of %s patterned messages each way compared equal on every rank" % messages))
+            return kind, None
+        try:
+            slab.transport_disconnect()
+        except Exception:               # noqa: BLE001
+            pass
+        reason = ("connect: %s" % err) if err else ("another rank could not connect" if not connected else "self-test: %s" % why)
+        log.append(dict(transport=kind, ok=False, why=str(reason)))
+        if want != "auto":
+            raise RuntimeError("transport %r could not be connected on every rank: %s" % (kind, reason))
+    return None, "%s did not connect on every rank (%s)" % (kind, reason)
+
+
 class DeviceBuffer:
     """Zero-copy torch view of a raw device allocation owned by liblbmpm_hip.so."""
 

@@ -477,3 +477,23 @@ def test_csf_ring_of_slabs_gloo(world):
         p.join(timeout=60)
         assert p.exitcode == 0
     assert sorted(results) == [(r, True) for r in range(world)]
+
+
+@pytest.mark.parametrize("world", [2, 3, 4])
+def test_chain_and_ring_topologies_of_the_transport_set_up(world):
+    """slab.slab_neighbours / slab_pairs, the two topologies connect_in_library serves: the chain of the perturbation model's slabs ends
+    at both ends, the ring of the CSF model's slabs wraps (with two ranks both neighbours are the same rank)"""
+    from openlbmpm_amd.slab import slab_neighbours, slab_pairs
+    chain = [slab_neighbours(r, world, False) for r in range(world)]
+    assert chain[0][0] is None and chain[-1][1] is None
+    assert [c[1] for c in chain[:-1]] == list(range(1, world)) and [c[0] for c in chain[1:]] == list(range(world - 1))
+    assert slab_pairs(world, False) == [(r, r + 1) for r in range(world - 1)] and len(slab_pairs(world, False)) == world - 1
+    ring = [slab_neighbours(r, world, True) for r in range(world)]
+    assert ring == [((r - 1) % world, (r + 1) % world) for r in range(world)]
+    assert ring[0][0] == world - 1 and ring[-1][1] == 0
+    assert (ring[0][0] == ring[0][1]) == (world == 2)
+    pairs = slab_pairs(world, True)
+    assert len(pairs) == world and pairs[-1] == (world - 1, 0)
+    # every cut's pair is (a rank, its upper neighbour), in both topologies
+    for ring_, nb in ((False, chain), (True, ring)):
+        assert all(nb[lo][1] == hi and nb[hi][0] == lo for lo, hi in slab_pairs(world, ring_))
