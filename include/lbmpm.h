@@ -482,6 +482,21 @@ int lbmpm_rk3d_sync_deadline(lbmpm_rk3d *ctx, double seconds);
 int lbmpm_rk3d_buffer(lbmpm_rk3d *ctx, int which, void **device_ptr, int64_t *bytes);
 /* owned planes [nz_local][ny][nx] */
 int lbmpm_rk3d_get_field(lbmpm_rk3d *ctx, int field, double *out);
+/* Plane integrals of the 3-D solvers: for every plane z the context owns, LBMPM_INTEGRAL_COLS doubles -- sums over the plane's fluid
+ * cells of the state that is recorded (perturbation model: the fields of the last lbmpm_rk3d_phase_field(ctx, 1) as lbmpm_rk3d_get_field
+ * hands them out; CSF model: what LBMPM_RK3DCSF_REC_RHO_R .. _REC_PHI hand out), reduced on the device in a fixed order: the table is the
+ * same bit for bit however the lattice is cut into slabs.  A cell where any of rho_R, rho_B, u, phi is not finite counts in CELLS and
+ * NONFINITE and contributes to nothing else.
+ *   CELLS fluid cells | CELLS_R finite cells with phi > 0 | MASS_R, MASS_B sum of rho_R, rho_B | FLUX_R, FLUX_B sum of rho_R u_z, rho_B u_z |
+ *   UZ_R, UZ_B sum of u_z over the cells with phi > 0, phi <= 0 | MOM_X, MOM_Y sum of (rho_R + rho_B) u_x, u_y | UMAX2 max of
+ *   ux ux + uy uy + uz uz (0 without finite cells) | NONFINITE the cells that are not finite */
+#define LBMPM_INTEGRAL_COLS 12
+enum { LBMPM_INT_CELLS = 0, LBMPM_INT_CELLS_R, LBMPM_INT_MASS_R, LBMPM_INT_MASS_B, LBMPM_INT_FLUX_R, LBMPM_INT_FLUX_B,
+       LBMPM_INT_UZ_R, LBMPM_INT_UZ_B, LBMPM_INT_MOM_X, LBMPM_INT_MOM_Y, LBMPM_INT_UMAX2, LBMPM_INT_NONFINITE };
+/* out: host [nz_local][LBMPM_INTEGRAL_COLS].  LBMPM_ERR_STATE when a step has been taken since the last lbmpm_rk3d_phase_field(ctx, 1)
+ * (never calls it itself: on slabs the halo exchange comes first, which is the caller's).  One stream synchronisation, nz_local * 96
+ * bytes copied */
+int lbmpm_rk3d_integrals(lbmpm_rk3d *ctx, double *out);
 /* out[4]: doubles stored per fluid cell (38, or 23 with the compressed compact storage: 19 colour-blind populations + k_R + the
  * recolouring vector, from which the pull rebuilds both colours -- AcceleratedRKGPU2D.py:1241-1267 makes the two lattices an affine
  * image of those), fluid cells owned, those of them in row segments flagged single-colour (no records kept), bytes one step moves
@@ -615,6 +630,9 @@ int lbmpm_rk3dcsf_sync(lbmpm_rk3dcsf *ctx);
 /* keep u and K of every step (four more stores per cell) */
 int lbmpm_rk3dcsf_enable_diagnostics(lbmpm_rk3dcsf *ctx, int on);
 int lbmpm_rk3dcsf_get_field(lbmpm_rk3dcsf *ctx, int field, double *out);
+/* out: host [own planes][LBMPM_INTEGRAL_COLS] (nz - ghost_lo - ghost_hi rows), see lbmpm_rk3d_integrals; reduced from the populations in
+ * registers (no per-cell staging).  LBMPM_ERR_STATE before set_macro / set_pdf; valid wherever get_field(REC_*) is, slabs included */
+int lbmpm_rk3dcsf_integrals(lbmpm_rk3dcsf *ctx, double *out);
 int64_t lbmpm_rk3dcsf_num_fluid_nodes(const lbmpm_rk3dcsf *ctx);
 int64_t lbmpm_rk3dcsf_num_wetting_solids(const lbmpm_rk3dcsf *ctx);
 /* fluid cells whose block took the bulk path in the last step (variant 0; see lbmpm_rk3dcsf_config.variant) */

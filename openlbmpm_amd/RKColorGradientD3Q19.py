@@ -25,6 +25,12 @@ One process per GPU: when torch.distributed is initialised with world size > 1 t
 into z-slabs (openlbmpm_amd/rk3d.py: RK3DDistributed, halos over xGMI) and rank 0 writes ONE result file with the
 whole lattice's arrays, gathered at the record cadence (gather_records = False: every rank its own planes in its own file);
 otherwise a single slab on `device`.
+
+integrals_every = N > 0: every N steps (step 0 and the last step included) the plane integrals of the recorded state
+(openlbmpm_amd/integrals.py; reduced on the device, a few kB per call) go to /Integrals/PlanesAtStep<step> [nz][12] of the result file
+(rank 0's in a distributed run: the whole lattice's table), /Integrals/Steps and /Integrals/Columns (the names as zero-padded bytes,
+integrals.column_names reads them) at the end; saturation, masses and the largest speed go to the log, and cells that are not finite are
+met with the nan_guard rule at that cadence.
 """
 import os
 
@@ -32,6 +38,7 @@ import numpy as np
 
 from . import config
 from .geometry import initial_densities_rk3d, voxel_domain
+from .integrals import column_bytes, fresh
 from .results import RecordGuard, ResultFile, find_result_file, read_planes
 from .rk3d import RK3DSlab, RK3DDistributed
 
@@ -100,7 +107,7 @@ def duct(nx, ny, nz):
 class RKColorGradient3D:
     def __init__(self, pathIniFile, output_dir=None, domain=None, device=0, record_every=None, num_buffering_layers=10,
                  structure_path=None, initial_dir=None, record_pdf=False, restart_from=None, checkpoint_every=0, csf_bulk_epsilon=0.0,
-                 csf_transport=None):
+                 csf_transport=None, integrals_every=0):
         self.pathIni = pathIniFile
         self.par = config.read_rk3d(pathIniFile)
         self.output_dir = output_dir or os.path.expanduser("~/LBMResults3D")       # main.py:28
@@ -115,6 +122,7 @@ class RKColorGradient3D:
         # 3-D CSF under torchrun only, opt-in: None = the face messages through torch.distributed; 'auto' | 'ipc' | 'rccl' = over a transport
         # inside the library, one C call per run of steps (rk3dcsf.RK3DCSFDistributed)
         self.csf_transport = csf_transport
+        self.integrals_every = int(integrals_every)      # 0: no /Integrals group, no extra stop of the step loop
         self.gather_records = True
         self.records = 0
         self.physicalVX = self.physicalVY = self.physicalVZ = None
@@ -261,6 +269,7 @@ class RKColorGradient3D:
             whole_arrays = self._distributed()
             slab = sim = _CSFSlab(self.isDomain, p, self.device, self.csf_bulk_epsilon, distributed=whole_arrays, transport=self.csf_transport)
             step, observe = slab.step_single, (lambda: None)
+            integrals = sim.solver.integrals
             self.z0, self.nzl = 0, self.zDomain
             if whole_arrays:
                 import torch.distributed as dist
@@ -283,6 +292,7 @@ class RKColorGradient3D:
                 sim.close()
                 sim = RK3DDistributed(self.isDomain, par, device=self.device, plane_cost=cost)
             step, observe, slab = sim.step, sim.observe, sim.slab
+            integrals = sim.integrals
             self.z0, self.nzl = sim.z0, sim.nzl
             if self.gather_records:
                 self._gather = sim.gather
@@ -292,6 +302,7 @@ class RKColorGradient3D:
             slab = sim = RK3DSlab(self.isDomain, 0, self.zDomain, par, self.device)
             step = slab.step_single
             observe = lambda: slab.phase_field(diagnostics=True)
+            integrals = lambda: fresh(slab.integrals, observe)
             self.z0, self.nzl = 0, self.zDomain
         self._slab, self._observe = slab, observe
         done = 0
@@ -302,7 +313,10 @@ class RKColorGradient3D:
             self.initializeDomainCondition(z0, nzl)
             self._upload_initial_state(slab)
         writes = rank == 0 or not (self._distributed() and self.gather_records)
-        out = ResultFile(self.output_dir, name, GROUPS) if writes else None
+        every = self.integrals_every
+        # (the table is gathered: the whole lattice's on rank 0, whether the records are gathered or not)
+        out = ResultFile(self.output_dir, name, GROUPS + ((("Integrals", "PlaneIntegrals"),) if every > 0 and rank == 0 else ())) if writes else None
+        self.integral_steps = []
         self.result_path = out.path if out else None
         # distributed: every rank checks its own slab, the verdict is collective (all ranks raise together, none is left in an exchange)
         self._guard = RecordGuard("rk3d", slab.num_fluid_nodes, getattr(self, "nan_guard", "raise"), collective=self._distributed(), device=self.device)
@@ -311,7 +325,11 @@ class RKColorGradient3D:
             if done % self.timeInterval == 0:      # (a restarted run records its first step again: the counters of the checkpoint precede it)
                 observe()
                 self._record(slab, out)
+            if every > 0 and done % every == 0:
+                self._integrals(integrals(), out, done)
             n = min(self.timeInterval - done % self.timeInterval, self.timeSteps - done)
+            if every > 0:
+                n = min(n, every - done % every)
             if self.checkpoint_every > 0:
                 n = min(n, self.checkpoint_every - done % self.checkpoint_every)
             step(n)
@@ -324,9 +342,22 @@ class RKColorGradient3D:
         observe()
         self._step_now = done
         self._record(slab, out)
+        if every > 0:
+            self._integrals(integrals(), out, done)
+            if rank == 0:
+                out.write("Integrals", "Steps", np.array(self.integral_steps, dtype=np.int64))
+                out.write("Integrals", "Columns", column_bytes())
         slab.sync()
         self.solver = sim
         return self.result_path
+
+    def _integrals(self, t, out, step):
+        """t: the Integrals of the whole lattice at `step` (None on the other ranks of a distributed run)"""
+        self.integrals = t
+        self.integral_steps.append(int(step))
+        if t is not None and out is not None:
+            out.write("Integrals", "PlanesAtStep%d" % step, t.planes)
+        self._guard.integrals(step, None if t is None else t.nonfinite, None if t is None else t.summary())
 
     def _record(self, slab, out):
         k = self.records

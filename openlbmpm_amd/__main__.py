@@ -7,6 +7,7 @@
     python -m openlbmpm_amd rk3d <ini-dir> ...     D3Q19 colour gradient (RKtwophasesetup3D.ini); under torchrun: z-slabs, one per GPU
         [--csf-transport auto|ipc|rccl]           rk3d with SurfaceTensionType = 'CSF' and tr3d under torchrun: the slabs' face messages over the library's
                                                   own transports (default: through torch.distributed)
+        [--integrals-every N]                     rk3d: saturation, masses, fluxes, Darcy velocities per plane every N steps (/Integrals of the result file)
 """
 import argparse
 import sys
@@ -40,6 +41,9 @@ def main(argv=None):
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--csf-transport", choices=["auto", "ipc", "rccl"], default=None,
                     help="rk3d with SurfaceTensionType = 'CSF', tr3d; under torchrun: move the slabs' face messages over the library's own transport")
+    ap.add_argument("--integrals-every", type=int, default=0, metavar="N",
+                    help="rk3d: every N steps the plane integrals (saturation, masses, fluxes, largest speed, non-finite cells), reduced on the device, "
+                         "to /Integrals of the result file and the log; 0: off")
     a = ap.parse_args(argv)
     t0 = time.time()
     if a.model == "rk":
@@ -52,7 +56,7 @@ def main(argv=None):
     elif a.model == "rk3d":
         from .RKColorGradientD3Q19 import RKColorGradient3D
         device = _rank_device(a.device)
-        sim = RKColorGradient3D(a.ini_dir, output_dir=a.out, device=device, csf_transport=a.csf_transport)
+        sim = RKColorGradient3D(a.ini_dir, output_dir=a.out, device=device, csf_transport=a.csf_transport, integrals_every=a.integrals_every)
         if a.steps is not None:
             sim.timeSteps = a.steps
         path = sim.runRKColorGradient3D()

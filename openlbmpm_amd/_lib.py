@@ -173,6 +173,7 @@ _SIGNATURES = {
     "lbmpm_rk3d_sync_deadline": (C.c_int, [C.c_void_p, C.c_double]),
     "lbmpm_rk3d_buffer": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), I64P]),
     "lbmpm_rk3d_get_field": (C.c_int, [C.c_void_p, C.c_int, F64P]),
+    "lbmpm_rk3d_integrals": (C.c_int, [C.c_void_p, F64P]),
     "lbmpm_rk3d_num_fluid_nodes": (C.c_int64, [C.c_void_p]),
     "lbmpm_rk3d_steps_done": (C.c_int64, [C.c_void_p]),
     "lbmpm_rk3d_dominant_kernel": (C.c_char_p, [C.c_void_p]),
@@ -195,6 +196,7 @@ _SIGNATURES = {
     "lbmpm_rk3dcsf_sync": (C.c_int, [C.c_void_p]),
     "lbmpm_rk3dcsf_enable_diagnostics": (C.c_int, [C.c_void_p, C.c_int]),
     "lbmpm_rk3dcsf_get_field": (C.c_int, [C.c_void_p, C.c_int, F64P]),
+    "lbmpm_rk3dcsf_integrals": (C.c_int, [C.c_void_p, F64P]),
     "lbmpm_rk3dcsf_num_fluid_nodes": (C.c_int64, [C.c_void_p]),
     "lbmpm_rk3dcsf_num_wetting_solids": (C.c_int64, [C.c_void_p]),
     "lbmpm_rk3dcsf_bulk_cells": (C.c_int64, [C.c_void_p]),

@@ -1163,6 +1163,25 @@ __global__ void rk3d_setup_solidnbr(RK3Dev p, uint32_t *solidnbr)
 
 #include "rk3dq.h"
 #include "rk3d_state.h"
+#include "rk3d_integrals.h"
+
+// the fields of the last lbmpm_rk3d_phase_field(ctx, 1) (rhoR, rhoB, vx, vy, vz in `diag`, the phase field in `phi`; pitch, plane2 and
+// halo planes as lbmpm_rk3d_get_field reads them), the mask from the device's flags
+struct Rk3dIntLoader {
+    const uint8_t *flags;
+    const double *diag, *phi;
+    unsigned nx, pitch;
+    size_t plane2, vol;
+    __device__ __forceinline__ bool operator()(unsigned plane, unsigned k, IntCell &c) const
+    {
+        const unsigned y = k / nx, x = k - y * nx;
+        const size_t idx = (size_t)(plane + 1u) * plane2 + (size_t)y * pitch + x;
+        if (!(flags[idx] & 1)) return false;
+        c.rR = diag[idx]; c.rB = diag[vol + idx]; c.ux = diag[2 * vol + idx]; c.uy = diag[3 * vol + idx]; c.uz = diag[4 * vol + idx];
+        c.phi = phi[idx];
+        return true;
+    }
+};
 
 }  // namespace
 
@@ -1179,6 +1198,7 @@ struct lbmpm_rk3d {
     uint8_t *flags = nullptr;
     uint32_t *solidnbr = nullptr;
     double *fA = nullptr, *fB = nullptr, *phi = nullptr, *diag = nullptr;
+    double *integ = nullptr;         // lbmpm_rk3d_integrals: chunk partials + the table (rk3d_integrals.h), allocated by the first call
     uint32_t *purA = nullptr, *purB = nullptr;       // row flags of the q23 storage, swapped with fA / fB
     double *send_up = nullptr, *send_dn = nullptr, *recv_below = nullptr, *recv_above = nullptr;
     std::vector<uint8_t> h_domain;   // owned planes only, [nzl][ny][nx]
@@ -1483,7 +1503,7 @@ extern "C" void lbmpm_rk3d_destroy(lbmpm_rk3d *c)
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->aux) (void)hipStreamSynchronize(c->aux);
     c->tx.destroy();
-    for (void *ptr : {(void *)c->seg, (void *)c->seg2, (void *)c->pstart, (void *)c->flags, (void *)c->solidnbr, (void *)c->fA, (void *)c->fB, (void *)c->purA, (void *)c->purB, (void *)c->trace, (void *)c->slotq, (void *)c->phi, (void *)c->diag,
+    for (void *ptr : {(void *)c->seg, (void *)c->seg2, (void *)c->pstart, (void *)c->flags, (void *)c->solidnbr, (void *)c->fA, (void *)c->fB, (void *)c->purA, (void *)c->purB, (void *)c->trace, (void *)c->slotq, (void *)c->phi, (void *)c->diag, (void *)c->integ,
                       (void *)c->send_up, (void *)c->send_dn, (void *)c->recv_below, (void *)c->recv_above})
         if (ptr) (void)hipFree(ptr);
     c->pool.destroy();
@@ -2518,6 +2538,24 @@ extern "C" int lbmpm_rk3d_get_field(lbmpm_rk3d *c, int field, double *out)
                 const size_t s = (size_t)z * hp + (size_t)y * c->nx + x;
                 out[s] = c->h_domain[s] == 1 ? h[(size_t)(z + 1) * c->plane2 + (size_t)y * c->pitch + x] : 0.0;
             }
+    return LBMPM_OK;
+}
+
+// Plane integrals of the fields of the last lbmpm_rk3d_phase_field(ctx, 1) (rk3d_integrals.h): out [nz_local][LBMPM_INTEGRAL_COLS].  Never
+// calls phase_field itself: on slabs that needs the halo exchange first, which is the caller's job.
+extern "C" int lbmpm_rk3d_integrals(lbmpm_rk3d *c, double *out)
+{
+    LBMPM_REQUIRE(c && out, "lbmpm_rk3d_integrals: null argument");
+    LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
+    if (c->observed_at != c->steps || !c->diag) {
+        set_error("the integrals are stale: call lbmpm_rk3d_phase_field(ctx, 1) after the last step (they are sums over the fields of the streamed, "
+                  "boundary-corrected lattice at that call; observed at step %lld, now %lld)", (long long)c->observed_at, (long long)c->steps);
+        return LBMPM_ERR_STATE;
+    }
+    const unsigned planes = (unsigned)c->nzl, plane_cells = (unsigned)c->nx * (unsigned)c->ny;
+    if (!c->integ) { const int rc = dev_alloc(c, &c->integ, integral_buffer_doubles(planes, plane_cells)); if (rc) return rc; }
+    const Rk3dIntLoader load{c->flags, c->diag, c->phi, (unsigned)c->nx, (unsigned)c->pitch, c->plane2, c->vol};
+    LBMPM_HIP_TRY(integrals_run(load, planes, plane_cells, c->integ, out, c->stream));
     return LBMPM_OK;
 }
 

@@ -1009,6 +1009,32 @@ __global__ __launch_bounds__(256) void csf3d_import(CsfDev p, double *f, const d
 }
 
 #include "rk3d_tracer.h"
+#include "rk3d_integrals.h"
+
+// what LBMPM_RK3DCSF_REC_RHO_R .. _REC_PHI hand out, from the populations: cell_state<FIRST, true>, the velocity with half the force and
+// the phase field in the arithmetic of csf3d_observe<FIRST, true>; own planes only (plane 0 is lattice plane p.glo)
+template <bool FIRST>
+struct CsfIntLoader {
+    CsfDev p;
+    __device__ __forceinline__ bool operator()(unsigned plane, unsigned k, IntCell &c) const
+    {
+        constexpr int CX[Q] = CSF_CX, CY[Q] = CSF_CY, CZ[Q] = CSF_CZ;
+        const int z = (int)plane + p.glo;
+        const unsigned n = (unsigned)z * ((unsigned)p.nx * (unsigned)p.ny) + k;
+        if (!(p.meta[n] & 1u)) return false;
+        const int y = (int)(k / (unsigned)p.nx), x = (int)(k - (unsigned)y * (unsigned)p.nx);
+        double fR[Q], fB[Q], rR, rB;
+        cell_state<FIRST, true>(p, x, y, z, fR, fB, rR, rB);
+        double mx = 0., my = 0., mz = 0.;
+#pragma unroll
+        for (int i = 1; i < Q; ++i) { const double t = fR[i] + fB[i]; addc(mx, CX[i], t); addc(my, CY[i], t); addc(mz, CZ[i], t); }
+        const double rs = rB + rR;
+        c.rR = rR; c.rB = rB;
+        c.ux = (mx + 0.5 * p.F[n]) / rs; c.uy = (my + 0.5 * p.F[p.NS + n]) / rs; c.uz = (mz + 0.5 * p.F[2 * p.NS + n]) / rs;
+        c.phi = (rR - rB) / (rR + rB);
+        return true;
+    }
+};
 
 }  // namespace
 
@@ -1032,6 +1058,7 @@ struct lbmpm_rk3dcsf {
     unsigned nblk = 0;
     bool skip = true;
     double *fA = nullptr, *fB = nullptr, *phi = nullptr, *G = nullptr, *nh = nullptr, *F = nullptr, *K = nullptr, *U = nullptr, *ns = nullptr;
+    double *integ = nullptr;       // lbmpm_rk3dcsf_integrals: chunk partials + the table (rk3d_integrals.h), allocated by the first call
     double *obs = nullptr;         // staging of the observe kernel: rho [2][N], u [3][N], phi [N] (the populations [2][N][19] come and go with the call)
     lbmpm::EventPool pool;
     size_t timed_steps = 0;
@@ -1205,7 +1232,7 @@ extern "C" void lbmpm_rk3dcsf_destroy(lbmpm_rk3dcsf *c)
     c->tx.destroy();
     for (void *q : {(void *)c->send_lo, (void *)c->send_hi}) if (q) (void)hipFree(q);
     c->slab_pool.destroy();
-    void *ptrs[] = {c->gA, c->gB, c->trflow, c->trsrc, c->wethome, c->rng, c->pfx, c->pure, c->deep_prev, c->bcblk, c->deep_now, c->work, c->tcnt, c->src, c->dom, c->meta, c->wetlist, c->cidx, c->cells, c->fA, c->fB, c->phi, c->G, c->nh, c->F, c->K, c->U, c->ns, c->obs};
+    void *ptrs[] = {c->gA, c->gB, c->trflow, c->trsrc, c->wethome, c->rng, c->pfx, c->pure, c->deep_prev, c->bcblk, c->deep_now, c->work, c->tcnt, c->src, c->dom, c->meta, c->wetlist, c->cidx, c->cells, c->fA, c->fB, c->phi, c->G, c->nh, c->F, c->K, c->U, c->ns, c->obs, c->integ};
     for (void *q : ptrs) if (q) (void)hipFree(q);
     c->pool.destroy();
     if (c->ev_lists) (void)hipEventDestroy(c->ev_lists);
@@ -1777,6 +1804,21 @@ extern "C" int lbmpm_rk3dcsf_get_field(lbmpm_rk3dcsf *c, int field, double *out)
         set_error("unknown field id %d", field);
         return LBMPM_ERR_INVALID;
     }
+}
+
+// Plane integrals of the recorded state (rk3d_integrals.h), reduced from the populations in registers: no staging array.  out: [own
+// planes][LBMPM_INTEGRAL_COLS]; valid wherever lbmpm_rk3dcsf_get_field(REC_*) is, slabs included.
+extern "C" int lbmpm_rk3dcsf_integrals(lbmpm_rk3dcsf *c, double *out)
+{
+    LBMPM_REQUIRE(c && out, "lbmpm_rk3dcsf_integrals: null argument");
+    if (!c->have_state) { set_error("lbmpm_rk3dcsf_integrals before set_macro / set_pdf"); return LBMPM_ERR_STATE; }
+    LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
+    const unsigned planes = (unsigned)(c->nz - c->cfg.ghost_lo - c->cfg.ghost_hi), plane_cells = (unsigned)c->nx * (unsigned)c->ny;
+    if (!c->integ) { const int rc = dev_alloc(c, &c->integ, integral_buffer_doubles(planes, plane_cells)); if (rc) return rc; }
+    const CsfDev p = make_dev(c);
+    if (c->first) LBMPM_HIP_TRY(integrals_run(CsfIntLoader<true>{p}, planes, plane_cells, c->integ, out, c->stream));
+    else LBMPM_HIP_TRY(integrals_run(CsfIntLoader<false>{p}, planes, plane_cells, c->integ, out, c->stream));
+    return LBMPM_OK;
 }
 
 extern "C" int64_t lbmpm_rk3dcsf_num_fluid_nodes(const lbmpm_rk3dcsf *c) { return c ? c->nfluid : 0; }

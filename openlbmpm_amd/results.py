@@ -195,6 +195,24 @@ class RecordGuard:
         dist.all_reduce(t, op=dist.ReduceOp.MAX, group=self.group)
         return bool(int(t.item()))
 
+    def integrals(self, step, nonfinite, sums=None):
+        """The same rule at the cadence of the plane integrals (openlbmpm_amd/integrals.py): `nonfinite` is the number of fluid cells
+        the device counted as not finite, `sums` what the log line carries; both None on a rank of a distributed run that does not hold
+        the gathered table -- the verdict is collective like a record's"""
+        if self.mode != "off":
+            msg = None
+            if nonfinite:
+                msg = "%s: step %d: the plane integrals count %d fluid cells with non-finite values" % (self.name, step, nonfinite)
+            if self._anyone_bad(msg is not None):
+                if msg is None:
+                    msg = "%s: step %d: the plane integrals count fluid cells with non-finite values" % (self.name, step)
+                if self.mode == "raise":
+                    raise SimulationDiverged(msg)
+                import warnings
+                warnings.warn(msg)
+        if sums is not None and self.log.isEnabledFor(20):
+            self.log.info("%s integrals step %d%s", self.name, step, "".join("  %s %.10g" % kv for kv in sums.items()))
+
     def __call__(self, record, step, fields, sums=None):
         if self.mode != "off":
             msg = None

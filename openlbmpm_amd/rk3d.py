@@ -206,6 +206,12 @@ class RK3DSlab(SlabTransportCalls):
         check(self._L.lbmpm_rk3d_get_field(self._h, FIELDS[name], out.ctypes.data_as(F64P)), "get_field(%s)" % name)
         return out
 
+    def integrals(self):
+        """integrals.Integrals of the slab's own planes: sums over the fields of the last phase_field(diagnostics=True), reduced on the
+        device (lbmpm_rk3d_integrals); LbmpmError (LBMPM_ERR_STATE) when a step has been taken since"""
+        from .integrals import Integrals, table
+        return Integrals(table(self._L, "lbmpm_rk3d_integrals", self._h, self.nzl), self.nx, self.ny)
+
     @property
     def num_fluid_nodes(self):
         return int(self._L.lbmpm_rk3d_num_fluid_nodes(self._h))
@@ -321,6 +327,12 @@ class RK3DCluster:
 
     def get(self, name):
         return np.concatenate([s.get(name) for s in self.slabs], axis=0)
+
+    def integrals(self):
+        """the slabs' tables in plane order (bit-equal to the undivided lattice's); observe() first when the diagnostics are stale"""
+        from .integrals import Integrals, fresh
+        s0 = self.slabs[0]
+        return Integrals(fresh(lambda: np.concatenate([s.integrals().planes for s in self.slabs], axis=0), self.observe), s0.nx, s0.ny)
 
     def close(self):
         for s in self.slabs:
@@ -505,6 +517,13 @@ class RK3DDistributed:
             self._halo_f()
             self.slab.phase_field(diagnostics=True)
         self.sync()
+
+    def integrals(self):
+        """collective: rank 0 returns the integrals.Integrals of the whole lattice (the ranks' tables through gather()), the others None;
+        observe() first when the diagnostics are stale (every rank is, or none: they step together)"""
+        from .integrals import Integrals, fresh
+        t = self.gather(fresh(lambda: self.slab.integrals().planes, self.observe))
+        return None if t is None else Integrals(t, self.slab.nx, self.slab.ny)
 
     def sync(self, deadline_s=None):
         """Wait for this rank's work.  With an in-library transport the wait is the library's watchdog (lbmpm_rk3d_sync_deadline,

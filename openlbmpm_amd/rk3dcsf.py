@@ -238,6 +238,12 @@ class RK3DCSFSolver(SlabTransportCalls):
         check(self._L.lbmpm_rk3dcsf_get_field(self._h, FIELDS[name], out.ctypes.data_as(F64P)), "get_field(%s)" % name)
         return out
 
+    def integrals(self):
+        """integrals.Integrals of the own planes (a slab: without its ghost planes): sums over what get("rec_*") hands out, reduced from
+        the populations on the device (lbmpm_rk3dcsf_integrals) -- no per-cell staging, nothing to call beforehand"""
+        from .integrals import Integrals, table
+        return Integrals(table(self._L, "lbmpm_rk3dcsf_integrals", self._h, self.nz - self.ghost[0] - self.ghost[1]), self.nx, self.ny)
+
     @property
     def num_fluid_nodes(self):
         return int(self._L.lbmpm_rk3dcsf_num_fluid_nodes(self._h))
@@ -376,6 +382,11 @@ class RK3DCSFCluster:
 
     def get(self, name):
         return np.concatenate([g.own(s.get(name)) for s, g in zip(self.slabs, self.geo)], axis=0)
+
+    def integrals(self):
+        """the slabs' tables in plane order: bit-equal to the undivided lattice's"""
+        from .integrals import Integrals
+        return Integrals(np.concatenate([s.integrals().planes for s in self.slabs], axis=0), self.nx, self.ny)
 
     num_fluid_nodes = property(lambda self: int(self.is_fluid_total))
     steps_done = property(lambda self: self.slabs[0].steps_done)
@@ -579,6 +590,12 @@ class RK3DCSFDistributed:
     def get(self, name):
         """this rank's own planes"""
         return np.ascontiguousarray(self.geo.own(self.slab.get(name)))
+
+    def integrals(self):
+        """collective: rank 0 returns the integrals.Integrals of the whole lattice (the ranks' tables through gather()), the others None"""
+        from .integrals import Integrals
+        t = self.gather(self.slab.integrals().planes)
+        return None if t is None else Integrals(t, self.shape[2], self.shape[1])
 
     def gather(self, a):
         """rank 0: the ranks' planes stacked along z (None elsewhere); slab.gather_planes"""
