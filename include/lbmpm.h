@@ -652,7 +652,10 @@ const char *lbmpm_rk3dcsf_dominant_kernel(const lbmpm_rk3dcsf *ctx);
  * LBMPM_CSF_MSG_PDF behind the ten flow populations: a step keeps its three messages per face, face_doubles(LBMPM_CSF_MSG_PDF, face) grows
  * by num_tracers x the fluid cells of that plane, the other two messages do not change.  Outlet and inlet are planes 0 and global_nz - 1
  * of the undivided lattice; the slabs compute what the undivided lattice computes, bit for bit.
- * NOT built: tracers on the perturbation model (lbmpm_rk3d_*). */
+ * Read through lbmpm_rk3dcsf_tracer_get_concentration / _get_pdf (dense fields through a staging array) or, for mass balances,
+ * breakthrough curves and the moments of a plume along the flow axis, through lbmpm_rk3dcsf_tracer_integrals (nine numbers per plane
+ * and tracer, reduced on the device, the same bit for bit however the lattice is cut).
+ * NOT built: tracers on the perturbation model (lbmpm_rk3d_*), which keeps refusing them; a split of the tracer mass by fluid phase. */
 typedef struct lbmpm_tracer3d_config {
     int32_t num_tracers;            /* [TransportParameters] NumberTracers, 1..4                                     */
     double diffusion_x[4];          /* [TransportMRT] DiffusionX                                                     */
@@ -689,6 +692,23 @@ int lbmpm_rk3dcsf_tracer_get_concentration(lbmpm_rk3dcsf *ctx, int tracer, doubl
  * bit for bit */
 int lbmpm_rk3dcsf_tracer_get_pdf(lbmpm_rk3dcsf *ctx, int tracer, double *out);
 int lbmpm_rk3dcsf_tracer_set_pdf(lbmpm_rk3dcsf *ctx, int tracer, const double *pdf);
+/* Plane integrals of the tracers: for every plane z the context owns and every tracer k, LBMPM_TRINT_COLS doubles over the plane's fluid
+ * cells, from the populations g[0..6] lbmpm_rk3dcsf_tracer_get_pdf hands out for that cell (streamed, inlet plane applied; on a slab the
+ * pulls out of the ghost planes) and the concentration C = g[0] + .. + g[6] summed in that order.  Reduced on the device by the scheme
+ * of lbmpm_rk3d_integrals, every addition in an order that (nx, ny) and the plane's mask fix alone: the table is the same bit for bit
+ * however the lattice is cut into slabs.  A cell where C or any of its seven populations is not finite counts in CELLS and NONFINITE and
+ * contributes to nothing else.
+ *   CELLS fluid cells | MASS sum of C | FLUX_X, FLUX_Y, FLUX_Z sum of g[1] - g[2], g[3] - g[4], g[5] - g[6]: the first moment of the
+ *   recorded populations, which a breakthrough curve integrates (the flow runs towards -z) | SUM_C2 sum of C C | CMIN, CMAX the least and
+ *   the largest C (both 0 on a plane without finite cells: the table itself is always finite) | NONFINITE the cells that are not finite */
+enum { LBMPM_TRINT_CELLS = 0, LBMPM_TRINT_MASS, LBMPM_TRINT_FLUX_X, LBMPM_TRINT_FLUX_Y, LBMPM_TRINT_FLUX_Z,
+       LBMPM_TRINT_SUM_C2, LBMPM_TRINT_CMIN, LBMPM_TRINT_CMAX, LBMPM_TRINT_NONFINITE };
+#define LBMPM_TRINT_COLS 9
+/* out: host [own planes][num_tracers][LBMPM_TRINT_COLS] (nz - ghost_lo - ghost_hi planes: the ghost planes are read, not reported).  All
+ * tracers in one pair of launches, from the populations and the table of source cells alone: no per-cell staging, the buffer of chunk
+ * partials is allocated by the first call.  LBMPM_ERR_STATE before lbmpm_rk3dcsf_tracer_configure(_slab) and before a concentration or
+ * populations were set.  One stream synchronisation, planes * num_tracers * 72 bytes copied */
+int lbmpm_rk3dcsf_tracer_integrals(lbmpm_rk3dcsf *ctx, double *out);
 
 /* ---- 3-D CSF slabs: the three face messages over a transport INSIDE the library (the perturbation model's transports above, "Transport
  * of the slab exchange": IPC landing areas filled by copy-engine transfers + stream value operations, or ncclSend / ncclRecv of a librccl

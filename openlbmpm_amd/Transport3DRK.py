@@ -15,11 +15,21 @@ g_i = w_i C, one tracer sub-step inside every flow step after the wetting-correc
 record holds two views: the flow arrays at the START of step iStep, the concentrations AFTER the tracer update of that step; the
 record the 3-D driver writes after the last step holds the concentrations as they stand.  The inlet concentrations are the file's.
 checkpoint() / restart_from= carry the tracers' populations behind the flow's (41 + 7 per tracer doubles per cell): bit for bit.
+
+integrals_every = N > 0: every N steps (step 0 and the last step included; the step loop's runs are cut there as at the record and
+checkpoint cadences) two tables, both reduced on the device and the same bit for bit on any number of ranks: the flow's plane integrals
+go to /Integrals/PlanesAtStep<step> [nz][12], /Integrals/Steps and /Integrals/Columns of SimulationResultsRK3D.h5 exactly as the flow's
+driver writes them, the tracers' (integrals.TracerIntegrals: cells, mass, flux_x, flux_y, flux_z, sum_c2, cmin, cmax, nonfinite per plane
+and tracer -- mass balances, the breakthrough -flux_z at the outlet, the plume's moments along z) to /TracerIntegrals/PlanesAtStep<step>
+[nz][nT][9], /TracerIntegrals/Steps and /TracerIntegrals/Columns of ConcentrationResults.h5.  Both counts of non-finite cells meet the
+nan_guard rule at that cadence (collective under torchrun; rank 0 writes), masses and extrema go to the log.  N = 0 writes no group and
+adds no stop; the records and checkpoints of a run do not depend on N.
 """
 import numpy as np
 
 from . import config
 from .RKColorGradientD3Q19 import GROUPS, RKColorGradient3D, _CSFSlab
+from .integrals import column_bytes, tracer_column_bytes
 from .results import RecordGuard, ResultFile
 
 
@@ -98,8 +108,11 @@ class Transport3DRK(RKColorGradient3D):
             self.initializeTransportDomain()
             for k in range(n):
                 slab.solver.set_concentration(k, self.tracerConc[k])
-        flow = ResultFile(self.output_dir, "SimulationResultsRK3D", GROUPS) if rank == 0 else None
-        conc = ResultFile(self.output_dir, "ConcentrationResults", (("TransportMacro", "MacroData"),)) if rank == 0 else None
+        every = self.integrals_every
+        more = lambda group: ((group, "PlaneIntegrals"),) if every > 0 else ()
+        flow = ResultFile(self.output_dir, "SimulationResultsRK3D", GROUPS + more("Integrals")) if rank == 0 else None
+        conc = ResultFile(self.output_dir, "ConcentrationResults", (("TransportMacro", "MacroData"),) + more("TracerIntegrals")) if rank == 0 else None
+        self.integral_steps = []
         self.result_path, self.concentration_path = (flow.path, conc.path) if rank == 0 else (None, None)
         # distributed: every rank checks its own planes, the verdict is collective (all ranks raise together, none is left in an exchange)
         self._guard = RecordGuard("rk3d+tracers", slab.num_fluid_nodes, getattr(self, "nan_guard", "raise"), collective=shared, device=self.device)
@@ -118,8 +131,19 @@ class Transport3DRK(RKColorGradient3D):
                 slab.sync()
                 self.checkpoint_path = self.checkpoint()
 
+        def maybe_integrals(last=False):
+            """both tables of the state after `done` steps (collective: rank 0 holds the whole lattice's and writes)"""
+            if every <= 0 or (done % every and not last) or (self.integral_steps and self.integral_steps[-1] == done):
+                return
+            self._integrals(slab.solver.integrals(), flow, done)
+            t = self.tracer_integrals = slab.solver.tracer_integrals()
+            if t is not None and conc is not None:
+                conc.write("TracerIntegrals", "PlanesAtStep%d" % done, t.planes)
+            tracer_guard.integrals(done, None if t is None else t.nonfinite, None if t is None else t.summary())
+
         while done < self.timeSteps:
             self._step_now = done
+            maybe_integrals()
             if done % self.timeInterval == 0:
                 k = self.records
                 self._record(slab, flow)                # the flow at the start of step done + 1
@@ -127,9 +151,12 @@ class Transport3DRK(RKColorGradient3D):
                 done += 1
                 record_tracers(k, done)                 # the concentrations after the tracer update of that step
                 maybe_checkpoint()
+                maybe_integrals()
             m = min(self.timeInterval - done % self.timeInterval, self.timeSteps - done) if done % self.timeInterval else 0
             if self.checkpoint_every > 0 and m:
                 m = min(m, self.checkpoint_every - done % self.checkpoint_every)
+            if every > 0 and m:
+                m = min(m, every - done % every)
             if m:
                 slab.step_single(m)
                 done += m
@@ -140,6 +167,11 @@ class Transport3DRK(RKColorGradient3D):
         k = self.records
         self._record(slab, flow)
         record_tracers(k, done)
+        maybe_integrals(last=True)
+        if every > 0 and rank == 0:
+            steps = np.array(self.integral_steps, dtype=np.int64)
+            flow.write("Integrals", "Steps", steps); flow.write("Integrals", "Columns", column_bytes())
+            conc.write("TracerIntegrals", "Steps", steps); conc.write("TracerIntegrals", "Columns", tracer_column_bytes())
         slab.sync()
         self.solver = slab
         return self.result_path, self.concentration_path

@@ -7,7 +7,9 @@
     python -m openlbmpm_amd rk3d <ini-dir> ...     D3Q19 colour gradient (RKtwophasesetup3D.ini); under torchrun: z-slabs, one per GPU
         [--csf-transport auto|ipc|rccl]           rk3d with SurfaceTensionType = 'CSF' and tr3d under torchrun: the slabs' face messages over the library's
                                                   own transports (default: through torch.distributed)
-        [--integrals-every N]                     rk3d: saturation, masses, fluxes, Darcy velocities per plane every N steps (/Integrals of the result file)
+        [--integrals-every N]                     rk3d, tr3d: saturation, masses, fluxes, Darcy velocities per plane every N steps (/Integrals of the result
+                                                  file); tr3d also the tracers' mass, fluxes and extrema per plane and tracer (/TracerIntegrals of
+                                                  ConcentrationResults)
 """
 import argparse
 import sys
@@ -42,8 +44,9 @@ def main(argv=None):
     ap.add_argument("--csf-transport", choices=["auto", "ipc", "rccl"], default=None,
                     help="rk3d with SurfaceTensionType = 'CSF', tr3d; under torchrun: move the slabs' face messages over the library's own transport")
     ap.add_argument("--integrals-every", type=int, default=0, metavar="N",
-                    help="rk3d: every N steps the plane integrals (saturation, masses, fluxes, largest speed, non-finite cells), reduced on the device, "
-                         "to /Integrals of the result file and the log; 0: off")
+                    help="rk3d, tr3d: every N steps the plane integrals (saturation, masses, fluxes, largest speed, non-finite cells), reduced on the device, "
+                         "to /Integrals of the result file and the log; tr3d also the tracers' (cells, mass, flux_x, flux_y, flux_z, sum_c2, cmin, cmax, "
+                         "nonfinite per plane and tracer) to /TracerIntegrals of ConcentrationResults; 0: off")
     a = ap.parse_args(argv)
     t0 = time.time()
     if a.model == "rk":
@@ -63,7 +66,8 @@ def main(argv=None):
         steps, nodes = sim.timeSteps, sim.voidSpace
     elif a.model == "tr3d":
         from .Transport3DRK import Transport3DRK
-        sim = Transport3DRK(a.ini_dir, output_dir=a.out, device=_rank_device(a.device), csf_transport=a.csf_transport)
+        sim = Transport3DRK(a.ini_dir, output_dir=a.out, device=_rank_device(a.device), csf_transport=a.csf_transport,
+                            integrals_every=a.integrals_every)
         if a.steps is not None:
             sim.timeSteps = a.steps
         path = " and ".join(str(f) for f in sim.runTransport3DMPMCRK())        # (under torchrun rank 0 writes both files)

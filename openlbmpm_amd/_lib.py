@@ -197,6 +197,7 @@ _SIGNATURES = {
     "lbmpm_rk3dcsf_enable_diagnostics": (C.c_int, [C.c_void_p, C.c_int]),
     "lbmpm_rk3dcsf_get_field": (C.c_int, [C.c_void_p, C.c_int, F64P]),
     "lbmpm_rk3dcsf_integrals": (C.c_int, [C.c_void_p, F64P]),
+    "lbmpm_rk3dcsf_tracer_integrals": (C.c_int, [C.c_void_p, F64P]),
     "lbmpm_rk3dcsf_num_fluid_nodes": (C.c_int64, [C.c_void_p]),
     "lbmpm_rk3dcsf_num_wetting_solids": (C.c_int64, [C.c_void_p]),
     "lbmpm_rk3dcsf_bulk_cells": (C.c_int64, [C.c_void_p]),

@@ -1172,7 +1172,7 @@ struct Rk3dIntLoader {
     const double *diag, *phi;
     unsigned nx, pitch;
     size_t plane2, vol;
-    __device__ __forceinline__ bool operator()(unsigned plane, unsigned k, IntCell &c) const
+    __device__ __forceinline__ bool operator()(unsigned, unsigned plane, unsigned k, IntCell &c) const
     {
         const unsigned y = k / nx, x = k - y * nx;
         const size_t idx = (size_t)(plane + 1u) * plane2 + (size_t)y * pitch + x;
@@ -2553,7 +2553,7 @@ extern "C" int lbmpm_rk3d_integrals(lbmpm_rk3d *c, double *out)
         return LBMPM_ERR_STATE;
     }
     const unsigned planes = (unsigned)c->nzl, plane_cells = (unsigned)c->nx * (unsigned)c->ny;
-    if (!c->integ) { const int rc = dev_alloc(c, &c->integ, integral_buffer_doubles(planes, plane_cells)); if (rc) return rc; }
+    if (!c->integ) { const int rc = dev_alloc(c, &c->integ, integral_buffer_doubles<FlowCols>(planes, plane_cells)); if (rc) return rc; }
     const Rk3dIntLoader load{c->flags, c->diag, c->phi, (unsigned)c->nx, (unsigned)c->pitch, c->plane2, c->vol};
     LBMPM_HIP_TRY(integrals_run(load, planes, plane_cells, c->integ, out, c->stream));
     return LBMPM_OK;

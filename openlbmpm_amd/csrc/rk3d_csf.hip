@@ -1010,13 +1010,14 @@ __global__ __launch_bounds__(256) void csf3d_import(CsfDev p, double *f, const d
 
 #include "rk3d_tracer.h"
 #include "rk3d_integrals.h"
+#include "rk3d_tracer_integrals.h"
 
 // what LBMPM_RK3DCSF_REC_RHO_R .. _REC_PHI hand out, from the populations: cell_state<FIRST, true>, the velocity with half the force and
 // the phase field in the arithmetic of csf3d_observe<FIRST, true>; own planes only (plane 0 is lattice plane p.glo)
 template <bool FIRST>
 struct CsfIntLoader {
     CsfDev p;
-    __device__ __forceinline__ bool operator()(unsigned plane, unsigned k, IntCell &c) const
+    __device__ __forceinline__ bool operator()(unsigned, unsigned plane, unsigned k, IntCell &c) const
     {
         constexpr int CX[Q] = CSF_CX, CY[Q] = CSF_CY, CZ[Q] = CSF_CZ;
         const int z = (int)plane + p.glo;
@@ -1059,6 +1060,7 @@ struct lbmpm_rk3dcsf {
     bool skip = true;
     double *fA = nullptr, *fB = nullptr, *phi = nullptr, *G = nullptr, *nh = nullptr, *F = nullptr, *K = nullptr, *U = nullptr, *ns = nullptr;
     double *integ = nullptr;       // lbmpm_rk3dcsf_integrals: chunk partials + the table (rk3d_integrals.h), allocated by the first call
+    double *trinteg = nullptr;     // lbmpm_rk3dcsf_tracer_integrals: the same for the tracers' tables (rk3d_tracer_integrals.h)
     double *obs = nullptr;         // staging of the observe kernel: rho [2][N], u [3][N], phi [N] (the populations [2][N][19] come and go with the call)
     lbmpm::EventPool pool;
     size_t timed_steps = 0;
@@ -1071,7 +1073,7 @@ struct lbmpm_rk3dcsf {
     int64_t slab_timed_steps = 0;
     // tracers (lbmpm_rk3dcsf_tracer_*; rk3d_tracer.h): nothing of this is allocated before a configure
     int ntr = 0;
-    bool tr_first = true;
+    bool tr_first = true, tr_given = false;     // tr_given: a concentration or populations were set since the configure
     lbmpm_tracer3d_config trcfg;
     double *gA = nullptr, *gB = nullptr, *trflow = nullptr;      // [ntr][7][FS] x 2, [4][FS]
     uint32_t *trsrc = nullptr;                                   // [6][FS] when the context has no table of source cells of its own
@@ -1232,7 +1234,7 @@ extern "C" void lbmpm_rk3dcsf_destroy(lbmpm_rk3dcsf *c)
     c->tx.destroy();
     for (void *q : {(void *)c->send_lo, (void *)c->send_hi}) if (q) (void)hipFree(q);
     c->slab_pool.destroy();
-    void *ptrs[] = {c->gA, c->gB, c->trflow, c->trsrc, c->wethome, c->rng, c->pfx, c->pure, c->deep_prev, c->bcblk, c->deep_now, c->work, c->tcnt, c->src, c->dom, c->meta, c->wetlist, c->cidx, c->cells, c->fA, c->fB, c->phi, c->G, c->nh, c->F, c->K, c->U, c->ns, c->obs, c->integ};
+    void *ptrs[] = {c->gA, c->gB, c->trflow, c->trsrc, c->wethome, c->rng, c->pfx, c->pure, c->deep_prev, c->bcblk, c->deep_now, c->work, c->tcnt, c->src, c->dom, c->meta, c->wetlist, c->cidx, c->cells, c->fA, c->fB, c->phi, c->G, c->nh, c->F, c->K, c->U, c->ns, c->obs, c->integ, c->trinteg};
     for (void *q : ptrs) if (q) (void)hipFree(q);
     c->pool.destroy();
     if (c->ev_lists) (void)hipEventDestroy(c->ev_lists);
@@ -1814,7 +1816,7 @@ extern "C" int lbmpm_rk3dcsf_integrals(lbmpm_rk3dcsf *c, double *out)
     if (!c->have_state) { set_error("lbmpm_rk3dcsf_integrals before set_macro / set_pdf"); return LBMPM_ERR_STATE; }
     LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
     const unsigned planes = (unsigned)(c->nz - c->cfg.ghost_lo - c->cfg.ghost_hi), plane_cells = (unsigned)c->nx * (unsigned)c->ny;
-    if (!c->integ) { const int rc = dev_alloc(c, &c->integ, integral_buffer_doubles(planes, plane_cells)); if (rc) return rc; }
+    if (!c->integ) { const int rc = dev_alloc(c, &c->integ, integral_buffer_doubles<FlowCols>(planes, plane_cells)); if (rc) return rc; }
     const CsfDev p = make_dev(c);
     if (c->first) LBMPM_HIP_TRY(integrals_run(CsfIntLoader<true>{p}, planes, plane_cells, c->integ, out, c->stream));
     else LBMPM_HIP_TRY(integrals_run(CsfIntLoader<false>{p}, planes, plane_cells, c->integ, out, c->stream));
@@ -2191,6 +2193,7 @@ static int tracer_import(lbmpm_rk3dcsf *c, int tracer, const double *conc, const
     }
     (void)hipStreamSynchronize(c->stream);
     (void)hipFree(st);
+    if (rc == LBMPM_OK) c->tr_given = true;
     return rc;
 }
 
@@ -2237,4 +2240,21 @@ extern "C" int lbmpm_rk3dcsf_tracer_get_pdf(lbmpm_rk3dcsf *c, int tracer, double
 {
     LBMPM_REQUIRE(c && out, "lbmpm_rk3dcsf_tracer_get_pdf: null argument");
     return tracer_observe(c, tracer, nullptr, out, "lbmpm_rk3dcsf_tracer_get_pdf");
+}
+
+// Plane integrals of the tracers (rk3d_tracer_integrals.h): the populations lbmpm_rk3dcsf_tracer_get_pdf hands out, reduced in registers
+// for all tracers in one pair of launches -- no staging array.  out: [own planes][num_tracers][LBMPM_TRINT_COLS]; slabs included.
+extern "C" int lbmpm_rk3dcsf_tracer_integrals(lbmpm_rk3dcsf *c, double *out)
+{
+    LBMPM_REQUIRE(c && out, "lbmpm_rk3dcsf_tracer_integrals: null argument");
+    { const int rc = tracer_ready(c, 0, "lbmpm_rk3dcsf_tracer_integrals"); if (rc) return rc; }
+    if (!c->tr_given) { set_error("lbmpm_rk3dcsf_tracer_integrals before lbmpm_rk3dcsf_tracer_set_concentration / _set_pdf"); return LBMPM_ERR_STATE; }
+    LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
+    const unsigned planes = (unsigned)(c->nz - c->cfg.ghost_lo - c->cfg.ghost_hi), plane_cells = (unsigned)c->nx * (unsigned)c->ny, nT = (unsigned)c->ntr;
+    if (!c->trinteg) { const int rc = dev_alloc(c, &c->trinteg, integral_buffer_doubles<TracerCols>(planes, plane_cells, nT)); if (rc) return rc; }
+    const CsfDev p = make_dev(c);
+    const TrDev t = make_trdev(c);
+    if (c->tr_first) LBMPM_HIP_TRY(tracer_integrals_run(TrIntLoader<true>{p, t}, planes, plane_cells, nT, c->trinteg, out, c->stream));
+    else LBMPM_HIP_TRY(tracer_integrals_run(TrIntLoader<false>{p, t}, planes, plane_cells, nT, c->trinteg, out, c->stream));
+    return LBMPM_OK;
 }

@@ -1,5 +1,6 @@
 """Plane integrals of the 3-D solvers: the table of lbmpm_rk3d_integrals / lbmpm_rk3dcsf_integrals (include/lbmpm.h) and what a
-two-phase run is read through -- saturation, masses, fluxes, Darcy velocities, the largest speed, the count of non-finite cells.
+two-phase run is read through -- saturation, masses, fluxes, Darcy velocities, the largest speed, the count of non-finite cells; and
+the tracers' table of lbmpm_rk3dcsf_tracer_integrals (TracerIntegrals): mass balances, breakthrough, the moments of a plume along z.
 
 The library reduces every plane on the device in a fixed order, so a table is the same bit for bit however the lattice was cut into
 slabs; `totals` keeps that: one loop over the planes in plane order, not a reduction whose order numpy may choose.
@@ -95,10 +96,131 @@ class Integrals:
         return dict(saturationR=self.saturation_R, massR=self.mass_R, massB=self.mass_B, maxSpeed=self.max_speed)
 
 
+# the tracers' columns, in the order of LBMPM_TRINT_* (csrc/rk3d_tracer_integrals.h is the only other place that knows it)
+TRACER_COLUMNS = ("cells", "mass", "flux_x", "flux_y", "flux_z", "sum_c2", "cmin", "cmax", "nonfinite")
+_T = {c: i for i, c in enumerate(TRACER_COLUMNS)}
+
+
+class TracerIntegrals:
+    """planes: [nz][nT][9], one row per lattice plane and tracer over the plane's fluid cells, from the populations g[0..6] that
+    get_tracer_pdf hands out and C = their sum (a cell where C or a population is not finite counts in `cells` and `nonfinite` only;
+    cmin = cmax = 0 on a plane without finite cells); nx, ny: the plane's extent.  Everything below is computed from the plane
+    profile alone."""
+    COLUMNS = TRACER_COLUMNS
+
+    def __init__(self, planes, nx, ny):
+        a = np.ascontiguousarray(planes, dtype=np.float64)
+        if a.ndim != 3 or a.shape[2] != len(TRACER_COLUMNS):
+            raise TypeError("planes must have shape [nz][nT][%d]" % len(TRACER_COLUMNS))
+        self.planes, self.nx, self.ny = a, int(nx), int(ny)
+        self.nz, self.num_tracers = a.shape[0], a.shape[1]
+        self._totals = None
+
+    def column(self, name, tracer):
+        """the profile of one column of one tracer along z"""
+        return self.planes[:, int(tracer), _T[name]]
+
+    @property
+    def totals(self):
+        """[nT][9]: the planes added in plane order; cmin / cmax: the least / largest over the planes that have finite cells (0 without)"""
+        if self._totals is None:
+            n = len(TRACER_COLUMNS)
+            t = [[0.0] * n for _ in range(self.num_tracers)]
+            seen = [False] * self.num_tracers
+            for plane in self.planes.tolist():
+                for k, row in enumerate(plane):
+                    good = row[_T["cells"]] - row[_T["nonfinite"]] > 0
+                    for c, v in enumerate(row):
+                        if c == _T["cmin"] or c == _T["cmax"]:
+                            if good:
+                                t[k][c] = v if not seen[k] else (min(t[k][c], v) if c == _T["cmin"] else max(t[k][c], v))
+                        else:
+                            t[k][c] = t[k][c] + v
+                    seen[k] = seen[k] or good
+            self._totals = np.array(t, dtype=np.float64).reshape(self.num_tracers, n)
+        return self._totals
+
+    def total(self, name, tracer):
+        return float(self.totals[int(tracer), _T[name]])
+
+    def good_cells(self, tracer):
+        return self.total("cells", tracer) - self.total("nonfinite", tracer)
+
+    def mass(self, tracer):
+        """sum of C over the finite fluid cells"""
+        return self.total("mass", tracer)
+
+    def mean(self, tracer):
+        g = self.good_cells(tracer)
+        return self.mass(tracer) / g if g else float("nan")
+
+    def variance(self, tracer):
+        """sum C^2 / cells - mean^2: the scalar variance (the mixing state)"""
+        g = self.good_cells(tracer)
+        return self.total("sum_c2", tracer) / g - self.mean(tracer) ** 2 if g else float("nan")
+
+    def cmin(self, tracer):
+        return self.total("cmin", tracer)
+
+    def cmax(self, tracer):
+        return self.total("cmax", tracer)
+
+    @property
+    def nonfinite(self):
+        """cells that are not finite, all tracers together"""
+        return int(sum(self.total("nonfinite", k) for k in range(self.num_tracers)))
+
+    def _z_sums(self, tracer):
+        """sum m(z), sum z m(z), sum z^2 m(z), added in plane order"""
+        s0 = s1 = s2 = 0.0
+        for z, m in enumerate(self.column("mass", tracer).tolist()):
+            s0 += m
+            s1 += z * m
+            s2 += z * z * m
+        return s0, s1, s2
+
+    def centre_z(self, tracer):
+        """sum z m(z) / sum m(z): the plume's centre of mass along the flow axis"""
+        s0, s1, _ = self._z_sums(tracer)
+        return s1 / s0 if s0 else float("nan")
+
+    def variance_z(self, tracer):
+        """the second central moment of the mass profile along z; it grows as 2 D_zz t"""
+        s0 = self._z_sums(tracer)[0]
+        if not s0:
+            return float("nan")
+        mu = self.centre_z(tracer)
+        v = 0.0
+        for z, m in enumerate(self.column("mass", tracer).tolist()):
+            v += (z - mu) ** 2 * m
+        return v / s0
+
+    def flux_z_at(self, tracer, z):
+        """sum of g(+z) - g(-z) over plane z: one entry of the profile.  The flow runs towards -z (inlet on plane nz-1, outlet on plane 0),
+        so the breakthrough at the outlet is -flux_z_at(k, 1)"""
+        return float(self.planes[int(z), int(tracer), _T["flux_z"]])
+
+    def summary(self):
+        """the numbers a log line carries: mass<k>, cmin<k>, cmax<k> per tracer"""
+        out = {}
+        for k in range(self.num_tracers):
+            out["mass%d" % k], out["cmin%d" % k], out["cmax%d" % k] = self.mass(k), self.cmin(k), self.cmax(k)
+        return out
+
+
+def _name_bytes(names):
+    width = max(len(c) for c in names)
+    return np.array([list(c.encode().ljust(width, b"\0")) for c in names], dtype=np.uint8)
+
+
 def column_bytes():
     """COLUMNS as a [12][width] uint8 array, zero-padded: what /Integrals/Columns of a result file holds (every backend writes it)"""
-    width = max(len(c) for c in COLUMNS)
-    return np.array([list(c.encode().ljust(width, b"\0")) for c in COLUMNS], dtype=np.uint8)
+    return _name_bytes(COLUMNS)
+
+
+def tracer_column_bytes():
+    """TRACER_COLUMNS the same way: /TracerIntegrals/Columns (column_names reads both)"""
+    return _name_bytes(TRACER_COLUMNS)
 
 
 def column_names(a):
@@ -123,4 +245,12 @@ def table(L, fn_name, handle, planes):
     from ._lib import F64P, check
     out = np.empty((int(planes), len(COLUMNS)), dtype=np.float64)
     check(getattr(L, fn_name)(handle, out.ctypes.data_as(F64P)), fn_name)
+    return out
+
+
+def tracer_table(L, handle, planes, num_tracers):
+    """[planes][nT][9] of one context through lbmpm_rk3dcsf_tracer_integrals"""
+    from ._lib import F64P, check
+    out = np.empty((int(planes), int(num_tracers), len(TRACER_COLUMNS)), dtype=np.float64)
+    check(L.lbmpm_rk3dcsf_tracer_integrals(handle, out.ctypes.data_as(F64P)), "lbmpm_rk3dcsf_tracer_integrals")
     return out

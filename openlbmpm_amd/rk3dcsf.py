@@ -244,6 +244,14 @@ class RK3DCSFSolver(SlabTransportCalls):
         from .integrals import Integrals, table
         return Integrals(table(self._L, "lbmpm_rk3dcsf_integrals", self._h, self.nz - self.ghost[0] - self.ghost[1]), self.nx, self.ny)
 
+    def tracer_integrals(self):
+        """integrals.TracerIntegrals of the own planes, [planes][nT][9]: cells, mass, the first moments g(+a) - g(-a) per axis, sum C^2,
+        the extrema of C and the non-finite count per plane and tracer, over the populations get_tracer_pdf hands out -- reduced on the
+        device for all tracers at once (lbmpm_rk3dcsf_tracer_integrals), no dense field staged or copied"""
+        from .integrals import TracerIntegrals, tracer_table
+        n = max(1, getattr(self, "num_tracers", 0))          # (without tracers the library refuses before it writes)
+        return TracerIntegrals(tracer_table(self._L, self._h, self.nz - self.ghost[0] - self.ghost[1], n), self.nx, self.ny)
+
     @property
     def num_fluid_nodes(self):
         return int(self._L.lbmpm_rk3dcsf_num_fluid_nodes(self._h))
@@ -387,6 +395,11 @@ class RK3DCSFCluster:
         """the slabs' tables in plane order: bit-equal to the undivided lattice's"""
         from .integrals import Integrals
         return Integrals(np.concatenate([s.integrals().planes for s in self.slabs], axis=0), self.nx, self.ny)
+
+    def tracer_integrals(self):
+        """the slabs' tracer tables in plane order: bit-equal to the undivided lattice's"""
+        from .integrals import TracerIntegrals
+        return TracerIntegrals(np.concatenate([s.tracer_integrals().planes for s in self.slabs], axis=0), self.nx, self.ny)
 
     num_fluid_nodes = property(lambda self: int(self.is_fluid_total))
     steps_done = property(lambda self: self.slabs[0].steps_done)
@@ -596,6 +609,13 @@ class RK3DCSFDistributed:
         from .integrals import Integrals
         t = self.gather(self.slab.integrals().planes)
         return None if t is None else Integrals(t, self.shape[2], self.shape[1])
+
+    def tracer_integrals(self):
+        """collective: rank 0 returns the integrals.TracerIntegrals of the whole lattice ([nz][nT][9]: axis 0 is z, so gather() stacks the
+        ranks' tables), the others None"""
+        from .integrals import TracerIntegrals
+        t = self.gather(self.slab.tracer_integrals().planes)
+        return None if t is None else TracerIntegrals(t, self.shape[2], self.shape[1])
 
     def gather(self, a):
         """rank 0: the ranks' planes stacked along z (None elsewhere); slab.gather_planes"""
