@@ -497,6 +497,35 @@ enum { LBMPM_INT_CELLS = 0, LBMPM_INT_CELLS_R, LBMPM_INT_MASS_R, LBMPM_INT_MASS_
  * (never calls it itself: on slabs the halo exchange comes first, which is the caller's).  One stream synchronisation, nz_local * 96
  * bytes copied */
 int lbmpm_rk3d_integrals(lbmpm_rk3d *ctx, double *out);
+/* Phase clusters of the 3-D solvers: the connected components of each phase, labelled on the device (csrc/rk3d_clusters.h).
+ *   Cells       the fluid cells of the planes the context owns -- the planes and the mask of lbmpm_*_integrals.  Perturbation model: phi
+ *               of the last lbmpm_rk3d_phase_field(ctx, 1) (LBMPM_ERR_STATE when a step has been taken since, as for the integrals); CSF
+ *               model: what LBMPM_RK3DCSF_REC_PHI hands out, computed from the populations.
+ *   Class       1 (R) if phi > phi_cut, 2 (B) if phi <= -phi_cut, 0 otherwise: solid, phi not finite, or -- with phi_cut > 0 -- the
+ *               interface band.  phi_cut >= 0; at 0 the R cells are the integrals' CELLS_R.
+ *   Neighbours  connectivity 6 (faces) or 18 (the D3Q19 links); anything else: LBMPM_ERR_UNSUPPORTED.  x and y wrap periodically as in
+ *               the solvers; z does not, in either model (nor does the CSF ring's last-to-first face): clusters are read between the
+ *               open planes.
+ *   Cluster     a maximal set of cells of one class connected through neighbours of that class.  Its label is the global cell number
+ *               (z_global * ny + y) * nx + x of its smallest cell, a uint32; 0xFFFFFFFF: in no cluster.  A lattice of 2^32 - 1 cells or
+ *               more: LBMPM_ERR_UNSUPPORTED.  The label makes the result unique and independent of how the lattice is cut.
+ *   Table       one row of LBMPM_CLUSTER_COLS int64 per cluster, rows by ascending label: LABEL, CLASS, CELLS, ZMIN, ZMAX (global plane
+ *               numbers).  Integers throughout: the same bits on every call.
+ * The labels and the table of a slab are those of the slab alone (a cluster cut by a slab face appears once on each side); the labels
+ * are global cell numbers all the same, and the faces are there for the caller to join slabs with.  Device memory: 17 bytes per own
+ * lattice cell, allocated by the first lbmpm_*_clusters call (counted by lbmpm_*_device_bytes), nothing before. */
+#define LBMPM_CLUSTER_COLS 5
+#define LBMPM_CLUSTER_NONE 0xFFFFFFFFu
+enum { LBMPM_CL_LABEL = 0, LBMPM_CL_CLASS, LBMPM_CL_CELLS, LBMPM_CL_ZMIN, LBMPM_CL_ZMAX };
+typedef struct lbmpm_clusters_config { double phi_cut; int32_t connectivity; int32_t reserved; } lbmpm_clusters_config;
+/* label and build the table on the device; *count = rows.  cfg NULL: phi_cut 0, connectivity 6 */
+int lbmpm_rk3d_clusters(lbmpm_rk3d *ctx, const lbmpm_clusters_config *cfg, int64_t *count);
+/* of the last lbmpm_rk3d_clusters; LBMPM_ERR_STATE before one, and after a step or a change of state since it.
+ * table: host [count][LBMPM_CLUSTER_COLS]; labels: host [nz_local][ny][nx]; faces: host [2][ny][nx] each, the lowest and the highest
+ * own plane */
+int lbmpm_rk3d_clusters_table(lbmpm_rk3d *ctx, int64_t *out);
+int lbmpm_rk3d_clusters_labels(lbmpm_rk3d *ctx, uint32_t *out);
+int lbmpm_rk3d_clusters_faces(lbmpm_rk3d *ctx, uint32_t *labels, uint8_t *classes);
 /* out[4]: doubles stored per fluid cell (38, or 23 with the compressed compact storage: 19 colour-blind populations + k_R + the
  * recolouring vector, from which the pull rebuilds both colours -- AcceleratedRKGPU2D.py:1241-1267 makes the two lattices an affine
  * image of those), fluid cells owned, those of them in row segments flagged single-colour (no records kept), bytes one step moves
@@ -633,6 +662,12 @@ int lbmpm_rk3dcsf_get_field(lbmpm_rk3dcsf *ctx, int field, double *out);
 /* out: host [own planes][LBMPM_INTEGRAL_COLS] (nz - ghost_lo - ghost_hi rows), see lbmpm_rk3d_integrals; reduced from the populations in
  * registers (no per-cell staging).  LBMPM_ERR_STATE before set_macro / set_pdf; valid wherever get_field(REC_*) is, slabs included */
 int lbmpm_rk3dcsf_integrals(lbmpm_rk3dcsf *ctx, double *out);
+/* phase clusters of the own planes, see lbmpm_rk3d_clusters: phi is what LBMPM_RK3DCSF_REC_PHI hands out, from the populations in
+ * registers (no dense phi staged); labels [own planes][ny][nx] */
+int lbmpm_rk3dcsf_clusters(lbmpm_rk3dcsf *ctx, const lbmpm_clusters_config *cfg, int64_t *count);
+int lbmpm_rk3dcsf_clusters_table(lbmpm_rk3dcsf *ctx, int64_t *out);
+int lbmpm_rk3dcsf_clusters_labels(lbmpm_rk3dcsf *ctx, uint32_t *out);
+int lbmpm_rk3dcsf_clusters_faces(lbmpm_rk3dcsf *ctx, uint32_t *labels, uint8_t *classes);
 int64_t lbmpm_rk3dcsf_num_fluid_nodes(const lbmpm_rk3dcsf *ctx);
 int64_t lbmpm_rk3dcsf_num_wetting_solids(const lbmpm_rk3dcsf *ctx);
 /* fluid cells whose block took the bulk path in the last step (variant 0; see lbmpm_rk3dcsf_config.variant) */

@@ -31,6 +31,11 @@ integrals_every = N > 0: every N steps (step 0 and the last step included) the p
 (rank 0's in a distributed run: the whole lattice's table), /Integrals/Steps and /Integrals/Columns (the names as zero-padded bytes,
 integrals.column_names reads them) at the end; saturation, masses and the largest speed go to the log, and cells that are not finite are
 met with the nan_guard rule at that cadence.
+
+clusters_every = N > 0: at the same kind of cadence the connected clusters of each phase, labelled on the device (openlbmpm_amd/clusters.py;
+clusters_connectivity 6 or 18): /Clusters/TableAtStep<step> [n][5] int64 (label, class, cells, zmin, zmax; the whole lattice's, joined on
+rank 0 in a distributed run), /Clusters/Steps and /Clusters/Columns at the end; counts, the largest cluster, percolation and the trapped
+cells of each phase go to the log.
 """
 import os
 
@@ -107,7 +112,7 @@ def duct(nx, ny, nz):
 class RKColorGradient3D:
     def __init__(self, pathIniFile, output_dir=None, domain=None, device=0, record_every=None, num_buffering_layers=10,
                  structure_path=None, initial_dir=None, record_pdf=False, restart_from=None, checkpoint_every=0, csf_bulk_epsilon=0.0,
-                 csf_transport=None, integrals_every=0):
+                 csf_transport=None, integrals_every=0, clusters_every=0, clusters_connectivity=6):
         self.pathIni = pathIniFile
         self.par = config.read_rk3d(pathIniFile)
         self.output_dir = output_dir or os.path.expanduser("~/LBMResults3D")       # main.py:28
@@ -123,6 +128,8 @@ class RKColorGradient3D:
         # inside the library, one C call per run of steps (rk3dcsf.RK3DCSFDistributed)
         self.csf_transport = csf_transport
         self.integrals_every = int(integrals_every)      # 0: no /Integrals group, no extra stop of the step loop
+        # 0: no /Clusters group, no extra stop of the step loop; connectivity 6 (faces) or 18 (the D3Q19 links)
+        self.clusters_every, self.clusters_connectivity = int(clusters_every), int(clusters_connectivity)
         self.gather_records = True
         self.records = 0
         self.physicalVX = self.physicalVY = self.physicalVZ = None
@@ -270,6 +277,7 @@ class RKColorGradient3D:
             slab = sim = _CSFSlab(self.isDomain, p, self.device, self.csf_bulk_epsilon, distributed=whole_arrays, transport=self.csf_transport)
             step, observe = slab.step_single, (lambda: None)
             integrals = sim.solver.integrals
+            clusters = sim.solver.clusters
             self.z0, self.nzl = 0, self.zDomain
             if whole_arrays:
                 import torch.distributed as dist
@@ -293,6 +301,7 @@ class RKColorGradient3D:
                 sim = RK3DDistributed(self.isDomain, par, device=self.device, plane_cost=cost)
             step, observe, slab = sim.step, sim.observe, sim.slab
             integrals = sim.integrals
+            clusters = sim.clusters
             self.z0, self.nzl = sim.z0, sim.nzl
             if self.gather_records:
                 self._gather = sim.gather
@@ -303,6 +312,7 @@ class RKColorGradient3D:
             step = slab.step_single
             observe = lambda: slab.phase_field(diagnostics=True)
             integrals = lambda: fresh(slab.integrals, observe)
+            clusters = lambda **kw: fresh(lambda: slab.clusters(**kw), observe)
             self.z0, self.nzl = 0, self.zDomain
         self._slab, self._observe = slab, observe
         done = 0
@@ -315,8 +325,10 @@ class RKColorGradient3D:
         writes = rank == 0 or not (self._distributed() and self.gather_records)
         every = self.integrals_every
         # (the table is gathered: the whole lattice's on rank 0, whether the records are gathered or not)
-        out = ResultFile(self.output_dir, name, GROUPS + ((("Integrals", "PlaneIntegrals"),) if every > 0 and rank == 0 else ())) if writes else None
-        self.integral_steps = []
+        cevery = self.clusters_every
+        more = ((("Integrals", "PlaneIntegrals"),) if every > 0 and rank == 0 else ()) + ((("Clusters", "PhaseClusters"),) if cevery > 0 and rank == 0 else ())
+        out = ResultFile(self.output_dir, name, GROUPS + more) if writes else None
+        self.integral_steps, self.cluster_steps = [], []
         self.result_path = out.path if out else None
         # distributed: every rank checks its own slab, the verdict is collective (all ranks raise together, none is left in an exchange)
         self._guard = RecordGuard("rk3d", slab.num_fluid_nodes, getattr(self, "nan_guard", "raise"), collective=self._distributed(), device=self.device)
@@ -327,9 +339,13 @@ class RKColorGradient3D:
                 self._record(slab, out)
             if every > 0 and done % every == 0:
                 self._integrals(integrals(), out, done)
+            if cevery > 0 and done % cevery == 0:
+                self._clusters(clusters(connectivity=self.clusters_connectivity), out, done)
             n = min(self.timeInterval - done % self.timeInterval, self.timeSteps - done)
             if every > 0:
                 n = min(n, every - done % every)
+            if cevery > 0:
+                n = min(n, cevery - done % cevery)
             if self.checkpoint_every > 0:
                 n = min(n, self.checkpoint_every - done % self.checkpoint_every)
             step(n)
@@ -347,6 +363,12 @@ class RKColorGradient3D:
             if rank == 0:
                 out.write("Integrals", "Steps", np.array(self.integral_steps, dtype=np.int64))
                 out.write("Integrals", "Columns", column_bytes())
+        if cevery > 0:
+            self._clusters(clusters(connectivity=self.clusters_connectivity), out, done)
+            if rank == 0:
+                from .clusters import column_bytes as cluster_column_bytes
+                out.write("Clusters", "Steps", np.array(self.cluster_steps, dtype=np.int64))
+                out.write("Clusters", "Columns", cluster_column_bytes())
         slab.sync()
         self.solver = sim
         return self.result_path
@@ -358,6 +380,15 @@ class RKColorGradient3D:
         if t is not None and out is not None:
             out.write("Integrals", "PlanesAtStep%d" % step, t.planes)
         self._guard.integrals(step, None if t is None else t.nonfinite, None if t is None else t.summary())
+
+    def _clusters(self, t, out, step):
+        """t: the Clusters of the whole lattice at `step` (None on the other ranks of a distributed run)"""
+        self.clusters = t
+        self.cluster_steps.append(int(step))
+        if t is not None:
+            if out is not None:
+                out.write("Clusters", "TableAtStep%d" % step, t.table)
+            self._guard.log.info("rk3d clusters step %d: %s", step, " ".join("%s=%s" % kv for kv in t.summary().items()))
 
     def _record(self, slab, out):
         k = self.records

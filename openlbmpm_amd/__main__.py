@@ -10,6 +10,8 @@
         [--integrals-every N]                     rk3d, tr3d: saturation, masses, fluxes, Darcy velocities per plane every N steps (/Integrals of the result
                                                   file); tr3d also the tracers' mass, fluxes and extrema per plane and tracer (/TracerIntegrals of
                                                   ConcentrationResults)
+        [--clusters-every N]                      rk3d: the connected clusters of each phase, labelled on the device, every N steps (/Clusters of the
+        [--clusters-connectivity 6|18]            result file: label, class, cells, zmin, zmax per cluster); percolation and trapped cells to the log
 """
 import argparse
 import sys
@@ -47,6 +49,10 @@ def main(argv=None):
                     help="rk3d, tr3d: every N steps the plane integrals (saturation, masses, fluxes, largest speed, non-finite cells), reduced on the device, "
                          "to /Integrals of the result file and the log; tr3d also the tracers' (cells, mass, flux_x, flux_y, flux_z, sum_c2, cmin, cmax, "
                          "nonfinite per plane and tracer) to /TracerIntegrals of ConcentrationResults; 0: off")
+    ap.add_argument("--clusters-every", type=int, default=0, metavar="N",
+                    help="rk3d: every N steps the connected clusters of each phase (label, class, cells, zmin, zmax per cluster), labelled on the device, "
+                         "to /Clusters of the result file; counts, the largest cluster, percolation and trapped cells to the log; 0: off")
+    ap.add_argument("--clusters-connectivity", type=int, choices=[6, 18], default=6, help="rk3d: neighbours of a cell: 6 faces, or the 18 D3Q19 links")
     a = ap.parse_args(argv)
     t0 = time.time()
     if a.model == "rk":
@@ -59,7 +65,8 @@ def main(argv=None):
     elif a.model == "rk3d":
         from .RKColorGradientD3Q19 import RKColorGradient3D
         device = _rank_device(a.device)
-        sim = RKColorGradient3D(a.ini_dir, output_dir=a.out, device=device, csf_transport=a.csf_transport, integrals_every=a.integrals_every)
+        sim = RKColorGradient3D(a.ini_dir, output_dir=a.out, device=device, csf_transport=a.csf_transport, integrals_every=a.integrals_every,
+                                clusters_every=a.clusters_every, clusters_connectivity=a.clusters_connectivity)
         if a.steps is not None:
             sim.timeSteps = a.steps
         path = sim.runRKColorGradient3D()

@@ -1164,6 +1164,7 @@ __global__ void rk3d_setup_solidnbr(RK3Dev p, uint32_t *solidnbr)
 #include "rk3dq.h"
 #include "rk3d_state.h"
 #include "rk3d_integrals.h"
+#include "rk3d_clusters.h"
 
 // the fields of the last lbmpm_rk3d_phase_field(ctx, 1) (rhoR, rhoB, vx, vy, vz in `diag`, the phase field in `phi`; pitch, plane2 and
 // halo planes as lbmpm_rk3d_get_field reads them), the mask from the device's flags
@@ -1179,6 +1180,22 @@ struct Rk3dIntLoader {
         if (!(flags[idx] & 1)) return false;
         c.rR = diag[idx]; c.rB = diag[vol + idx]; c.ux = diag[2 * vol + idx]; c.uy = diag[3 * vol + idx]; c.uz = diag[4 * vol + idx];
         c.phi = phi[idx];
+        return true;
+    }
+};
+
+// phi of the last lbmpm_rk3d_phase_field(ctx, 1) under the mask of the device's flags, as Rk3dIntLoader reads them (rk3d_clusters.h)
+struct Rk3dPhiLoader {
+    const uint8_t *flags;
+    const double *phi;
+    unsigned nx, pitch;
+    size_t plane2;
+    __device__ __forceinline__ bool operator()(unsigned plane, unsigned k, double &v) const
+    {
+        const unsigned y = k / nx, x = k - y * nx;
+        const size_t idx = (size_t)(plane + 1u) * plane2 + (size_t)y * pitch + x;
+        if (!(flags[idx] & 1)) return false;
+        v = phi[idx];
         return true;
     }
 };
@@ -1199,6 +1216,7 @@ struct lbmpm_rk3d {
     uint32_t *solidnbr = nullptr;
     double *fA = nullptr, *fB = nullptr, *phi = nullptr, *diag = nullptr;
     double *integ = nullptr;         // lbmpm_rk3d_integrals: chunk partials + the table (rk3d_integrals.h), allocated by the first call
+    ClState cl;                      // lbmpm_rk3d_clusters: classes, labels, rows (rk3d_clusters.h), allocated by the first call
     uint32_t *purA = nullptr, *purB = nullptr;       // row flags of the q23 storage, swapped with fA / fB
     double *send_up = nullptr, *send_dn = nullptr, *recv_below = nullptr, *recv_above = nullptr;
     std::vector<uint8_t> h_domain;   // owned planes only, [nzl][ny][nx]
@@ -1503,7 +1521,7 @@ extern "C" void lbmpm_rk3d_destroy(lbmpm_rk3d *c)
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->aux) (void)hipStreamSynchronize(c->aux);
     c->tx.destroy();
-    for (void *ptr : {(void *)c->seg, (void *)c->seg2, (void *)c->pstart, (void *)c->flags, (void *)c->solidnbr, (void *)c->fA, (void *)c->fB, (void *)c->purA, (void *)c->purB, (void *)c->trace, (void *)c->slotq, (void *)c->phi, (void *)c->diag, (void *)c->integ,
+    for (void *ptr : {(void *)c->seg, (void *)c->seg2, (void *)c->pstart, (void *)c->flags, (void *)c->solidnbr, (void *)c->fA, (void *)c->fB, (void *)c->purA, (void *)c->purB, (void *)c->trace, (void *)c->slotq, (void *)c->phi, (void *)c->diag, (void *)c->integ, (void *)c->cl.cls, (void *)c->cl.lab, (void *)c->cl.rows, (void *)c->cl.chunks,
                       (void *)c->send_up, (void *)c->send_dn, (void *)c->recv_below, (void *)c->recv_above})
         if (ptr) (void)hipFree(ptr);
     c->pool.destroy();
@@ -1562,6 +1580,7 @@ extern "C" int lbmpm_rk3d_set_density(lbmpm_rk3d *c, const double *rho_r, const 
     c->halo_valid = false;
     c->steps = 0;
     c->observed_at = -1;
+    c->cl.valid = false;
     return LBMPM_OK;
 }
 
@@ -1648,6 +1667,7 @@ void state_was_set(lbmpm_rk3d *c, int64_t steps, bool streamed)
     c->halo_valid = false;
     c->steps = steps;
     c->observed_at = -1;
+    c->cl.valid = false;
 }
 }  // namespace
 
@@ -2556,6 +2576,67 @@ extern "C" int lbmpm_rk3d_integrals(lbmpm_rk3d *c, double *out)
     if (!c->integ) { const int rc = dev_alloc(c, &c->integ, integral_buffer_doubles<FlowCols>(planes, plane_cells)); if (rc) return rc; }
     const Rk3dIntLoader load{c->flags, c->diag, c->phi, (unsigned)c->nx, (unsigned)c->pitch, c->plane2, c->vol};
     LBMPM_HIP_TRY(integrals_run(load, planes, plane_cells, c->integ, out, c->stream));
+    return LBMPM_OK;
+}
+
+// Phase clusters of phi of the last lbmpm_rk3d_phase_field(ctx, 1) (rk3d_clusters.h; the definition: include/lbmpm.h)
+extern "C" int lbmpm_rk3d_clusters(lbmpm_rk3d *c, const lbmpm_clusters_config *cfg, int64_t *count)
+{
+    LBMPM_REQUIRE(c && count, "lbmpm_rk3d_clusters: null argument");
+    LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
+    ClState &s = c->cl;
+    double cut = 0.;
+    ClGeom g{};
+    { const int rc = clusters_configure("lbmpm_rk3d_clusters", cfg, (unsigned long long)c->nx * c->ny * (unsigned long long)c->cfg.nz_global, &cut, &g); if (rc) return rc; }
+    if (c->observed_at != c->steps) {
+        set_error("the phase field is stale: call lbmpm_rk3d_phase_field(ctx, 1) after the last step (clusters are those of phi at that call; "
+                  "observed at step %lld, now %lld)", (long long)c->observed_at, (long long)c->steps);
+        return LBMPM_ERR_STATE;
+    }
+    g.nx = (unsigned)c->nx; g.ny = (unsigned)c->ny; g.planes = (unsigned)c->nzl; g.plane_cells = g.nx * g.ny; g.n = g.planes * g.plane_cells;
+    g.z0 = (unsigned)c->cfg.z_offset; g.base = g.z0 * g.plane_cells;
+    s.valid = false;
+    if (!s.chunks) {
+        size_t n[4];
+        clusters_sizes_of(g.n, n);
+        int rc = dev_alloc(c, &s.cls, n[0]);
+        if (!rc) rc = dev_alloc(c, &s.lab, n[1]);
+        if (!rc) rc = dev_alloc(c, &s.rows, n[2]);
+        if (!rc) rc = dev_alloc(c, &s.chunks, n[3]);
+        if (rc) return rc;
+    }
+    s.g = g;
+    const Rk3dPhiLoader load{c->flags, c->phi, (unsigned)c->nx, (unsigned)c->pitch, c->plane2};
+    LBMPM_HIP_TRY(clusters_run(load, s, cut, c->stream));
+    s.valid = true; s.at_step = c->steps;
+    *count = s.count;
+    return LBMPM_OK;
+}
+
+extern "C" int lbmpm_rk3d_clusters_table(lbmpm_rk3d *c, int64_t *out)
+{
+    LBMPM_REQUIRE(c && out, "lbmpm_rk3d_clusters_table: null argument");
+    { const int rc = clusters_current("lbmpm_rk3d_clusters_table", c->cl, c->steps); if (rc) return rc; }
+    LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
+    LBMPM_HIP_TRY(clusters_table(c->cl, out, c->stream));
+    return LBMPM_OK;
+}
+
+extern "C" int lbmpm_rk3d_clusters_labels(lbmpm_rk3d *c, uint32_t *out)
+{
+    LBMPM_REQUIRE(c && out, "lbmpm_rk3d_clusters_labels: null argument");
+    { const int rc = clusters_current("lbmpm_rk3d_clusters_labels", c->cl, c->steps); if (rc) return rc; }
+    LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
+    LBMPM_HIP_TRY(clusters_labels(c->cl, out, c->stream));
+    return LBMPM_OK;
+}
+
+extern "C" int lbmpm_rk3d_clusters_faces(lbmpm_rk3d *c, uint32_t *labels, uint8_t *classes)
+{
+    LBMPM_REQUIRE(c && labels && classes, "lbmpm_rk3d_clusters_faces: null argument");
+    { const int rc = clusters_current("lbmpm_rk3d_clusters_faces", c->cl, c->steps); if (rc) return rc; }
+    LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
+    LBMPM_HIP_TRY(clusters_faces(c->cl, labels, classes, c->stream));
     return LBMPM_OK;
 }
 

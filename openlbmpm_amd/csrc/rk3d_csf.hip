@@ -1011,6 +1011,7 @@ __global__ __launch_bounds__(256) void csf3d_import(CsfDev p, double *f, const d
 #include "rk3d_tracer.h"
 #include "rk3d_integrals.h"
 #include "rk3d_tracer_integrals.h"
+#include "rk3d_clusters.h"
 
 // what LBMPM_RK3DCSF_REC_RHO_R .. _REC_PHI hand out, from the populations: cell_state<FIRST, true>, the velocity with half the force and
 // the phase field in the arithmetic of csf3d_observe<FIRST, true>; own planes only (plane 0 is lattice plane p.glo)
@@ -1033,6 +1034,23 @@ struct CsfIntLoader {
         c.rR = rR; c.rB = rB;
         c.ux = (mx + 0.5 * p.F[n]) / rs; c.uy = (my + 0.5 * p.F[p.NS + n]) / rs; c.uz = (mz + 0.5 * p.F[2 * p.NS + n]) / rs;
         c.phi = (rR - rB) / (rR + rB);
+        return true;
+    }
+};
+
+// phi as LBMPM_RK3DCSF_REC_PHI hands it out, in the arithmetic of CsfIntLoader (rk3d_clusters.h)
+template <bool FIRST>
+struct CsfPhiLoader {
+    CsfDev p;
+    __device__ __forceinline__ bool operator()(unsigned plane, unsigned k, double &phi) const
+    {
+        const int z = (int)plane + p.glo;
+        const unsigned n = (unsigned)z * ((unsigned)p.nx * (unsigned)p.ny) + k;
+        if (!(p.meta[n] & 1u)) return false;
+        const int y = (int)(k / (unsigned)p.nx), x = (int)(k - (unsigned)y * (unsigned)p.nx);
+        double fR[Q], fB[Q], rR, rB;
+        cell_state<FIRST, true>(p, x, y, z, fR, fB, rR, rB);
+        phi = (rR - rB) / (rR + rB);
         return true;
     }
 };
@@ -1061,6 +1079,7 @@ struct lbmpm_rk3dcsf {
     double *fA = nullptr, *fB = nullptr, *phi = nullptr, *G = nullptr, *nh = nullptr, *F = nullptr, *K = nullptr, *U = nullptr, *ns = nullptr;
     double *integ = nullptr;       // lbmpm_rk3dcsf_integrals: chunk partials + the table (rk3d_integrals.h), allocated by the first call
     double *trinteg = nullptr;     // lbmpm_rk3dcsf_tracer_integrals: the same for the tracers' tables (rk3d_tracer_integrals.h)
+    ClState cl;                    // lbmpm_rk3dcsf_clusters: classes, labels, rows (rk3d_clusters.h), allocated by the first call
     double *obs = nullptr;         // staging of the observe kernel: rho [2][N], u [3][N], phi [N] (the populations [2][N][19] come and go with the call)
     lbmpm::EventPool pool;
     size_t timed_steps = 0;
@@ -1234,7 +1253,7 @@ extern "C" void lbmpm_rk3dcsf_destroy(lbmpm_rk3dcsf *c)
     c->tx.destroy();
     for (void *q : {(void *)c->send_lo, (void *)c->send_hi}) if (q) (void)hipFree(q);
     c->slab_pool.destroy();
-    void *ptrs[] = {c->gA, c->gB, c->trflow, c->trsrc, c->wethome, c->rng, c->pfx, c->pure, c->deep_prev, c->bcblk, c->deep_now, c->work, c->tcnt, c->src, c->dom, c->meta, c->wetlist, c->cidx, c->cells, c->fA, c->fB, c->phi, c->G, c->nh, c->F, c->K, c->U, c->ns, c->obs, c->integ, c->trinteg};
+    void *ptrs[] = {c->gA, c->gB, c->trflow, c->trsrc, c->wethome, c->rng, c->pfx, c->pure, c->deep_prev, c->bcblk, c->deep_now, c->work, c->tcnt, c->src, c->dom, c->meta, c->wetlist, c->cidx, c->cells, c->fA, c->fB, c->phi, c->G, c->nh, c->F, c->K, c->U, c->ns, c->obs, c->integ, c->trinteg, c->cl.cls, c->cl.lab, c->cl.rows, c->cl.chunks};
     for (void *q : ptrs) if (q) (void)hipFree(q);
     c->pool.destroy();
     if (c->ev_lists) (void)hipEventDestroy(c->ev_lists);
@@ -1457,6 +1476,7 @@ static int reset_state(lbmpm_rk3dcsf *c, const double *fx, const double *fy, con
     LBMPM_HIP_TRY(hipMemsetAsync(c->deep_prev, 0, c->nblk, c->stream));
     LBMPM_HIP_TRY(hipStreamSynchronize(c->stream));
     c->first = true; c->have_state = true; c->steps = 0; c->diag_valid = false; c->next_stage = 0;
+    c->cl.valid = false;
     return LBMPM_OK;
 }
 
@@ -1820,6 +1840,66 @@ extern "C" int lbmpm_rk3dcsf_integrals(lbmpm_rk3dcsf *c, double *out)
     const CsfDev p = make_dev(c);
     if (c->first) LBMPM_HIP_TRY(integrals_run(CsfIntLoader<true>{p}, planes, plane_cells, c->integ, out, c->stream));
     else LBMPM_HIP_TRY(integrals_run(CsfIntLoader<false>{p}, planes, plane_cells, c->integ, out, c->stream));
+    return LBMPM_OK;
+}
+
+// Phase clusters of the recorded phase field (rk3d_clusters.h; the definition: include/lbmpm.h), classified from the populations in
+// registers: no dense phi is staged.  Valid wherever lbmpm_rk3dcsf_integrals is, slabs included.
+extern "C" int lbmpm_rk3dcsf_clusters(lbmpm_rk3dcsf *c, const lbmpm_clusters_config *cfg, int64_t *count)
+{
+    LBMPM_REQUIRE(c && count, "lbmpm_rk3dcsf_clusters: null argument");
+    if (!c->have_state) { set_error("lbmpm_rk3dcsf_clusters before set_macro / set_pdf"); return LBMPM_ERR_STATE; }
+    LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
+    ClState &s = c->cl;
+    double cut = 0.;
+    ClGeom g{};
+    { const int rc = clusters_configure("lbmpm_rk3dcsf_clusters", cfg, (unsigned long long)c->nx * c->ny * (unsigned long long)c->nzg, &cut, &g); if (rc) return rc; }
+    g.nx = (unsigned)c->nx; g.ny = (unsigned)c->ny; g.planes = (unsigned)(c->nz - c->cfg.ghost_lo - c->cfg.ghost_hi);
+    g.plane_cells = g.nx * g.ny; g.n = g.planes * g.plane_cells;
+    g.z0 = (unsigned)(c->zoff + c->cfg.ghost_lo); g.base = g.z0 * g.plane_cells;
+    s.valid = false;
+    if (!s.chunks) {
+        size_t n[4];
+        clusters_sizes_of(g.n, n);
+        int rc = dev_alloc(c, &s.cls, n[0]);
+        if (!rc) rc = dev_alloc(c, &s.lab, n[1]);
+        if (!rc) rc = dev_alloc(c, &s.rows, n[2]);
+        if (!rc) rc = dev_alloc(c, &s.chunks, n[3]);
+        if (rc) return rc;
+    }
+    s.g = g;
+    const CsfDev p = make_dev(c);
+    if (c->first) LBMPM_HIP_TRY(clusters_run(CsfPhiLoader<true>{p}, s, cut, c->stream));
+    else LBMPM_HIP_TRY(clusters_run(CsfPhiLoader<false>{p}, s, cut, c->stream));
+    s.valid = true; s.at_step = c->steps;
+    *count = s.count;
+    return LBMPM_OK;
+}
+
+extern "C" int lbmpm_rk3dcsf_clusters_table(lbmpm_rk3dcsf *c, int64_t *out)
+{
+    LBMPM_REQUIRE(c && out, "lbmpm_rk3dcsf_clusters_table: null argument");
+    { const int rc = clusters_current("lbmpm_rk3dcsf_clusters_table", c->cl, c->steps); if (rc) return rc; }
+    LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
+    LBMPM_HIP_TRY(clusters_table(c->cl, out, c->stream));
+    return LBMPM_OK;
+}
+
+extern "C" int lbmpm_rk3dcsf_clusters_labels(lbmpm_rk3dcsf *c, uint32_t *out)
+{
+    LBMPM_REQUIRE(c && out, "lbmpm_rk3dcsf_clusters_labels: null argument");
+    { const int rc = clusters_current("lbmpm_rk3dcsf_clusters_labels", c->cl, c->steps); if (rc) return rc; }
+    LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
+    LBMPM_HIP_TRY(clusters_labels(c->cl, out, c->stream));
+    return LBMPM_OK;
+}
+
+extern "C" int lbmpm_rk3dcsf_clusters_faces(lbmpm_rk3dcsf *c, uint32_t *labels, uint8_t *classes)
+{
+    LBMPM_REQUIRE(c && labels && classes, "lbmpm_rk3dcsf_clusters_faces: null argument");
+    { const int rc = clusters_current("lbmpm_rk3dcsf_clusters_faces", c->cl, c->steps); if (rc) return rc; }
+    LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
+    LBMPM_HIP_TRY(clusters_faces(c->cl, labels, classes, c->stream));
     return LBMPM_OK;
 }
 

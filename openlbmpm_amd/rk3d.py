@@ -212,6 +212,18 @@ class RK3DSlab(SlabTransportCalls):
         from .integrals import Integrals, table
         return Integrals(table(self._L, "lbmpm_rk3d_integrals", self._h, self.nzl), self.nx, self.ny)
 
+    def clusters_part(self, phi_cut=0.0, connectivity=6, labels=False, faces=True):
+        """clusters.take of the slab's own planes: the table (and labels, faces) of this slab alone, for clusters.merge_slabs"""
+        from .clusters import take
+        return take(self._L, "rk3d", self._h, self.nzl, self.ny, self.nx, phi_cut, connectivity, labels, faces)
+
+    def clusters(self, phi_cut=0.0, connectivity=6, labels=False):
+        """clusters.Clusters of the slab's own planes: the connected cells of each phase of phi of the last phase_field(diagnostics=True),
+        labelled on the device (lbmpm_rk3d_clusters); LbmpmError (LBMPM_ERR_STATE) when a step has been taken since"""
+        from .clusters import Clusters
+        got = self.clusters_part(phi_cut, connectivity, labels, faces=False)
+        return Clusters(got["table"], self.nx, self.ny, self.nz, got.get("labels"))
+
     @property
     def num_fluid_nodes(self):
         return int(self._L.lbmpm_rk3d_num_fluid_nodes(self._h))
@@ -333,6 +345,15 @@ class RK3DCluster:
         from .integrals import Integrals, fresh
         s0 = self.slabs[0]
         return Integrals(fresh(lambda: np.concatenate([s.integrals().planes for s in self.slabs], axis=0), self.observe), s0.nx, s0.ny)
+
+    def clusters(self, phi_cut=0.0, connectivity=6, labels=False):
+        """clusters.Clusters of the whole lattice: the slabs' tables joined through their face planes (equal to the undivided lattice's);
+        observe() first when the phase field is stale"""
+        from .clusters import merged
+        from .integrals import fresh
+        s0 = self.slabs[0]
+        parts = fresh(lambda: [s.clusters_part(phi_cut, connectivity, labels) for s in self.slabs], self.observe)
+        return merged(parts, s0.nx, s0.ny, s0.nz, connectivity, labels)
 
     def close(self):
         for s in self.slabs:
@@ -524,6 +545,14 @@ class RK3DDistributed:
         from .integrals import Integrals, fresh
         t = self.gather(fresh(lambda: self.slab.integrals().planes, self.observe))
         return None if t is None else Integrals(t, self.slab.nx, self.slab.ny)
+
+    def clusters(self, phi_cut=0.0, connectivity=6, labels=False):
+        """collective: rank 0 returns the clusters.Clusters of the whole lattice (the ranks' tables and face planes, joined there; with
+        labels=True the label planes too), the others None; observe() first when the phase field is stale"""
+        from .clusters import gather_merged
+        from .integrals import fresh
+        part = fresh(lambda: self.slab.clusters_part(phi_cut, connectivity, labels), self.observe)
+        return gather_merged(part, self.rank, self.world, self.group, self.slab.nx, self.slab.ny, self.slab.nz, connectivity, labels)
 
     def sync(self, deadline_s=None):
         """Wait for this rank's work.  With an in-library transport the wait is the library's watchdog (lbmpm_rk3d_sync_deadline,

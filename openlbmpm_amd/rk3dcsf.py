@@ -100,6 +100,7 @@ class RK3DCSFSolver(SlabTransportCalls):
         cfg.bulk_epsilon = float(p["bulk_epsilon"])      # 0: exact (2^-51); opt-in: cut a colour's tail below this fraction of the density
         self.ghost = (GHOST, GHOST) if slab else (0, 0)
         cfg.ghost_lo, cfg.ghost_hi = self.ghost
+        self.global_nz = int(slab[1]) if slab else self.nz
         if slab:
             cfg.slab_z0, cfg.global_nz = int(slab[0]), int(slab[1])
         if p["rates"] is not None:
@@ -243,6 +244,18 @@ class RK3DCSFSolver(SlabTransportCalls):
         the populations on the device (lbmpm_rk3dcsf_integrals) -- no per-cell staging, nothing to call beforehand"""
         from .integrals import Integrals, table
         return Integrals(table(self._L, "lbmpm_rk3dcsf_integrals", self._h, self.nz - self.ghost[0] - self.ghost[1]), self.nx, self.ny)
+
+    def clusters_part(self, phi_cut=0.0, connectivity=6, labels=False, faces=True):
+        """clusters.take of the own planes: the table (and labels, faces) of this lattice or slab alone, for clusters.merge_slabs"""
+        from .clusters import take
+        return take(self._L, "rk3dcsf", self._h, self.nz - self.ghost[0] - self.ghost[1], self.ny, self.nx, phi_cut, connectivity, labels, faces)
+
+    def clusters(self, phi_cut=0.0, connectivity=6, labels=False):
+        """clusters.Clusters of the own planes: the connected cells of each phase of what get("rec_phi") hands out, classified from the
+        populations and labelled on the device (lbmpm_rk3dcsf_clusters) -- nothing staged, nothing to call beforehand"""
+        from .clusters import Clusters
+        got = self.clusters_part(phi_cut, connectivity, labels, faces=False)
+        return Clusters(got["table"], self.nx, self.ny, self.global_nz, got.get("labels"))
 
     def tracer_integrals(self):
         """integrals.TracerIntegrals of the own planes, [planes][nT][9]: cells, mass, the first moments g(+a) - g(-a) per axis, sum C^2,
@@ -395,6 +408,11 @@ class RK3DCSFCluster:
         """the slabs' tables in plane order: bit-equal to the undivided lattice's"""
         from .integrals import Integrals
         return Integrals(np.concatenate([s.integrals().planes for s in self.slabs], axis=0), self.nx, self.ny)
+
+    def clusters(self, phi_cut=0.0, connectivity=6, labels=False):
+        """clusters.Clusters of the whole lattice: the slabs' tables joined through their face planes (equal to the undivided lattice's)"""
+        from .clusters import merged
+        return merged([s.clusters_part(phi_cut, connectivity, labels) for s in self.slabs], self.nx, self.ny, self.nz, connectivity, labels)
 
     def tracer_integrals(self):
         """the slabs' tracer tables in plane order: bit-equal to the undivided lattice's"""
@@ -609,6 +627,13 @@ class RK3DCSFDistributed:
         from .integrals import Integrals
         t = self.gather(self.slab.integrals().planes)
         return None if t is None else Integrals(t, self.shape[2], self.shape[1])
+
+    def clusters(self, phi_cut=0.0, connectivity=6, labels=False):
+        """collective: rank 0 returns the clusters.Clusters of the whole lattice (the ranks' tables and face planes, joined there; with
+        labels=True the label planes too), the others None"""
+        from .clusters import gather_merged
+        part = self.slab.clusters_part(phi_cut, connectivity, labels)
+        return gather_merged(part, self.rank, self.world, None, self.shape[2], self.shape[1], self.nz, connectivity, labels)
 
     def tracer_integrals(self):
         """collective: rank 0 returns the integrals.TracerIntegrals of the whole lattice ([nz][nT][9]: axis 0 is z, so gather() stacks the
