@@ -287,6 +287,8 @@ int lbmpm_sc2d_enable_diagnostics(lbmpm_sc2d *ctx, int on);
 int lbmpm_sc2d_get_field(lbmpm_sc2d *ctx, int field, double *out);
 int64_t lbmpm_sc2d_num_fluid_nodes(const lbmpm_sc2d *ctx);
 int64_t lbmpm_sc2d_steps_done(const lbmpm_sc2d *ctx);
+/* hipGraph replays launched so far (small lattices replay batches of captured steps; 0 while every step was launched directly) */
+int64_t lbmpm_sc2d_graph_launches(const lbmpm_sc2d *ctx);
 const char *lbmpm_sc2d_dominant_kernel(const lbmpm_sc2d *ctx);
 int64_t lbmpm_sc2d_device_bytes(const lbmpm_sc2d *ctx);
 

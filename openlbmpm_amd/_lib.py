@@ -141,6 +141,7 @@ _SIGNATURES = {
     "lbmpm_sc2d_get_field": (C.c_int, [C.c_void_p, C.c_int, F64P]),
     "lbmpm_sc2d_num_fluid_nodes": (C.c_int64, [C.c_void_p]),
     "lbmpm_sc2d_steps_done": (C.c_int64, [C.c_void_p]),
+    "lbmpm_sc2d_graph_launches": (C.c_int64, [C.c_void_p]),
     "lbmpm_sc2d_dominant_kernel": (C.c_char_p, [C.c_void_p]),
     "lbmpm_sc2d_device_bytes": (C.c_int64, [C.c_void_p]),
     "lbmpm_rk3d_create": (C.c_int, [C.POINTER(RK3DConfig), U8P, C.POINTER(C.c_void_p)]),

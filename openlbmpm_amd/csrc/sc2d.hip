@@ -1267,5 +1267,6 @@ extern "C" int lbmpm_sc2d_get_field(lbmpm_sc2d *c, int field, double *out)
 
 extern "C" int64_t lbmpm_sc2d_num_fluid_nodes(const lbmpm_sc2d *c) { return c ? c->nfluid : 0; }
 extern "C" int64_t lbmpm_sc2d_steps_done(const lbmpm_sc2d *c) { return c ? c->steps : 0; }
+extern "C" int64_t lbmpm_sc2d_graph_launches(const lbmpm_sc2d *c) { return c ? c->graph_launches : 0; }
 extern "C" int64_t lbmpm_sc2d_device_bytes(const lbmpm_sc2d *c) { return c ? c->bytes : 0; }
 extern "C" const char *lbmpm_sc2d_dominant_kernel(const lbmpm_sc2d *c) { (void)c; return "sc2d_fused"; }

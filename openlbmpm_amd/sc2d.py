@@ -126,5 +126,10 @@ class SC2DSolver:
         return int(self._L.lbmpm_sc2d_steps_done(self._h))
 
     @property
+    def graph_launches(self):
+        """hipGraph replays launched so far (0 while every step was launched directly)"""
+        return int(self._L.lbmpm_sc2d_graph_launches(self._h))
+
+    @property
     def dominant_kernel(self):
         return self._L.lbmpm_sc2d_dominant_kernel(self._h).decode()

@@ -79,7 +79,8 @@ def initial_densities(dom, image, p):
 class SCOracle:
     """runOptimizedEFLBM (inter='EFS') or runOptimizedLBM (inter='ShanChen') on the CPU."""
 
-    def __init__(self, dom, params=None, rho_init=None, image=False):
+    def __init__(self, dom, params=None, rho_init=None, image=False, f_init=None):
+        """f_init [2][ny][nx][9]: start from these populations (a driver that resumes from fluidPDF) instead of weightsCoeff * rho"""
         L = lib()
         p = dict(DEFAULT_PARAMS); p.update(params or {})
         self.p = p
@@ -100,6 +101,9 @@ class SCOracle:
         self.rho = np.ascontiguousarray(rho_init.reshape(2, -1)[:, sel])
         w = np.array([4. / 9.] + [1. / 9.] * 4 + [1. / 36.] * 4)
         self.f = np.ascontiguousarray(w[None, None, :] * self.rho[:, :, None])   # weightsCoeff * rho
+        if f_init is not None:
+            self.f = np.ascontiguousarray(np.asarray(f_init, dtype=np.float64).reshape(2, -1, 9)[:, sel, :])
+            self.rho = np.ascontiguousarray(self.f.sum(axis=2))
         z = lambda *s: np.zeros(s)
         for name in ("fOld", "fNew", "feq", "ff", "fM", "ffM"):
             setattr(self, name, z(2, N, 9))

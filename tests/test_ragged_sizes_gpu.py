@@ -96,6 +96,71 @@ def test_sc2d_ragged(nx, ny):
     s.close()
 
 
+# (the coupling of test_sc2d_gpu's sc-conv case; tau != 1: at tau = 1 the BGK collision returns the equilibrium alone and forgets what a
+# boundary rule did to the populations beyond density and momentum -- the Chang inlet's kept rows enter through nothing else)
+TAUS = dict(tau0=0.9, tau1=1.1)
+SC_ORIGINAL = dict(inter="ShanChen", relax="SRT", G=2.6, Gs0=-0.2, Gs1=0.2, vy1=-1.01e-3, **TAUS)
+SC_DENS = dict(rho0=1.0, rho1=1.0, bg0=0.15, bg1=0.15)
+
+
+def _populations(dom, rho):
+    """Populations [2][ny][nx][9] on the densities rho that are no equilibrium at rest and vary along x.  The 'Chang' inlet reads the
+    populations o4, o7, o8 that the last step left on its row only through c = o4 - 2 (o7 + o8), and leaves c as it found it
+    (bc_inlet_chang, sc2d.hip: g4 - 2 (g7 + g8) = c).  With f = w rho, what set_density gives, c is zero on every node for the whole run and
+    the rows kept from step to step (sc2d_chang_seed, keep_inlet_row) could hold anything with c = 0, zeros included, unnoticed."""
+    w = np.array([4. / 9.] + [1. / 9.] * 4 + [1. / 36.] * 4)
+    yy, xx = np.mgrid[0:dom.shape[0], 0:dom.shape[1]]
+    f = np.empty((2,) + dom.shape + (9,))
+    for k in range(2):
+        for j in range(9):
+            f[k, :, :, j] = w[j] * rho[k] * (1.0 + 1.0e-2 * np.sin(0.41 * xx + 0.23 * yy + j + 2 * k))
+    return f
+
+
+def _sc2d_against_oracle(nx, ny, par, checkpoints, populations=False):
+    from openlbmpm_amd.sc2d import SC2DSolver
+    from oracle.sc import SCOracle, initial_densities
+    dom = _image(nx, ny + 30, nx * 3 + ny, 20)
+    rho = initial_densities(dom, True, dict(par, **SC_DENS))
+    s = SC2DSolver(dom, par, diagnostics=True)
+    if populations:
+        f = _populations(dom, rho)
+        o = SCOracle(dom, dict(par, **SC_DENS), image=True, f_init=f)
+        s.set_pdf(f[0], f[1])
+    else:
+        o = SCOracle(dom, dict(par, **SC_DENS), image=True)
+        s.set_density(rho[0], rho[1])
+    for n in checkpoints:
+        s.step(n - s.steps_done); o.run(n - o.iterations)
+        for k in range(2):
+            assert rel_err(s.get_compact("f%d" % k), o.f[k]) < 1e-9, (k, dom.shape, par, n)
+            assert rel_err(s.get_compact("rho%d" % k), o.rho[k]) < 1e-9, (k, dom.shape, par, n)
+    s.close()
+
+
+@pytest.mark.parametrize("nx,ny", SIZES_2D, ids=["%dx%d" % s for s in SIZES_2D])
+def test_sc2d_ragged_original(nx, ny):
+    """the original Shan-Chen loop (velocity shift, Zou-He inlet) at the ragged sizes, pressure and convective outlet in turn"""
+    _sc2d_against_oracle(nx, ny, dict(SC_ORIGINAL, method="ZouHe", outlet="Convective" if ny % 2 else "Dirichlet"), (10,))
+
+
+SIZES_ROWS = [(65, 49), (129, 53), (200, 41), (2050, 44)]
+ROW_CONFIGS = {"sc-chang": dict(SC_ORIGINAL, method="Chang"), "efs-chang": dict(inter="EFS", relax="SRT", method="Chang", **TAUS),
+               "efs-freeflow": dict(inter="EFS", relax="SRT", method="ZouHe", outlet="Freeflow", **TAUS)}
+
+
+@pytest.mark.parametrize("name", list(ROW_CONFIGS))
+@pytest.mark.parametrize("nx,ny", SIZES_ROWS, ids=["%dx%d" % s for s in SIZES_ROWS])
+def test_sc2d_ragged_boundary_rows(nx, ny, name):
+    """The row kernels beyond one tile column: the 'Chang' inlet (sc2d_chang_seed, keep_inlet_row, the rows kept from step to step) and
+    the 'Freeflow' outlet (sc2d_freeflow_rows) with two and more workgroups along x, a partial last tile, and 33 tile columns (staggered
+    XCD bands).  Chang at 129 is also compared after steps 1 and 2: the seed kernel and the first read of the kept rows.  The run starts
+    from populations that make the kept rows count (_populations)."""
+    par = dict(ROW_CONFIGS[name])
+    par.setdefault("outlet", "Convective" if ny % 2 else "Dirichlet")
+    _sc2d_against_oracle(nx, ny, par, (1, 2, 10) if par["method"] == "Chang" and nx == 129 else (10,), populations=True)
+
+
 SIZES_3D = [(64, 5, 9), (128, 8, 10), (40, 5, 9), (192, 12, 8), (65, 9, 13), (64, 17, 40), (4, 4, 8)]
 
 
