@@ -108,6 +108,17 @@ __device__ __forceinline__ i64 row_node(const i64 *fluidNodes, i64 N, i64 nx, i6
     return j < nx ? find_node(fluidNodes, N, row * nx + j) : -1;
 }
 
+// A row kernel that copies nodes from nodes which the same launch may overwrite: the ghost rows take their source from the neighbour
+// table unlooked-at, so a solid neighbour is the LAST node (nbr_node), which lies on row ny-1 -- a row the inlet ghost kernels write;
+// and A:1045 walks COMPACT indices < nx, which reach into row 1 (the sources of row 0) wherever row 0 holds a solid cell.  The source
+// is never a column to the left (a lower compact index), so the reference's threads, taken one after the other, all read what was
+// there before the launch.  With one workgroup per 64 columns that is a race between workgroups: such kernels run as ONE workgroup
+// (GRID_ROW_ORDERED) that walks the row in chunks of its size, left to right, each chunk reading, then -- past a barrier -- writing.
+__device__ __forceinline__ i64 row_node_at(const i64 *fluidNodes, i64 N, i64 nx, i64 row, i64 j)
+{
+    return j < nx ? find_node(fluidNodes, N, row * nx + j) : -1;
+}
+#define GRID_ROW_ORDERED dim3(1), dim3(256), 0, st
 #define GRID_NODES(N) dim3((unsigned)(((N) + NB - 1) / NB)), dim3(NB), 0, st
 #define GRID_FLAT(cnt) dim3((unsigned)(((cnt) + 255) / 256)), dim3(256), 0, st
 #define GRID_ROW(nx) dim3((unsigned)(((nx) + 63) / 64)), dim3(64), 0, st
@@ -770,19 +781,26 @@ __device__ __forceinline__ void copy_node2(double *fR, double *fB, i64 n, i64 sr
 // A:607-650 ghostPointsConstantVelocityRK (row ny-1 <- its S neighbour, rho = sum)
 __global__ void k_rk_ghost_inlet_velocity(i64 N, i64 nx, i64 ny, const i64 *fluidNodes, const i64 *nbr, double *rhoR, double *rhoB, double *fR, double *fB)
 {
-    const i64 n = row_node(fluidNodes, N, nx, ny - 1);
-    if (n < 0) return;
-    const i64 L = nbr_node(nbr[8 * n + 3], N);
-    double *r = fR + 9 * n, *b = fB + 9 * n;
-    for (int i = 0; i < 9; ++i) r[i] = fR[9 * L + i];
-    rhoR[n] = r[0] + r[1] + r[2] + r[3] + r[4] + r[5] + r[6] + r[7] + r[8];
-    for (int i = 0; i < 9; ++i) b[i] = fB[9 * L + i];
-    rhoB[n] = b[0] + b[1] + b[2] + b[3] + b[4] + b[5] + b[6] + b[7] + b[8];
+    for (i64 j0 = 0; j0 < nx; j0 += blockDim.x) {
+        const i64 n = row_node_at(fluidNodes, N, nx, ny - 1, j0 + threadIdx.x);
+        double r[9], b[9];
+        if (n >= 0) {
+            const i64 L = nbr_node(nbr[8 * n + 3], N);
+            for (int i = 0; i < 9; ++i) { r[i] = fR[9 * L + i]; b[i] = fB[9 * L + i]; }
+        }
+        __syncthreads();
+        if (n >= 0) {
+            for (int i = 0; i < 9; ++i) { fR[9 * n + i] = r[i]; fB[9 * n + i] = b[i]; }
+            rhoR[n] = r[0] + r[1] + r[2] + r[3] + r[4] + r[5] + r[6] + r[7] + r[8];
+            rhoB[n] = b[0] + b[1] + b[2] + b[3] + b[4] + b[5] + b[6] + b[7] + b[8];
+        }
+        __syncthreads();
+    }
 }
 static inline void launch_rk_ghost_inlet_velocity(hipStream_t st, i64 N, i64 nx, i64 ny, const i64 *fluidNodes, const i64 *nbr, double *rhoR, double *rhoB,
                                                   double *fR, double *fB)
 {
-    if (N > 0) k_rk_ghost_inlet_velocity<<<GRID_ROW(nx)>>>(N, nx, ny, fluidNodes, nbr, rhoR, rhoB, fR, fB);
+    if (N > 0) k_rk_ghost_inlet_velocity<<<GRID_ROW_ORDERED>>>(N, nx, ny, fluidNodes, nbr, rhoR, rhoB, fR, fB);
 }
 // A:925-962 calConstPressureInletGPU (row ny-2, Zou-He pressure per colour)
 __device__ __forceinline__ void zouhe_pressure_top(double *f, double p)
@@ -807,16 +825,26 @@ static inline void launch_rk_inlet_pressure(hipStream_t st, i64 N, i64 nx, i64 n
 // A:968-1002 ghostPointsConstPressureInletRK (row ny-1 <- its S neighbour incl. rho)
 __global__ void k_rk_ghost_inlet_pressure(i64 N, i64 nx, i64 ny, const i64 *fluidNodes, const i64 *nbr, double *rhoR, double *rhoB, double *fR, double *fB)
 {
-    const i64 n = row_node(fluidNodes, N, nx, ny - 1);
-    if (n < 0) return;
-    const i64 H = nbr_node(nbr[8 * n + 3], N);
-    for (int i = 0; i < 9; ++i) { fR[9 * n + i] = fR[9 * H + i]; fB[9 * n + i] = fB[9 * H + i]; }
-    rhoR[n] = rhoR[H]; rhoB[n] = rhoB[H];
+    for (i64 j0 = 0; j0 < nx; j0 += blockDim.x) {
+        const i64 n = row_node_at(fluidNodes, N, nx, ny - 1, j0 + threadIdx.x);
+        double r[9], b[9], dR = 0., dB = 0.;
+        if (n >= 0) {
+            const i64 H = nbr_node(nbr[8 * n + 3], N);
+            for (int i = 0; i < 9; ++i) { r[i] = fR[9 * H + i]; b[i] = fB[9 * H + i]; }
+            dR = rhoR[H]; dB = rhoB[H];
+        }
+        __syncthreads();
+        if (n >= 0) {
+            for (int i = 0; i < 9; ++i) { fR[9 * n + i] = r[i]; fB[9 * n + i] = b[i]; }
+            rhoR[n] = dR; rhoB[n] = dB;
+        }
+        __syncthreads();
+    }
 }
 static inline void launch_rk_ghost_inlet_pressure(hipStream_t st, i64 N, i64 nx, i64 ny, const i64 *fluidNodes, const i64 *nbr, double *rhoR, double *rhoB,
                                                   double *fR, double *fB)
 {
-    if (N > 0) k_rk_ghost_inlet_pressure<<<GRID_ROW(nx)>>>(N, nx, ny, fluidNodes, nbr, rhoR, rhoB, fR, fB);
+    if (N > 0) k_rk_ghost_inlet_pressure<<<GRID_ROW_ORDERED>>>(N, nx, ny, fluidNodes, nbr, rhoR, rhoB, fR, fB);
 }
 // A:2560-2590 calConstPressureLowerGPUTotal (row 1, Zou-He pressure on f_tot)
 __global__ void k_rk_outlet_pressure_total(i64 N, i64 nx, double pL, const i64 *fluidNodes, double *fT, double *vy, const double *rhoR, const double *rhoB,
@@ -869,22 +897,31 @@ static inline void launch_rk_pert_outlet_pressure(hipStream_t st, i64 N, i64 nx,
 // RKGPU2DBoundary.py:452-490 on grid row 0 (by_grid)
 __global__ void k_rk_ghost_outlet_pressure(i64 N, i64 nx, const i64 *fluidNodes, const i64 *nbr, double *rhoR, double *rhoB, double *fR, double *fB, int by_grid)
 {
-    i64 n;
-    if (by_grid) n = row_node(fluidNodes, N, nx, 0);
-    else { n = (i64)blockIdx.x * blockDim.x + threadIdx.x; if (n >= nx || n >= N) n = -1; }
-    if (n < 0) return;
-    const i64 L = nbr_node(nbr[8 * n + 1], N);
-    for (int i = 0; i < 9; ++i) { fR[9 * n + i] = fR[9 * L + i]; fB[9 * n + i] = fB[9 * L + i]; }
-    rhoR[n] = rhoR[L]; rhoB[n] = rhoB[L];
+    for (i64 j0 = 0; j0 < nx; j0 += blockDim.x) {
+        const i64 j = j0 + threadIdx.x;
+        const i64 n = by_grid ? row_node_at(fluidNodes, N, nx, 0, j) : (j < nx && j < N ? j : -1);
+        double r[9], b[9], dR = 0., dB = 0.;
+        if (n >= 0) {
+            const i64 L = nbr_node(nbr[8 * n + 1], N);
+            for (int i = 0; i < 9; ++i) { r[i] = fR[9 * L + i]; b[i] = fB[9 * L + i]; }
+            dR = rhoR[L]; dB = rhoB[L];
+        }
+        __syncthreads();
+        if (n >= 0) {
+            for (int i = 0; i < 9; ++i) { fR[9 * n + i] = r[i]; fB[9 * n + i] = b[i]; }
+            rhoR[n] = dR; rhoB[n] = dB;
+        }
+        __syncthreads();
+    }
 }
 static inline void launch_rk_ghost_outlet_pressure(hipStream_t st, i64 N, i64 nx, const i64 *nbr, double *rhoR, double *rhoB, double *fR, double *fB)
 {
-    if (N > 0) k_rk_ghost_outlet_pressure<<<GRID_ROW(nx)>>>(N, nx, nullptr, nbr, rhoR, rhoB, fR, fB, 0);
+    if (N > 0) k_rk_ghost_outlet_pressure<<<GRID_ROW_ORDERED>>>(N, nx, nullptr, nbr, rhoR, rhoB, fR, fB, 0);
 }
 static inline void launch_rk_ghost_outlet_pressure_grid(hipStream_t st, i64 N, i64 nx, const i64 *fluidNodes, const i64 *nbr, double *rhoR, double *rhoB,
                                                         double *fR, double *fB)
 {
-    if (N > 0) k_rk_ghost_outlet_pressure<<<GRID_ROW(nx)>>>(N, nx, fluidNodes, nbr, rhoR, rhoB, fR, fB, 1);
+    if (N > 0) k_rk_ghost_outlet_pressure<<<GRID_ROW_ORDERED>>>(N, nx, fluidNodes, nbr, rhoR, rhoB, fR, fB, 1);
 }
 // A:700-784 convectiveOutletGPU / Ghost2GPU / Ghost3GPU: row r <- its N neighbour, rho re-summed
 __global__ void k_rk_outlet_convective_row(i64 N, i64 nx, i64 row, const i64 *fluidNodes, const i64 *nbr, double *fR, double *fB, double *rhoR, double *rhoB)

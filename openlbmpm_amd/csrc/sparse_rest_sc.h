@@ -182,8 +182,8 @@ static inline void launch_sc_inlet_pressure_row(hipStream_t st, i64 N, i64 nx, i
 static inline void launch_sc_ghost_pressure_inlet(hipStream_t st, i64 N, i64 nx, i64 ny, const i64 *fluidNodes, const i64 *nbr, double *rho, double *f)
 {
     if (N <= 0) return;
-    k_sc_ghost_row<<<GRID_ROW(nx)>>>(N, nx, 0, 1, fluidNodes, nbr, rho, f);
-    k_sc_ghost_row<<<GRID_ROW(nx)>>>(N, nx, ny - 1, 3, fluidNodes, nbr, rho, f);
+    k_sc_ghost_row<<<GRID_ROW_ORDERED>>>(N, nx, 0, 1, fluidNodes, nbr, rho, f);
+    k_sc_ghost_row<<<GRID_ROW_ORDERED>>>(N, nx, ny - 1, 3, fluidNodes, nbr, rho, f);
 }
 
 // O:1127-1161 calVelocityBoundaryHigherChangGPU, O:1172-1215 calPressureBoundaryHigherChangGPU (row ny-2),

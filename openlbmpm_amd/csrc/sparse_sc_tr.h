@@ -110,25 +110,32 @@ static inline void launch_sc_inlet_velocity_row(hipStream_t st, i64 N, i64 nx, i
 // row <- the node `which` (3: S neighbour, 1: N neighbour) of the table, rho re-summed in the order 0..8
 __global__ void k_sc_ghost_row(i64 N, i64 nx, i64 row, int which, const i64 *fluidNodes, const i64 *nbr, double *rho, double *f)
 {
-    const i64 n = row_node(fluidNodes, N, nx, row);
-    if (n < 0) return;
-    const i64 q = nbr_node(nbr[8 * n + which], N);
-    for (int k = 0; k < NF; ++k) {
-        double *g = COMP(f, k, 9) + 9 * n;
-        const double *s = COMP(f, k, 9) + 9 * q;
-        for (int j = 0; j < 9; ++j) g[j] = s[j];
-        COMP(rho, k, 1)[n] = g[0] + g[1] + g[2] + g[3] + g[4] + g[5] + g[6] + g[7] + g[8];
+    for (i64 j0 = 0; j0 < nx; j0 += blockDim.x) {             // (one workgroup, read then write: GRID_ROW_ORDERED)
+        const i64 n = row_node_at(fluidNodes, N, nx, row, j0 + threadIdx.x);
+        double g[NF][9];
+        if (n >= 0) {
+            const i64 q = nbr_node(nbr[8 * n + which], N);
+            for (int k = 0; k < NF; ++k)
+                for (int j = 0; j < 9; ++j) g[k][j] = COMP(f, k, 9)[9 * q + j];
+        }
+        __syncthreads();
+        if (n >= 0)
+            for (int k = 0; k < NF; ++k) {
+                for (int j = 0; j < 9; ++j) COMP(f, k, 9)[9 * n + j] = g[k][j];
+                COMP(rho, k, 1)[n] = g[k][0] + g[k][1] + g[k][2] + g[k][3] + g[k][4] + g[k][5] + g[k][6] + g[k][7] + g[k][8];
+            }
+        __syncthreads();
     }
 }
 // O:710-738, O:897-955 ghostPointsConstantVelocityInlet / ...Velocity8 / ...82
 static inline void launch_sc_ghost_inlet_row(hipStream_t st, i64 N, i64 nx, i64 row, const i64 *fluidNodes, const i64 *nbr, double *rho, double *f)
 {
-    if (N > 0) k_sc_ghost_row<<<GRID_ROW(nx)>>>(N, nx, row, 3, fluidNodes, nbr, rho, f);
+    if (N > 0) k_sc_ghost_row<<<GRID_ROW_ORDERED>>>(N, nx, row, 3, fluidNodes, nbr, rho, f);
 }
 // O:743-770, O:775-836 ghostPointsConstantPressureOutlet / ...Outlet8 / ...82
 static inline void launch_sc_ghost_outlet_row(hipStream_t st, i64 N, i64 nx, i64 row, const i64 *fluidNodes, const i64 *nbr, double *rho, double *f)
 {
-    if (N > 0) k_sc_ghost_row<<<GRID_ROW(nx)>>>(N, nx, row, 1, fluidNodes, nbr, rho, f);
+    if (N > 0) k_sc_ghost_row<<<GRID_ROW_ORDERED>>>(N, nx, row, 1, fluidNodes, nbr, rho, f);
 }
 // O:555-585 / O:590-620 constantPressureZouHeBoundaryLower / ...Lower8: the outlet densities are the reference's
 // hard-coded 1.0 / 0.02 (O:560-561), whatever densityL says

@@ -9,6 +9,11 @@ in a table of seeded inputs, so a case is just (module, kernel, overrides).  Sto
 
 tests/test_kats_gpu.py replays each case through the same-named HIP entry point.  Container-only.
 Writes tests/golden/kats_<module tag>.npz.
+
+`wide_rk`, `wide_sc`, `wide_tr` emit the same cases on a second geometry, 66 x 9 with 513 fluid nodes: two full tiles of 256 nodes and a
+tile of one, two blocks of 64 columns for the boundary-row kernels.  Those go to tests/golden/kats_wide_<module tag>.npz in the
+deduplicated format of tests/helpers.py (write_kat_cases): every distinct array once, outputs only where the launch changed the array;
+a module whose file would pass 1e6 bytes is written as parts kats_wide_<module tag>_<i>.npz of consecutive cases.
 """
 import inspect
 import os
@@ -19,6 +24,8 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 import refenv  # noqa: E402
+sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
+from helpers import write_kat_cases  # noqa: E402
 
 OUT = os.environ.get("LBMPM_GOLDEN_OUT") or os.path.dirname(HERE)
 
@@ -26,13 +33,32 @@ EX = np.array([0., 1., 0., -1., 0., 1., -1., -1., 1.]); EY = np.array([0., 0., 1
 W9 = np.array([4. / 9.] + [1. / 9.] * 4 + [1. / 36.] * 4)
 
 
+WIDE = False                 # set by the wide_* targets
+
+
 def geometry(nx=14, ny=18):
     """walls at x = 0 and x = nx-1, a disc, rows 0..3 and ny-4..ny-1 otherwise fluid"""
+    if WIDE:
+        return wide_geometry()
     dom = np.ones((ny, nx), dtype=np.int64)
     dom[:, 0] = 0; dom[:, -1] = 0
     yy, xx = np.mgrid[0:ny, 0:nx]
     dom[(xx - 6.5) ** 2 + (yy - 9.0) ** 2 <= 2.3 ** 2] = 0
     fluidNodes = np.flatnonzero(dom.reshape(-1) == 1).astype(np.int64)
+    newIndex = -np.ones(ny * nx, dtype=np.int64)
+    newIndex[fluidNodes] = np.arange(fluidNodes.size)
+    return dom, fluidNodes, newIndex.reshape(ny, nx)
+
+
+def wide_geometry(nx=66, ny=9):
+    """walls at x = 0 and x = 65, a bar of solid cells in row 5; rows 0..3 and ny-2, ny-1 otherwise fluid.  513 = 2 * 256 + 1 fluid nodes:
+    the last node, the one the row kernels reach through a solid neighbour, lies alone in the third tile; the second block of 64 columns
+    holds column 64 (fluid) and 65 (wall)"""
+    dom = np.ones((ny, nx), dtype=np.int64)
+    dom[:, 0] = 0; dom[:, -1] = 0
+    dom[5, 2:65] = 0
+    fluidNodes = np.flatnonzero(dom.reshape(-1) == 1).astype(np.int64)
+    assert fluidNodes.size == 513
     newIndex = -np.ones(ny * nx, dtype=np.int64)
     newIndex[fluidNodes] = np.arange(fluidNodes.size)
     return dom, fluidNodes, newIndex.reshape(ny, nx)
@@ -71,6 +97,8 @@ class Cases:
         return {n: a for n, a in zip(names, args)}
 
     def save(self):
+        if WIDE:
+            return self.save_wide()
         np.savez_compressed(os.path.join(OUT, "kats_%s.npz" % self.tag), **self.out)
         refenv.say("kats_%s: %d cases" % (self.tag, sum(1 for k in self.out if k.endswith("|kernel"))))
 
@@ -131,6 +159,8 @@ def rk_cases():
     # Boundary rows next to a SOLID cell (an image geometry without all-fluid rows beside the inlet / outlet rows): these kernels index
     # with the neighbour id unlooked-at, and numba wraps the -1 of a solid neighbour like Python does -- the LAST node.
     dom2 = dom.copy(); dom2[1, 4] = 0; dom2[ny - 2, 9] = 0; dom2[2, 8] = 0
+    if WIDE:
+        dom2[1, 64] = 0                         # the second block of 64 columns meets a solid neighbour too
     fn2 = np.flatnonzero(dom2.reshape(-1) == 1).astype(np.int64)
     ni2 = -np.ones(ny * nx, dtype=np.int64); ni2[fn2] = np.arange(fn2.size)
     N2 = fn2.size
@@ -222,12 +252,12 @@ def tr_cases():
     nT = 2
     VX5 = np.array([0., 1., -1., 0., 0.]); VY5 = np.array([0., 0., 0., 1., -1.]); W5 = np.array([1. / 3.] + [1. / 6.] * 4)
     yrow = fluidNodes // nx
-    mask = (yrow < 9)                                            # boolean masks: True in the lower half
+    mask = (yrow < (5 if WIDE else 9))                           # boolean masks: True in the lower half
     mask[rng.integers(0, N, 6)] ^= True
     C = rng.uniform(0.2, 1.0, (nT, N))
     g5 = C[:, :, None] * W5[None, None, :] * rng.uniform(0.8, 1.2, (nT, N, 5))
     g9 = C[:, :, None] * W9[None, None, :] * rng.uniform(0.8, 1.2, (nT, N, 9))
-    newList = np.array(sorted(set(rng.choice(np.flatnonzero((yrow >= 3) & (yrow <= 8)), 7).tolist())), dtype=np.int64)
+    newList = np.array(sorted(set(rng.choice(np.flatnonzero((yrow >= 2) & (yrow <= 4) if WIDE else (yrow >= 3) & (yrow <= 8)), 7).tolist())), dtype=np.int64)
     # every listed node needs a masked, unlisted surrounding node (the reference divides by their count, T:239)
     ok = []
     for n in newList:
@@ -295,8 +325,40 @@ def tr_cases():
     c.save()
 
 
+PART_LIMIT = 1000000          # bytes; no committed file of this repository exceeds 1 MiB
+
+
+def _save_wide(self):
+    """kats_wide_<tag>.npz, or -- where that would exceed PART_LIMIT -- the fewest parts kats_wide_<tag>_<i>.npz of consecutive cases
+    (equal counts) that all stay below it"""
+    records = []
+    for key in self.out:
+        if key.endswith("|kernel"):
+            case = key[:-len("|kernel")]
+            names = [str(n) for n in self.out[case + "|args"]]
+            records.append(dict(case=case, kernel=str(self.out[key]), module=str(self.out[case + "|module"]), args=names,
+                                inputs={n: self.out["%s|in|%s" % (case, n)] for n in names},
+                                outputs={n: self.out["%s|out|%s" % (case, n)] for n in names if "%s|out|%s" % (case, n) in self.out}))
+        elif key.endswith("|raises"):
+            records.append(dict(case=key[:-len("|raises")], raises=str(self.out[key])))
+    for parts in range(1, len(records) + 1):
+        per = -(-len(records) // parts)
+        paths = [os.path.join(OUT, "kats_wide_%s%s.npz" % (self.tag, "_%d" % i if parts > 1 else "")) for i in range(parts)]
+        for i, path in enumerate(paths):
+            write_kat_cases(path, records[i * per: (i + 1) * per])
+        if max(os.path.getsize(path) for path in paths) <= PART_LIMIT:
+            break
+        for path in paths:
+            os.remove(path)
+    refenv.say("kats_wide_%s: %d cases in %d file(s)" % (self.tag, sum(1 for r in records if "kernel" in r), parts))
+
+
+Cases.save_wide = _save_wide
+
+
 if __name__ == "__main__":
     refenv.setup()
     which = sys.argv[1:] or ["rk"]
     for w in which:
-        globals()[w + "_cases"]()
+        WIDE = w.startswith("wide_")
+        globals()[(w[5:] if WIDE else w) + "_cases"]()

@@ -106,20 +106,22 @@ def csf_sequence(par, has_wetting):
     return seq
 
 
-@pytest.mark.parametrize("scenario", ["csf_mrt_capillary", "csf_mrt_convective", "csf_mrt_pinlet", "csf_mrt_wetting1", "csf_srt_capillary"])
-def test_colour_gradient_loop(rt, scenario):
-    """velocity / pressure inlet, pressure / convective outlet, wetting type 1 / 2, SRT / MRT: one capture of the real driver each"""
+CSF_FIELDS = dict(fR="fluidPDFR", fB="fluidPDFB", rhoR="fluidRhoR", rhoB="fluidRhoB", vx="physicalVX", vy="physicalVY", phi="ColorValue",
+                  Gx="gradientX", Gy="gradientY", Fx="forceX", Fy="forceY", K="KValue")
+
+
+def csf_table(rt, dom, par, rhoR0=None, rhoB0=None):
+    """The table of the CSF loop on the domain `dom` (RKD2Q9.py:1225-1294) with both neighbour tables filled by their kernels, and the oracle
+    whose HOST set-up it starts from (compaction tables, normals, initial fields); the oracle has not run yet"""
     from oracle.rk import RKOracle, mrt_matrices
-    d = np.load(os.path.join(GOLDEN, "rk_%s.npz" % scenario))
-    par = load_params(d)
-    o = RKOracle(d["isDomain"], par)                           # host set-up only (compaction tables, normals, initial fields)
-    assert np.array_equal(o.fluidNodes, d["fluidNodes"])
+    o = RKOracle(dom, par, rhoR0, rhoB0)
+    par = o.p
     N = o.N
     M, Minv, S = mrt_matrices()
     th = par["theta"] / 180. * np.pi
     z = lambda *s: np.zeros(s)
     t = Table(rt, totalNodes=N, totalNum=N, totalSolidWetting=o.W, totalWettingNodes=o.W, numColorSolid=o.W, totalFluidWettingNodes=o.Wf,
-              nx=par["nx"], ny=par["ny"], xDim=128, fluidNodes=o.fluidNodes, domainNewIndex=o.newIndex, wettingNodes=o.wettingSolidNodes,
+              nx=o.nx, ny=o.ny, xDim=128, fluidNodes=o.fluidNodes, domainNewIndex=o.newIndex, wettingNodes=o.wettingSolidNodes,
               neighboringNodes=np.zeros(8 * N, dtype=np.int64), neighboringWettingNodes=np.zeros(8 * max(o.W, 1), dtype=np.int64),
               fluidRhoR=o.rhoR, fluidRhoB=o.rhoB, fluidPDFR=o.fR, fluidPDFB=o.fB, fluidPDFRNew=z(N, 9), fluidPDFBNew=z(N, 9),
               fluidPDFTotal=o.fR + o.fB, physicalVX=z(N), physicalVY=z(N), ColorValue=z(N), colorValueSolid=z(max(o.W, 1)),
@@ -129,32 +131,46 @@ def test_colour_gradient_loop(rt, scenario):
               constPHB=par["rhoBH"], constPHR=par["rhoRH"], surfaceTension=par["sigma"], optionF=par["tautype"], tauR=par["tauR"],
               tauB=par["tauB"], deltaValue=par["delta"], betaValue=par["beta"])
     run(rt, "rk", t, [("fillNeighboringNodes", {})])                       # RKD2Q9.py:709-716
-    assert np.array_equal(t.host("neighboringNodes"), d["neighboringNodes"])
     if o.W:
         run(rt, "rk", t, [("fillNeighboringWettingNodes", {})])
-        assert np.array_equal(t.host("neighboringWettingNodes"), d["neighboringWettingSolidNodes"])
     t["neighboringWettingSolid"] = t["neighboringWettingNodes"]
+    return t, o
+
+
+@pytest.mark.parametrize("scenario", ["csf_mrt_capillary", "csf_mrt_convective", "csf_mrt_pinlet", "csf_mrt_wetting1", "csf_srt_capillary"])
+def test_colour_gradient_loop(rt, scenario):
+    """velocity / pressure inlet, pressure / convective outlet, wetting type 1 / 2, SRT / MRT: one capture of the real driver each"""
+    d = np.load(os.path.join(GOLDEN, "rk_%s.npz" % scenario))
+    par = load_params(d)
+    t, o = csf_table(rt, d["isDomain"], par)
+    assert np.array_equal(o.fluidNodes, d["fluidNodes"])
+    assert (o.nx, o.ny) == (par["nx"], par["ny"])
+    assert np.array_equal(t.host("neighboringNodes"), d["neighboringNodes"])
+    if o.W:
+        assert np.array_equal(t.host("neighboringWettingNodes"), d["neighboringWettingSolidNodes"])
     seq = csf_sequence(par, o.Wf > 0)
-    fields = dict(fR="fluidPDFR", fB="fluidPDFB", rhoR="fluidRhoR", rhoB="fluidRhoB", vx="physicalVX", vy="physicalVY", phi="ColorValue",
-                  Gx="gradientX", Gy="gradientY", Fx="forceX", Fy="forceY", K="KValue")
     snaps = [int(k) for k in d["snaps"] if int(k) <= 50]
     for step in range(1, max(snaps) + 1):
         run(rt, "rk", t, seq)
         if step in snaps:
-            check(t, d, "s%d_" % step, fields, 1e-11, "%s step %d" % (scenario, step))
+            check(t, d, "s%d_" % step, CSF_FIELDS, 1e-11, "%s step %d" % (scenario, step))
 
 
 # ------------------------------------------------------------------------------------------------ Shan-Chen family
-def sc_table(rt, g, par, with_iso):
-    from oracle.sc import simple_geometry, initial_densities
-    nx, ny = par["nx"], par["ny"]
-    dom = simple_geometry(nx, ny)
+def sc_table(rt, dom, par, with_iso, f0=None):
+    """The table of the two Shan-Chen loops on the domain `dom` (ShanChenD2Q9.py:1395-1478, :1632-1713), the neighbour tables filled by their
+    kernels.  rho0 as `par` layers it (the reference's initial condition on its simple geometry) with f = w rho, or the populations
+    f0 [2][N][9] of a driver that resumes from fluidPDF"""
+    from oracle.sc import initial_densities
+    ny, nx = dom.shape
     fluidNodes = np.flatnonzero(dom.reshape(-1) == 1).astype(np.int64)
-    assert np.array_equal(fluidNodes, g["fluidNodes"])
     N = fluidNodes.size
     newIndex = -np.ones(nx * ny, dtype=np.int64); newIndex[fluidNodes] = np.arange(N)
-    rho0 = np.ascontiguousarray(initial_densities(dom, False, par).reshape(2, -1)[:, fluidNodes])
-    f0 = np.ascontiguousarray(W9[None, None, :] * rho0[:, :, None])
+    if f0 is None:
+        rho0 = np.ascontiguousarray(initial_densities(dom, False, par).reshape(2, -1)[:, fluidNodes])
+        f0 = np.ascontiguousarray(W9[None, None, :] * rho0[:, :, None])
+    else:
+        f0 = np.ascontiguousarray(f0); rho0 = np.ascontiguousarray(f0.sum(axis=2))
     scheme = int(par.get("scheme", 4))
     weights = {4: [1. / 3.] * 4 + [1. / 12.] * 4,
                8: [4. / 21.] * 4 + [4. / 45.] * 4 + [1. / 60.] * 4 + [1. / 5040.] * 4 + [2. / 315.] * 8,
@@ -171,20 +187,28 @@ def sc_table(rt, g, par, with_iso):
               specificVY=np.array([par["vy0"], par["vy1"]]), densityL=1.002, conserveS=np.ones(2), primeVX=z(N), primeVY=z(N))
     t["physicalVY"] = t["velocityPY"]; t["equilibriumVX"] = t["eqVX"]; t["equilibriumVY"] = t["eqVY"]
     run(rt, "sc", t, [("fillNeighboringNodes", {})])
-    assert np.array_equal(t.host("neighboringNodes"), g["neighboringNodes"])
     if with_iso and scheme in (8, 10):
         t.put(isoNodes=np.zeros((24 if scheme == 8 else 36) * N, dtype=np.int64))
         run(rt, "sc", t, [("fillNeighboringNodesISO8" if scheme == 8 else "fillNeighboringNodesISO10", dict(neighboringNodes="isoNodes"))])
     return t, N, f0, tau, scheme
 
 
-@pytest.mark.parametrize("scenario", ["efs_srt_dirichlet", "efs_mrt_dirichlet", "efs_srt_convective", "efs_srt_iso8", "efs_srt_iso10",
-                                      "efs_srt_freeflow", "efs_srt_chang"])
-def test_explicit_forcing_loop(rt, scenario):
+def golden_sc_table(rt, g, par, with_iso):
+    from oracle.sc import simple_geometry
+    t, N, f0, tau, scheme = sc_table(rt, simple_geometry(par["nx"], par["ny"]), par, with_iso)
+    assert np.array_equal(t.host("fluidNodes"), g["fluidNodes"])
+    assert np.array_equal(t.host("neighboringNodes"), g["neighboringNodes"])
+    return t, N, f0, tau, scheme
+
+
+EFS_FIELDS = dict(f="fluidPDF", rho="fluidRho", Fx="forceX", Fy="forceY", vx="velocityPX", vy="velocityPY", ueqx="eqVX", ueqy="eqVY", feq="fEq",
+                  fforce="fForce")
+SC_FIELDS = dict(f="fluidPDF", rho="fluidRho", Fx="forceX", Fy="forceY", vx="velocityPX", vy="velocityPY")
+
+
+def efs_sequences(t, par, f0, tau, scheme):
+    """(what runs before the loop, one pass of the loop) of the explicit-forcing driver, ShanChenD2Q9.py:1714-2087; the MRT arrays join `t`"""
     from oracle.sc import collision_matrices
-    g = np.load(os.path.join(GOLDEN, "sc_%s.npz" % scenario))
-    par = load_params(g)
-    t, N, f0, tau, scheme = sc_table(rt, g, par, True)
     mrt = par["relax"] == "MRT"
     if mrt:
         t.put(collisionMatrix=collision_matrices(tau), fForceM=np.zeros_like(f0), fluidPDFM=f0)
@@ -209,25 +233,28 @@ def test_explicit_forcing_loop(rt, scenario):
                else freeflow + [("calCollisionEXGPU", {})])
     macro = [("calFluidRhoGPU", {}), ("calPhysicalVelocity", {})]
     # before the loop, ShanChenD2Q9.py:1714-1849
-    run(rt, "sc", t, chain + [("transformPDFGPU", {})] + inlet + (outlet_p if par["outlet"] == "Dirichlet" else []))
+    before = chain + [("transformPDFGPU", {})] + inlet + (outlet_p if par["outlet"] == "Dirichlet" else [])
     loop = [("savePDFLastStep", {})] + collide + [("calStreaming1GPU", {}), ("calStreaming2GPU", {})] + macro + outlet + inlet + macro + chain   # S:1852-2087
-    fields = dict(f="fluidPDF", rho="fluidRho", Fx="forceX", Fy="forceY", vx="velocityPX", vy="velocityPY", ueqx="eqVX", ueqy="eqVY", feq="fEq",
-                  fforce="fForce")
+    return before, loop
+
+
+@pytest.mark.parametrize("scenario", ["efs_srt_dirichlet", "efs_mrt_dirichlet", "efs_srt_convective", "efs_srt_iso8", "efs_srt_iso10",
+                                      "efs_srt_freeflow", "efs_srt_chang"])
+def test_explicit_forcing_loop(rt, scenario):
+    g = np.load(os.path.join(GOLDEN, "sc_%s.npz" % scenario))
+    par = load_params(g)
+    t, N, f0, tau, scheme = golden_sc_table(rt, g, par, True)
+    before, loop = efs_sequences(t, par, f0, tau, scheme)
+    run(rt, "sc", t, before)
     snaps = [int(k) for k in g["snaps"] if int(k) <= 10]
     for i in range(max(snaps) + 1):
         run(rt, "sc", t, loop)
         if i in snaps:
-            check(t, g, "s%d_" % i, fields, 1e-11, "%s pass %d" % (scenario, i))
+            check(t, g, "s%d_" % i, EFS_FIELDS, 1e-11, "%s pass %d" % (scenario, i))
 
 
-@pytest.mark.parametrize("scenario", ["sc_srt_convective", "sc_srt_chang"])
-def test_original_shan_chen_loop(rt, scenario):
-    """runOptimizedLBM (Neumann / Zou-He inlet, convective outlet): the fused interaction + collision kernel, the three
-    outlet-row kernels and the (result-less) whole-fluid velocity"""
-    g = np.load(os.path.join(GOLDEN, "sc_%s.npz" % scenario))
-    par = load_params(g)
-    t, N, f0, tau, _ = sc_table(rt, g, par, False)
-    assert rel_err(f0, g["init_f"]) < 1e-15
+def original_sequences(t, par):
+    """(head, tail) of one pass of runOptimizedLBM, ShanChenD2Q9.py:1492-1629; its interaction weights join `t`"""
     t.put(weightInter=np.array([1. / 9.] * 4 + [1. / 36.] * 4))                 # ShanChenD2Q9.py:1478
     inlet = (("calVelocityBoundaryHigherChangGPU", dict(fluidPDFOld="fluidPDFOld", fluidPDFNew="fluidPDF")) if par.get("method") == "Chang"      # S:1529
              else ("constantVelocityZouHeBoundaryHigher", {}))
@@ -236,7 +263,18 @@ def test_original_shan_chen_loop(rt, scenario):
             ("calStreaming2GPU", {}), ("convectiveOutletGPU", dict(fluidPDFNew="fluidPDF")), ("convectiveOutletGhost2GPU", dict(fluidPDFNew="fluidPDF")),
             ("convectiveOutletGhost3GPU", dict(fluidPDFNew="fluidPDF")),
             ("calFluidRhoGPU", {}), ("calPhysicalVelocity", {})]
-    fields = dict(f="fluidPDF", rho="fluidRho", Fx="forceX", Fy="forceY", vx="velocityPX", vy="velocityPY")
+    return head, tail
+
+
+@pytest.mark.parametrize("scenario", ["sc_srt_convective", "sc_srt_chang"])
+def test_original_shan_chen_loop(rt, scenario):
+    """runOptimizedLBM (Neumann / Zou-He inlet, convective outlet): the fused interaction + collision kernel, the three
+    outlet-row kernels and the (result-less) whole-fluid velocity"""
+    g = np.load(os.path.join(GOLDEN, "sc_%s.npz" % scenario))
+    par = load_params(g)
+    t, N, f0, tau, _ = golden_sc_table(rt, g, par, False)
+    assert rel_err(f0, g["init_f"]) < 1e-15
+    head, tail = original_sequences(t, par)
     snaps = [int(k) for k in g["snaps"]]
     for step in range(1, max(snaps) + 1):
         run(rt, "sc", t, head)
@@ -248,7 +286,7 @@ def test_original_shan_chen_loop(rt, scenario):
             assert rel_err(t.host("primeVX"), mx / rt_) < 1e-12 and rel_err(t.host("primeVY"), my / rt_) < 1e-12
         run(rt, "sc", t, tail)
         if step in snaps:
-            check(t, g, "s%d_" % step, fields, 1e-11, "%s step %d" % (scenario, step))
+            check(t, g, "s%d_" % step, SC_FIELDS, 1e-11, "%s step %d" % (scenario, step))
 
 
 # ------------------------------------------------------------------------------------------------ tracer kernels

@@ -42,6 +42,37 @@ def test_fixture_is_reproduced_from_the_reference(tmp_path, script, args, fixtur
         assert np.array_equal(new[k], old[k], equal_nan=new[k].dtype.kind == "f"), k
 
 
+@pytest.mark.parametrize("tag", ["rk", "sc", "tr"])
+def test_wide_known_answer_fixture_is_reproduced_from_the_reference(tmp_path, tag):
+    """tests/golden/kats_wide_<tag>*.npz (the second geometry of make_golden_kats.py, 513 nodes; one file or parts of consecutive cases):
+    regenerated and compared through the loader, case by case and bit for bit -- inputs, outputs, what is recorded as unchanged"""
+    import glob
+    from helpers import KatFile
+    env = dict(os.environ, LBMPM_GOLDEN_OUT=str(tmp_path))
+    subprocess.check_call([sys.executable, os.path.join(GEN, "make_golden_kats.py"), "wide_" + tag], env=env, cwd=str(tmp_path),
+                          stdout=subprocess.DEVNULL, timeout=600)
+
+    def load(folder):
+        files = [KatFile(f) for f in sorted(glob.glob(os.path.join(str(folder), "kats_wide_%s*.npz" % tag)))]
+        assert files
+        cases = {case: f.case(case) for f in files for case in f.cases}
+        assert len(cases) == sum(len(f.cases) for f in files)
+        return cases, {k: v for f in files for k, v in f.raises.items()}
+
+    def same(x, y):
+        return (x is None and y is None) or (x is not None and y is not None and x.dtype == y.dtype and x.shape == y.shape
+                                             and x.tobytes() == y.tobytes())
+
+    (new, new_raises), (old, old_raises) = load(tmp_path), load(os.path.join(ROOT, "tests", "golden"))
+    assert sorted(new) == sorted(old) and new_raises == old_raises
+    for case in old:
+        assert new[case][:3] == old[case][:3] and new[case][5] == old[case][5], case
+        for k in (3, 4):
+            assert list(new[case][k]) == list(old[case][k]), case
+            for arg in old[case][k]:
+                assert same(new[case][k][arg], old[case][k][arg]), (case, arg)
+
+
 def test_every_kernel_of_the_five_kernel_modules_has_an_entry_point():
     """completeness of the kernel-level ABI: every function the reference compiles with @cuda.jit as a KERNEL (not
     device=True) in its five kernel modules has a same-named entry point in include/lbmpm_kernels.h, with the same

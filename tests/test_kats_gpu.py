@@ -10,21 +10,46 @@ import sys
 import numpy as np
 import pytest
 
-from helpers import GOLDEN
+from helpers import GOLDEN, KatFile
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TOL = 2e-14                   # relative to the largest entry of the array: a few roundings (pow vs x*x, sum orders kept)
+# The wide files (kats_wide_*.npz, the format of helpers.write_kat_cases) hold the same cases on a 66 x 9 lattice with 513 = 2 * 256 + 1
+# fluid nodes: three tiles of 256 nodes, the last of one node, and two blocks of 64 columns for the boundary-row kernels.
+WIDE = sorted(os.path.basename(p) for p in glob.glob(os.path.join(GOLDEN, "kats_wide_*.npz")))
+_open = {}
+
+
+def wide(fixture):
+    if fixture not in _open:
+        _open[fixture] = KatFile(os.path.join(GOLDEN, fixture))
+    return _open[fixture]
 
 
 def cases():
     out = []
     for path in sorted(glob.glob(os.path.join(GOLDEN, "kats_*.npz"))):
+        if os.path.basename(path) in WIDE:
+            continue
         d = np.load(path)
         for key in d.files:
             if key.endswith("|kernel"):
                 out.append((os.path.basename(path), key[:-len("|kernel")]))
+    for fixture in WIDE:
+        out += [(fixture, case) for case in wide(fixture).cases]
     return out
+
+
+def load(fixture, case):
+    """(module, kernel, args, inputs, outputs, noop) of either format; outputs[arg] is None where a wide file records the array as unchanged"""
+    if fixture in WIDE:
+        return wide(fixture).case(case)
+    d = np.load(os.path.join(GOLDEN, fixture))
+    names = [str(n) for n in d[case + "|args"]]
+    inputs = {n: d["%s|in|%s" % (case, n)] for n in names}
+    return (str(d[case + "|module"]), str(d[case + "|kernel"]), names, inputs,
+            {n: d["%s|out|%s" % (case, n)] for n in names if inputs[n].ndim}, bool(d[case + "|noop"]))
 
 
 @pytest.fixture(scope="module")
@@ -37,22 +62,24 @@ def rt():
 
 @pytest.mark.parametrize("fixture,case", cases())
 def test_kernel_reproduces_the_reference_kernel(rt, fixture, case):
-    d = np.load(os.path.join(GOLDEN, fixture))
-    module, kernel = str(d[case + "|module"]), str(d[case + "|kernel"])
-    names = [str(n) for n in d[case + "|args"]]
+    module, kernel, names, inputs, outputs, noop = load(fixture, case)
     from openlbmpm_amd._kernel_specs import KERNELS
     assert tuple(names) == KERNELS[(module, kernel)][2], "the entry point must take the reference kernel's arguments, in its order"
     values, arrays = {}, {}
     for n in names:
-        v = d["%s|in|%s" % (case, n)]
+        v = inputs[n]
         if v.ndim == 0:
             values[n] = v.item()
         else:
             arrays[n] = values[n] = rt.to_device(np.ascontiguousarray(v))
+    assert set(arrays) == set(outputs)
     rt.launch_by_name(module, kernel, values)
     changed = 0
     for n, dev in arrays.items():
-        want, got, before = d["%s|out|%s" % (case, n)], dev.copy_to_host(), d["%s|in|%s" % (case, n)]
+        want, got, before = outputs[n], dev.copy_to_host(), inputs[n]
+        if want is None:          # recorded as unchanged by the reference kernel: bit for bit what went in
+            assert got.dtype == before.dtype and got.shape == before.shape and got.tobytes() == before.tobytes(), (case, n)
+            continue
         if want.dtype.kind in "ib":
             assert np.array_equal(got, want), (case, n)
         else:
@@ -61,7 +88,35 @@ def test_kernel_reproduces_the_reference_kernel(rt, fixture, case):
             err = np.nanmax(np.abs(got - want)) / scale if want.size else 0.0
             assert err < TOL, (case, n, err)
         changed += not np.array_equal(want, before, equal_nan=True)
-    assert bool(d[case + "|noop"]) == (changed == 0)        # (two reference kernels change nothing at all: O:320 with two fluids, E:38)
+    assert noop == (changed == 0)        # (two reference kernels change nothing at all: O:320 with two fluids, E:38)
+
+
+@pytest.mark.parametrize("fixture", WIDE)
+def test_wide_fixtures_hold_three_tiles_and_two_row_blocks(fixture):
+    """a later regeneration must not slide back under one tile of 256 nodes or one block of 64 columns: 513 nodes on the main geometry
+    (509 with the four extra solid cells of the #solid_neighbour cases; the reference's quadratic tracer collision takes five nodes at
+    most, see below), nx = 66 wherever a kernel takes nx"""
+    f = wide(fixture)
+    assert f.cases
+    for case in f.cases:
+        module, kernel, names, inputs, outputs, noop = f.case(case)
+        assert names[0] in ("totalNodes", "totaNodes", "totalNum"), (case, names[0])
+        n = int(inputs[names[0]])
+        if kernel == "calCollisionTransportQuadraticEqlMRTGPU":
+            assert n == 5
+        elif case.endswith("#solid_neighbour"):
+            assert n == 509, (case, n)
+        else:
+            assert n == 513, (case, n)
+        if "nx" in inputs:
+            assert int(inputs["nx"]) == 66, case
+            assert int(inputs["fluidNodes"].size) == n or kernel == "calCollisionTransportQuadraticEqlMRTGPU", case
+
+
+def test_wide_fixtures_hold_every_case_of_the_narrow_ones():
+    narrow = sorted(c for f, c in cases() if f not in WIDE)
+    assert sorted(c for f, c in cases() if f in WIDE) == narrow and len(narrow) == 62
+    assert [f.raises for f in map(wide, WIDE) if f.raises] == [{"calUpdateConcInTransportDomainByVQ9": "IndexError"}]
 
 
 def test_kernels_that_cannot_run_in_the_reference_say_so(rt):
