@@ -64,3 +64,5 @@ struct EventPool {
 };
 
 }  // namespace lbmpm
+
+#include "device_memory.h"

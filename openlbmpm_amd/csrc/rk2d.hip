@@ -1354,7 +1354,7 @@ struct lbmpm_rk2d {
     bool streamed = false;    // false: fA holds the initial (already "post-streaming") state
     bool diag_valid = false;
     int64_t steps = 0;
-    int64_t bytes = 0;
+    lbmpm::DeviceBlocks mem;  // every device block the context keeps (lbmpm_rk2d_device_bytes)
     lbmpm::EventPool pool;
 };
 
@@ -1494,24 +1494,6 @@ int run_steps(lbmpm_rk2d *c, int64_t n, bool timed)
     return LBMPM_OK;
 }
 
-template <typename T>
-int dev_alloc(lbmpm_rk2d *c, T **ptr, size_t count)
-{
-    void *v = nullptr;
-    hipError_t e = hipMalloc(&v, count * sizeof(T));
-    if (e != hipSuccess) {
-        set_error("hipMalloc(%zu bytes) failed: %s", count * sizeof(T), hipGetErrorString(e));
-        return LBMPM_ERR_NOMEM;
-    }
-    // zero on the context's own stream: a null-stream memset is not ordered against the
-    // non-blocking solver stream and could land after a kernel that already wrote the buffer
-    e = hipMemsetAsync(v, 0, count * sizeof(T), c->stream);
-    if (e != hipSuccess) { set_error("hipMemsetAsync failed: %s", hipGetErrorString(e)); return LBMPM_ERR_HIP; }
-    *ptr = static_cast<T *>(v);
-    c->bytes += (int64_t)(count * sizeof(T));
-    return LBMPM_OK;
-}
-
 }  // namespace
 
 extern "C" int lbmpm_rk2d_create(const lbmpm_rk2d_config *cfg, const uint8_t *is_domain, lbmpm_rk2d **out)
@@ -1554,14 +1536,14 @@ extern "C" int lbmpm_rk2d_create(const lbmpm_rk2d_config *cfg, const uint8_t *is
         if (e != hipSuccess) { set_error("hipStreamCreate failed: %s", hipGetErrorString(e)); delete c; return LBMPM_ERR_HIP; }
         c->own_stream = true;
     }
-    TRY_RC(dev_alloc(c, &c->flags, c->plane));
-    TRY_RC(dev_alloc(c, &c->solidnbr, c->plane));
-    TRY_RC(dev_alloc(c, &c->fA, 18 * c->plane));
-    TRY_RC(dev_alloc(c, &c->fB, 18 * c->plane));
-    TRY_RC(dev_alloc(c, &c->F, 2 * c->plane));
-    TRY_RC(dev_alloc(c, &c->ns, 2 * c->plane));
-    TRY_RC(dev_alloc(c, &c->phi, c->plane));
-    TRY_RC(dev_alloc(c, &c->G, 2 * c->plane));
+    TRY_RC(c->mem.alloc(&c->flags, c->plane, c->stream));
+    TRY_RC(c->mem.alloc(&c->solidnbr, c->plane, c->stream));
+    TRY_RC(c->mem.alloc(&c->fA, 18 * c->plane, c->stream));
+    TRY_RC(c->mem.alloc(&c->fB, 18 * c->plane, c->stream));
+    TRY_RC(c->mem.alloc(&c->F, 2 * c->plane, c->stream));
+    TRY_RC(c->mem.alloc(&c->ns, 2 * c->plane, c->stream));
+    TRY_RC(c->mem.alloc(&c->phi, c->plane, c->stream));
+    TRY_RC(c->mem.alloc(&c->G, 2 * c->plane, c->stream));
     {
         // every transfer goes through the context's stream: the null stream is not ordered
         // against it (hipStreamNonBlocking)
@@ -1587,9 +1569,7 @@ extern "C" void lbmpm_rk2d_destroy(lbmpm_rk2d *c)
     if (!c) return;
     (void)hipSetDevice(c->cfg.device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    for (void *ptr : {(void *)c->flags, (void *)c->solidnbr, (void *)c->fA, (void *)c->fB, (void *)c->F,
-                      (void *)c->ns, (void *)c->phi, (void *)c->G, (void *)c->diag, (void *)c->obs, (void *)c->gA, (void *)c->gB, (void *)c->pd})
-        if (ptr) (void)hipFree(ptr);
+    c->mem.release_all();
     c->pool.destroy();
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
@@ -1665,31 +1645,8 @@ extern "C" int lbmpm_rk2d_step_timed(lbmpm_rk2d *c, int64_t nsteps, double *ms_t
 {
     LBMPM_REQUIRE(c && nsteps >= 0, "lbmpm_rk2d_step_timed: bad argument");
     LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
-    const size_t pairs = (size_t)(nsteps < 4096 ? nsteps : 4096);
-    if (c->pool.reserve(pairs + 1) != LBMPM_OK) { set_error("hipEventCreate failed"); return LBMPM_ERR_HIP; }
-    c->pool.reset();
-    hipEvent_t t0, t1;
-    c->pool.take(&t0, &t1);
-    LBMPM_HIP_TRY(hipEventRecord(t0, c->stream));
-    const int rc = run_steps(c, nsteps, true);
-    if (rc != LBMPM_OK) return rc;
-    LBMPM_HIP_TRY(hipEventRecord(t1, c->stream));
-    LBMPM_HIP_TRY(hipStreamSynchronize(c->stream));
-    float ms = 0.f;
-    LBMPM_HIP_TRY(hipEventElapsedTime(&ms, t0, t1));
-    if (ms_total) *ms_total = ms;
-    if (ms_dominant) {
-        const size_t timed_launches = c->pool.used / 2 - 1;
-        double s = 0.0;
-        for (size_t k = 2; k + 1 < c->pool.used; k += 2) {
-            float m = 0.f;
-            LBMPM_HIP_TRY(hipEventElapsedTime(&m, c->pool.ev[k], c->pool.ev[k + 1]));
-            s += m;
-        }
-        // scale to all launches when more steps than pooled event pairs were run
-        *ms_dominant = timed_launches ? s * (double)nsteps / (double)timed_launches : 0.0;
-    }
-    return LBMPM_OK;
+    // one launch per pair: scaled to all launches when more steps than pooled event pairs were run
+    return lbmpm::step_timed(c->stream, c->pool, nsteps, ms_total, ms_dominant, [&] { return run_steps(c, nsteps, true); }, [&] { return c->pool.used / 2 - 1; });
 }
 
 extern "C" int lbmpm_rk2d_sync(lbmpm_rk2d *c)
@@ -1703,12 +1660,12 @@ extern "C" int lbmpm_rk2d_enable_diagnostics(lbmpm_rk2d *c, int on)
 {
     LBMPM_REQUIRE(c, "null context");
     LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
-    if (on && !c->diag) { const int rc = dev_alloc(c, &c->diag, 3 * c->plane); if (rc) return rc; }
-    if (on && c->model == 1 && !c->pd) { const int rc = dev_alloc(c, &c->pd, 4 * c->plane); if (rc) return rc; }
+    if (on && !c->diag) { const int rc = c->mem.alloc(&c->diag, 3 * c->plane, c->stream); if (rc) return rc; }
+    if (on && c->model == 1 && !c->pd) { const int rc = c->mem.alloc(&c->pd, 4 * c->plane, c->stream); if (rc) return rc; }
     if (!on && c->diag) {
         LBMPM_HIP_TRY(hipStreamSynchronize(c->stream));
-        (void)hipFree(c->diag); c->diag = nullptr; c->diag_valid = false;
-        c->bytes -= (int64_t)(3 * c->plane * sizeof(double));
+        c->mem.release(&c->diag);
+        c->diag_valid = false;
     }
     return LBMPM_OK;
 }
@@ -1743,7 +1700,7 @@ extern "C" int lbmpm_rk2d_get_field(lbmpm_rk2d *c, int field, double *out)
         // densities / velocity / phase field computed DURING that step (kept by the kernel when diagnostics are on); the "rec" fields
         // are what the next step would record after its streaming and boundary kernels
         if (rec || field == LBMPM_RK_PDF_R || field == LBMPM_RK_PDF_B) {
-            if (!c->obs) { const int rc = dev_alloc(c, &c->obs, 22 * c->plane); if (rc) return rc; }
+            if (!c->obs) { const int rc = c->mem.alloc(&c->obs, 22 * c->plane, c->stream); if (rc) return rc; }
             RKDev p = make_dev(c);
             const dim3 g = grid_of(c), b(BX, BY);
             if (rec) rk2dp_observe<<<g, b, 0, c->stream>>>(p, make_pert(c, false), c->obs);
@@ -1778,7 +1735,7 @@ extern "C" int lbmpm_rk2d_get_field(lbmpm_rk2d *c, int field, double *out)
         return LBMPM_ERR_INVALID;
     }
     if (rec || cur_obs) {
-        if (!c->obs) { const int rc = dev_alloc(c, &c->obs, 22 * c->plane); if (rc) return rc; }
+        if (!c->obs) { const int rc = c->mem.alloc(&c->obs, 22 * c->plane, c->stream); if (rc) return rc; }
         RKDev p = make_dev(c);
         const dim3 g = grid_of(c), b(BX, BY);
         if (rec) rk2d_observe<true><<<g, b, 0, c->stream>>>(p, c->obs);
@@ -1869,7 +1826,7 @@ extern "C" int lbmpm_rk2d_set_perturbation(lbmpm_rk2d *c, const lbmpm_rk2d_pertu
     LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
     c->pert = *par;
     c->model = 1;
-    if (c->diag && !c->pd) { const int rc = dev_alloc(c, &c->pd, 4 * c->plane); if (rc) return rc; }
+    if (c->diag && !c->pd) { const int rc = c->mem.alloc(&c->pd, 4 * c->plane, c->stream); if (rc) return rc; }
     c->diag_valid = false;
     return LBMPM_OK;
 }
@@ -1906,10 +1863,11 @@ extern "C" int lbmpm_rk2d_tracer_configure(lbmpm_rk2d *c, const lbmpm_tracer_con
     c->trRate = t->reaction_rate;
     c->trCrit = t->criteria_rho; c->trFree = t->free_outlet ? 1 : 0; c->trDirichlet = t->dirichlet_inlet ? 1 : 0;
     LBMPM_HIP_TRY(hipStreamSynchronize(c->stream));
-    if (c->gA) { (void)hipFree(c->gA); (void)hipFree(c->gB); c->gA = c->gB = nullptr; c->bytes -= (int64_t)(2 * c->ntr * 5 * c->plane * sizeof(double)); }
+    c->mem.release(&c->gA);      // (a second configure starts over)
+    c->mem.release(&c->gB);
     c->ntr = t->num_tracers;
-    int rc = dev_alloc(c, &c->gA, (size_t)c->ntr * 5 * c->plane);
-    if (rc == LBMPM_OK) rc = dev_alloc(c, &c->gB, (size_t)c->ntr * 5 * c->plane);
+    int rc = c->mem.alloc(&c->gA, (size_t)c->ntr * 5 * c->plane, c->stream);
+    if (rc == LBMPM_OK) rc = c->mem.alloc(&c->gB, (size_t)c->ntr * 5 * c->plane, c->stream);
     return rc;
 }
 
@@ -1937,7 +1895,7 @@ extern "C" int lbmpm_rk2d_tracer_get_concentration(lbmpm_rk2d *c, int tracer, do
     LBMPM_REQUIRE(c && out, "lbmpm_rk2d_tracer_get_concentration: null argument");
     LBMPM_REQUIRE(tracer >= 0 && tracer < c->ntr, "tracer index %d out of range (configured: %d)", tracer, c->ntr);
     LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
-    if (!c->obs) { const int rc = dev_alloc(c, &c->obs, 22 * c->plane); if (rc) return rc; }
+    if (!c->obs) { const int rc = c->mem.alloc(&c->obs, 22 * c->plane, c->stream); if (rc) return rc; }
     RKDev p = make_dev(c);
     rk2d_observe_tracer<<<grid_of(c), dim3(BX, BY), 0, c->stream>>>(p, tracer, c->obs);
     LBMPM_HIP_TRY(hipGetLastError());
@@ -1958,7 +1916,7 @@ extern "C" int lbmpm_dev_rk2d_phases(unsigned long long *out16)
 #endif
 extern "C" int64_t lbmpm_rk2d_num_fluid_nodes(const lbmpm_rk2d *c) { return c ? c->nfluid : 0; }
 extern "C" int64_t lbmpm_rk2d_steps_done(const lbmpm_rk2d *c) { return c ? c->steps : 0; }
-extern "C" int64_t lbmpm_rk2d_device_bytes(const lbmpm_rk2d *c) { return c ? c->bytes : 0; }
+extern "C" int64_t lbmpm_rk2d_device_bytes(const lbmpm_rk2d *c) { return c ? c->mem.bytes() : 0; }
 extern "C" const char *lbmpm_rk2d_dominant_kernel(const lbmpm_rk2d *c)
 {
     if (c && c->model == 1) return "rk2dp_fused";

@@ -1252,7 +1252,8 @@ struct lbmpm_rk3d {
     hipStream_t aux = nullptr;       // second stream for the interior planes (lbmpm_rk3d_collide_interior)
     hipEvent_t ev_dep = nullptr, ev_done = nullptr;
     bool interior_pending = false;
-    int64_t steps = 0, bytes = 0;
+    int64_t steps = 0;
+    lbmpm::DeviceBlocks mem;         // every device block the context keeps (lbmpm_rk3d_device_bytes); the transport's landing areas are its own
     lbmpm::EventPool slab_pool;      // lbmpm_rk3d_step_slab(timed): 4 event pairs per step {step, interior, exchange chain, boundary}
     int64_t slab_timed_steps = 0;
     // steady-state watchdog (lbmpm_rk3d_sync_deadline): a word in pinned host memory that the exchange chain of every slab step writes
@@ -1288,19 +1289,6 @@ RK3Dev make_dev(const lbmpm_rk3d *c)
 #endif
     p.pur_in = c->purA; p.pur_out = c->purB;
     return p;
-}
-
-template <typename T>
-int dev_alloc(lbmpm_rk3d *c, T **ptr, size_t count)
-{
-    void *v = nullptr;
-    hipError_t e = hipMalloc(&v, count * sizeof(T));
-    if (e != hipSuccess) { set_error("hipMalloc(%zu bytes) failed: %s", count * sizeof(T), hipGetErrorString(e)); return LBMPM_ERR_NOMEM; }
-    e = hipMemsetAsync(v, 0, count * sizeof(T), c->stream);
-    if (e != hipSuccess) { set_error("hipMemsetAsync failed: %s", hipGetErrorString(e)); return LBMPM_ERR_HIP; }
-    *ptr = static_cast<T *>(v);
-    c->bytes += (int64_t)(count * sizeof(T));
-    return LBMPM_OK;
 }
 
 dim3 grid3(const lbmpm_rk3d *c, int planes) { return dim3((c->nx + BX3 - 1) / BX3, (c->ny + BY3 - 1) / BY3, planes); }
@@ -1405,8 +1393,8 @@ extern "C" int lbmpm_rk3d_create(const lbmpm_rk3d_config *cfg, const uint8_t *is
     }
     int rc = LBMPM_OK;
 #define TRY_RC(e) do { rc = (e); if (rc != LBMPM_OK) { lbmpm_rk3d_destroy(c); return rc; } } while (0)
-    TRY_RC(dev_alloc(c, &c->flags, c->vol));
-    TRY_RC(dev_alloc(c, &c->solidnbr, c->vol));
+    TRY_RC(c->mem.alloc(&c->flags, c->vol, c->stream));
+    TRY_RC(c->mem.alloc(&c->solidnbr, c->vol, c->stream));
     std::vector<uint32_t> hseg, hseg2;
     if (c->compact) {
         // segment records of the compact storage; numbering: plane, tile (64 x TILE_ROWS), row, x
@@ -1468,34 +1456,34 @@ extern "C" int lbmpm_rk3d_create(const lbmpm_rk3d_config *cfg, const uint8_t *is
         }
         c->h_pstart[c->nzl + 2] = total;
         c->ncells = (size_t)total;
-        TRY_RC(dev_alloc(c, &c->seg, hseg.size()));
-        TRY_RC(dev_alloc(c, &c->seg2, hseg2.size()));
-        TRY_RC(dev_alloc(c, &c->pstart, c->h_pstart.size()));
+        TRY_RC(c->mem.alloc(&c->seg, hseg.size(), c->stream));
+        TRY_RC(c->mem.alloc(&c->seg2, hseg2.size(), c->stream));
+        TRY_RC(c->mem.alloc(&c->pstart, c->h_pstart.size(), c->stream));
     }
     const size_t fcount = c->q23 ? (size_t)QS * (c->ncells + 2) : (c->compact ? 2 * Q * (c->ncells + 1) : 2 * Q * c->vol);
-    TRY_RC(dev_alloc(c, &c->fA, fcount));
-    TRY_RC(dev_alloc(c, &c->fB, fcount));
+    TRY_RC(c->mem.alloc(&c->fA, fcount, c->stream));
+    TRY_RC(c->mem.alloc(&c->fB, fcount, c->stream));
     if (c->q23) {
         bool by_xcc = true;       // tiles handed out by the XCD a workgroup runs on (rk3dq_fused); LBMPM_RK3D_XCC=0 (development builds): by block index
 #ifdef LBMPM_DEV
         if (getenv("LBMPM_RK3D_XCC") && atoi(getenv("LBMPM_RK3D_XCC")) == 0) by_xcc = false;
 #endif
-        if (by_xcc) TRY_RC(dev_alloc(c, &c->slotq, 2 * 4096 * 8));     // zeroed
+        if (by_xcc) TRY_RC(c->mem.alloc(&c->slotq, 2 * 4096 * 8, c->stream));     // zeroed
         // (row segments of a slab are indexed with 32 bits in the kernels: rk3dq.h::row_index)
         LBMPM_REQUIRE((size_t)(c->nzl + 2) * c->ny * c->nseg < ((size_t)1 << 31), "rk3d: more than 2^31 row segments in one slab");
-        TRY_RC(dev_alloc(c, &c->purA, (size_t)(c->nzl + 2) * c->ny * c->nseg));
-        TRY_RC(dev_alloc(c, &c->purB, (size_t)(c->nzl + 2) * c->ny * c->nseg));
+        TRY_RC(c->mem.alloc(&c->purA, (size_t)(c->nzl + 2) * c->ny * c->nseg, c->stream));
+        TRY_RC(c->mem.alloc(&c->purB, (size_t)(c->nzl + 2) * c->ny * c->nseg, c->stream));
     }
-    TRY_RC(dev_alloc(c, &c->phi, c->vol));
+    TRY_RC(c->mem.alloc(&c->phi, c->vol, c->stream));
     // q23: 13 per cell + the row flags (rk3dq.h).  Per STORED cell of a plane: the tile padding and the odd-stride padding count (a regular
     // plane's cnt exceeds its nx * ny cells), so the buffers follow the largest plane
     size_t max_cnt = c->plane2;
     if (c->compact) for (int z = 0; z < c->nzl + 2; ++z) max_cnt = std::max(max_cnt, (size_t)(c->h_pstart[z + 1] - c->h_pstart[z]));
     const size_t face_doubles = (c->q23 ? FACE_DOUBLES + 1 : 10) * max_cnt;
-    TRY_RC(dev_alloc(c, &c->send_up, face_doubles));
-    TRY_RC(dev_alloc(c, &c->send_dn, face_doubles));
-    TRY_RC(dev_alloc(c, &c->recv_below, face_doubles));
-    TRY_RC(dev_alloc(c, &c->recv_above, face_doubles));
+    TRY_RC(c->mem.alloc(&c->send_up, face_doubles, c->stream));
+    TRY_RC(c->mem.alloc(&c->send_dn, face_doubles, c->stream));
+    TRY_RC(c->mem.alloc(&c->recv_below, face_doubles, c->stream));
+    TRY_RC(c->mem.alloc(&c->recv_above, face_doubles, c->stream));
 #undef TRY_RC
     hipError_t e = hipMemcpyAsync(c->flags, hflags.data(), c->vol, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess && c->compact) e = hipMemcpyAsync(c->seg, hseg.data(), hseg.size() * sizeof(hseg[0]), hipMemcpyHostToDevice, c->stream);
@@ -1521,9 +1509,8 @@ extern "C" void lbmpm_rk3d_destroy(lbmpm_rk3d *c)
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->aux) (void)hipStreamSynchronize(c->aux);
     c->tx.destroy();
-    for (void *ptr : {(void *)c->seg, (void *)c->seg2, (void *)c->pstart, (void *)c->flags, (void *)c->solidnbr, (void *)c->fA, (void *)c->fB, (void *)c->purA, (void *)c->purB, (void *)c->trace, (void *)c->slotq, (void *)c->phi, (void *)c->diag, (void *)c->integ, (void *)c->cl.cls, (void *)c->cl.lab, (void *)c->cl.rows, (void *)c->cl.chunks,
-                      (void *)c->send_up, (void *)c->send_dn, (void *)c->recv_below, (void *)c->recv_above})
-        if (ptr) (void)hipFree(ptr);
+    c->mem.release_all();
+    if (c->trace) (void)hipFree(c->trace);       // (development builds: not a block of the context's count)
     c->pool.destroy();
     c->slab_pool.destroy();
     if (c->aux) { (void)hipStreamDestroy(c->aux); (void)hipEventDestroy(c->ev_dep); (void)hipEventDestroy(c->ev_done); }
@@ -1551,8 +1538,9 @@ extern "C" int lbmpm_rk3d_set_density(lbmpm_rk3d *c, const double *rho_r, const 
     // stage the two density fields on the device, expand there
     const size_t n = (size_t)c->nx * c->ny * c->nzl;
     const size_t fbytes = (c->q23 ? (size_t)QS * (c->ncells + 2) : (c->compact ? 2 * Q * (c->ncells + 1) : 2 * Q * c->vol)) * sizeof(double);
-    double *stage = nullptr;
-    LBMPM_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&stage), 2 * n * sizeof(double)));
+    lbmpm::DeviceTemp<double> staged;
+    LBMPM_HIP_TRY(staged.alloc(2 * n));
+    double *const stage = staged.get();
     hipError_t e = hipMemcpyAsync(stage, rho_r, n * sizeof(double), hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(stage + n, rho_b, n * sizeof(double), hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemsetAsync(c->fA, 0, fbytes, c->stream);
@@ -1573,7 +1561,6 @@ extern "C" int lbmpm_rk3d_set_density(lbmpm_rk3d *c, const double *rho_r, const 
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(stage);
     if (e != hipSuccess) { set_error("lbmpm_rk3d_set_density: %s", hipGetErrorString(e)); return LBMPM_ERR_HIP; }
     LBMPM_HIP_TRY(hipStreamSynchronize(c->stream));
     c->streamed = false;
@@ -1613,12 +1600,13 @@ int state_transfer(lbmpm_rk3d *c, double *ha, int wa, double *hb, int wb, const 
     const int per = MODE == IO_SET_MACRO ? 5 : wa + wb;
     int batch = (int)(((size_t)256 << 20) / (pcells * (size_t)per * sizeof(double)));
     batch = batch < 1 ? 1 : (batch > c->nzl ? c->nzl : batch);
-    double *stage = nullptr;
-    if (hipMalloc(reinterpret_cast<void **>(&stage), (size_t)batch * pcells * per * sizeof(double)) != hipSuccess) {
+    lbmpm::DeviceTemp<double> staged;
+    if (staged.alloc((size_t)batch * pcells * per) != hipSuccess) {
         (void)hipGetLastError();
         set_error("state transfer: hipMalloc of the %d-plane staging buffer failed", batch);
         return LBMPM_ERR_NOMEM;
     }
+    double *const stage = staged.get();
     hipError_t e = hipSuccess;
     if (!GET) e = hipMemsetAsync(c->fA, 0, state_fbytes(c), c->stream);
     const RK3Dev p = make_dev(c);
@@ -1656,7 +1644,6 @@ int state_transfer(lbmpm_rk3d *c, double *ha, int wa, double *hb, int wb, const 
         if (e == hipSuccess) e = hipMemcpyAsync(c->fB, c->fA, state_fbytes(c), hipMemcpyDeviceToDevice, c->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     }
-    (void)hipFree(stage);
     if (e != hipSuccess) { set_error("state transfer: %s", hipGetErrorString(e)); return LBMPM_ERR_HIP; }
     return LBMPM_OK;
 }
@@ -1770,7 +1757,7 @@ extern "C" int lbmpm_rk3d_phase_field(lbmpm_rk3d *c, int with_diagnostics)
 {
     LBMPM_REQUIRE(c, "null context");
     LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
-    if (with_diagnostics && !c->diag) { const int rc = dev_alloc(c, &c->diag, 5 * c->vol); if (rc) return rc; }
+    if (with_diagnostics && !c->diag) { const int rc = c->mem.alloc(&c->diag, 5 * c->vol, c->stream); if (rc) return rc; }
     RK3Dev p = make_dev(c);
     p.diag = with_diagnostics ? c->diag : nullptr;
     auto k1 = [&](int planes, int zl0) {
@@ -2442,38 +2429,20 @@ extern "C" int lbmpm_rk3d_step_timed(lbmpm_rk3d *c, int64_t nsteps, double *ms_t
     LBMPM_REQUIRE(c && nsteps >= 0, "lbmpm_rk3d_step_timed: bad argument");
     LBMPM_REQUIRE(c->cfg.z_offset == 0 && c->cfg.nz_local == c->cfg.nz_global, "single-slab only");
     LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
-    const size_t pairs = (size_t)(nsteps < 4096 ? nsteps : 4096);
-    if (c->pool.reserve(pairs + 1) != LBMPM_OK) { set_error("hipEventCreate failed"); return LBMPM_ERR_HIP; }
-    c->pool.reset();
-    hipEvent_t t0, t1;
-    c->pool.take(&t0, &t1);
-    LBMPM_HIP_TRY(hipEventRecord(t0, c->stream));
-    for (int64_t k = 0; k < nsteps; ++k) {
-        int rc = lbmpm_rk3d_phase_field(c, 0);
-        if (rc != LBMPM_OK) return rc;
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        const bool ev = c->pool.take(&e0, &e1);
-        if (ev) LBMPM_HIP_TRY(hipEventRecord(e0, c->stream));
-        rc = lbmpm_rk3d_collide(c);
-        if (rc != LBMPM_OK) return rc;
-        if (ev) LBMPM_HIP_TRY(hipEventRecord(e1, c->stream));
-    }
-    LBMPM_HIP_TRY(hipEventRecord(t1, c->stream));
-    LBMPM_HIP_TRY(hipStreamSynchronize(c->stream));
-    float ms = 0.f;
-    LBMPM_HIP_TRY(hipEventElapsedTime(&ms, t0, t1));
-    if (ms_total) *ms_total = ms;
-    if (ms_dominant) {
-        const size_t timed_launches = c->pool.used / 2 - 1;
-        double s = 0.0;
-        for (size_t k = 2; k + 1 < c->pool.used; k += 2) {
-            float m = 0.f;
-            LBMPM_HIP_TRY(hipEventElapsedTime(&m, c->pool.ev[k], c->pool.ev[k + 1]));
-            s += m;
+    const auto run = [&]() -> int {
+        for (int64_t k = 0; k < nsteps; ++k) {
+            int rc = lbmpm_rk3d_phase_field(c, 0);
+            if (rc != LBMPM_OK) return rc;
+            hipEvent_t e0 = nullptr, e1 = nullptr;
+            const bool ev = c->pool.take(&e0, &e1);
+            if (ev) LBMPM_HIP_TRY(hipEventRecord(e0, c->stream));
+            rc = lbmpm_rk3d_collide(c);
+            if (rc != LBMPM_OK) return rc;
+            if (ev) LBMPM_HIP_TRY(hipEventRecord(e1, c->stream));
         }
-        *ms_dominant = timed_launches ? s * (double)nsteps / (double)timed_launches : 0.0;
-    }
-    return LBMPM_OK;
+        return LBMPM_OK;
+    };
+    return lbmpm::step_timed(c->stream, c->pool, nsteps, ms_total, ms_dominant, run, [&] { return c->pool.used / 2 - 1; });      // one launch per pair
 }
 
 extern "C" int lbmpm_rk3d_sync(lbmpm_rk3d *c)
@@ -2573,7 +2542,7 @@ extern "C" int lbmpm_rk3d_integrals(lbmpm_rk3d *c, double *out)
         return LBMPM_ERR_STATE;
     }
     const unsigned planes = (unsigned)c->nzl, plane_cells = (unsigned)c->nx * (unsigned)c->ny;
-    if (!c->integ) { const int rc = dev_alloc(c, &c->integ, integral_buffer_doubles<FlowCols>(planes, plane_cells)); if (rc) return rc; }
+    { const int rc = integral_buffer<FlowCols>(c->mem, &c->integ, planes, plane_cells, 1, c->stream); if (rc) return rc; }
     const Rk3dIntLoader load{c->flags, c->diag, c->phi, (unsigned)c->nx, (unsigned)c->pitch, c->plane2, c->vol};
     LBMPM_HIP_TRY(integrals_run(load, planes, plane_cells, c->integ, out, c->stream));
     return LBMPM_OK;
@@ -2584,7 +2553,6 @@ extern "C" int lbmpm_rk3d_clusters(lbmpm_rk3d *c, const lbmpm_clusters_config *c
 {
     LBMPM_REQUIRE(c && count, "lbmpm_rk3d_clusters: null argument");
     LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
-    ClState &s = c->cl;
     double cut = 0.;
     ClGeom g{};
     { const int rc = clusters_configure("lbmpm_rk3d_clusters", cfg, (unsigned long long)c->nx * c->ny * (unsigned long long)c->cfg.nz_global, &cut, &g); if (rc) return rc; }
@@ -2595,49 +2563,26 @@ extern "C" int lbmpm_rk3d_clusters(lbmpm_rk3d *c, const lbmpm_clusters_config *c
     }
     g.nx = (unsigned)c->nx; g.ny = (unsigned)c->ny; g.planes = (unsigned)c->nzl; g.plane_cells = g.nx * g.ny; g.n = g.planes * g.plane_cells;
     g.z0 = (unsigned)c->cfg.z_offset; g.base = g.z0 * g.plane_cells;
-    s.valid = false;
-    if (!s.chunks) {
-        size_t n[4];
-        clusters_sizes_of(g.n, n);
-        int rc = dev_alloc(c, &s.cls, n[0]);
-        if (!rc) rc = dev_alloc(c, &s.lab, n[1]);
-        if (!rc) rc = dev_alloc(c, &s.rows, n[2]);
-        if (!rc) rc = dev_alloc(c, &s.chunks, n[3]);
-        if (rc) return rc;
-    }
-    s.g = g;
     const Rk3dPhiLoader load{c->flags, c->phi, (unsigned)c->nx, (unsigned)c->pitch, c->plane2};
-    LBMPM_HIP_TRY(clusters_run(load, s, cut, c->stream));
-    s.valid = true; s.at_step = c->steps;
-    *count = s.count;
-    return LBMPM_OK;
+    return clusters_label(load, c->cl, g, cut, c->steps, c->mem, c->stream, c->stream, count);
 }
 
 extern "C" int lbmpm_rk3d_clusters_table(lbmpm_rk3d *c, int64_t *out)
 {
     LBMPM_REQUIRE(c && out, "lbmpm_rk3d_clusters_table: null argument");
-    { const int rc = clusters_current("lbmpm_rk3d_clusters_table", c->cl, c->steps); if (rc) return rc; }
-    LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
-    LBMPM_HIP_TRY(clusters_table(c->cl, out, c->stream));
-    return LBMPM_OK;
+    return clusters_table("lbmpm_rk3d_clusters_table", c->cl, c->steps, c->cfg.device, c->stream, out);
 }
 
 extern "C" int lbmpm_rk3d_clusters_labels(lbmpm_rk3d *c, uint32_t *out)
 {
     LBMPM_REQUIRE(c && out, "lbmpm_rk3d_clusters_labels: null argument");
-    { const int rc = clusters_current("lbmpm_rk3d_clusters_labels", c->cl, c->steps); if (rc) return rc; }
-    LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
-    LBMPM_HIP_TRY(clusters_labels(c->cl, out, c->stream));
-    return LBMPM_OK;
+    return clusters_labels("lbmpm_rk3d_clusters_labels", c->cl, c->steps, c->cfg.device, c->stream, out);
 }
 
 extern "C" int lbmpm_rk3d_clusters_faces(lbmpm_rk3d *c, uint32_t *labels, uint8_t *classes)
 {
     LBMPM_REQUIRE(c && labels && classes, "lbmpm_rk3d_clusters_faces: null argument");
-    { const int rc = clusters_current("lbmpm_rk3d_clusters_faces", c->cl, c->steps); if (rc) return rc; }
-    LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
-    LBMPM_HIP_TRY(clusters_faces(c->cl, labels, classes, c->stream));
-    return LBMPM_OK;
+    return clusters_faces("lbmpm_rk3d_clusters_faces", c->cl, c->steps, c->cfg.device, c->stream, labels, classes);
 }
 
 // What the storage moves, by its own count (bench.py's "bytes moved" beside the algorithmic 608 B): out[0] doubles stored per fluid
@@ -2694,18 +2639,17 @@ extern "C" int lbmpm_rk3d_debug_plane(lbmpm_rk3d *c, int comp, int zl, double *o
         for (int y = 0; y < c->ny; ++y) for (int x = 0; x < c->nx; ++x) out[(size_t)y * c->nx + x] = h[(size_t)y * c->pitch + x];
         return LBMPM_OK;
     }
-    double *d = nullptr;
-    LBMPM_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d), n * sizeof(double)));
+    lbmpm::DeviceTemp<double> d;
+    LBMPM_HIP_TRY(d.alloc(n));
     const RK3Dev p = make_dev(c);
-    rk3dq_debug_plane<<<dim3(c->nseg, (c->ny + BY3 - 1) / BY3), dim3(BX3, BY3), 0, c->stream>>>(p, c->fA, zl, comp, d);
-    hipError_t e = hipMemcpyAsync(out, d, n * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+    rk3dq_debug_plane<<<dim3(c->nseg, (c->ny + BY3 - 1) / BY3), dim3(BX3, BY3), 0, c->stream>>>(p, c->fA, zl, comp, d.get());
+    hipError_t e = hipMemcpyAsync(out, d.get(), n * sizeof(double), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(d);
     if (e != hipSuccess) { set_error("lbmpm_rk3d_debug_plane: %s", hipGetErrorString(e)); return LBMPM_ERR_HIP; }
     return LBMPM_OK;
 }
 
 extern "C" int64_t lbmpm_rk3d_num_fluid_nodes(const lbmpm_rk3d *c) { return c ? c->nfluid : 0; }
 extern "C" int64_t lbmpm_rk3d_steps_done(const lbmpm_rk3d *c) { return c ? c->steps : 0; }
-extern "C" int64_t lbmpm_rk3d_device_bytes(const lbmpm_rk3d *c) { return c ? c->bytes : 0; }
+extern "C" int64_t lbmpm_rk3d_device_bytes(const lbmpm_rk3d *c) { return c ? c->mem.bytes() : 0; }
 extern "C" const char *lbmpm_rk3d_dominant_kernel(const lbmpm_rk3d *c) { return !c ? "" : (c->variant == 1 ? "rk3d_collide" : (c->q23 ? "rk3dq_fused" : (c->compact ? "rk3dc_fused" : "rk3d_fused"))); }

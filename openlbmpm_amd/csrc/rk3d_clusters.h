@@ -270,18 +270,50 @@ hipError_t clusters_run(const Loader &load, ClState &s, double cut, hipStream_t 
     return e;
 }
 
+// The clusters of a context's state after `steps` steps, labelled and counted with g and cut: the body of the lbmpm_*_clusters entry
+// points behind their own checks.  The four device arrays come from `mem` with the first call (zero_on: as DeviceBlocks::alloc).
+template <typename Loader>
+int clusters_label(const Loader &load, ClState &s, const ClGeom &g, double cut, int64_t steps, lbmpm::DeviceBlocks &mem, hipStream_t zero_on, hipStream_t stream,
+                   int64_t *count)
+{
+    s.valid = false;
+    if (!s.chunks) {
+        int rc = mem.alloc(&s.cls, g.n, zero_on);
+        if (!rc) rc = mem.alloc(&s.lab, g.n, zero_on);
+        if (!rc) rc = mem.alloc(&s.rows, 3 * (size_t)g.n, zero_on);
+        if (!rc) rc = mem.alloc(&s.chunks, cl_chunks(g.n) + 1u, zero_on);
+        if (rc) return rc;
+    }
+    s.g = g;
+    LBMPM_HIP_TRY(clusters_run(load, s, cut, stream));
+    s.valid = true; s.at_step = steps;
+    *count = s.count;
+    return LBMPM_OK;
+}
+
+// LBMPM_ERR_STATE unless the labels are those of the state after `steps` steps; then the context's device is the current one
+inline int clusters_current(const char *who, const ClState &s, int64_t steps, int device)
+{
+    if (!(s.valid && s.at_step == steps)) {
+        set_error("%s: no clusters of the current state (call the _clusters function first, and again after a step or a change of state)", who);
+        return LBMPM_ERR_STATE;
+    }
+    LBMPM_HIP_TRY(hipSetDevice(device));
+    return LBMPM_OK;
+}
+
+// The bodies of the lbmpm_*_clusters_table / _labels / _faces entry points (`who`) behind their null checks.
 // out: [count][LBMPM_CLUSTER_COLS]
-inline hipError_t clusters_table(const ClState &s, int64_t *out, hipStream_t stream)
+inline int clusters_table(const char *who, const ClState &s, int64_t steps, int device, hipStream_t stream, int64_t *out)
 {
     static_assert(LBMPM_CLUSTER_COLS == 5 && LBMPM_CL_LABEL == 0 && LBMPM_CL_ZMAX == 4, "the columns of rk3d_clusters.h");
+    { const int rc = clusters_current(who, s, steps, device); if (rc) return rc; }
     const size_t m = (size_t)s.count;
-    if (!m) return hipSuccess;
+    if (!m) return LBMPM_OK;
     std::vector<unsigned> h(3 * m);
-    hipError_t e = hipSuccess;
-    for (int col = 0; col < 3 && e == hipSuccess; ++col)
-        e = hipMemcpyAsync(h.data() + col * m, s.rows + (size_t)col * s.g.n, m * sizeof(unsigned), hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    if (e != hipSuccess) return e;
+    for (int col = 0; col < 3; ++col)
+        LBMPM_HIP_TRY(hipMemcpyAsync(h.data() + col * m, s.rows + (size_t)col * s.g.n, m * sizeof(unsigned), hipMemcpyDeviceToHost, stream));
+    LBMPM_HIP_TRY(hipStreamSynchronize(stream));
     for (size_t r = 0; r < m; ++r) {
         int64_t *row = out + r * LBMPM_CLUSTER_COLS;
         row[LBMPM_CL_LABEL] = h[r];
@@ -290,26 +322,28 @@ inline hipError_t clusters_table(const ClState &s, int64_t *out, hipStream_t str
         row[LBMPM_CL_ZMIN] = h[r] / s.g.plane_cells;
         row[LBMPM_CL_ZMAX] = h[2 * m + r] & 0x3FFFFFFFu;
     }
-    return hipSuccess;
+    return LBMPM_OK;
 }
 
-inline hipError_t clusters_labels(const ClState &s, uint32_t *out, hipStream_t stream)
+inline int clusters_labels(const char *who, const ClState &s, int64_t steps, int device, hipStream_t stream, uint32_t *out)
 {
-    hipError_t e = hipMemcpyAsync(out, s.lab, (size_t)s.g.n * sizeof(unsigned), hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    return e;
+    { const int rc = clusters_current(who, s, steps, device); if (rc) return rc; }
+    LBMPM_HIP_TRY(hipMemcpyAsync(out, s.lab, (size_t)s.g.n * sizeof(unsigned), hipMemcpyDeviceToHost, stream));
+    LBMPM_HIP_TRY(hipStreamSynchronize(stream));
+    return LBMPM_OK;
 }
 
 // [2][ny][nx]: the lowest and the highest own plane
-inline hipError_t clusters_faces(const ClState &s, uint32_t *labels, uint8_t *classes, hipStream_t stream)
+inline int clusters_faces(const char *who, const ClState &s, int64_t steps, int device, hipStream_t stream, uint32_t *labels, uint8_t *classes)
 {
+    { const int rc = clusters_current(who, s, steps, device); if (rc) return rc; }
     const size_t pc = s.g.plane_cells, top = (size_t)(s.g.planes - 1u) * pc;
-    hipError_t e = hipMemcpyAsync(labels, s.lab, pc * sizeof(unsigned), hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(labels + pc, s.lab + top, pc * sizeof(unsigned), hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(classes, s.cls, pc, hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(classes + pc, s.cls + top, pc, hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    return e;
+    LBMPM_HIP_TRY(hipMemcpyAsync(labels, s.lab, pc * sizeof(unsigned), hipMemcpyDeviceToHost, stream));
+    LBMPM_HIP_TRY(hipMemcpyAsync(labels + pc, s.lab + top, pc * sizeof(unsigned), hipMemcpyDeviceToHost, stream));
+    LBMPM_HIP_TRY(hipMemcpyAsync(classes, s.cls, pc, hipMemcpyDeviceToHost, stream));
+    LBMPM_HIP_TRY(hipMemcpyAsync(classes + pc, s.cls + top, pc, hipMemcpyDeviceToHost, stream));
+    LBMPM_HIP_TRY(hipStreamSynchronize(stream));
+    return LBMPM_OK;
 }
 
 // the configuration of a call (cfg may be null: phi_cut 0, faces) into cut and g.nlink; an LBMPM_* status
@@ -323,18 +357,4 @@ inline int clusters_configure(const char *who, const lbmpm_clusters_config *cfg,
     *cut = pc;
     g->nlink = conn == 6 ? 3 : 9;
     return LBMPM_OK;
-}
-
-// bytes of the four device arrays of a context with n own cells, in the order cls, lab, rows, chunks
-inline void clusters_sizes_of(unsigned n, size_t count[4])
-{
-    count[0] = n; count[1] = n; count[2] = 3 * (size_t)n; count[3] = cl_chunks(n) + 1u;
-}
-
-// LBMPM_ERR_STATE unless the labels are those of the state after `steps` steps
-inline int clusters_current(const char *who, const ClState &s, int64_t steps)
-{
-    if (s.valid && s.at_step == steps) return LBMPM_OK;
-    set_error("%s: no clusters of the current state (call the _clusters function first, and again after a step or a change of state)", who);
-    return LBMPM_ERR_STATE;
 }

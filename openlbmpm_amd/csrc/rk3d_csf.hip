@@ -1061,7 +1061,8 @@ struct lbmpm_rk3dcsf {
     lbmpm_rk3dcsf_config cfg;
     int nx = 0, ny = 0, nz = 0;
     size_t N = 0, NS = 0, FS = 0;
-    int64_t nfluid = 0, steps = 0, bytes = 0;
+    int64_t nfluid = 0, steps = 0;
+    lbmpm::DeviceBlocks mem;       // every device block the context keeps (lbmpm_rk3dcsf_device_bytes); not the transport's: send_lo, send_hi
     unsigned nwet = 0;
     bool first = true, have_state = false, diag = false, diag_valid = false;
     hipStream_t stream = nullptr, stream2 = nullptr;        // stream2: the deep blocks' collision beside the full path's four launches
@@ -1100,15 +1101,6 @@ struct lbmpm_rk3dcsf {
 };
 
 namespace {
-
-template <typename T>
-int dev_alloc(lbmpm_rk3dcsf *c, T **ptr, size_t count)
-{
-    const hipError_t e = hipMalloc(reinterpret_cast<void **>(ptr), count * sizeof(T));
-    if (e != hipSuccess) { set_error("hipMalloc of %zu bytes failed: %s", count * sizeof(T), hipGetErrorString(e)); return LBMPM_ERR_NOMEM; }
-    c->bytes += (int64_t)(count * sizeof(T));
-    return LBMPM_OK;
-}
 
 CsfDev make_dev(const lbmpm_rk3dcsf *c)
 {
@@ -1253,8 +1245,7 @@ extern "C" void lbmpm_rk3dcsf_destroy(lbmpm_rk3dcsf *c)
     c->tx.destroy();
     for (void *q : {(void *)c->send_lo, (void *)c->send_hi}) if (q) (void)hipFree(q);
     c->slab_pool.destroy();
-    void *ptrs[] = {c->gA, c->gB, c->trflow, c->trsrc, c->wethome, c->rng, c->pfx, c->pure, c->deep_prev, c->bcblk, c->deep_now, c->work, c->tcnt, c->src, c->dom, c->meta, c->wetlist, c->cidx, c->cells, c->fA, c->fB, c->phi, c->G, c->nh, c->F, c->K, c->U, c->ns, c->obs, c->integ, c->trinteg, c->cl.cls, c->cl.lab, c->cl.rows, c->cl.chunks};
-    for (void *q : ptrs) if (q) (void)hipFree(q);
+    c->mem.release_all();
     c->pool.destroy();
     if (c->ev_lists) (void)hipEventDestroy(c->ev_lists);
     if (c->ev_deep) (void)hipEventDestroy(c->ev_deep);
@@ -1347,19 +1338,20 @@ extern "C" int lbmpm_rk3dcsf_create(const lbmpm_rk3dcsf_config *cfg, const uint8
     int rc = LBMPM_OK;
 #define TRY_RC(e) do { rc = (e); if (rc != LBMPM_OK) { lbmpm_rk3dcsf_destroy(c); return rc; } } while (0)
 #define TRY_HIP(e) do { const hipError_t e_ = (e); if (e_ != hipSuccess) { set_error("%s failed: %s", #e, hipGetErrorString(e_)); lbmpm_rk3dcsf_destroy(c); return LBMPM_ERR_HIP; } } while (0)
-    TRY_RC(dev_alloc(c, &c->dom, N));
-    TRY_RC(dev_alloc(c, &c->meta, N));
-    TRY_RC(dev_alloc(c, &c->cidx, N));
-    TRY_RC(dev_alloc(c, &c->cells, (size_t)c->nfluid));
-    TRY_RC(dev_alloc(c, &c->fA, 2 * Q * c->FS));
-    TRY_RC(dev_alloc(c, &c->fB, 2 * Q * c->FS));
-    TRY_RC(dev_alloc(c, &c->phi, c->NS));
-    TRY_RC(dev_alloc(c, &c->G, 3 * c->NS));
-    TRY_RC(dev_alloc(c, &c->nh, 3 * c->NS));
-    TRY_RC(dev_alloc(c, &c->F, 3 * c->NS));
-    TRY_RC(dev_alloc(c, &c->ns, 3 * c->NS));
-    unsigned *counters = nullptr;
-    TRY_HIP(hipMalloc(reinterpret_cast<void **>(&counters), 2 * sizeof(unsigned)));
+    TRY_RC(c->mem.alloc(&c->dom, N, nullptr));
+    TRY_RC(c->mem.alloc(&c->meta, N, nullptr));
+    TRY_RC(c->mem.alloc(&c->cidx, N, nullptr));
+    TRY_RC(c->mem.alloc(&c->cells, (size_t)c->nfluid, nullptr));
+    TRY_RC(c->mem.alloc(&c->fA, 2 * Q * c->FS, nullptr));
+    TRY_RC(c->mem.alloc(&c->fB, 2 * Q * c->FS, nullptr));
+    TRY_RC(c->mem.alloc(&c->phi, c->NS, nullptr));
+    TRY_RC(c->mem.alloc(&c->G, 3 * c->NS, nullptr));
+    TRY_RC(c->mem.alloc(&c->nh, 3 * c->NS, nullptr));
+    TRY_RC(c->mem.alloc(&c->F, 3 * c->NS, nullptr));
+    TRY_RC(c->mem.alloc(&c->ns, 3 * c->NS, nullptr));
+    lbmpm::DeviceTemp<unsigned> counted;          // for the length of the call, like `counts` and `ranges` below
+    TRY_HIP(counted.alloc(2));
+    unsigned *const counters = counted.get();
     hipError_t e = hipMemsetAsync(counters, 0, 2 * sizeof(unsigned), c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(c->dom, is_domain, N, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(c->cidx, hidx.data(), N * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
@@ -1372,14 +1364,15 @@ extern "C" int lbmpm_rk3dcsf_create(const lbmpm_rk3dcsf_config *cfg, const uint8
     }
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e == hipSuccess) e = hipGetLastError();
-    if (e != hipSuccess) { (void)hipFree(counters); set_error("set-up failed: %s", hipGetErrorString(e)); lbmpm_rk3dcsf_destroy(c); return LBMPM_ERR_HIP; }
+    if (e != hipSuccess) { set_error("set-up failed: %s", hipGetErrorString(e)); lbmpm_rk3dcsf_destroy(c); return LBMPM_ERR_HIP; }
     if (c->nwet) {
         const unsigned nb = blocks_of(N);
-        uint32_t *cnt = nullptr;
+        lbmpm::DeviceTemp<uint32_t> counts;
         std::vector<uint32_t> h(nb);
-        rc = dev_alloc(c, &c->wetlist, c->nwet);
-        if (rc == LBMPM_OK && hipMalloc(reinterpret_cast<void **>(&cnt), nb * sizeof(uint32_t)) != hipSuccess) { set_error("hipMalloc failed"); rc = LBMPM_ERR_NOMEM; }
+        rc = c->mem.alloc(&c->wetlist, c->nwet, nullptr);
+        if (rc == LBMPM_OK && counts.alloc(nb) != hipSuccess) { set_error("hipMalloc failed"); rc = LBMPM_ERR_NOMEM; }
         if (rc == LBMPM_OK) {
+            uint32_t *const cnt = counts.get();
             csf3d_setup_wetcount<<<nb, 256, 0, c->stream>>>((unsigned)N, c->meta, cnt);
             e = hipMemcpyAsync(h.data(), cnt, nb * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
             if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
@@ -1394,27 +1387,26 @@ extern "C" int lbmpm_rk3dcsf_create(const lbmpm_rk3dcsf_config *cfg, const uint8
             }
             if (e != hipSuccess) { set_error("set-up failed: %s", hipGetErrorString(e)); rc = LBMPM_ERR_HIP; }
         }
-        if (cnt) (void)hipFree(cnt);
-        if (rc != LBMPM_OK) { (void)hipFree(counters); lbmpm_rk3dcsf_destroy(c); return rc; }
+        if (rc != LBMPM_OK) { lbmpm_rk3dcsf_destroy(c); return rc; }
     }
     {   // the bulk skip's tables
         c->skip = cfg->variant == 0;
         c->nblk = blocks_of((size_t)c->nfluid);
         const unsigned nb = c->nblk;
-        uint32_t *lo0 = nullptr, *hi0 = nullptr, *lo1 = nullptr, *hi1 = nullptr;
-        rc = dev_alloc(c, &c->pure, (size_t)nb + 4);      // (csf3d_face_flags works on whole words)
-        if (rc == LBMPM_OK) rc = dev_alloc(c, &c->deep_prev, nb);
-        if (rc == LBMPM_OK) rc = dev_alloc(c, &c->bcblk, nb);
-        if (rc == LBMPM_OK) rc = dev_alloc(c, &c->rng, 2 * (size_t)nb);
-        if (rc == LBMPM_OK) rc = dev_alloc(c, &c->pfx, 2 * ((size_t)nb + 1));
-        if (rc == LBMPM_OK) rc = dev_alloc(c, &c->deep_now, nb);
-        if (rc == LBMPM_OK) rc = dev_alloc(c, &c->work, 3 * ((size_t)nb + 1));
-        if (rc == LBMPM_OK) rc = dev_alloc(c, &c->tcnt, 3 * ((size_t)nb / 1024 + 1));
-        if (rc == LBMPM_OK && c->skip) rc = dev_alloc(c, &c->src, 18 * c->FS);
-        if (rc == LBMPM_OK && c->nwet) rc = dev_alloc(c, &c->wethome, c->nwet);
-        if (rc == LBMPM_OK && hipMalloc(reinterpret_cast<void **>(&lo0), 4 * (size_t)nb * sizeof(uint32_t)) != hipSuccess) { set_error("hipMalloc failed"); rc = LBMPM_ERR_NOMEM; }
+        lbmpm::DeviceTemp<uint32_t> ranges;       // lo0, hi0, lo1, hi1: [nb] each
+        rc = c->mem.alloc(&c->pure, (size_t)nb + 4, nullptr);      // (csf3d_face_flags works on whole words)
+        if (rc == LBMPM_OK) rc = c->mem.alloc(&c->deep_prev, nb, nullptr);
+        if (rc == LBMPM_OK) rc = c->mem.alloc(&c->bcblk, nb, nullptr);
+        if (rc == LBMPM_OK) rc = c->mem.alloc(&c->rng, 2 * (size_t)nb, nullptr);
+        if (rc == LBMPM_OK) rc = c->mem.alloc(&c->pfx, 2 * ((size_t)nb + 1), nullptr);
+        if (rc == LBMPM_OK) rc = c->mem.alloc(&c->deep_now, nb, nullptr);
+        if (rc == LBMPM_OK) rc = c->mem.alloc(&c->work, 3 * ((size_t)nb + 1), nullptr);
+        if (rc == LBMPM_OK) rc = c->mem.alloc(&c->tcnt, 3 * ((size_t)nb / 1024 + 1), nullptr);
+        if (rc == LBMPM_OK && c->skip) rc = c->mem.alloc(&c->src, 18 * c->FS, nullptr);
+        if (rc == LBMPM_OK && c->nwet) rc = c->mem.alloc(&c->wethome, c->nwet, nullptr);
+        if (rc == LBMPM_OK && ranges.alloc(4 * (size_t)nb) != hipSuccess) { set_error("hipMalloc failed"); rc = LBMPM_ERR_NOMEM; }
         if (rc == LBMPM_OK) {
-            hi0 = lo0 + nb; lo1 = hi0 + nb; hi1 = lo1 + nb;
+            uint32_t *const lo0 = ranges.get(), *const hi0 = lo0 + nb, *const lo1 = hi0 + nb, *const hi1 = lo1 + nb;
             const CsfDev p = make_dev(c);
             e = hipMemsetAsync(lo0, 0xFF, nb * sizeof(uint32_t), c->stream);
             if (e == hipSuccess) e = hipMemsetAsync(hi0, 0, nb * sizeof(uint32_t), c->stream);
@@ -1436,10 +1428,8 @@ extern "C" int lbmpm_rk3dcsf_create(const lbmpm_rk3dcsf_config *cfg, const uint8
             }
             if (e != hipSuccess) { set_error("set-up failed: %s", hipGetErrorString(e)); rc = LBMPM_ERR_HIP; }
         }
-        if (lo0) (void)hipFree(lo0);
-        if (rc != LBMPM_OK) { (void)hipFree(counters); lbmpm_rk3dcsf_destroy(c); return rc; }
+        if (rc != LBMPM_OK) { lbmpm_rk3dcsf_destroy(c); return rc; }
     }
-    (void)hipFree(counters);
 #undef TRY_RC
 #undef TRY_HIP
     *out = c;
@@ -1451,8 +1441,8 @@ extern "C" int lbmpm_rk3dcsf_enable_diagnostics(lbmpm_rk3dcsf *c, int on)
     LBMPM_REQUIRE(c, "null context");
     LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
     if (on && !c->K) {
-        int rc = dev_alloc(c, &c->K, c->NS); if (rc) return rc;
-        rc = dev_alloc(c, &c->U, 3 * c->NS); if (rc) return rc;
+        int rc = c->mem.alloc(&c->K, c->NS, nullptr); if (rc) return rc;
+        rc = c->mem.alloc(&c->U, 3 * c->NS, nullptr); if (rc) return rc;
         LBMPM_HIP_TRY(hipMemsetAsync(c->K, 0, c->NS * sizeof(double), c->stream));
         LBMPM_HIP_TRY(hipMemsetAsync(c->U, 0, 3 * c->NS * sizeof(double), c->stream));
     }
@@ -1498,8 +1488,9 @@ extern "C" int lbmpm_rk3dcsf_set_pdf(lbmpm_rk3dcsf *c, const double *pdf_r, cons
 {
     LBMPM_REQUIRE(c && pdf_r && pdf_b, "lbmpm_rk3dcsf_set_pdf: null argument");
     LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
-    double *st = nullptr;                        // [2][N][19] in the host's layout, for the length of the call
-    LBMPM_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&st), 2 * c->N * Q * sizeof(double)));
+    lbmpm::DeviceTemp<double> staged;            // [2][N][19] in the host's layout, for the length of the call
+    LBMPM_HIP_TRY(staged.alloc(2 * c->N * Q));
+    double *const st = staged.get();
     int rc = upload(c, st, pdf_r, c->N * Q);
     if (rc == LBMPM_OK) rc = upload(c, st + c->N * Q, pdf_b, c->N * Q);
     if (rc == LBMPM_OK) {
@@ -1509,7 +1500,6 @@ extern "C" int lbmpm_rk3dcsf_set_pdf(lbmpm_rk3dcsf *c, const double *pdf_r, cons
     }
     if (rc == LBMPM_OK) rc = reset_state(c, fx, fy, fz);        // (synchronises the stream)
     else (void)hipStreamSynchronize(c->stream);
-    (void)hipFree(st);
     return rc;
 }
 
@@ -1735,30 +1725,8 @@ extern "C" int lbmpm_rk3dcsf_step_timed(lbmpm_rk3dcsf *c, int64_t nsteps, double
 {
     LBMPM_REQUIRE(c && nsteps >= 0, "lbmpm_rk3dcsf_step_timed: bad argument");
     LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
-    const size_t pairs = (size_t)(nsteps < 4096 ? nsteps : 4096);
-    if (c->pool.reserve(pairs + 1) != LBMPM_OK) { set_error("hipEventCreate failed"); return LBMPM_ERR_HIP; }
-    c->pool.reset();
     c->timed_steps = 0;
-    hipEvent_t t0, t1;
-    c->pool.take(&t0, &t1);
-    LBMPM_HIP_TRY(hipEventRecord(t0, c->stream));
-    const int rc = run_steps(c, nsteps, true);
-    if (rc != LBMPM_OK) return rc;
-    LBMPM_HIP_TRY(hipEventRecord(t1, c->stream));
-    LBMPM_HIP_TRY(hipStreamSynchronize(c->stream));
-    float ms = 0.f;
-    LBMPM_HIP_TRY(hipEventElapsedTime(&ms, t0, t1));
-    if (ms_total) *ms_total = ms;
-    if (ms_dominant) {
-        double s = 0.0;
-        for (size_t k = 2; k + 1 < c->pool.used; k += 2) {
-            float m = 0.f;
-            LBMPM_HIP_TRY(hipEventElapsedTime(&m, c->pool.ev[k], c->pool.ev[k + 1]));
-            s += m;
-        }
-        *ms_dominant = c->timed_steps ? s * (double)nsteps / (double)c->timed_steps : 0.0;
-    }
-    return LBMPM_OK;
+    return lbmpm::step_timed(c->stream, c->pool, nsteps, ms_total, ms_dominant, [&] { return run_steps(c, nsteps, true); }, [&] { return c->timed_steps; });
 }
 
 extern "C" int lbmpm_rk3dcsf_sync(lbmpm_rk3dcsf *c)
@@ -1770,7 +1738,7 @@ extern "C" int lbmpm_rk3dcsf_sync(lbmpm_rk3dcsf *c)
 
 static int observe(lbmpm_rk3dcsf *c, bool rec, double *pdf)
 {
-    if (!c->obs) { const int rc = dev_alloc(c, &c->obs, 6 * c->N); if (rc) return rc; }
+    if (!c->obs) { const int rc = c->mem.alloc(&c->obs, 6 * c->N, nullptr); if (rc) return rc; }
     const CsfDev p = make_dev(c);
     double *rho = c->obs, *u = rho + 2 * c->N, *phi = u + 3 * c->N;
     const unsigned g = blocks_of(c->N);
@@ -1798,11 +1766,10 @@ extern "C" int lbmpm_rk3dcsf_get_field(lbmpm_rk3dcsf *c, int field, double *out)
     case LBMPM_RK3DCSF_REC_PDF_R: case LBMPM_RK3DCSF_REC_PDF_B: case LBMPM_RK3DCSF_REC_RHO_R: case LBMPM_RK3DCSF_REC_RHO_B:
     case LBMPM_RK3DCSF_REC_VX: case LBMPM_RK3DCSF_REC_VY: case LBMPM_RK3DCSF_REC_VZ: case LBMPM_RK3DCSF_REC_PHI: {
         const int base = rec ? field - LBMPM_RK3DCSF_REC_PDF_R : field;
-        double *pdf = nullptr;                   // [2][N][19] in the host's layout, for the length of the call
-        if (base <= 1) LBMPM_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&pdf), 2 * N * Q * sizeof(double)));
-        int rc = observe(c, rec, pdf);
-        if (rc == LBMPM_OK && base <= 1) rc = down(pdf + (size_t)base * N * Q, N * Q);
-        if (pdf) (void)hipFree(pdf);
+        lbmpm::DeviceTemp<double> pdf;           // [2][N][19] in the host's layout, for the length of the call
+        if (base <= 1) LBMPM_HIP_TRY(pdf.alloc(2 * N * Q));
+        int rc = observe(c, rec, pdf.get());
+        if (rc == LBMPM_OK && base <= 1) rc = down(pdf.get() + (size_t)base * N * Q, N * Q);
         if (rc != LBMPM_OK || base <= 1) return rc;
         const double *rho = c->obs, *u = rho + 2 * N, *phi = u + 3 * N;
         if (base <= 3) return down(rho + (size_t)(base - 2) * N, N);
@@ -1836,7 +1803,7 @@ extern "C" int lbmpm_rk3dcsf_integrals(lbmpm_rk3dcsf *c, double *out)
     if (!c->have_state) { set_error("lbmpm_rk3dcsf_integrals before set_macro / set_pdf"); return LBMPM_ERR_STATE; }
     LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
     const unsigned planes = (unsigned)(c->nz - c->cfg.ghost_lo - c->cfg.ghost_hi), plane_cells = (unsigned)c->nx * (unsigned)c->ny;
-    if (!c->integ) { const int rc = dev_alloc(c, &c->integ, integral_buffer_doubles<FlowCols>(planes, plane_cells)); if (rc) return rc; }
+    { const int rc = integral_buffer<FlowCols>(c->mem, &c->integ, planes, plane_cells, 1, nullptr); if (rc) return rc; }
     const CsfDev p = make_dev(c);
     if (c->first) LBMPM_HIP_TRY(integrals_run(CsfIntLoader<true>{p}, planes, plane_cells, c->integ, out, c->stream));
     else LBMPM_HIP_TRY(integrals_run(CsfIntLoader<false>{p}, planes, plane_cells, c->integ, out, c->stream));
@@ -1850,57 +1817,33 @@ extern "C" int lbmpm_rk3dcsf_clusters(lbmpm_rk3dcsf *c, const lbmpm_clusters_con
     LBMPM_REQUIRE(c && count, "lbmpm_rk3dcsf_clusters: null argument");
     if (!c->have_state) { set_error("lbmpm_rk3dcsf_clusters before set_macro / set_pdf"); return LBMPM_ERR_STATE; }
     LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
-    ClState &s = c->cl;
     double cut = 0.;
     ClGeom g{};
     { const int rc = clusters_configure("lbmpm_rk3dcsf_clusters", cfg, (unsigned long long)c->nx * c->ny * (unsigned long long)c->nzg, &cut, &g); if (rc) return rc; }
     g.nx = (unsigned)c->nx; g.ny = (unsigned)c->ny; g.planes = (unsigned)(c->nz - c->cfg.ghost_lo - c->cfg.ghost_hi);
     g.plane_cells = g.nx * g.ny; g.n = g.planes * g.plane_cells;
     g.z0 = (unsigned)(c->zoff + c->cfg.ghost_lo); g.base = g.z0 * g.plane_cells;
-    s.valid = false;
-    if (!s.chunks) {
-        size_t n[4];
-        clusters_sizes_of(g.n, n);
-        int rc = dev_alloc(c, &s.cls, n[0]);
-        if (!rc) rc = dev_alloc(c, &s.lab, n[1]);
-        if (!rc) rc = dev_alloc(c, &s.rows, n[2]);
-        if (!rc) rc = dev_alloc(c, &s.chunks, n[3]);
-        if (rc) return rc;
-    }
-    s.g = g;
     const CsfDev p = make_dev(c);
-    if (c->first) LBMPM_HIP_TRY(clusters_run(CsfPhiLoader<true>{p}, s, cut, c->stream));
-    else LBMPM_HIP_TRY(clusters_run(CsfPhiLoader<false>{p}, s, cut, c->stream));
-    s.valid = true; s.at_step = c->steps;
-    *count = s.count;
-    return LBMPM_OK;
+    if (c->first) return clusters_label(CsfPhiLoader<true>{p}, c->cl, g, cut, c->steps, c->mem, nullptr, c->stream, count);
+    return clusters_label(CsfPhiLoader<false>{p}, c->cl, g, cut, c->steps, c->mem, nullptr, c->stream, count);
 }
 
 extern "C" int lbmpm_rk3dcsf_clusters_table(lbmpm_rk3dcsf *c, int64_t *out)
 {
     LBMPM_REQUIRE(c && out, "lbmpm_rk3dcsf_clusters_table: null argument");
-    { const int rc = clusters_current("lbmpm_rk3dcsf_clusters_table", c->cl, c->steps); if (rc) return rc; }
-    LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
-    LBMPM_HIP_TRY(clusters_table(c->cl, out, c->stream));
-    return LBMPM_OK;
+    return clusters_table("lbmpm_rk3dcsf_clusters_table", c->cl, c->steps, c->cfg.device, c->stream, out);
 }
 
 extern "C" int lbmpm_rk3dcsf_clusters_labels(lbmpm_rk3dcsf *c, uint32_t *out)
 {
     LBMPM_REQUIRE(c && out, "lbmpm_rk3dcsf_clusters_labels: null argument");
-    { const int rc = clusters_current("lbmpm_rk3dcsf_clusters_labels", c->cl, c->steps); if (rc) return rc; }
-    LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
-    LBMPM_HIP_TRY(clusters_labels(c->cl, out, c->stream));
-    return LBMPM_OK;
+    return clusters_labels("lbmpm_rk3dcsf_clusters_labels", c->cl, c->steps, c->cfg.device, c->stream, out);
 }
 
 extern "C" int lbmpm_rk3dcsf_clusters_faces(lbmpm_rk3dcsf *c, uint32_t *labels, uint8_t *classes)
 {
     LBMPM_REQUIRE(c && labels && classes, "lbmpm_rk3dcsf_clusters_faces: null argument");
-    { const int rc = clusters_current("lbmpm_rk3dcsf_clusters_faces", c->cl, c->steps); if (rc) return rc; }
-    LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
-    LBMPM_HIP_TRY(clusters_faces(c->cl, labels, classes, c->stream));
-    return LBMPM_OK;
+    return clusters_faces("lbmpm_rk3dcsf_clusters_faces", c->cl, c->steps, c->cfg.device, c->stream, labels, classes);
 }
 
 extern "C" int64_t lbmpm_rk3dcsf_num_fluid_nodes(const lbmpm_rk3dcsf *c) { return c ? c->nfluid : 0; }
@@ -1916,7 +1859,7 @@ extern "C" int64_t lbmpm_rk3dcsf_bulk_cells(lbmpm_rk3dcsf *c)
     return n;
 }
 extern "C" int64_t lbmpm_rk3dcsf_steps_done(const lbmpm_rk3dcsf *c) { return c ? c->steps : 0; }
-extern "C" int64_t lbmpm_rk3dcsf_device_bytes(const lbmpm_rk3dcsf *c) { return c ? c->bytes : 0; }
+extern "C" int64_t lbmpm_rk3dcsf_device_bytes(const lbmpm_rk3dcsf *c) { return c ? c->mem.bytes() : 0; }
 extern "C" const char *lbmpm_rk3dcsf_dominant_kernel(const lbmpm_rk3dcsf *c) { (void)c; return "csf3d_collide"; }
 
 // ---- the three face messages over a transport inside the library (include/lbmpm.h, CSF block; rk3d_transport.h, shared with the
@@ -2233,15 +2176,13 @@ static int tracer_configure(lbmpm_rk3dcsf *c, const lbmpm_tracer3d_config *k, co
     }
     LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
     const size_t per = (size_t)k->num_tracers * TQ * c->FS;
-    const int64_t bytes_before = c->bytes;
-    int rc = dev_alloc(c, &c->gA, per);
-    if (rc == LBMPM_OK) rc = dev_alloc(c, &c->gB, per);
-    if (rc == LBMPM_OK) rc = dev_alloc(c, &c->trflow, 4 * c->FS);
-    if (rc == LBMPM_OK && !c->src) rc = dev_alloc(c, &c->trsrc, 6 * c->FS);
+    int rc = c->mem.alloc(&c->gA, per, nullptr);
+    if (rc == LBMPM_OK) rc = c->mem.alloc(&c->gB, per, nullptr);
+    if (rc == LBMPM_OK) rc = c->mem.alloc(&c->trflow, 4 * c->FS, nullptr);
+    if (rc == LBMPM_OK && !c->src) rc = c->mem.alloc(&c->trsrc, 6 * c->FS, nullptr);
     if (rc != LBMPM_OK) {                        // all or nothing: a later configure starts from scratch
-        for (double **q : {&c->gA, &c->gB, &c->trflow}) if (*q) { (void)hipFree(*q); *q = nullptr; }
-        if (c->trsrc) { (void)hipFree(c->trsrc); c->trsrc = nullptr; }
-        c->bytes = bytes_before;
+        for (double **q : {&c->gA, &c->gB, &c->trflow}) c->mem.release(q);
+        c->mem.release(&c->trsrc);
         return rc;
     }
     LBMPM_HIP_TRY(hipMemsetAsync(c->gA, 0, per * sizeof(double), c->stream));
@@ -2264,15 +2205,15 @@ static int tracer_import(lbmpm_rk3dcsf *c, int tracer, const double *conc, const
     { const int rc = tracer_ready(c, tracer, who); if (rc) return rc; }
     LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
     const size_t count = conc ? c->N : c->N * TQ;
-    double *st = nullptr;
-    LBMPM_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&st), count * sizeof(double)));
+    lbmpm::DeviceTemp<double> staged;
+    LBMPM_HIP_TRY(staged.alloc(count));
+    double *const st = staged.get();
     int rc = upload(c, st, conc ? conc : pdf, count);
     if (rc == LBMPM_OK) {
         tr3d_import<<<blocks_of(c->N), 256, 0, c->stream>>>(make_dev(c), c->gA + (size_t)tracer * TQ * c->FS, conc ? st : nullptr, conc ? nullptr : st);
         if (hipGetLastError() != hipSuccess) { set_error("tr3d_import did not launch"); rc = LBMPM_ERR_HIP; }
     }
     (void)hipStreamSynchronize(c->stream);
-    (void)hipFree(st);
     if (rc == LBMPM_OK) c->tr_given = true;
     return rc;
 }
@@ -2295,8 +2236,9 @@ static int tracer_observe(lbmpm_rk3dcsf *c, int tracer, double *conc, double *pd
 {
     { const int rc = tracer_ready(c, tracer, who); if (rc) return rc; }
     LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
-    double *st = nullptr;                        // [N] + [N][7], for the length of the call
-    LBMPM_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&st), c->N * (pdf ? 1 + TQ : 1) * sizeof(double)));
+    lbmpm::DeviceTemp<double> staged;            // [N] + [N][7], for the length of the call
+    LBMPM_HIP_TRY(staged.alloc(c->N * (pdf ? 1 + TQ : 1)));
+    double *const st = staged.get();
     const CsfDev p = make_dev(c);
     const TrDev t = make_trdev(c);
     if (c->tr_first) tr3d_observe<true><<<blocks_of(c->N), 256, 0, c->stream>>>(p, t, tracer, pdf ? st + c->N : nullptr, st);
@@ -2305,7 +2247,6 @@ static int tracer_observe(lbmpm_rk3dcsf *c, int tracer, double *conc, double *pd
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e == hipSuccess && conc) e = hipMemcpy(conc, st, c->N * sizeof(double), hipMemcpyDeviceToHost);
     if (e == hipSuccess && pdf) e = hipMemcpy(pdf, st + c->N, c->N * TQ * sizeof(double), hipMemcpyDeviceToHost);
-    (void)hipFree(st);
     if (e != hipSuccess) { set_error("%s failed: %s", who, hipGetErrorString(e)); return LBMPM_ERR_HIP; }
     return LBMPM_OK;
 }
@@ -2331,7 +2272,7 @@ extern "C" int lbmpm_rk3dcsf_tracer_integrals(lbmpm_rk3dcsf *c, double *out)
     if (!c->tr_given) { set_error("lbmpm_rk3dcsf_tracer_integrals before lbmpm_rk3dcsf_tracer_set_concentration / _set_pdf"); return LBMPM_ERR_STATE; }
     LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
     const unsigned planes = (unsigned)(c->nz - c->cfg.ghost_lo - c->cfg.ghost_hi), plane_cells = (unsigned)c->nx * (unsigned)c->ny, nT = (unsigned)c->ntr;
-    if (!c->trinteg) { const int rc = dev_alloc(c, &c->trinteg, integral_buffer_doubles<TracerCols>(planes, plane_cells, nT)); if (rc) return rc; }
+    { const int rc = integral_buffer<TracerCols>(c->mem, &c->trinteg, planes, plane_cells, nT, nullptr); if (rc) return rc; }
     const CsfDev p = make_dev(c);
     const TrDev t = make_trdev(c);
     if (c->tr_first) LBMPM_HIP_TRY(tracer_integrals_run(TrIntLoader<true>{p, t}, planes, plane_cells, nT, c->trinteg, out, c->stream));

@@ -131,6 +131,13 @@ inline double *integral_table(double *buf, unsigned planes, unsigned plane_cells
     return buf + (size_t)sets * planes * integral_chunks(plane_cells) * Cols::COLS;
 }
 
+// the device buffer of a context, from `mem` with the first call (zero_on: as DeviceBlocks::alloc)
+template <typename Cols>
+inline int integral_buffer(lbmpm::DeviceBlocks &mem, double **buf, unsigned planes, unsigned plane_cells, unsigned sets, hipStream_t zero_on)
+{
+    return *buf ? LBMPM_OK : mem.alloc(buf, integral_buffer_doubles<Cols>(planes, plane_cells, sets), zero_on);
+}
+
 // after both launches on `stream`: the table to the host -- one synchronisation, planes * sets * COLS * 8 bytes
 template <typename Cols>
 hipError_t integrals_download(const double *table, unsigned planes, unsigned sets, double *host_out, hipStream_t stream)

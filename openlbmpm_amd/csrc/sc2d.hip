@@ -843,7 +843,8 @@ struct lbmpm_sc2d {
     int scheme = 4;                  // [ForceScheme] ExplicitScheme
     int iso_sweeps = 1;              // schemes 8 / 10: 1 = sc2d_iso_fused, 2 = sc2d_iso_psi + sc2d_iso_collide (LBMPM_SC2D_ISO_SWEEPS, the cross-check)
     double *psi = nullptr;           // [2][plane], schemes 8 / 10 only
-    int64_t steps = 0, bytes = 0;
+    int64_t steps = 0;
+    lbmpm::DeviceBlocks mem;         // every device block the context keeps (lbmpm_sc2d_device_bytes)
     hipGraphExec_t graph_exec = nullptr;              // GRAPH_STEPS captured time steps, valid while fA is where it was at capture
     const double *graph_fA = nullptr;
     bool graph_keep = false;
@@ -872,28 +873,14 @@ SCDev make_dev(const lbmpm_sc2d *c)
     return p;
 }
 
-template <typename T>
-int dev_alloc(lbmpm_sc2d *c, T **ptr, size_t count)
-{
-    void *v = nullptr;
-    hipError_t e = hipMalloc(&v, count * sizeof(T));
-    if (e != hipSuccess) { set_error("hipMalloc(%zu bytes) failed: %s", count * sizeof(T), hipGetErrorString(e)); return LBMPM_ERR_NOMEM; }
-    e = hipMemsetAsync(v, 0, count * sizeof(T), c->stream);
-    if (e != hipSuccess) { set_error("hipMemsetAsync failed: %s", hipGetErrorString(e)); return LBMPM_ERR_HIP; }
-    *ptr = static_cast<T *>(v);
-    c->bytes += (int64_t)(count * sizeof(T));
-    return LBMPM_OK;
-}
-
 // EFS: everything the reference does before its loop plus the collision of iteration 0.
 int efs_initialise(lbmpm_sc2d *c)
 {
-    double *psi = nullptr, *scrA = nullptr, *scrB = nullptr;
-    int rc;
-    if ((rc = dev_alloc(c, &psi, 2 * c->plane)) || (rc = dev_alloc(c, &scrA, 18 * c->plane)) ||
-        (rc = dev_alloc(c, &scrB, 18 * c->plane))) return rc;
+    lbmpm::DeviceTemp<double> tmp;                   // psi [2][plane], scrA and scrB [18][plane], zeroed, for the length of the call
+    LBMPM_HIP_TRY(tmp.alloc(38 * c->plane));
+    LBMPM_HIP_TRY(hipMemsetAsync(tmp.get(), 0, 38 * c->plane * sizeof(double), c->stream));
     SCDev p = make_dev(c);
-    p.psi = psi; p.scrA = scrA; p.scrB = scrB;
+    p.psi = tmp.get(); p.scrA = p.psi + 2 * c->plane; p.scrB = p.scrA + 18 * c->plane;
     const dim3 g((c->nx + 63) / 64, (c->ny + 3) / 4), b(64, 4);
     const bool mrt = p.mrt;
     if (p.chang) sc2d_chang_seed<<<dim3((c->nx + 63) / 64), dim3(64), 0, c->stream>>>(p, c->chgB);
@@ -908,8 +895,6 @@ int efs_initialise(lbmpm_sc2d *c)
     if (p.outlet == LBMPM_OUTLET_FREEFLOW) sc2d_freeflow_rows<<<dim3((c->nx + 63) / 64, 3), dim3(64), 0, c->stream>>>(p, c->fA);
     LBMPM_HIP_TRY(hipGetLastError());
     LBMPM_HIP_TRY(hipStreamSynchronize(c->stream));
-    (void)hipFree(psi); (void)hipFree(scrA); (void)hipFree(scrB);
-    c->bytes -= (int64_t)(38 * c->plane * sizeof(double));
     c->streamed = true;
     c->initialised = true;
     return LBMPM_OK;
@@ -1085,18 +1070,18 @@ extern "C" int lbmpm_sc2d_create(const lbmpm_sc2d_config *cfg, const uint8_t *is
     }
     int rc = LBMPM_OK;
 #define TRY_RC(e) do { rc = (e); if (rc != LBMPM_OK) { lbmpm_sc2d_destroy(c); return rc; } } while (0)
-    TRY_RC(dev_alloc(c, &c->flags, c->plane));
-    TRY_RC(dev_alloc(c, &c->solidnbr, c->plane));
-    TRY_RC(dev_alloc(c, &c->fA, 18 * c->plane));
-    TRY_RC(dev_alloc(c, &c->fB, 18 * c->plane));
-    TRY_RC(dev_alloc(c, &c->F, 4 * c->plane));
+    TRY_RC(c->mem.alloc(&c->flags, c->plane, c->stream));
+    TRY_RC(c->mem.alloc(&c->solidnbr, c->plane, c->stream));
+    TRY_RC(c->mem.alloc(&c->fA, 18 * c->plane, c->stream));
+    TRY_RC(c->mem.alloc(&c->fB, 18 * c->plane, c->stream));
+    TRY_RC(c->mem.alloc(&c->F, 4 * c->plane, c->stream));
     c->scheme = cfg->force_scheme ? cfg->force_scheme : 4;
     if (const char *e = getenv("LBMPM_SC2D_ISO_SWEEPS")) c->iso_sweeps = atoi(e) == 2 ? 2 : 1;
-    if (c->scheme != 4) TRY_RC(dev_alloc(c, &c->psi, 2 * c->plane));
-    TRY_RC(dev_alloc(c, &c->foldA, (size_t)(18 * 3 + 2) * c->pitch));
-    TRY_RC(dev_alloc(c, &c->foldB, (size_t)(18 * 3 + 2) * c->pitch));
-    TRY_RC(dev_alloc(c, &c->chgA, (size_t)6 * c->pitch));
-    TRY_RC(dev_alloc(c, &c->chgB, (size_t)6 * c->pitch));
+    if (c->scheme != 4) TRY_RC(c->mem.alloc(&c->psi, 2 * c->plane, c->stream));
+    TRY_RC(c->mem.alloc(&c->foldA, (size_t)(18 * 3 + 2) * c->pitch, c->stream));
+    TRY_RC(c->mem.alloc(&c->foldB, (size_t)(18 * 3 + 2) * c->pitch, c->stream));
+    TRY_RC(c->mem.alloc(&c->chgA, (size_t)6 * c->pitch, c->stream));
+    TRY_RC(c->mem.alloc(&c->chgB, (size_t)6 * c->pitch, c->stream));
 #undef TRY_RC
     hipError_t e = hipMemcpyAsync(c->flags, hflags.data(), c->plane, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
@@ -1115,10 +1100,7 @@ extern "C" void lbmpm_sc2d_destroy(lbmpm_sc2d *c)
     if (!c) return;
     (void)hipSetDevice(c->cfg.device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    for (void *ptr : {(void *)c->flags, (void *)c->solidnbr, (void *)c->fA, (void *)c->fB, (void *)c->F,
-                      (void *)c->foldA, (void *)c->foldB, (void *)c->diag, (void *)c->obs, (void *)c->psi,
-                      (void *)c->chgA, (void *)c->chgB})
-        if (ptr) (void)hipFree(ptr);
+    c->mem.release_all();
     if (c->graph_exec) (void)hipGraphExecDestroy(c->graph_exec);
     c->pool.destroy();
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -1170,30 +1152,9 @@ extern "C" int lbmpm_sc2d_step_timed(lbmpm_sc2d *c, int64_t nsteps, double *ms_t
     LBMPM_REQUIRE(c && nsteps >= 0, "lbmpm_sc2d_step_timed: bad argument");
     LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
     if (c->cfg.model == LBMPM_SC_MODEL_EFS && !c->initialised) { const int rc = efs_initialise(c); if (rc) return rc; }
-    const size_t pairs = (size_t)(nsteps < 4096 ? nsteps : 4096);
-    if (c->pool.reserve(pairs + 1) != LBMPM_OK) { set_error("hipEventCreate failed"); return LBMPM_ERR_HIP; }
-    c->pool.reset();
     c->timed_steps = 0;
-    hipEvent_t t0, t1;
-    c->pool.take(&t0, &t1);
-    LBMPM_HIP_TRY(hipEventRecord(t0, c->stream));
-    const int rc = run_steps(c, nsteps, true);
-    if (rc != LBMPM_OK) return rc;
-    LBMPM_HIP_TRY(hipEventRecord(t1, c->stream));
-    LBMPM_HIP_TRY(hipStreamSynchronize(c->stream));
-    float ms = 0.f;
-    LBMPM_HIP_TRY(hipEventElapsedTime(&ms, t0, t1));
-    if (ms_total) *ms_total = ms;
-    if (ms_dominant) {
-        double s = 0.0;
-        for (size_t k = 2; k + 1 < c->pool.used; k += 2) {
-            float m = 0.f;
-            LBMPM_HIP_TRY(hipEventElapsedTime(&m, c->pool.ev[k], c->pool.ev[k + 1]));
-            s += m;
-        }
-        *ms_dominant = c->timed_steps ? s * (double)nsteps / (double)c->timed_steps : 0.0;    // (a graph replay is timed as a whole)
-    }
-    return LBMPM_OK;
+    // the pairs cover c->timed_steps time steps, not launches: a graph replay is timed as a whole
+    return lbmpm::step_timed(c->stream, c->pool, nsteps, ms_total, ms_dominant, [&] { return run_steps(c, nsteps, true); }, [&] { return c->timed_steps; });
 }
 
 extern "C" int lbmpm_sc2d_sync(lbmpm_sc2d *c)
@@ -1207,11 +1168,11 @@ extern "C" int lbmpm_sc2d_enable_diagnostics(lbmpm_sc2d *c, int on)
 {
     LBMPM_REQUIRE(c, "null context");
     LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
-    if (on && !c->diag) { const int rc = dev_alloc(c, &c->diag, D_PLANES * c->plane); if (rc) return rc; }
+    if (on && !c->diag) { const int rc = c->mem.alloc(&c->diag, D_PLANES * c->plane, c->stream); if (rc) return rc; }
     if (!on && c->diag) {
         LBMPM_HIP_TRY(hipStreamSynchronize(c->stream));
-        (void)hipFree(c->diag); c->diag = nullptr; c->diag_valid = false;
-        c->bytes -= (int64_t)(D_PLANES * c->plane * sizeof(double));
+        c->mem.release(&c->diag);
+        c->diag_valid = false;
     }
     c->keep_force = on != 0;
     return LBMPM_OK;
@@ -1239,7 +1200,7 @@ extern "C" int lbmpm_sc2d_get_field(lbmpm_sc2d *c, int field, double *out)
         src = c->diag;
     } else {
         LBMPM_REQUIRE(field < LBMPM_SC_UEQX, "u_eq is an EFS field");
-        if (!c->obs) { const int rc = dev_alloc(c, &c->obs, D_PLANES * c->plane); if (rc) return rc; }
+        if (!c->obs) { const int rc = c->mem.alloc(&c->obs, D_PLANES * c->plane, c->stream); if (rc) return rc; }
         SCDev p = make_dev(c);
         const dim3 b(64, 4), g((c->nx + 63) / 64, (c->ny + 3) / 4);
         if (rec) sc2d_observe<true><<<g, b, 0, c->stream>>>(p, c->obs);
@@ -1268,5 +1229,5 @@ extern "C" int lbmpm_sc2d_get_field(lbmpm_sc2d *c, int field, double *out)
 extern "C" int64_t lbmpm_sc2d_num_fluid_nodes(const lbmpm_sc2d *c) { return c ? c->nfluid : 0; }
 extern "C" int64_t lbmpm_sc2d_steps_done(const lbmpm_sc2d *c) { return c ? c->steps : 0; }
 extern "C" int64_t lbmpm_sc2d_graph_launches(const lbmpm_sc2d *c) { return c ? c->graph_launches : 0; }
-extern "C" int64_t lbmpm_sc2d_device_bytes(const lbmpm_sc2d *c) { return c ? c->bytes : 0; }
+extern "C" int64_t lbmpm_sc2d_device_bytes(const lbmpm_sc2d *c) { return c ? c->mem.bytes() : 0; }
 extern "C" const char *lbmpm_sc2d_dominant_kernel(const lbmpm_sc2d *c) { (void)c; return "sc2d_fused"; }

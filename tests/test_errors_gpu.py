@@ -167,20 +167,87 @@ def test_device_memory_accounting():
     compact.close(); dense.close()
 
 
-def test_create_destroy_does_not_leak_device_memory():
-    """EFS with an iso-8 force keeps a psi array (16 B per cell) that destroy once forgot"""
-    import torch
+def _duct3():
+    """a 64 x 64 x 32 duct (solid side walls) with one solid block in it: the CSF context has wetting solids"""
+    dom = np.ones((32, 64, 64), dtype=np.uint8)
+    dom[:, 0, :] = dom[:, -1, :] = 0
+    dom[:, :, 0] = dom[:, :, -1] = 0
+    dom[12:20, 24:40, 24:40] = 0
+    return dom
+
+
+def contexts_with_every_optional_block(dom, dom3):
+    """[(name, open solver)]: the four solver contexts after everything that allocates a device block on demand has run.  The 2-D
+    colour-gradient solver comes twice: its perturbation model (with that model's diagnostics) and its tracers exclude each other."""
     from openlbmpm_amd.sc2d import SC2DSolver
     from openlbmpm_amd.rk2d import RK2DSolver
     from openlbmpm_amd.rk3d import RK3DSlab
+    from openlbmpm_amd.rk3dcsf import RK3DCSFSolver
+    from openlbmpm_amd.geometry import initial_densities_rk, initial_densities_rk3d
+    fluid, fluid3 = (dom == 1).astype(np.float64), (dom3 == 1).astype(np.float64)
+    rR, rB = initial_densities_rk(dom, False, 10)
+    rR3, rB3 = initial_densities_rk3d(dom3, 5)
+    out = []
+    s = SC2DSolver(dom, dict(inter="EFS", scheme=8))
+    s.set_density(fluid, 0.02 * fluid)
+    s.step(1)                                                 # the EFS initialisation and its staging arrays
+    s.enable_diagnostics(True); s.enable_diagnostics(False); s.enable_diagnostics(True)
+    s.step(1)
+    out.append(("sc2d", s))
+    s = RK2DSolver(dom, None, diagnostics=True, perturbation=dict(AkR=0.007, AkB=0.009, solidPhi=0.5))
+    s.set_macro(rR, rB)
+    s.step(1)
+    s.get("rhoR")
+    out.append(("rk2d perturbation", s))
+    s = RK2DSolver(dom, None, diagnostics=True)
+    two = dict(diffX=(1. / 6.,) * 2, diffY=(1. / 6.,) * 2, beta=(1.0,) * 2, inlet_conc=(1.0,) * 2)
+    s.configure_tracers(**two)
+    s.configure_tracers(**two)                                # the second configure gives the first one's buffers back
+    s.set_macro(rR, rB)
+    for k in range(2):
+        s.set_tracer(k, 0.1 * fluid)
+    s.step(1)
+    s.get_tracer(0); s.get("rhoR")
+    out.append(("rk2d tracers", s))
+    s = RK3DSlab(dom3, 0, dom3.shape[0])
+    s.set_density(rR3, rB3)
+    s.phase_field(diagnostics=True)
+    s.integrals()
+    s.clusters(labels=True)
+    state, info = s.get_state()
+    s.set_state(state, steps=info["steps"], post_collision=info["post_collision"])
+    out.append(("rk3d", s))
+    s = RK3DCSFSolver(dom3, None, diagnostics=True, tracers=dict(num_tracers=2))
+    assert s.num_wetting_solids > 0
+    s.set_macro(rR3, rB3)
+    for k in range(2):
+        s.set_concentration(k, 0.1 * fluid3)
+    s.step(1)
+    s.integrals()
+    s.clusters(labels=True)
+    s.tracer_integrals()
+    s.get("rec_fR")
+    s.get_tracer_pdf(0)
+    out.append(("rk3dcsf", s))
+    return out
+
+
+def test_create_destroy_does_not_leak_device_memory():
+    """Create / destroy cycles over every block a context allocates on demand: diagnostics (switched on and off), the EFS
+    initialisation's staging arrays, the perturbation model's diagnostics, tracers (configured twice), the observe buffers, integral and
+    cluster buffers, the state's and the populations' staging buffers.  EFS with an iso-8 force keeps a psi array (16 B per cell) that
+    destroy once forgot; at these sizes (512 x 512, 64 x 64 x 32) a forgotten per-cell block of a byte per cell or more exceeds the cap
+    within the ten cycles.  The small tables (integral tables, counters, cluster rows of the 2^17-cell duct's chunks) lie below what
+    free memory can resolve: they are covered by construction -- a context's blocks all come from one owner (csrc/device_memory.h),
+    which frees everything it handed out."""
+    import torch
     from openlbmpm_amd.geometry import simple_geometry
     dom = simple_geometry(512, 512)
-    dom3 = np.ones((12, 16, 64), dtype=np.uint8)
+    dom3 = _duct3()
 
     def cycle():
-        s = SC2DSolver(dom, dict(inter="EFS", scheme=8)); s.close()
-        s = RK2DSolver(dom, None, diagnostics=True); s.close()
-        s = RK3DSlab(dom3, 0, 12); s.close()
+        for _name, s in contexts_with_every_optional_block(dom, dom3):
+            s.close()
     cycle()
     torch.cuda.synchronize()
     free0 = torch.cuda.mem_get_info()[0]
@@ -189,6 +256,46 @@ def test_create_destroy_does_not_leak_device_memory():
     torch.cuda.synchronize()
     free1 = torch.cuda.mem_get_info()[0]
     assert free0 - free1 < 4 << 20, "device memory shrank by %d bytes over 10 create/destroy cycles" % (free0 - free1)
+
+
+def test_device_bytes_round_trips():
+    """lbmpm_*_device_bytes follows what is given back: diagnostics off returns it to its value before they were on, the EFS
+    initialisation's staging arrays are not part of it, and tracers configured again count once"""
+    from openlbmpm_amd.sc2d import SC2DSolver
+    from openlbmpm_amd.rk2d import RK2DSolver
+    from openlbmpm_amd.geometry import simple_geometry
+    dom = simple_geometry(72, 96)
+    fluid = (dom == 1).astype(np.float64)
+    plane = 96 * 96                                           # rows are padded to a multiple of 32 nodes
+    for s in (RK2DSolver(dom, None), SC2DSolver(dom, dict(inter="EFS", scheme=8))):
+        before = s.device_bytes
+        s.enable_diagnostics(True)
+        on = s.device_bytes
+        assert on >= before + 3 * 8 * plane
+        s.enable_diagnostics(False)
+        assert s.device_bytes == before
+        s.enable_diagnostics(True)
+        assert s.device_bytes == on
+        s.close()
+    s = SC2DSolver(dom, dict(inter="EFS", scheme=8))
+    s.set_density(fluid, 0.02 * fluid)
+    before = s.device_bytes
+    s.step(1)                                                 # the first step initialises (38 planes of staging arrays come and go)
+    assert s.device_bytes == before
+    s.step(1)
+    assert s.device_bytes == before
+    s.close()
+
+    def tracers(n):
+        return dict(diffX=(1. / 6.,) * n, diffY=(1. / 6.,) * n, beta=(1.0,) * n, inlet_conc=(1.0,) * n)
+    s, fresh = RK2DSolver(dom, None), RK2DSolver(dom, None)
+    bare = s.device_bytes
+    s.configure_tracers(**tracers(2))
+    assert s.device_bytes == bare + 2 * 2 * 5 * 8 * plane      # two buffers of 5 populations per tracer
+    s.configure_tracers(**tracers(3))
+    fresh.configure_tracers(**tracers(3))
+    assert s.device_bytes == fresh.device_bytes == bare + 2 * 3 * 5 * 8 * plane
+    s.close(); fresh.close()
 
 
 def test_rk3d_fields_are_refused_when_stale():
