@@ -528,6 +528,48 @@ int lbmpm_rk3d_clusters(lbmpm_rk3d *ctx, const lbmpm_clusters_config *cfg, int64
 int lbmpm_rk3d_clusters_table(lbmpm_rk3d *ctx, int64_t *out);
 int lbmpm_rk3d_clusters_labels(lbmpm_rk3d *ctx, uint32_t *out);
 int lbmpm_rk3d_clusters_faces(lbmpm_rk3d *ctx, uint32_t *labels, uint8_t *classes);
+/* Phase morphology of the 3-D solvers: per own plane, counts over the 2 x 2 x 2 neighbourhoods of a class field plus two density sums,
+ * reduced on the device (csrc/rk3d_morphology.h).  Interfacial and wetted areas, the Euler characteristic of each phase and a
+ * phase-averaged pressure difference follow from them.
+ *   Cells       those of the planes the context owns, with the mask of lbmpm_*_integrals.  phi, rho_R and rho_B are read as
+ *               lbmpm_*_integrals reads them.  Perturbation model: the fields of the last lbmpm_rk3d_phase_field(ctx, 1); LBMPM_ERR_STATE
+ *               when a step has been taken since.  CSF model: from the populations, nothing staged.
+ *   Class       one byte per cell.  LBMPM_MORPH_S (0): solid.  _R (1): phi > phi_cut.  _B (2): phi <= -phi_cut.  _N (3): fluid in neither
+ *               phase -- the band of a phi_cut > 0, and any cell where phi, rho_R or rho_B is not finite.  phi_cut is finite and >= 0;
+ *               anything else: LBMPM_ERR_INVALID.
+ *   Elements    x and y wrap as in the solvers; z does not, in either model (as for the clusters).  An element is a set of cells
+ *               anchored at its corner cell c = (x, y, z), the cell with the lowest x, y and z before any wrap; its other cells are at
+ *               x + 1 mod nx, y + 1 mod ny and z + 1.  An element belongs to the plane of c.  Elements that would need plane nz do not
+ *               exist.  There is no special case for a small nx or ny: one element per anchor cell and kind, literally.
+ *   Table       [own planes][LBMPM_MORPH_COLS] doubles, every count far below 2^53:
+ *               CELLS_R, CELLS_B, CELLS_N   cells of each class in the plane
+ *               RHO_R, RHO_B                sum of rho_R + rho_B over the plane's R cells, and over its B cells
+ *               RR_a, BB_a, RB_a, RS_a, BS_a for the axis a = X, Y, Z in turn: the pairs (c, c + e_a) by their unordered pair of
+ *                                           classes.  Pairs with an N cell and S-S pairs are not counted
+ *               SQ_R_XY, _XZ, _YZ, SQ_B_..  2 x 2 squares anchored at c whose four cells are all of the phase
+ *               CUBE_R, CUBE_B              2 x 2 x 2 cubes anchored at c whose eight cells are all of the phase
+ *   Derived     faces of an interface: the sum over a of XY_a.  Euler characteristic of a phase, chi_6(X) = cells - sum_a XX_a + squares
+ *               - cubes: that of the open cubical complex, 6-connectivity, the default of the clusters.
+ * Every count is an integer: the same bits on every call and under every cut.  RHO_* are summed in the fixed order of the plane
+ * integrals, so they too are the same bit for bit however the lattice is cut.
+ * Slabs: `above` is the class plane over the highest own plane -- what lbmpm_*_morphology_face of the slab above hands out; the join is
+ * done on the device of the lower slab, the host moves ny * nx bytes per cut.  With above == NULL the highest own plane has no element
+ * that reaches upwards.  An `above` byte > 3: LBMPM_ERR_INVALID.
+ * Device memory: (own planes + 1) * ny * nx bytes, allocated by the first call of either function (counted by lbmpm_*_device_bytes),
+ * nothing before; the reducer's chunk partials live for the length of a call. */
+#define LBMPM_MORPH_COLS 28
+enum { LBMPM_MORPH_S = 0, LBMPM_MORPH_R, LBMPM_MORPH_B, LBMPM_MORPH_N };
+enum { LBMPM_MO_CELLS_R = 0, LBMPM_MO_CELLS_B, LBMPM_MO_CELLS_N, LBMPM_MO_RHO_R, LBMPM_MO_RHO_B,
+       LBMPM_MO_RR_X, LBMPM_MO_BB_X, LBMPM_MO_RB_X, LBMPM_MO_RS_X, LBMPM_MO_BS_X,
+       LBMPM_MO_RR_Y, LBMPM_MO_BB_Y, LBMPM_MO_RB_Y, LBMPM_MO_RS_Y, LBMPM_MO_BS_Y,
+       LBMPM_MO_RR_Z, LBMPM_MO_BB_Z, LBMPM_MO_RB_Z, LBMPM_MO_RS_Z, LBMPM_MO_BS_Z,
+       LBMPM_MO_SQ_R_XY, LBMPM_MO_SQ_R_XZ, LBMPM_MO_SQ_R_YZ, LBMPM_MO_SQ_B_XY, LBMPM_MO_SQ_B_XZ, LBMPM_MO_SQ_B_YZ,
+       LBMPM_MO_CUBE_R, LBMPM_MO_CUBE_B };
+typedef struct lbmpm_morphology_config { double phi_cut; } lbmpm_morphology_config;   /* NULL: phi_cut 0 */
+/* classes of the lowest own plane, host [ny][nx]: what the slab below passes as `above` */
+int lbmpm_rk3d_morphology_face(lbmpm_rk3d *ctx, const lbmpm_morphology_config *cfg, uint8_t *classes);
+/* above: host [ny][nx] classes (0..3) of the plane over the highest own plane, NULL at the lattice's end; out: host [nz_local][LBMPM_MORPH_COLS] */
+int lbmpm_rk3d_morphology(lbmpm_rk3d *ctx, const lbmpm_morphology_config *cfg, const uint8_t *above, double *out);
 /* out[4]: doubles stored per fluid cell (38, or 23 with the compressed compact storage: 19 colour-blind populations + k_R + the
  * recolouring vector, from which the pull rebuilds both colours -- AcceleratedRKGPU2D.py:1241-1267 makes the two lattices an affine
  * image of those), fluid cells owned, those of them in row segments flagged single-colour (no records kept), bytes one step moves
@@ -670,6 +712,10 @@ int lbmpm_rk3dcsf_clusters(lbmpm_rk3dcsf *ctx, const lbmpm_clusters_config *cfg,
 int lbmpm_rk3dcsf_clusters_table(lbmpm_rk3dcsf *ctx, int64_t *out);
 int lbmpm_rk3dcsf_clusters_labels(lbmpm_rk3dcsf *ctx, uint32_t *out);
 int lbmpm_rk3dcsf_clusters_faces(lbmpm_rk3dcsf *ctx, uint32_t *labels, uint8_t *classes);
+/* phase morphology of the own planes, see lbmpm_rk3d_morphology: phi, rho_R and rho_B are what LBMPM_RK3DCSF_REC_* hand out, from the
+ * populations in registers; out: host [own planes][LBMPM_MORPH_COLS].  LBMPM_ERR_STATE before set_macro / set_pdf */
+int lbmpm_rk3dcsf_morphology_face(lbmpm_rk3dcsf *ctx, const lbmpm_morphology_config *cfg, uint8_t *classes);
+int lbmpm_rk3dcsf_morphology(lbmpm_rk3dcsf *ctx, const lbmpm_morphology_config *cfg, const uint8_t *above, double *out);
 int64_t lbmpm_rk3dcsf_num_fluid_nodes(const lbmpm_rk3dcsf *ctx);
 int64_t lbmpm_rk3dcsf_num_wetting_solids(const lbmpm_rk3dcsf *ctx);
 /* fluid cells whose block took the bulk path in the last step (variant 0; see lbmpm_rk3dcsf_config.variant) */

@@ -36,6 +36,12 @@ clusters_every = N > 0: at the same kind of cadence the connected clusters of ea
 clusters_connectivity 6 or 18): /Clusters/TableAtStep<step> [n][5] int64 (label, class, cells, zmin, zmax; the whole lattice's, joined on
 rank 0 in a distributed run), /Clusters/Steps and /Clusters/Columns at the end; counts, the largest cluster, percolation and the trapped
 cells of each phase go to the log.
+
+morphology_every = N > 0: at the same kind of cadence the phase morphology, counted on the device (openlbmpm_amd/morphology.py;
+morphology_phi_cut: the band around phi = 0 that belongs to neither phase): /Morphology/PlanesAtStep<step> [nz][28] (cells, density
+sums, class pairs, squares and cubes per plane; the whole lattice's table on rank 0 in a distributed run), /Morphology/Steps and
+/Morphology/Columns at the end; the interfacial area, the wetted fraction, the Euler characteristics and the capillary pressure go to
+the log.
 """
 import os
 
@@ -112,7 +118,8 @@ def duct(nx, ny, nz):
 class RKColorGradient3D:
     def __init__(self, pathIniFile, output_dir=None, domain=None, device=0, record_every=None, num_buffering_layers=10,
                  structure_path=None, initial_dir=None, record_pdf=False, restart_from=None, checkpoint_every=0, csf_bulk_epsilon=0.0,
-                 csf_transport=None, integrals_every=0, clusters_every=0, clusters_connectivity=6):
+                 csf_transport=None, integrals_every=0, clusters_every=0, clusters_connectivity=6, morphology_every=0,
+                 morphology_phi_cut=0.0):
         self.pathIni = pathIniFile
         self.par = config.read_rk3d(pathIniFile)
         self.output_dir = output_dir or os.path.expanduser("~/LBMResults3D")       # main.py:28
@@ -130,6 +137,8 @@ class RKColorGradient3D:
         self.integrals_every = int(integrals_every)      # 0: no /Integrals group, no extra stop of the step loop
         # 0: no /Clusters group, no extra stop of the step loop; connectivity 6 (faces) or 18 (the D3Q19 links)
         self.clusters_every, self.clusters_connectivity = int(clusters_every), int(clusters_connectivity)
+        # 0: no /Morphology group, no extra stop of the step loop
+        self.morphology_every, self.morphology_phi_cut = int(morphology_every), float(morphology_phi_cut)
         self.gather_records = True
         self.records = 0
         self.physicalVX = self.physicalVY = self.physicalVZ = None
@@ -278,6 +287,7 @@ class RKColorGradient3D:
             step, observe = slab.step_single, (lambda: None)
             integrals = sim.solver.integrals
             clusters = sim.solver.clusters
+            morphology = sim.solver.morphology
             self.z0, self.nzl = 0, self.zDomain
             if whole_arrays:
                 import torch.distributed as dist
@@ -302,6 +312,7 @@ class RKColorGradient3D:
             step, observe, slab = sim.step, sim.observe, sim.slab
             integrals = sim.integrals
             clusters = sim.clusters
+            morphology = sim.morphology
             self.z0, self.nzl = sim.z0, sim.nzl
             if self.gather_records:
                 self._gather = sim.gather
@@ -313,6 +324,7 @@ class RKColorGradient3D:
             observe = lambda: slab.phase_field(diagnostics=True)
             integrals = lambda: fresh(slab.integrals, observe)
             clusters = lambda **kw: fresh(lambda: slab.clusters(**kw), observe)
+            morphology = lambda cut: fresh(lambda: slab.morphology(cut), observe)
             self.z0, self.nzl = 0, self.zDomain
         self._slab, self._observe = slab, observe
         done = 0
@@ -326,9 +338,11 @@ class RKColorGradient3D:
         every = self.integrals_every
         # (the table is gathered: the whole lattice's on rank 0, whether the records are gathered or not)
         cevery = self.clusters_every
-        more = ((("Integrals", "PlaneIntegrals"),) if every > 0 and rank == 0 else ()) + ((("Clusters", "PhaseClusters"),) if cevery > 0 and rank == 0 else ())
+        mevery = self.morphology_every
+        more = ((("Integrals", "PlaneIntegrals"),) if every > 0 and rank == 0 else ()) + ((("Clusters", "PhaseClusters"),) if cevery > 0 and rank == 0 else ()) + \
+            ((("Morphology", "PhaseMorphology"),) if mevery > 0 and rank == 0 else ())
         out = ResultFile(self.output_dir, name, GROUPS + more) if writes else None
-        self.integral_steps, self.cluster_steps = [], []
+        self.integral_steps, self.cluster_steps, self.morphology_steps = [], [], []
         self.result_path = out.path if out else None
         # distributed: every rank checks its own slab, the verdict is collective (all ranks raise together, none is left in an exchange)
         self._guard = RecordGuard("rk3d", slab.num_fluid_nodes, getattr(self, "nan_guard", "raise"), collective=self._distributed(), device=self.device)
@@ -341,11 +355,15 @@ class RKColorGradient3D:
                 self._integrals(integrals(), out, done)
             if cevery > 0 and done % cevery == 0:
                 self._clusters(clusters(connectivity=self.clusters_connectivity), out, done)
+            if mevery > 0 and done % mevery == 0:
+                self._morphology(morphology(self.morphology_phi_cut), out, done)
             n = min(self.timeInterval - done % self.timeInterval, self.timeSteps - done)
             if every > 0:
                 n = min(n, every - done % every)
             if cevery > 0:
                 n = min(n, cevery - done % cevery)
+            if mevery > 0:
+                n = min(n, mevery - done % mevery)
             if self.checkpoint_every > 0:
                 n = min(n, self.checkpoint_every - done % self.checkpoint_every)
             step(n)
@@ -369,6 +387,12 @@ class RKColorGradient3D:
                 from .clusters import column_bytes as cluster_column_bytes
                 out.write("Clusters", "Steps", np.array(self.cluster_steps, dtype=np.int64))
                 out.write("Clusters", "Columns", cluster_column_bytes())
+        if mevery > 0:
+            self._morphology(morphology(self.morphology_phi_cut), out, done)
+            if rank == 0:
+                from .morphology import column_bytes as morphology_column_bytes
+                out.write("Morphology", "Steps", np.array(self.morphology_steps, dtype=np.int64))
+                out.write("Morphology", "Columns", morphology_column_bytes())
         slab.sync()
         self.solver = sim
         return self.result_path
@@ -389,6 +413,15 @@ class RKColorGradient3D:
             if out is not None:
                 out.write("Clusters", "TableAtStep%d" % step, t.table)
             self._guard.log.info("rk3d clusters step %d: %s", step, " ".join("%s=%s" % kv for kv in t.summary().items()))
+
+    def _morphology(self, t, out, step):
+        """t: the Morphology of the whole lattice at `step` (None on the other ranks of a distributed run)"""
+        self.morphology = t
+        self.morphology_steps.append(int(step))
+        if t is not None:
+            if out is not None:
+                out.write("Morphology", "PlanesAtStep%d" % step, t.planes)
+            self._guard.log.info("rk3d morphology step %d: %s", step, " ".join("%s=%s" % kv for kv in t.summary().items()))
 
     def _record(self, slab, out):
         k = self.records

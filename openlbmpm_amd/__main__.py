@@ -12,6 +12,8 @@
                                                   ConcentrationResults)
         [--clusters-every N]                      rk3d: the connected clusters of each phase, labelled on the device, every N steps (/Clusters of the
         [--clusters-connectivity 6|18]            result file: label, class, cells, zmin, zmax per cluster); percolation and trapped cells to the log
+        [--morphology-every N]                    rk3d: cells, class pairs, squares and cubes per plane, counted on the device, every N steps (/Morphology
+        [--morphology-phi-cut c]                  of the result file); interfacial area, wetted fraction, Euler characteristics, capillary pressure to the log
 """
 import argparse
 import sys
@@ -53,6 +55,10 @@ def main(argv=None):
                     help="rk3d: every N steps the connected clusters of each phase (label, class, cells, zmin, zmax per cluster), labelled on the device, "
                          "to /Clusters of the result file; counts, the largest cluster, percolation and trapped cells to the log; 0: off")
     ap.add_argument("--clusters-connectivity", type=int, choices=[6, 18], default=6, help="rk3d: neighbours of a cell: 6 faces, or the 18 D3Q19 links")
+    ap.add_argument("--morphology-every", type=int, default=0, metavar="N",
+                    help="rk3d: every N steps the phase morphology (cells, density sums, class pairs, squares and cubes per plane), counted on the device, "
+                         "to /Morphology of the result file; interfacial area, wetted fraction, Euler characteristics and capillary pressure to the log; 0: off")
+    ap.add_argument("--morphology-phi-cut", type=float, default=0.0, metavar="c", help="rk3d: cells with |phi| within c of 0 belong to neither phase")
     a = ap.parse_args(argv)
     t0 = time.time()
     if a.model == "rk":
@@ -66,7 +72,8 @@ def main(argv=None):
         from .RKColorGradientD3Q19 import RKColorGradient3D
         device = _rank_device(a.device)
         sim = RKColorGradient3D(a.ini_dir, output_dir=a.out, device=device, csf_transport=a.csf_transport, integrals_every=a.integrals_every,
-                                clusters_every=a.clusters_every, clusters_connectivity=a.clusters_connectivity)
+                                clusters_every=a.clusters_every, clusters_connectivity=a.clusters_connectivity,
+                                morphology_every=a.morphology_every, morphology_phi_cut=a.morphology_phi_cut)
         if a.steps is not None:
             sim.timeSteps = a.steps
         path = sim.runRKColorGradient3D()

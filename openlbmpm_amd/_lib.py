@@ -100,6 +100,11 @@ class ClustersConfig(C.Structure):
     _fields_ = [("phi_cut", C.c_double), ("connectivity", C.c_int32), ("reserved", C.c_int32)]
 
 
+class MorphologyConfig(C.Structure):
+    # mirrors struct lbmpm_morphology_config (include/lbmpm.h)
+    _fields_ = [("phi_cut", C.c_double)]
+
+
 U32P = C.POINTER(C.c_uint32)
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int)      # lbmpm_rk3d_exchange_fn
 IPC_BLOB_BYTES, RCCL_ID_BYTES = 256, 128                     # LBMPM_IPC_BLOB_BYTES, LBMPM_RCCL_ID_BYTES
@@ -185,6 +190,8 @@ _SIGNATURES = {
     "lbmpm_rk3d_clusters_table": (C.c_int, [C.c_void_p, I64P]),
     "lbmpm_rk3d_clusters_labels": (C.c_int, [C.c_void_p, U32P]),
     "lbmpm_rk3d_clusters_faces": (C.c_int, [C.c_void_p, U32P, U8P]),
+    "lbmpm_rk3d_morphology_face": (C.c_int, [C.c_void_p, C.POINTER(MorphologyConfig), U8P]),
+    "lbmpm_rk3d_morphology": (C.c_int, [C.c_void_p, C.POINTER(MorphologyConfig), U8P, F64P]),
     "lbmpm_rk3d_num_fluid_nodes": (C.c_int64, [C.c_void_p]),
     "lbmpm_rk3d_steps_done": (C.c_int64, [C.c_void_p]),
     "lbmpm_rk3d_dominant_kernel": (C.c_char_p, [C.c_void_p]),
@@ -212,6 +219,8 @@ _SIGNATURES = {
     "lbmpm_rk3dcsf_clusters_table": (C.c_int, [C.c_void_p, I64P]),
     "lbmpm_rk3dcsf_clusters_labels": (C.c_int, [C.c_void_p, U32P]),
     "lbmpm_rk3dcsf_clusters_faces": (C.c_int, [C.c_void_p, U32P, U8P]),
+    "lbmpm_rk3dcsf_morphology_face": (C.c_int, [C.c_void_p, C.POINTER(MorphologyConfig), U8P]),
+    "lbmpm_rk3dcsf_morphology": (C.c_int, [C.c_void_p, C.POINTER(MorphologyConfig), U8P, F64P]),
     "lbmpm_rk3dcsf_tracer_integrals": (C.c_int, [C.c_void_p, F64P]),
     "lbmpm_rk3dcsf_num_fluid_nodes": (C.c_int64, [C.c_void_p]),
     "lbmpm_rk3dcsf_num_wetting_solids": (C.c_int64, [C.c_void_p]),

@@ -1165,6 +1165,7 @@ __global__ void rk3d_setup_solidnbr(RK3Dev p, uint32_t *solidnbr)
 #include "rk3d_state.h"
 #include "rk3d_integrals.h"
 #include "rk3d_clusters.h"
+#include "rk3d_morphology.h"
 
 // the fields of the last lbmpm_rk3d_phase_field(ctx, 1) (rhoR, rhoB, vx, vy, vz in `diag`, the phase field in `phi`; pitch, plane2 and
 // halo planes as lbmpm_rk3d_get_field reads them), the mask from the device's flags
@@ -1217,6 +1218,7 @@ struct lbmpm_rk3d {
     double *fA = nullptr, *fB = nullptr, *phi = nullptr, *diag = nullptr;
     double *integ = nullptr;         // lbmpm_rk3d_integrals: chunk partials + the table (rk3d_integrals.h), allocated by the first call
     ClState cl;                      // lbmpm_rk3d_clusters: classes, labels, rows (rk3d_clusters.h), allocated by the first call
+    uint8_t *morph = nullptr;        // lbmpm_rk3d_morphology: classes [nzl + 1][ny][nx] (rk3d_morphology.h), allocated by the first call
     uint32_t *purA = nullptr, *purB = nullptr;       // row flags of the q23 storage, swapped with fA / fB
     double *send_up = nullptr, *send_dn = nullptr, *recv_below = nullptr, *recv_above = nullptr;
     std::vector<uint8_t> h_domain;   // owned planes only, [nzl][ny][nx]
@@ -2583,6 +2585,38 @@ extern "C" int lbmpm_rk3d_clusters_faces(lbmpm_rk3d *c, uint32_t *labels, uint8_
 {
     LBMPM_REQUIRE(c && labels && classes, "lbmpm_rk3d_clusters_faces: null argument");
     return clusters_faces("lbmpm_rk3d_clusters_faces", c->cl, c->steps, c->cfg.device, c->stream, labels, classes);
+}
+
+// Phase morphology of the fields of the last lbmpm_rk3d_phase_field(ctx, 1) (rk3d_morphology.h; the definition: include/lbmpm.h).  The
+// checks and the class array of both entry points; then the context's device is the current one.
+static int morphology_ready(const char *who, lbmpm_rk3d *c, const lbmpm_morphology_config *cfg, double *cut)
+{
+    LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
+    { const int rc = morphology_configure(who, cfg, (unsigned long long)(c->nzl + 1) * c->nx * c->ny, cut); if (rc) return rc; }
+    if (c->observed_at != c->steps || !c->diag) {
+        set_error("the phase field is stale: call lbmpm_rk3d_phase_field(ctx, 1) after the last step (the morphology is that of the fields at that "
+                  "call; observed at step %lld, now %lld)", (long long)c->observed_at, (long long)c->steps);
+        return LBMPM_ERR_STATE;
+    }
+    return morphology_classes(c->mem, &c->morph, (unsigned)c->nzl, (unsigned)c->nx * (unsigned)c->ny, c->stream);
+}
+
+extern "C" int lbmpm_rk3d_morphology_face(lbmpm_rk3d *c, const lbmpm_morphology_config *cfg, uint8_t *classes)
+{
+    LBMPM_REQUIRE(c && classes, "lbmpm_rk3d_morphology_face: null argument");
+    double cut = 0.;
+    { const int rc = morphology_ready("lbmpm_rk3d_morphology_face", c, cfg, &cut); if (rc) return rc; }
+    const Rk3dIntLoader load{c->flags, c->diag, c->phi, (unsigned)c->nx, (unsigned)c->pitch, c->plane2, c->vol};
+    return morphology_face(load, c->morph, (unsigned)c->nx * (unsigned)c->ny, cut, classes, c->stream);
+}
+
+extern "C" int lbmpm_rk3d_morphology(lbmpm_rk3d *c, const lbmpm_morphology_config *cfg, const uint8_t *above, double *out)
+{
+    LBMPM_REQUIRE(c && out, "lbmpm_rk3d_morphology: null argument");
+    double cut = 0.;
+    { const int rc = morphology_ready("lbmpm_rk3d_morphology", c, cfg, &cut); if (rc) return rc; }
+    const Rk3dIntLoader load{c->flags, c->diag, c->phi, (unsigned)c->nx, (unsigned)c->pitch, c->plane2, c->vol};
+    return morphology_run("lbmpm_rk3d_morphology", load, c->morph, (unsigned)c->nzl, (unsigned)c->nx, (unsigned)c->ny, cut, above, out, c->stream);
 }
 
 // What the storage moves, by its own count (bench.py's "bytes moved" beside the algorithmic 608 B): out[0] doubles stored per fluid

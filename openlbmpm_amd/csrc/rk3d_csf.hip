@@ -1012,6 +1012,7 @@ __global__ __launch_bounds__(256) void csf3d_import(CsfDev p, double *f, const d
 #include "rk3d_integrals.h"
 #include "rk3d_tracer_integrals.h"
 #include "rk3d_clusters.h"
+#include "rk3d_morphology.h"
 
 // what LBMPM_RK3DCSF_REC_RHO_R .. _REC_PHI hand out, from the populations: cell_state<FIRST, true>, the velocity with half the force and
 // the phase field in the arithmetic of csf3d_observe<FIRST, true>; own planes only (plane 0 is lattice plane p.glo)
@@ -1081,6 +1082,7 @@ struct lbmpm_rk3dcsf {
     double *integ = nullptr;       // lbmpm_rk3dcsf_integrals: chunk partials + the table (rk3d_integrals.h), allocated by the first call
     double *trinteg = nullptr;     // lbmpm_rk3dcsf_tracer_integrals: the same for the tracers' tables (rk3d_tracer_integrals.h)
     ClState cl;                    // lbmpm_rk3dcsf_clusters: classes, labels, rows (rk3d_clusters.h), allocated by the first call
+    uint8_t *morph = nullptr;      // lbmpm_rk3dcsf_morphology: classes [own planes + 1][ny][nx] (rk3d_morphology.h), allocated by the first call
     double *obs = nullptr;         // staging of the observe kernel: rho [2][N], u [3][N], phi [N] (the populations [2][N][19] come and go with the call)
     lbmpm::EventPool pool;
     size_t timed_steps = 0;
@@ -1844,6 +1846,42 @@ extern "C" int lbmpm_rk3dcsf_clusters_faces(lbmpm_rk3dcsf *c, uint32_t *labels, 
 {
     LBMPM_REQUIRE(c && labels && classes, "lbmpm_rk3dcsf_clusters_faces: null argument");
     return clusters_faces("lbmpm_rk3dcsf_clusters_faces", c->cl, c->steps, c->cfg.device, c->stream, labels, classes);
+}
+
+// Phase morphology of the recorded state (rk3d_morphology.h; the definition: include/lbmpm.h), classified from the populations in registers.
+// The checks and the class array of both entry points; then the context's device is the current one.  Valid wherever
+// lbmpm_rk3dcsf_integrals is, slabs included.
+static int morphology_ready(const char *who, lbmpm_rk3dcsf *c, const lbmpm_morphology_config *cfg, double *cut, unsigned *planes)
+{
+    if (!c->have_state) { set_error("%s before set_macro / set_pdf", who); return LBMPM_ERR_STATE; }
+    LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
+    *planes = (unsigned)(c->nz - c->cfg.ghost_lo - c->cfg.ghost_hi);
+    { const int rc = morphology_configure(who, cfg, (unsigned long long)(*planes + 1u) * c->nx * c->ny, cut); if (rc) return rc; }
+    return morphology_classes(c->mem, &c->morph, *planes, (unsigned)c->nx * (unsigned)c->ny, nullptr);
+}
+
+extern "C" int lbmpm_rk3dcsf_morphology_face(lbmpm_rk3dcsf *c, const lbmpm_morphology_config *cfg, uint8_t *classes)
+{
+    LBMPM_REQUIRE(c && classes, "lbmpm_rk3dcsf_morphology_face: null argument");
+    double cut = 0.;
+    unsigned planes = 0;
+    { const int rc = morphology_ready("lbmpm_rk3dcsf_morphology_face", c, cfg, &cut, &planes); if (rc) return rc; }
+    const CsfDev p = make_dev(c);
+    const unsigned plane_cells = (unsigned)c->nx * (unsigned)c->ny;
+    if (c->first) return morphology_face(CsfIntLoader<true>{p}, c->morph, plane_cells, cut, classes, c->stream);
+    return morphology_face(CsfIntLoader<false>{p}, c->morph, plane_cells, cut, classes, c->stream);
+}
+
+extern "C" int lbmpm_rk3dcsf_morphology(lbmpm_rk3dcsf *c, const lbmpm_morphology_config *cfg, const uint8_t *above, double *out)
+{
+    LBMPM_REQUIRE(c && out, "lbmpm_rk3dcsf_morphology: null argument");
+    double cut = 0.;
+    unsigned planes = 0;
+    { const int rc = morphology_ready("lbmpm_rk3dcsf_morphology", c, cfg, &cut, &planes); if (rc) return rc; }
+    const CsfDev p = make_dev(c);
+    const unsigned nx = (unsigned)c->nx, ny = (unsigned)c->ny;
+    if (c->first) return morphology_run("lbmpm_rk3dcsf_morphology", CsfIntLoader<true>{p}, c->morph, planes, nx, ny, cut, above, out, c->stream);
+    return morphology_run("lbmpm_rk3dcsf_morphology", CsfIntLoader<false>{p}, c->morph, planes, nx, ny, cut, above, out, c->stream);
 }
 
 extern "C" int64_t lbmpm_rk3dcsf_num_fluid_nodes(const lbmpm_rk3dcsf *c) { return c ? c->nfluid : 0; }

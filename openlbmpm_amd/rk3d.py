@@ -224,6 +224,24 @@ class RK3DSlab(SlabTransportCalls):
         got = self.clusters_part(phi_cut, connectivity, labels, faces=False)
         return Clusters(got["table"], self.nx, self.ny, self.nz, got.get("labels"))
 
+    def morphology_face(self, phi_cut=0.0):
+        """[ny][nx] uint8: the classes of the slab's lowest plane -- what the slab below passes to morphology_part as `above`"""
+        from .morphology import face
+        return face(self._L, "rk3d", self._h, self.ny, self.nx, phi_cut)
+
+    def morphology_part(self, phi_cut=0.0, above=None):
+        """[nzl][28]: the morphology table of the slab's own planes; above: the morphology_face of the slab over it (None: the highest
+        plane anchors nothing that reaches upwards)"""
+        from .morphology import table
+        return table(self._L, "rk3d", self._h, self.nzl, self.ny, self.nx, phi_cut, above)
+
+    def morphology(self, phi_cut=0.0):
+        """morphology.Morphology of the slab's own planes: cells, class pairs, squares and cubes of the fields of the last
+        phase_field(diagnostics=True), counted on the device (lbmpm_rk3d_morphology); LbmpmError (LBMPM_ERR_STATE) when a step has been
+        taken since"""
+        from .morphology import Morphology
+        return Morphology(self.morphology_part(phi_cut), self.nx, self.ny)
+
     @property
     def num_fluid_nodes(self):
         return int(self._L.lbmpm_rk3d_num_fluid_nodes(self._h))
@@ -354,6 +372,14 @@ class RK3DCluster:
         s0 = self.slabs[0]
         parts = fresh(lambda: [s.clusters_part(phi_cut, connectivity, labels) for s in self.slabs], self.observe)
         return merged(parts, s0.nx, s0.ny, s0.nz, connectivity, labels)
+
+    def morphology(self, phi_cut=0.0):
+        """morphology.Morphology of the whole lattice: every slab joins the lowest plane of the slab over it on its device (bit-equal to
+        the undivided lattice's); observe() first when the diagnostics are stale"""
+        from .integrals import fresh
+        from .morphology import Morphology, stacked
+        s0 = self.slabs[0]
+        return Morphology(fresh(lambda: stacked(self.slabs, phi_cut), self.observe), s0.nx, s0.ny)
 
     def close(self):
         for s in self.slabs:
@@ -553,6 +579,17 @@ class RK3DDistributed:
         from .integrals import fresh
         part = fresh(lambda: self.slab.clusters_part(phi_cut, connectivity, labels), self.observe)
         return gather_merged(part, self.rank, self.world, self.group, self.slab.nx, self.slab.ny, self.slab.nz, connectivity, labels)
+
+    def morphology(self, phi_cut=0.0):
+        """collective: rank 0 returns the morphology.Morphology of the whole lattice (every rank takes the lowest class plane of the rank
+        above it, one all_gather of [ny][nx] bytes, and joins on its device; the tables through gather()), the others None; observe()
+        first when the diagnostics are stale"""
+        from .integrals import fresh
+        from .morphology import Morphology, face_from_above
+        mine = fresh(lambda: self.slab.morphology_face(phi_cut), self.observe)
+        above = face_from_above(mine, self.rank, self.world, self.group, self.device)
+        t = self.gather(self.slab.morphology_part(phi_cut, above))
+        return None if t is None else Morphology(t, self.slab.nx, self.slab.ny)
 
     def sync(self, deadline_s=None):
         """Wait for this rank's work.  With an in-library transport the wait is the library's watchdog (lbmpm_rk3d_sync_deadline,

@@ -257,6 +257,24 @@ class RK3DCSFSolver(SlabTransportCalls):
         got = self.clusters_part(phi_cut, connectivity, labels, faces=False)
         return Clusters(got["table"], self.nx, self.ny, self.global_nz, got.get("labels"))
 
+    def morphology_face(self, phi_cut=0.0):
+        """[ny][nx] uint8: the classes of the lowest own plane -- what the slab below passes to morphology_part as `above`"""
+        from .morphology import face
+        return face(self._L, "rk3dcsf", self._h, self.ny, self.nx, phi_cut)
+
+    def morphology_part(self, phi_cut=0.0, above=None):
+        """[own planes][28]: the morphology table of this lattice or slab alone; above: the morphology_face of the slab over it (None:
+        the highest own plane anchors nothing that reaches upwards)"""
+        from .morphology import table
+        return table(self._L, "rk3dcsf", self._h, self.nz - self.ghost[0] - self.ghost[1], self.ny, self.nx, phi_cut, above)
+
+    def morphology(self, phi_cut=0.0):
+        """morphology.Morphology of the own planes: cells, class pairs, squares and cubes of what get("rec_phi") and get("rec_rho*") hand
+        out, classified from the populations and counted on the device (lbmpm_rk3dcsf_morphology) -- nothing staged, nothing to call
+        beforehand"""
+        from .morphology import Morphology
+        return Morphology(self.morphology_part(phi_cut), self.nx, self.ny)
+
     def tracer_integrals(self):
         """integrals.TracerIntegrals of the own planes, [planes][nT][9]: cells, mass, the first moments g(+a) - g(-a) per axis, sum C^2,
         the extrema of C and the non-finite count per plane and tracer, over the populations get_tracer_pdf hands out -- reduced on the
@@ -413,6 +431,12 @@ class RK3DCSFCluster:
         """clusters.Clusters of the whole lattice: the slabs' tables joined through their face planes (equal to the undivided lattice's)"""
         from .clusters import merged
         return merged([s.clusters_part(phi_cut, connectivity, labels) for s in self.slabs], self.nx, self.ny, self.nz, connectivity, labels)
+
+    def morphology(self, phi_cut=0.0):
+        """morphology.Morphology of the whole lattice: every slab joins the lowest own plane of the slab over it on its device, the top
+        slab nothing -- z does not wrap here, whatever the ring of the flow does (bit-equal to the undivided lattice's)"""
+        from .morphology import Morphology, stacked
+        return Morphology(stacked(self.slabs, phi_cut), self.nx, self.ny)
 
     def tracer_integrals(self):
         """the slabs' tracer tables in plane order: bit-equal to the undivided lattice's"""
@@ -634,6 +658,14 @@ class RK3DCSFDistributed:
         from .clusters import gather_merged
         part = self.slab.clusters_part(phi_cut, connectivity, labels)
         return gather_merged(part, self.rank, self.world, None, self.shape[2], self.shape[1], self.nz, connectivity, labels)
+
+    def morphology(self, phi_cut=0.0):
+        """collective: rank 0 returns the morphology.Morphology of the whole lattice (every rank takes the lowest class plane of the rank
+        above it, one all_gather of [ny][nx] bytes, and joins on its device; the tables through gather()), the others None"""
+        from .morphology import Morphology, face_from_above
+        above = face_from_above(self.slab.morphology_face(phi_cut), self.rank, self.world, None, self._dev.index)
+        t = self.gather(self.slab.morphology_part(phi_cut, above))
+        return None if t is None else Morphology(t, self.shape[2], self.shape[1])
 
     def tracer_integrals(self):
         """collective: rank 0 returns the integrals.TracerIntegrals of the whole lattice ([nz][nT][9]: axis 0 is z, so gather() stacks the
