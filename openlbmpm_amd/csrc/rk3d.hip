@@ -1256,7 +1256,7 @@ struct lbmpm_rk3d {
     bool interior_pending = false;
     int64_t steps = 0;
     lbmpm::DeviceBlocks mem;         // every device block the context keeps (lbmpm_rk3d_device_bytes); the transport's landing areas are its own
-    lbmpm::EventPool slab_pool;      // lbmpm_rk3d_step_slab(timed): 4 event pairs per step {step, interior, exchange chain, boundary}
+    lbmpm::EventPool slab_pool;      // lbmpm_rk3d_step_slab(timed): the event pairs of every timed step (enum SlabEvent)
     int64_t slab_timed_steps = 0;
     // steady-state watchdog (lbmpm_rk3d_sync_deadline): a word in pinned host memory that the exchange chain of every slab step writes
     // its step number into -- the host's evidence of progress -- and a private stream for the watchdog's own copies
@@ -1713,14 +1713,24 @@ static int64_t face_bytes(const lbmpm_rk3d *c, int zl)
     return c->compact ? (int64_t)((c->h_pstart[zl + 1] - c->h_pstart[zl]) * 10 * sizeof(double)) : (int64_t)(10 * c->plane2 * sizeof(double));
 }
 
+// ---- the face kernels of the q23 storage (rk3dq.h), each launched from here alone: one workgroup per row tile of a row segment and face.
+// `q` is the state whose faces move (make_dev: the current one; the slab step: the one it has just written)
+static dim3 face_grid(const lbmpm_rk3d *c) { return dim3(c->nseg, (c->ny + BY3 - 1) / BY3, 2); }
+static void face_pack(lbmpm_rk3d *c, const RK3Dev &q, hipStream_t st, int below, int above) { rk3dq_face_pack<<<face_grid(c), dim3(BX3, BY3), 0, st>>>(q, c->send_up, c->send_dn, below, above); }
+// the neighbours' face messages into the halo planes of (f, pur), then the phase field of those planes from the class sums they carry
+static void face_unpack(lbmpm_rk3d *c, const RK3Dev &q, double *f, uint32_t *pur, const double *from_below, const double *from_above, int below, int above, hipStream_t st)
+{
+    rk3dq_face_unpack<<<face_grid(c), dim3(BX3, BY3), 0, st>>>(q, f, pur, from_below, from_above, below, above);
+    rk3dq_halo_phi<<<face_grid(c), dim3(BX3, BY3), 0, st>>>(q, from_below, from_above, below, above);
+}
+
 extern "C" int lbmpm_rk3d_pack_halo(lbmpm_rk3d *c)
 {
     LBMPM_REQUIRE(c, "null context");
     if (c->q23) {       // the whole face message of the current state (rk3dq.h): populations, records, class sums, row flags
         const int below = c->cfg.z_offset > 0, above = c->cfg.z_offset + c->cfg.nz_local < c->cfg.nz_global;
         if (!below && !above) return LBMPM_OK;
-        RK3Dev q = make_dev(c);
-        rk3dq_face_pack<<<dim3(c->nseg, (c->ny + BY3 - 1) / BY3, 2), dim3(BX3, BY3), 0, c->stream>>>(q, c->send_up, c->send_dn, below, above);
+        face_pack(c, make_dev(c), c->stream, below, above);
         LBMPM_HIP_TRY(hipGetLastError());
         return LBMPM_OK;
     }
@@ -1738,10 +1748,7 @@ extern "C" int lbmpm_rk3d_unpack_halo(lbmpm_rk3d *c, int have_below, int have_ab
     LBMPM_REQUIRE(c, "null context");
     if (c->q23) {
         if (!have_below && !have_above) return LBMPM_OK;
-        RK3Dev q = make_dev(c);
-        const dim3 grid(c->nseg, (c->ny + BY3 - 1) / BY3, 2), block(BX3, BY3);
-        rk3dq_face_unpack<<<grid, block, 0, c->stream>>>(q, c->fA, c->purA, c->recv_below, c->recv_above, have_below, have_above);
-        rk3dq_halo_phi<<<grid, block, 0, c->stream>>>(q, c->recv_below, c->recv_above, have_below, have_above);
+        face_unpack(c, make_dev(c), c->fA, c->purA, c->recv_below, c->recv_above, have_below, have_above, c->stream);
         LBMPM_HIP_TRY(hipGetLastError());
         c->halo_valid = true;
         return LBMPM_OK;
@@ -1920,16 +1927,38 @@ extern "C" int lbmpm_rk3d_collide(lbmpm_rk3d *c)
     return LBMPM_OK;
 }
 
+// the second stream and its two events, made by whoever needs them first.  may_mask: the q23 slab step (a development build can keep the interior off some CUs)
+static int second_stream(lbmpm_rk3d *c, bool may_mask)
+{
+    if (c->aux) return LBMPM_OK;
+#ifdef LBMPM_DEV
+    // rk3dq_fused holds a CU's whole register file and most of its LDS: while the interior launch runs, the kernels of the exchange (pack, RCCL's send /
+    // recv, unpack) find room only where one of its workgroups retires, so on one GPU the pack .. unpack chain ends with the interior launch
+    // (tools/slab_rank_cost.py).  LBMPM_RK3D_COMM_CUS = k (default 0 = off) runs the interior on a stream whose CU mask leaves k CUs alone.  Measured at
+    // 512^3 / 8 ranks: any mask slows the interior launch from 1.3 to 1.8 ms (k = 8, 16, 32 alike), the chain drops to 0.55 ms only at k = 32: a net loss, hence off.
+    int reserve = 0, ncu = 0;
+    if (const char *e = may_mask ? getenv("LBMPM_RK3D_COMM_CUS") : nullptr) reserve = atoi(e);
+    (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c->cfg.device);
+    if (reserve > 0 && ncu >= 64 && reserve < ncu / 2) {
+        std::vector<uint32_t> mask((size_t)(ncu + 31) / 32, 0u);
+        // Bit i of the mask is CU (i / 8) of XCD (i % 8) (measured: leaving out every 32nd / 16th bit slowed the interior by 25 % / 100 %,
+        // i.e. took 8 / 16 CUs from ONE of the eight XCDs, whose share of the workgroups stays 1/8).  The highest `reserve` bits are
+        // reserve / 8 CUs of every XCD: the exchange's workgroups, dealt round-robin to the XCDs like all others, find room in each.
+        for (int i = 0; i < ncu - reserve; ++i) mask[(size_t)i / 32] |= 1u << (i % 32);
+        if (hipExtStreamCreateWithCUMask(&c->aux, (uint32_t)mask.size(), mask.data()) != hipSuccess) { (void)hipGetLastError(); c->aux = nullptr; }
+    }
+#endif
+    if (!c->aux) LBMPM_HIP_TRY(hipStreamCreateWithFlags(&c->aux, hipStreamNonBlocking));
+    LBMPM_HIP_TRY(hipEventCreateWithFlags(&c->ev_dep, hipEventDisableTiming));
+    LBMPM_HIP_TRY(hipEventCreateWithFlags(&c->ev_done, hipEventDisableTiming));
+    return LBMPM_OK;
+}
+
 // Overlap of the halo exchange with the bulk of the step (fused variant): the planes at least
 // `boundary` planes away from both faces of the slab need neither the neighbours' populations nor
 // their phase field, so they are collided on a second stream while the caller packs, exchanges
 // and unpacks on the context's stream; lbmpm_rk3d_collide_boundary then does the planes next to
 // the faces and joins the two streams.
-static int collide_interior_ev(lbmpm_rk3d *c, hipEvent_t e0, hipEvent_t e1);
-static int collide_boundary_ev(lbmpm_rk3d *c, hipEvent_t e0, hipEvent_t e1);
-extern "C" int lbmpm_rk3d_collide_interior(lbmpm_rk3d *c) { return collide_interior_ev(c, nullptr, nullptr); }
-extern "C" int lbmpm_rk3d_collide_boundary(lbmpm_rk3d *c) { return collide_boundary_ev(c, nullptr, nullptr); }
-
 static int collide_interior_ev(lbmpm_rk3d *c, hipEvent_t e0, hipEvent_t e1)
 {
     LBMPM_REQUIRE(c, "null context");
@@ -1937,11 +1966,7 @@ static int collide_interior_ev(lbmpm_rk3d *c, hipEvent_t e0, hipEvent_t e1)
     const int cb = c->boundary;
     if (c->variant == 1 || c->nzl < 2 * cb + 1) return LBMPM_OK;       // nothing to overlap: collide_boundary does the whole slab
     LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
-    if (!c->aux) {
-        LBMPM_HIP_TRY(hipStreamCreateWithFlags(&c->aux, hipStreamNonBlocking));
-        LBMPM_HIP_TRY(hipEventCreateWithFlags(&c->ev_dep, hipEventDisableTiming));
-        LBMPM_HIP_TRY(hipEventCreateWithFlags(&c->ev_done, hipEventDisableTiming));
-    }
+    if (const int rc = second_stream(c, false)) return rc;
     LBMPM_HIP_TRY(hipEventRecord(c->ev_dep, c->stream));                // everything issued so far (previous step) first
     LBMPM_HIP_TRY(hipStreamWaitEvent(c->aux, c->ev_dep, 0));
     RK3Dev p = make_dev(c);
@@ -1975,6 +2000,12 @@ static int collide_boundary_ev(lbmpm_rk3d *c, hipEvent_t e0, hipEvent_t e1)
     finish_step(c);
     return LBMPM_OK;
 }
+
+extern "C" int lbmpm_rk3d_collide_interior(lbmpm_rk3d *c) { return collide_interior_ev(c, nullptr, nullptr); }
+extern "C" int lbmpm_rk3d_collide_boundary(lbmpm_rk3d *c) { return collide_boundary_ev(c, nullptr, nullptr); }
+
+// nothing pending on either stream, and the halo planes no longer taken for the current state's (a failed slab step; a transport that goes away)
+static void quiesce(lbmpm_rk3d *c) { if (c->aux) (void)hipStreamSynchronize(c->aux); (void)hipStreamSynchronize(c->stream); c->halo_valid = false; }
 
 // ---- transports of the slab exchange inside the library (include/lbmpm.h; rk3d_transport.h)
 static int tx_shape(lbmpm_rk3d *c)
@@ -2047,10 +2078,8 @@ extern "C" int lbmpm_rk3d_transport_disconnect(lbmpm_rk3d *c)
 {
     LBMPM_REQUIRE(c, "null context");
     LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
-    (void)hipStreamSynchronize(c->stream);
-    if (c->aux) (void)hipStreamSynchronize(c->aux);
+    quiesce(c);
     c->tx.disconnect();
-    c->halo_valid = false;
     return LBMPM_OK;
 }
 
@@ -2135,18 +2164,43 @@ extern "C" int lbmpm_transport_selftest(int kind, int device, int64_t bytes, con
     return done(LBMPM_OK);
 }
 
-// the face message of the state (f, pur) over the connected transport, enqueued on the context's stream: pack is the caller's
-static int tx_exchange_unpack(lbmpm_rk3d *c, const RK3Dev &q, double *f, uint32_t *pur, bool unpack)
+// ---- the slab step (lbmpm_rk3d_step_slab): its arguments, the pieces its schedules share, then one function per schedule
+struct SlabStep {
+    int64_t nsteps, tsteps;                 // steps to take; the first tsteps of them are timed
+    int has_below, has_above;
+    lbmpm_rk3d_exchange_fn exchange; void *user;        // the caller's transport (include/lbmpm.h) and its argument, or
+    bool own_tx;                            // the transport connected to the context
+};
+
+// The events of a timed step as they lie in slab_pool: begin and end of the whole step, of the interior launch, of the exchange chain (pack ..
+// unpack on the context's stream, transfers included) and of the boundary launch.  timed_events: those of step k, null when it is not timed.
+enum SlabEvent { EV_STEP, EV_STEP_END, EV_INTERIOR, EV_INTERIOR_END, EV_CHAIN, EV_CHAIN_END, EV_BOUNDARY, EV_BOUNDARY_END, EV_PER_STEP };
+static const hipEvent_t *timed_events(const lbmpm_rk3d *c, int64_t k, int64_t tsteps)
 {
-    const double *fb = nullptr, *fa = nullptr;
-    const int rc = c->tx.exchange(c->stream, c->send_up, c->send_dn, &fb, &fa);
-    if (rc != LBMPM_OK) return rc;
-    if (unpack) {
-        const dim3 grid(c->nseg, (c->ny + BY3 - 1) / BY3, 2), block(BX3, BY3);
-        rk3dq_face_unpack<<<grid, block, 0, c->stream>>>(q, f, pur, fb, fa, c->tx.has_below, c->tx.has_above);
-        rk3dq_halo_phi<<<grid, block, 0, c->stream>>>(q, fb, fa, c->tx.has_below, c->tx.has_above);
-        LBMPM_HIP_TRY(hipGetLastError());
-    }
+    static const hipEvent_t none[EV_PER_STEP] = {};
+    return k < tsteps ? &c->slab_pool.ev[(size_t)(EV_PER_STEP * k)] : none;
+}
+
+// One exchange, enqueued on the context's stream.  own_tx (the q23 storage's one face message): the library's transport -- copies / ncclSend +
+// ncclRecv and the waits for the neighbours' messages -- says where the messages land; else the caller's callback fills the receive buffers.
+static int exchange_faces(lbmpm_rk3d *c, const SlabStep &a, int what, const char *during, const double **from_below, const double **from_above)
+{
+    *from_below = c->recv_below; *from_above = c->recv_above;
+    if (a.own_tx) return c->tx.exchange(c->stream, c->send_up, c->send_dn, from_below, from_above);
+    if (a.exchange(a.user, what) != 0) { set_error("lbmpm_rk3d_step_slab: the exchange callback failed%s", during); return LBMPM_ERR_STATE; }
+    return LBMPM_OK;
+}
+
+// the halo planes of the CURRENT state of the q23 storage: pack -> exchange -> unpack on the context's stream (lbmpm_rk3d_halo_exchange; the
+// slab step whenever they are not valid: after set_density, a state set from outside, a failed step)
+static int prime_halo(lbmpm_rk3d *c, const SlabStep &a)
+{
+    const double *from_below, *from_above;
+    if (const int rc = lbmpm_rk3d_pack_halo(c)) return rc;
+    if (const int rc = exchange_faces(c, a, 0, " (priming the halo planes)", &from_below, &from_above)) return rc;
+    face_unpack(c, make_dev(c), c->fA, c->purA, from_below, from_above, a.has_below, a.has_above, c->stream);
+    LBMPM_HIP_TRY(hipGetLastError());
+    c->halo_valid = true;
     return LBMPM_OK;
 }
 
@@ -2155,241 +2209,186 @@ extern "C" int lbmpm_rk3d_halo_exchange(lbmpm_rk3d *c)
     LBMPM_REQUIRE(c && c->tx.connected, "lbmpm_rk3d_halo_exchange: no transport connected (lbmpm_rk3d_ipc_connect / lbmpm_rk3d_rccl_connect)");
     LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
     if (!c->tx.has_below && !c->tx.has_above) return LBMPM_OK;
-    int rc = lbmpm_rk3d_pack_halo(c);
-    if (rc == LBMPM_OK) rc = tx_exchange_unpack(c, make_dev(c), c->fA, c->purA, true);
-    if (rc == LBMPM_OK) c->halo_valid = true;
-    return rc;
+    return prime_halo(c, SlabStep{0, 0, c->tx.has_below, c->tx.has_above, nullptr, nullptr, true});
 }
 
-// The whole time step of a slab behind ONE call: interior planes on the second stream, then on the context's
-// stream pack -> exchange(populations) -> unpack -> phase field of the face planes -> exchange(phase field) ->
-// boundary planes -> join.  `exchange(user, what)` (what = 0 populations, 1 phase field) is the caller's transport:
-// it must enqueue the transfer of the LBMPM_RK3D_BUF_* send buffers into the neighbours' receive buffers on the
-// context's stream (torch.distributed P2P under torch.cuda.stream(...) does exactly that; so would ncclSend /
-// ncclRecv) and return 0.  The library never blocks the host here.
-extern "C" int lbmpm_rk3d_step_slab(lbmpm_rk3d *c, int64_t nsteps, int has_below, int has_above, lbmpm_rk3d_exchange_fn exchange,
-                                    void *user, int timed)
+static RK3Dev written_state(const lbmpm_rk3d *c, RK3Dev p) { p.fin = c->fB; p.pur_in = c->purB; p.first = 0; return p; }      // what the kernels get of the state the step writes
+
+// The planes of a q23 slab in two launches.  Boundary: the ranges that feed a face message, in one launch; a face without a neighbour (the lattice's
+// inlet / outlet end) has no message to hurry for: its planes march with the interior (one range, one prologue and two fill steps less on the end ranks)
+static void launch_q23_boundary(lbmpm_rk3d *c, const RK3Dev &p, hipStream_t st, const SlabStep &a)
+{
+    const int cb = c->boundary;
+    if (a.has_below && a.has_above) launch_q23(c, p, st, 1, cb, c->nzl - cb + 1, c->nzl);
+    else if (a.has_below) launch_q23(c, p, st, 1, cb, 1, 0);
+    else launch_q23(c, p, st, c->nzl - cb + 1, c->nzl, 1, 0);
+}
+static void launch_q23_interior(lbmpm_rk3d *c, const RK3Dev &p, hipStream_t st, const SlabStep &a) { launch_step_range(c, p, st, a.has_below ? c->boundary + 1 : 1, a.has_above ? c->nzl - c->boundary : c->nzl); }
+
+// q23 storage with neighbours: ONE exchange per step, software-pipelined.  The halo planes of the current state are valid on entry (primed here after
+// set_density).  Step: boundary planes first -> face message of the NEW state packed, exchanged and unpacked while the interior planes run on the second
+// stream -> join.  The next step's boundary planes find their halo ready; the transfer hides behind the interior planes of THIS step.  Before the first:
+static int slab_q23_prepare(lbmpm_rk3d *c, const SlabStep &a)
+{
+    LBMPM_HIP_TRY(c->tx.beat_ready());
+    const int rc = c->halo_valid ? LBMPM_OK : prime_halo(c, a);
+    return rc != LBMPM_OK ? rc : second_stream(c, true);
+}
+
+// Schedule "lattice in one stream" (the default): boundary launch -> pack -> interior launch back to back on the SECOND stream, the chain
+// wait(pack) -> exchange -> unpack -> halo phase field  on the context's stream beside the interior launch; the next step's boundary launch
+// waits for the chain -- which has long finished.  No cross-stream event sits between two lattice launches.
+static int slab_steps_one_stream(lbmpm_rk3d *c, const SlabStep &a)
+{
+    LBMPM_HIP_TRY(hipEventRecord(c->ev_dep, c->stream));                // everything enqueued so far (the primed halo planes included)
+    for (int64_t k = 0; k < a.nsteps; ++k) {
+        const hipEvent_t *ev = timed_events(c, k, a.tsteps);
+        const RK3Dev p = make_dev(c), q = written_state(c, p);
+        if (ev[EV_STEP]) LBMPM_HIP_TRY(hipEventRecord(ev[EV_STEP], c->aux));    // (before the wait: a chain that ended late counts into this step)
+        LBMPM_HIP_TRY(hipStreamWaitEvent(c->aux, c->ev_dep, 0));        // the previous step's chain: its halo planes
+        if (ev[EV_BOUNDARY]) LBMPM_HIP_TRY(hipEventRecord(ev[EV_BOUNDARY], c->aux));
+        launch_q23_boundary(c, p, c->aux, a);
+        if (ev[EV_BOUNDARY_END]) LBMPM_HIP_TRY(hipEventRecord(ev[EV_BOUNDARY_END], c->aux));
+        face_pack(c, q, c->aux, a.has_below, a.has_above);
+        LBMPM_HIP_TRY(hipEventRecord(c->ev_done, c->aux));              // (here: "the face message is packed")
+        LBMPM_HIP_TRY(hipGetLastError());
+        if (ev[EV_INTERIOR]) LBMPM_HIP_TRY(hipEventRecord(ev[EV_INTERIOR], c->aux));
+        launch_q23_interior(c, p, c->aux, a);                           // straight behind the pack in the lattice stream
+        if (ev[EV_INTERIOR_END]) LBMPM_HIP_TRY(hipEventRecord(ev[EV_INTERIOR_END], c->aux));
+        // the chain.  (Enqueued BEHIND the interior launch: its dispatch is then in the lattice stream's queue when the pack retires, and the
+        // interior's workgroups take the CUs first -- with the chain first, a rank's copy / unpack kernels sometimes won that race and the
+        // interior started 0.05 ms late (one rank in eight on one GPU).  A copy engine needs no CU; RCCL keeps the split schedule.)
+        LBMPM_HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_done, 0));
+        if (ev[EV_CHAIN]) LBMPM_HIP_TRY(hipEventRecord(ev[EV_CHAIN], c->stream));
+        const double *from_below, *from_above;
+        if (const int rc = exchange_faces(c, a, 0, "", &from_below, &from_above)) return rc;
+        face_unpack(c, q, c->fB, c->purB, from_below, from_above, a.has_below, a.has_above, c->stream);
+        c->tx.beat(c->stream, (unsigned long long)(c->steps + 1));      // "the exchange of this step is through"
+        if (ev[EV_CHAIN_END]) LBMPM_HIP_TRY(hipEventRecord(ev[EV_CHAIN_END], c->stream));
+        LBMPM_HIP_TRY(hipEventRecord(c->ev_dep, c->stream));
+        LBMPM_HIP_TRY(hipGetLastError());
+        finish_step(c);
+        c->halo_valid = true;
+        if (ev[EV_STEP_END]) LBMPM_HIP_TRY(hipEventRecord(ev[EV_STEP_END], c->aux));
+    }
+    LBMPM_HIP_TRY(hipEventRecord(c->ev_done, c->aux));                  // join: whoever uses the context's stream next finds the lattice launches done
+    LBMPM_HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_done, 0));
+    return LBMPM_OK;
+}
+
+// The split schedule (rounds 3 - 4): boundary launch + pack on the context's stream, the interior behind an event on the second, the step ends with
+// the context's stream waiting for it.  It pays two such waits per step on the critical path (~ 10 - 15 us each) but enqueues the exchange ahead of the
+// interior launch: it stays the choice for the RCCL transport, whose send / recv kernels need CUs that the interior launch would otherwise take first.
+static int slab_steps_split(lbmpm_rk3d *c, const SlabStep &a)
+{
+    const bool has_interior = c->nzl >= 2 * c->boundary + 1;
+#ifdef LBMPM_DEV
+    const int skip = c->dbg;        // timing knock-outs (LBMPM_RK3D_DBG: 1 no pack, 2 no exchange, 4 no unpack / halo phase field)
+#else
+    constexpr int skip = 0;         // (the knock-outs exist in development builds only)
+#endif
+    for (int64_t k = 0; k < a.nsteps; ++k) {
+        const hipEvent_t *ev = timed_events(c, k, a.tsteps);
+        if (ev[EV_STEP]) LBMPM_HIP_TRY(hipEventRecord(ev[EV_STEP], c->stream));
+        const RK3Dev p = make_dev(c), q = written_state(c, p);
+        LBMPM_HIP_TRY(hipEventRecord(c->ev_dep, c->stream));            // the previous step, its unpack included
+        if (ev[EV_BOUNDARY]) LBMPM_HIP_TRY(hipEventRecord(ev[EV_BOUNDARY], c->stream));
+        if (has_interior) launch_q23_boundary(c, p, c->stream, a);
+        else launch_step_range(c, p, c->stream, 1, c->nzl);             // (a slab too thin for interior planes: all of it, here)
+        if (ev[EV_BOUNDARY_END]) LBMPM_HIP_TRY(hipEventRecord(ev[EV_BOUNDARY_END], c->stream));
+        LBMPM_HIP_TRY(hipGetLastError());
+        if (ev[EV_CHAIN]) LBMPM_HIP_TRY(hipEventRecord(ev[EV_CHAIN], c->stream));
+        if (!(skip & 1)) face_pack(c, q, c->stream, a.has_below, a.has_above);
+        if (has_interior) {
+            // Order (per-workgroup time stamps, 512^3 on 8 ranks, tools/dev/k3trace_slab.py): rk3dq_fused fills every CU, so whatever is launched
+            // beside a running interior launch trickles through where its workgroups retire and slows them (7.5 instead of 6.3 us per march step,
+            // second-round workgroups start late).  Hence: boundary launch -> pack -> THEN the interior launch, enqueued at the same moment as the
+            // exchange: the transport's few workgroups (RCCL send / recv, or copies) are placed first on an empty GPU, the interior's take the rest.
+            LBMPM_HIP_TRY(hipEventRecord(c->ev_dep, c->stream));
+            LBMPM_HIP_TRY(hipStreamWaitEvent(c->aux, c->ev_dep, 0));
+        }
+        const double *from_below = c->recv_below, *from_above = c->recv_above;
+        if (const int rc = (skip & 2) ? LBMPM_OK : exchange_faces(c, a, 0, "", &from_below, &from_above)) return rc;
+        if (has_interior) {
+            hipStream_t ist = (skip & 8) ? c->stream : c->aux;          // (knock-out 8: the interior on the context's own stream)
+            if (ev[EV_INTERIOR]) LBMPM_HIP_TRY(hipEventRecord(ev[EV_INTERIOR], ist));
+            launch_q23_interior(c, p, ist, a);
+            if (ev[EV_INTERIOR_END]) LBMPM_HIP_TRY(hipEventRecord(ev[EV_INTERIOR_END], ist));
+            LBMPM_HIP_TRY(hipEventRecord(c->ev_done, ist));
+        }
+        if (!(skip & 4)) {
+            face_unpack(c, q, c->fB, c->purB, from_below, from_above, a.has_below, a.has_above, c->stream);
+            c->tx.beat(c->stream, (unsigned long long)(c->steps + 1));
+        }
+        LBMPM_HIP_TRY(hipGetLastError());
+        if (ev[EV_CHAIN_END]) LBMPM_HIP_TRY(hipEventRecord(ev[EV_CHAIN_END], c->stream));
+        if (has_interior) LBMPM_HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_done, 0));
+        finish_step(c);
+        c->halo_valid = !(skip & 6);        // the face message of the state just written has been exchanged and unpacked above
+        if (ev[EV_STEP_END]) LBMPM_HIP_TRY(hipEventRecord(ev[EV_STEP_END], c->stream));
+    }
+    return LBMPM_OK;
+}
+
+// The dense and 38-value storages and variant 1 (and any slab without neighbours): interior planes on the second stream, then on the
+// context's stream pack -> exchange(populations) -> unpack -> phase field of the face planes -> exchange(phase field) -> boundary planes -> join
+static int slab_steps_two_exchange(lbmpm_rk3d *c, const SlabStep &a)
+{
+    const bool nb = a.has_below || a.has_above;
+    // a failed exchange must not leave the interior launch pending (the context would refuse every later call); fA / fB stay half-updated: set_density or restart
+    auto abandon = [&](int code) { if (c->interior_pending) { (void)hipStreamSynchronize(c->aux); c->interior_pending = false; } return code; };
+    for (int64_t k = 0; k < a.nsteps; ++k) {
+        const hipEvent_t *ev = timed_events(c, k, a.tsteps);
+        if (ev[EV_STEP]) LBMPM_HIP_TRY(hipEventRecord(ev[EV_STEP], c->stream));
+        const double *from_below, *from_above;      // (the receive buffers, whose readers know them)
+        int rc = nb ? collide_interior_ev(c, ev[EV_INTERIOR], ev[EV_INTERIOR_END]) : LBMPM_OK;
+        if (rc != LBMPM_OK) return rc;
+        if (ev[EV_CHAIN]) LBMPM_HIP_TRY(hipEventRecord(ev[EV_CHAIN], c->stream));
+        if (nb && c->streamed) {
+            rc = lbmpm_rk3d_pack_halo(c);
+            if (rc == LBMPM_OK) rc = exchange_faces(c, a, 0, " (populations)", &from_below, &from_above);
+            if (rc == LBMPM_OK) rc = lbmpm_rk3d_unpack_halo(c, a.has_below, a.has_above);
+            if (rc != LBMPM_OK) return abandon(rc);
+        }
+        rc = lbmpm_rk3d_phase_field(c, 0);
+        if (rc == LBMPM_OK && nb) rc = exchange_faces(c, a, 1, " (phase field)", &from_below, &from_above);
+        if (rc != LBMPM_OK) return abandon(rc);
+        if (ev[EV_CHAIN_END]) LBMPM_HIP_TRY(hipEventRecord(ev[EV_CHAIN_END], c->stream));
+        if ((rc = collide_boundary_ev(c, ev[EV_BOUNDARY], ev[EV_BOUNDARY_END])) != LBMPM_OK) return rc;
+        if (ev[EV_STEP_END]) LBMPM_HIP_TRY(hipEventRecord(ev[EV_STEP_END], c->stream));
+    }
+    return LBMPM_OK;
+}
+
+// The whole time step of a slab behind ONE call, nsteps times, in the schedule that fits the storage and the transport.
+extern "C" int lbmpm_rk3d_step_slab(lbmpm_rk3d *c, int64_t nsteps, int has_below, int has_above, lbmpm_rk3d_exchange_fn exchange, void *user, int timed)
 {
     LBMPM_REQUIRE(c && nsteps >= 0, "lbmpm_rk3d_step_slab: bad argument");
-    const bool nb = has_below || has_above;
-    const bool own_tx = nb && !exchange && c->tx.connected;
+    const bool nb = has_below || has_above, own_tx = nb && !exchange && c->tx.connected;
     LBMPM_REQUIRE(!nb || exchange || own_tx, "lbmpm_rk3d_step_slab: a slab with neighbours needs an exchange callback or a connected transport");
     LBMPM_REQUIRE(!own_tx || c->q23, "the in-library transports serve the compact 23-value storage");
     LBMPM_REQUIRE((has_below != 0) == (c->cfg.z_offset > 0) && (has_above != 0) == (c->cfg.z_offset + c->cfg.nz_local < c->cfg.nz_global),
                   "lbmpm_rk3d_step_slab: has_below / has_above contradict the slab's position in the lattice");
     LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
-    const int64_t tsteps = timed ? (nsteps < 256 ? nsteps : 256) : 0;
-    if (timed) {
-        if (c->slab_pool.reserve((size_t)(4 * tsteps)) != LBMPM_OK) { set_error("hipEventCreate failed"); return LBMPM_ERR_HIP; }
-        c->slab_pool.reset();
-        c->slab_timed_steps = tsteps;
-    }
-    if (c->q23 && nb) {
-        // q23 storage: ONE exchange per step, software-pipelined.  The halo planes of the current state are valid on entry (primed below
-        // after set_density).  Step: boundary planes first (context's stream) -> face message of the NEW state packed, exchanged
-        // and unpacked (same stream) while the interior planes run on the second stream -> join.  The next step's boundary planes find
-        // their halo ready; the transfer hides behind the interior planes of THIS step.
-        LBMPM_REQUIRE(!c->interior_pending, "lbmpm_rk3d_step_slab: finish the step begun with lbmpm_rk3d_collide_interior first");
-        auto fail = [&](int code) {         // leave the context consistent: nothing pending on the second stream
-            if (c->aux) (void)hipStreamSynchronize(c->aux);
-            (void)hipStreamSynchronize(c->stream);
-            c->halo_valid = false;
-            return code;
-        };
-        // every error exit of this block goes through fail(): the lattice launches live on the second stream (advisor, round 5)
-#define SLAB_HIP_TRY(expr) do { const hipError_t e_ = (expr); if (e_ != hipSuccess) { set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); return fail(LBMPM_ERR_HIP); } } while (0)
-        SLAB_HIP_TRY(c->tx.beat_ready());
-        if (!c->halo_valid) {
-            int rc;
-            if (own_tx) rc = lbmpm_rk3d_halo_exchange(c);
-            else {
-                rc = lbmpm_rk3d_pack_halo(c);
-                if (rc == LBMPM_OK && exchange(user, 0) != 0) { set_error("lbmpm_rk3d_step_slab: the exchange callback failed (priming the halo planes)"); rc = LBMPM_ERR_STATE; }
-                if (rc == LBMPM_OK) rc = lbmpm_rk3d_unpack_halo(c, has_below, has_above);
-            }
-            if (rc != LBMPM_OK) return fail(rc);
-        }
-        if (!c->aux) {
+    const SlabStep a{nsteps, timed ? (nsteps < 256 ? nsteps : 256) : 0, has_below, has_above, exchange, user, own_tx};
+    if (timed && c->slab_pool.reserve((size_t)(EV_PER_STEP / 2 * a.tsteps)) != LBMPM_OK) { set_error("hipEventCreate failed"); return LBMPM_ERR_HIP; }
+    if (timed) c->slab_timed_steps = a.tsteps;
+    if (!c->q23 || !nb) return slab_steps_two_exchange(c, a);
+    LBMPM_REQUIRE(!c->interior_pending, "lbmpm_rk3d_step_slab: finish the step begun with lbmpm_rk3d_collide_interior first");
+    const char *sched = nullptr;
 #ifdef LBMPM_DEV
-            // rk3dq_fused holds a CU's whole register file and most of its LDS: while the interior launch runs, the kernels of the exchange
-            // (pack, RCCL's send / recv, unpack) find room only where one of its workgroups retires, so on one GPU the pack .. unpack chain
-            // ends with the interior launch (tools/slab_rank_cost.py).  LBMPM_RK3D_COMM_CUS = k (default 0 = off) runs the interior on a
-            // stream whose CU mask leaves k CUs alone.  Measured at 512^3 / 8 ranks: any mask slows the interior launch from 1.3 to 1.8 ms
-            // (k = 8, 16, 32 alike), the chain drops to 0.55 ms only at k = 32 -- a net loss, hence off.
-            int reserve = 0, ncu = 0;
-            if (const char *e = getenv("LBMPM_RK3D_COMM_CUS")) reserve = atoi(e);
-            (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c->cfg.device);
-            if (reserve > 0 && ncu >= 64 && reserve < ncu / 2) {
-                std::vector<uint32_t> mask((size_t)(ncu + 31) / 32, 0u);
-                // Bit i of the mask is CU (i / 8) of XCD (i % 8) (measured: leaving out every 32nd / 16th bit slowed the interior by 25 % / 100 %,
-                // i.e. took 8 / 16 CUs from ONE of the eight XCDs, whose share of the workgroups stays 1/8).  The highest `reserve` bits are
-                // reserve / 8 CUs of every XCD: the exchange's workgroups, dealt round-robin to the XCDs like all others, find room in each.
-                for (int i = 0; i < ncu - reserve; ++i) mask[(size_t)i / 32] |= 1u << (i % 32);
-                if (hipExtStreamCreateWithCUMask(&c->aux, (uint32_t)mask.size(), mask.data()) != hipSuccess) { (void)hipGetLastError(); c->aux = nullptr; }
-            }
+    sched = getenv("LBMPM_RK3D_SLAB_SCHEDULE");         // one | split forces either schedule
 #endif
-            if (!c->aux) SLAB_HIP_TRY(hipStreamCreateWithFlags(&c->aux, hipStreamNonBlocking));
-            SLAB_HIP_TRY(hipEventCreateWithFlags(&c->ev_dep, hipEventDisableTiming));
-            SLAB_HIP_TRY(hipEventCreateWithFlags(&c->ev_done, hipEventDisableTiming));
-        }
-        const int cb = c->boundary;
-        const bool has_interior = c->nzl >= 2 * cb + 1;
-        const dim3 fgrid(c->nseg, (c->ny + BY3 - 1) / BY3, 2), fblock(BX3, BY3);
-        // Two schedules.  "lattice in one stream" (default; LBMPM_RK3D_SLAB_SCHEDULE=split for the other): boundary launch -> pack ->
-        // interior launch back to back on the SECOND stream, the chain  wait(pack) -> exchange -> unpack -> halo phase field  on the
-        // context's stream beside the interior launch; the next step's boundary launch waits for the chain -- which has long finished.
-        // No cross-stream event sits between two lattice launches.  The split schedule (rounds 3 - 4: boundary + pack on the context's
-        // stream, the interior behind an event on the second, the step ends with the context's stream waiting for it) pays two such
-        // waits per step on the critical path (~ 10 - 15 us each) but enqueues the exchange ahead of the interior launch: it stays the
-        // choice for the RCCL transport, whose send / recv kernels need CUs that the interior launch would otherwise take first.
-#ifdef LBMPM_DEV
-        const char *sched = getenv("LBMPM_RK3D_SLAB_SCHEDULE");
-#else
-        const char *sched = nullptr;
-#endif
-        const bool one_stream = has_interior && !(sched && !strcmp(sched, "split")) && ((sched && !strcmp(sched, "one")) || !own_tx || c->tx.kind != LBMPM_TRANSPORT_RCCL);
-        if (one_stream) {
-            SLAB_HIP_TRY(hipEventRecord(c->ev_dep, c->stream));            // everything enqueued so far (the primed halo planes included)
-            for (int64_t k = 0; k < nsteps; ++k) {
-                hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-                if (k < tsteps) for (int i = 0; i < 4; ++i) c->slab_pool.take(&ev[2 * i], &ev[2 * i + 1]);
-                const RK3Dev p = make_dev(c);
-                if (ev[0]) SLAB_HIP_TRY(hipEventRecord(ev[0], c->aux));     // (before the wait: a chain that ended late counts into this step)
-                SLAB_HIP_TRY(hipStreamWaitEvent(c->aux, c->ev_dep, 0));     // the previous step's chain: its halo planes
-                if (ev[6]) SLAB_HIP_TRY(hipEventRecord(ev[6], c->aux));
-                const int zi0 = has_below ? cb + 1 : 1, zi1 = has_above ? c->nzl - cb : c->nzl;
-                if (has_below && has_above) launch_q23(c, p, c->aux, 1, cb, c->nzl - cb + 1, c->nzl);
-                else if (has_below) launch_q23(c, p, c->aux, 1, cb, 1, 0);
-                else launch_q23(c, p, c->aux, c->nzl - cb + 1, c->nzl, 1, 0);
-                if (ev[7]) SLAB_HIP_TRY(hipEventRecord(ev[7], c->aux));
-                RK3Dev q = p;                                                 // the state this step writes
-                q.fin = c->fB; q.pur_in = c->purB; q.first = 0;
-                rk3dq_face_pack<<<fgrid, fblock, 0, c->aux>>>(q, c->send_up, c->send_dn, has_below, has_above);
-                SLAB_HIP_TRY(hipEventRecord(c->ev_done, c->aux));           // (here: "the face message is packed")
-                if (hipGetLastError() != hipSuccess) { set_error("lbmpm_rk3d_step_slab: kernel launch failed"); return fail(LBMPM_ERR_HIP); }
-                // the interior planes, straight behind the pack in the lattice stream
-                if (ev[2]) SLAB_HIP_TRY(hipEventRecord(ev[2], c->aux));
-                launch_step_range(c, p, c->aux, zi0, zi1);
-                if (ev[3]) SLAB_HIP_TRY(hipEventRecord(ev[3], c->aux));
-                // the chain.  (Enqueued BEHIND the interior launch: its dispatch is then in the lattice stream's queue when the pack retires, and the
-                // interior's workgroups take the CUs first -- with the chain first, a rank's copy / unpack kernels sometimes won that race and the
-                // interior started 0.05 ms late (one rank in eight on one GPU).  A copy engine needs no CU; RCCL keeps the split schedule.)
-                SLAB_HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_done, 0));
-                if (ev[4]) SLAB_HIP_TRY(hipEventRecord(ev[4], c->stream));
-                const double *from_below = c->recv_below, *from_above = c->recv_above;
-                if (own_tx) { const int rc = c->tx.exchange(c->stream, c->send_up, c->send_dn, &from_below, &from_above); if (rc != LBMPM_OK) return fail(rc); }
-                else if (exchange(user, 0) != 0) { set_error("lbmpm_rk3d_step_slab: the exchange callback failed"); return fail(LBMPM_ERR_STATE); }
-                rk3dq_face_unpack<<<fgrid, fblock, 0, c->stream>>>(q, c->fB, c->purB, from_below, from_above, has_below, has_above);
-                rk3dq_halo_phi<<<fgrid, fblock, 0, c->stream>>>(q, from_below, from_above, has_below, has_above);
-                c->tx.beat(c->stream, (unsigned long long)(c->steps + 1));      // "the exchange of this step is through"
-                if (ev[5]) SLAB_HIP_TRY(hipEventRecord(ev[5], c->stream));
-                SLAB_HIP_TRY(hipEventRecord(c->ev_dep, c->stream));
-                if (hipGetLastError() != hipSuccess) { set_error("lbmpm_rk3d_step_slab: kernel launch failed"); return fail(LBMPM_ERR_HIP); }
-                finish_step(c);
-                c->halo_valid = true;
-                if (ev[1]) SLAB_HIP_TRY(hipEventRecord(ev[1], c->aux));
-            }
-            // join: whoever uses the context's stream next finds the lattice launches done
-            SLAB_HIP_TRY(hipEventRecord(c->ev_done, c->aux));
-            SLAB_HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_done, 0));
-            return LBMPM_OK;
-        }
-        for (int64_t k = 0; k < nsteps; ++k) {
-            hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-            if (k < tsteps) for (int i = 0; i < 4; ++i) c->slab_pool.take(&ev[2 * i], &ev[2 * i + 1]);
-            if (ev[0]) SLAB_HIP_TRY(hipEventRecord(ev[0], c->stream));
-            const RK3Dev p = make_dev(c);
-            SLAB_HIP_TRY(hipEventRecord(c->ev_dep, c->stream));            // the previous step, its unpack included
-            if (ev[6]) SLAB_HIP_TRY(hipEventRecord(ev[6], c->stream));
-            // the boundary ranges that feed a face message, in one launch; a face without a neighbour (the lattice's inlet / outlet end)
-            // has no message to hurry for: its planes march with the interior (one range, one prologue and two fill steps less on the end ranks)
-            const int zi0 = has_below ? cb + 1 : 1, zi1 = has_above ? c->nzl - cb : c->nzl;
-            if (has_interior) {
-                if (has_below && has_above) launch_q23(c, p, c->stream, 1, cb, c->nzl - cb + 1, c->nzl);
-                else if (has_below) launch_q23(c, p, c->stream, 1, cb, 1, 0);
-                else launch_q23(c, p, c->stream, c->nzl - cb + 1, c->nzl, 1, 0);
-            }
-            else launch_step_range(c, p, c->stream, 1, c->nzl);
-            if (ev[7]) SLAB_HIP_TRY(hipEventRecord(ev[7], c->stream));
-            if (hipGetLastError() != hipSuccess) { set_error("lbmpm_rk3d_step_slab: kernel launch failed"); return fail(LBMPM_ERR_HIP); }
-            if (ev[4]) SLAB_HIP_TRY(hipEventRecord(ev[4], c->stream));
-            RK3Dev q = p;                                                     // the state this step writes
-            q.fin = c->fB; q.pur_in = c->purB; q.first = 0;
-#ifdef LBMPM_DEV
-            const int skip = c->dbg;        // timing knock-outs (LBMPM_RK3D_DBG: 1 no pack, 2 no exchange, 4 no unpack / halo phase field)
-#else
-            constexpr int skip = 0;         // (the knock-outs exist in development builds only)
-#endif
-            if (!(skip & 1)) rk3dq_face_pack<<<fgrid, fblock, 0, c->stream>>>(q, c->send_up, c->send_dn, has_below, has_above);
-            if (has_interior) {
-                // Order (per-workgroup time stamps, 512^3 on 8 ranks, tools/dev/k3trace_slab.py): rk3dq_fused fills every CU, so whatever
-                // is launched beside a running interior launch trickles through where its workgroups retire and slows them (7.5 instead
-                // of 6.3 us per march step, second-round workgroups start late).  Hence: boundary launch -> pack -> THEN the interior
-                // launch, enqueued at the same moment as the exchange: the transport's few workgroups (RCCL send / recv, or copies) are
-                // placed first on an empty GPU, the interior's workgroups take the rest, the transfer runs beside them.
-                SLAB_HIP_TRY(hipEventRecord(c->ev_dep, c->stream));
-                SLAB_HIP_TRY(hipStreamWaitEvent(c->aux, c->ev_dep, 0));
-            }
-            const double *from_below = c->recv_below, *from_above = c->recv_above;
-            if (own_tx) {          // copies / ncclSend + ncclRecv and the waits for the neighbours' messages, enqueued here
-                if (!(skip & 2)) { const int rc = c->tx.exchange(c->stream, c->send_up, c->send_dn, &from_below, &from_above); if (rc != LBMPM_OK) return fail(rc); }
-            }
-            else if (!(skip & 2) && exchange(user, 0) != 0) { set_error("lbmpm_rk3d_step_slab: the exchange callback failed"); return fail(LBMPM_ERR_STATE); }
-            if (has_interior) {
-                hipStream_t ist = (skip & 8) ? c->stream : c->aux;       // (knock-out 8: the interior on the context's own stream)
-                if (ev[2]) SLAB_HIP_TRY(hipEventRecord(ev[2], ist));
-                launch_step_range(c, p, ist, zi0, zi1);
-                if (ev[3]) SLAB_HIP_TRY(hipEventRecord(ev[3], ist));
-                SLAB_HIP_TRY(hipEventRecord(c->ev_done, ist));
-            }
-            if (!(skip & 4)) {
-                rk3dq_face_unpack<<<fgrid, fblock, 0, c->stream>>>(q, c->fB, c->purB, from_below, from_above, has_below, has_above);
-                rk3dq_halo_phi<<<fgrid, fblock, 0, c->stream>>>(q, from_below, from_above, has_below, has_above);
-                c->tx.beat(c->stream, (unsigned long long)(c->steps + 1));
-            }
-            if (hipGetLastError() != hipSuccess) { set_error("lbmpm_rk3d_step_slab: face kernel launch failed"); return fail(LBMPM_ERR_HIP); }
-            if (ev[5]) SLAB_HIP_TRY(hipEventRecord(ev[5], c->stream));
-            if (has_interior) SLAB_HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_done, 0));
-            finish_step(c);
-            c->halo_valid = !(skip & 6);       // the face message of the state just written has been exchanged and unpacked above
-            if (ev[1]) SLAB_HIP_TRY(hipEventRecord(ev[1], c->stream));
-        }
-        return LBMPM_OK;
-    }
-#undef SLAB_HIP_TRY
-    for (int64_t k = 0; k < nsteps; ++k) {
-        hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-        if (k < tsteps) for (int i = 0; i < 4; ++i) c->slab_pool.take(&ev[2 * i], &ev[2 * i + 1]);
-        if (ev[0]) LBMPM_HIP_TRY(hipEventRecord(ev[0], c->stream));
-        int rc = LBMPM_OK;
-        if (nb) rc = collide_interior_ev(c, ev[2], ev[3]);
-        if (rc != LBMPM_OK) return rc;
-        if (ev[4]) LBMPM_HIP_TRY(hipEventRecord(ev[4], c->stream));
-        // a failed exchange must not leave the interior launch pending: the context would refuse every later call
-        auto abandon = [&](int code) {
-            if (c->interior_pending) { (void)hipStreamSynchronize(c->aux); c->interior_pending = false; }
-            return code;        // fA / fB are half-updated: the caller has to set_density (or restart) before stepping again
-        };
-        if (nb && c->streamed) {
-            rc = lbmpm_rk3d_pack_halo(c);
-            if (rc == LBMPM_OK && exchange(user, 0) != 0) { set_error("lbmpm_rk3d_step_slab: the exchange callback failed (populations)"); rc = LBMPM_ERR_STATE; }
-            if (rc == LBMPM_OK) rc = lbmpm_rk3d_unpack_halo(c, has_below, has_above);
-            if (rc != LBMPM_OK) return abandon(rc);
-        }
-        rc = lbmpm_rk3d_phase_field(c, 0);
-        if (rc != LBMPM_OK) return abandon(rc);
-        if (nb && exchange(user, 1) != 0) { set_error("lbmpm_rk3d_step_slab: the exchange callback failed (phase field)"); return abandon(LBMPM_ERR_STATE); }
-        if (ev[5]) LBMPM_HIP_TRY(hipEventRecord(ev[5], c->stream));
-        rc = collide_boundary_ev(c, ev[6], ev[7]);
-        if (rc != LBMPM_OK) return rc;
-        if (ev[1]) LBMPM_HIP_TRY(hipEventRecord(ev[1], c->stream));
-    }
-    return LBMPM_OK;
+    const bool one_stream = c->nzl >= 2 * c->boundary + 1 && !(sched && !strcmp(sched, "split")) &&
+                            ((sched && !strcmp(sched, "one")) || !own_tx || c->tx.kind != LBMPM_TRANSPORT_RCCL);
+    int rc = slab_q23_prepare(c, a);
+    if (rc == LBMPM_OK) rc = one_stream ? slab_steps_one_stream(c, a) : slab_steps_split(c, a);
+    if (rc != LBMPM_OK) quiesce(c);         // leave the context consistent: the lattice launches live on the second stream
+    return rc;
 }
 
-// averages [ms] over the timed steps of the last lbmpm_rk3d_step_slab(..., timed = 1): out[0] whole step,
-// out[1] interior planes (second stream), out[2] pack .. phase-field exchange on the context's stream (transfers
-// included), out[3] boundary planes; out[4] = number of steps averaged.  Synchronises the context's streams.
+// averages [ms] over the timed steps of the last lbmpm_rk3d_step_slab(..., timed = 1): out[0] whole step, out[1] interior planes (second stream), out[2] pack ..
+// phase-field exchange on the context's stream (transfers included), out[3] boundary planes; out[4] = number of steps averaged.  Synchronises the context's streams.
 extern "C" int lbmpm_rk3d_slab_timing(lbmpm_rk3d *c, double *out)
 {
     LBMPM_REQUIRE(c && out, "lbmpm_rk3d_slab_timing: null argument");
@@ -2401,11 +2400,11 @@ extern "C" int lbmpm_rk3d_slab_timing(lbmpm_rk3d *c, double *out)
     const bool has_interior = c->aux && !(c->variant == 1 || c->nzl < 2 * c->boundary + 1) &&
                               (c->cfg.z_offset > 0 || c->cfg.z_offset + c->cfg.nz_local < c->cfg.nz_global);
     for (int64_t k = 0; k < n; ++k)
-        for (int i = 0; i < 4; ++i) {
-            if (i == 1 && !has_interior) continue;
+        for (int b : {EV_STEP, EV_INTERIOR, EV_CHAIN, EV_BOUNDARY}) {      // out[] keeps the events' order
+            if (b == EV_INTERIOR && !has_interior) continue;
             float ms = 0.f;
-            LBMPM_HIP_TRY(hipEventElapsedTime(&ms, c->slab_pool.ev[(size_t)(8 * k + 2 * i)], c->slab_pool.ev[(size_t)(8 * k + 2 * i + 1)]));
-            out[i] += ms;
+            LBMPM_HIP_TRY(hipEventElapsedTime(&ms, timed_events(c, k, n)[b], timed_events(c, k, n)[b + 1]));
+            out[b / 2] += ms;
         }
     for (int i = 0; i < 4; ++i) out[i] /= (double)n;
     out[4] = (double)n;

@@ -18,6 +18,99 @@ def _case(nx=40, ny=21, nz=38, seed=4):
     return dom, rR, rB
 
 
+FIELDS = ("phi", "rhoR", "rhoB", "vx", "vy", "vz")
+
+
+def _rank_slabs(dom, rR, rB, parts, par, st):
+    """one RK3DSlab per (z0, nz) of `parts`, all on the torch stream `st`, the densities set"""
+    from openlbmpm_amd.rk3d import RK3DSlab
+    slabs = []
+    for z0, nz in parts:
+        s = RK3DSlab(dom, z0, nz, par); s.set_density(rR[z0:z0 + nz], rB[z0:z0 + nz]); s.use_torch_stream(st); slabs.append(s)
+    return slabs
+
+
+def _land_faces(slabs, r, kind="f"):
+    """the neighbours' `kind` ("f" | "phi") send buffers into rank r's receive buffers, on the current torch stream"""
+    if r > 0: slabs[r].buffer(kind + "_recv_below").copy_(slabs[r - 1].buffer(kind + "_send_up"))
+    if r + 1 < len(slabs): slabs[r].buffer(kind + "_recv_above").copy_(slabs[r + 1].buffer(kind + "_send_down"))
+
+
+def _step_ranks(slabs, st, counts, timed=False, fail_at=None):
+    """The pipelined step as the ranks of a real run make it, with an exact exchange: one host thread per rank calls step_slab(n) for
+    every n of `counts` (the last one `timed`), a barrier inside the exchange callback, device copies between the ranks' buffers on
+    the one stream `st`.  fail_at = i: every rank's callback raises a RuntimeError at its i-th call, before it touches the barrier.
+    Returns (what each rank's thread raised or None, the RuntimeErrors planned for the ranks)."""
+    import threading
+    import torch
+    K = len(slabs)
+    gate, raised, planned = threading.Barrier(K), [None] * K, [RuntimeError("exchange of rank %d failed" % r) for r in range(K)]
+
+    def rank(r):
+        s, calls = slabs[r], [0]
+
+        def exchange(what):
+            calls[0] += 1
+            if calls[0] == fail_at:
+                raise planned[r]
+            gate.wait()
+            with torch.cuda.stream(st):
+                _land_faces(slabs, r, "phi" if what else "f")
+            gate.wait()
+        try:
+            for i, n in enumerate(counts):
+                s.step_slab(n, r > 0, r + 1 < K, exchange, timed=timed and i + 1 == len(counts))
+        except BaseException as e:      # noqa: BLE001 -- reported by the main thread
+            raised[r] = e
+            if e is not planned[r]: gate.abort()
+    th = [threading.Thread(target=rank, args=(r,)) for r in range(K)]
+    for t in th: t.start()
+    for t in th: t.join()
+    return raised, planned
+
+
+def _observe_ranks(slabs, st, fields=FIELDS):
+    """the lattice's fields of the state the ranks hold: face messages moved once more, then the diagnostics"""
+    import torch
+    with torch.cuda.stream(st):
+        if slabs[0].post_collision or slabs[0].one_exchange:
+            for s in slabs: s.pack()
+            for r in range(len(slabs)): _land_faces(slabs, r)
+            for r, s in enumerate(slabs): s.unpack(r > 0, r + 1 < len(slabs))
+        for s in slabs: s.phase_field(diagnostics=True)
+    return {f: np.concatenate([s.get(f) for s in slabs], axis=0) for f in fields}
+
+
+def _threaded_slab_run(dom, rR, rB, parts, par, counts, timed=False, fields=FIELDS):
+    """fresh ranks for `parts`, _step_ranks(counts), _observe_ranks: (fields of the whole lattice, each rank's slab_timing())"""
+    import torch
+    st = torch.cuda.Stream(0)
+    slabs = _rank_slabs(dom, rR, rB, parts, par, st)
+    raised, _ = _step_ranks(slabs, st, counts, timed)
+    assert not any(raised), raised
+    got = _observe_ranks(slabs, st, fields)
+    timing = [s.slab_timing() for s in slabs]
+    for s in slabs: s.close()
+    return got, timing
+
+
+_SLAB_CASE_PAR = dict(relax="MRT")
+_single_domain = {}
+
+
+def _slab_case_reference(steps, layout="q23"):
+    """_case(nx=70, ny=19, nz=41, seed=11) and its single-domain fields after `steps` steps (computed once per layout, never changed)"""
+    from openlbmpm_amd.rk3d import RK3DSlab
+    dom, rR, rB = _case(nx=70, ny=19, nz=41, seed=11)
+    if (steps, layout) not in _single_domain:
+        ref = RK3DSlab(dom, 0, 41, _SLAB_CASE_PAR)
+        assert ref.dominant_kernel == ("rk3dq_fused" if layout == "q23" else "rk3d_fused")
+        ref.set_density(rR, rB); ref.step_single(steps); ref.phase_field(diagnostics=True)
+        _single_domain[steps, layout] = {f: ref.get(f) for f in FIELDS}
+        ref.close()
+    return dom, rR, rB, _single_domain[steps, layout]
+
+
 @pytest.mark.parametrize("layout", ["q23", "dense"])
 @pytest.mark.parametrize("relax", ["SRT", "MRT"])
 def test_single_slab_vs_oracle(relax, layout, monkeypatch):
@@ -206,7 +299,6 @@ def test_q23_slabs_of_a_wide_lattice_equal_single_domain_bitwise():
     private copy of their argument struct in scratch memory; tests/test_codeobj.py keeps scratch out of these kernels): every face
     message must come out the same every time, and three slabs must equal the single domain bit for bit, phase by phase
     (RK3DCluster) and through the pipelined lbmpm_rk3d_step_slab with one host thread per rank."""
-    import threading
     import torch
     import bench
     from openlbmpm_amd.rk3d import RK3DCluster, RK3DDistributed, RK3DSlab
@@ -234,39 +326,63 @@ def test_q23_slabs_of_a_wide_lattice_equal_single_domain_bitwise():
         assert np.array_equal(c.get(f), want[f]), ("cluster", f)
     c.close()
     # the pipelined step as the ranks of a real run make it, with an exact exchange: a barrier inside the callback
-    parts = RK3DDistributed.partition(dom, K)
-    st = torch.cuda.Stream(0)
-    slabs = []
-    for z0, nz in parts:
-        s = RK3DSlab(dom, z0, nz, par); s.set_density(rR[z0:z0 + nz], rB[z0:z0 + nz]); s.use_torch_stream(st); slabs.append(s)
-    gate, errors = threading.Barrier(K), []
-
-    def rank(r):
-        s, below, above = slabs[r], r > 0, r + 1 < K
-
-        def exchange(what):
-            gate.wait()
-            with torch.cuda.stream(st):
-                if below: s.buffer("f_recv_below").copy_(slabs[r - 1].buffer("f_send_up"))
-                if above: s.buffer("f_recv_above").copy_(slabs[r + 1].buffer("f_send_down"))
-            gate.wait()
-        try:
-            s.step_slab(steps, below, above, exchange)
-        except BaseException as e:      # noqa: BLE001 -- reported by the main thread
-            errors.append(e); gate.abort()
-    th = [threading.Thread(target=rank, args=(r,)) for r in range(K)]
-    for t in th: t.start()
-    for t in th: t.join()
-    assert not errors, errors
-    with torch.cuda.stream(st):
-        for s in slabs: s.pack()
-        for r, s in enumerate(slabs):
-            if r > 0: s.buffer("f_recv_below").copy_(slabs[r - 1].buffer("f_send_up"))
-            if r + 1 < K: s.buffer("f_recv_above").copy_(slabs[r + 1].buffer("f_send_down"))
-        for r, s in enumerate(slabs):
-            s.unpack(r > 0, r + 1 < K); s.phase_field(diagnostics=True)
+    got, _ = _threaded_slab_run(dom, rR, rB, RK3DDistributed.partition(dom, K), par, [steps], fields=tuple(want))
     for f in want:
-        assert np.array_equal(np.concatenate([s.get(f) for s in slabs], axis=0), want[f]), ("pipelined", f)
+        assert np.array_equal(got[f], want[f]), ("pipelined", f)
+
+
+@pytest.mark.parametrize("env,parts", [({}, [(0, 14), (14, 13), (27, 14)]),
+                                       ({"LBMPM_RK3D_SLAB_SCHEDULE": "split"}, [(0, 14), (14, 13), (27, 14)]),
+                                       ({"LBMPM_RK3D_SLAB_SCHEDULE": "split", "LBMPM_RK3D_BOUNDARY": "3"}, [(0, 14), (14, 13), (27, 14)]),
+                                       ({}, [(0, 19), (19, 4), (23, 18)])],
+                         ids=["one-stream", "split", "split,BOUNDARY=3", "thin-middle-rank"])
+def test_slab_step_schedules_equal_single_domain_bitwise(env, parts, knobs):
+    """lbmpm_rk3d_step_slab of the q23 storage, every schedule it has, on two ragged row segments and fewer rows than a row tile: the
+    one-stream schedule (a rank with two neighbours between two with one), the split schedule (development build), the split schedule
+    with a deeper boundary, and a middle rank of 4 planes -- fewer than 2 * boundary + 1, no interior planes: the whole slab in the
+    split loop's one launch -- between two ranks on the one-stream schedule.  4 steps, then 3 timed ones: the single domain's bits
+    after 7, and every timed part that the rank has took time."""
+    dom, rR, rB, want = _slab_case_reference(7)
+    knobs(env)
+    from openlbmpm_amd.rk3d import RK3DSlab
+    probe = RK3DSlab(dom, *parts[1], _SLAB_CASE_PAR)
+    assert probe.dominant_kernel == "rk3dq_fused" and probe.one_exchange
+    probe.close()
+    got, timing = _threaded_slab_run(dom, rR, rB, parts, _SLAB_CASE_PAR, [4, 3], timed=True)
+    for f in FIELDS:
+        assert np.array_equal(got[f], want[f]), f
+    boundary = int(env.get("LBMPM_RK3D_BOUNDARY", 2))
+    for (z0, nz), t in zip(parts, timing):
+        assert t["steps"] == 3 and t["step_ms"] > 0 and t["boundary_ms"] > 0 and t["exchange_chain_ms"] > 0, (z0, nz, t)
+        if nz >= 2 * boundary + 1: assert t["interior_ms"] > 0, (z0, nz, t)
+        else: assert t["interior_ms"] == 0, (z0, nz, t)
+
+
+@pytest.mark.parametrize("layout", ["q23", "dense"])
+def test_a_failing_exchange_callback_leaves_the_slab_reusable(layout, monkeypatch):
+    """Every rank's exchange callback raises at its third call (q23: the exchange of step 2, with the lattice launches of that step
+    enqueued on the second stream; dense: the phase-field exchange of step 2, with the interior launch pending): step_slab raises that
+    error on every rank after one whole step, and the same contexts, given their densities again, then run as fresh ones do."""
+    import torch
+    if layout == "dense":
+        monkeypatch.setenv("LBMPM_RK3D_LAYOUT", "dense")
+    dom, rR, rB, want = _slab_case_reference(5, layout)
+    parts = [(0, 21), (21, 20)]
+    st = torch.cuda.Stream(0)
+    slabs = _rank_slabs(dom, rR, rB, parts, _SLAB_CASE_PAR, st)
+    assert all(s.one_exchange == (layout == "q23") for s in slabs)
+    raised, planned = _step_ranks(slabs, st, [6], fail_at=3)
+    for r in range(len(slabs)):
+        assert raised[r] is planned[r], (r, raised[r])
+    done = [s.steps_done for s in slabs]
+    assert done[0] == done[1] and 0 < done[0] < 6, done
+    for s, (z0, nz) in zip(slabs, parts):
+        s.set_density(rR[z0:z0 + nz], rB[z0:z0 + nz])
+    raised, _ = _step_ranks(slabs, st, [5])
+    assert not any(raised), raised
+    got = _observe_ranks(slabs, st)
+    for f in FIELDS:
+        assert np.array_equal(got[f], want[f]), f
     for s in slabs: s.close()
 
 
