@@ -528,6 +528,46 @@ int lbmpm_rk3d_clusters(lbmpm_rk3d *ctx, const lbmpm_clusters_config *cfg, int64
 int lbmpm_rk3d_clusters_table(lbmpm_rk3d *ctx, int64_t *out);
 int lbmpm_rk3d_clusters_labels(lbmpm_rk3d *ctx, uint32_t *out);
 int lbmpm_rk3d_clusters_faces(lbmpm_rk3d *ctx, uint32_t *labels, uint8_t *classes);
+/* Per-cluster properties of the 3-D solvers: a second table beside the cluster table, one row of LBMPM_CLUSTER_PROP_COLS int64 per
+ * cluster, reduced on the device (csrc/rk3d_cluster_props.h).  Both functions refer to the last lbmpm_*_clusters call on the current
+ * state -- its phi_cut, connectivity, labels and rows; LBMPM_ERR_STATE before one, and after a step or a change of state since it (the
+ * perturbation model also needs the fields of lbmpm_rk3d_phase_field(ctx, 1), as the morphology does).  `count` is that call's count,
+ * rows by ascending label; LABEL, CLASS and CELLS equal the cluster table's.
+ *   Class byte    the values of LBMPM_MORPH_*: R or B exactly where the clusters put the cell into a cluster of that class, S where the
+ *                 flow's loader says solid, N for every other fluid cell.  lbmpm_*_cluster_props_face hands out the classes of the
+ *                 lowest and the highest own plane; `below` / `above` are the highest plane of the slab below and the lowest plane of
+ *                 the slab above.  A byte > 3 in either: LBMPM_ERR_INVALID.  NULL: nothing is there -- z never wraps.
+ *   FACES_FLUID,  cell-centred: of the six face neighbours of every cell of the cluster (x +- 1 mod nx, y +- 1 mod ny, literally for a
+ *   FACES_SOLID   small nx or ny: each direction counts once; z +- 1 from the own planes, `below` or `above`) those of the other phase,
+ *                 and the S ones.  An R-B face counts once for the R cluster and once for the B cluster.
+ *   PAIRS,        the morphology's elements with its anchoring (lowest corner; x and y wrapped, z + 1 from the own planes or `above`)
+ *   SQUARES,      whose cells are all of the anchor's class, credited to the anchor's cluster: PAIRS over the three axes, SQUARES over
+ *   CUBES         the three orientations.  Such an element is face-connected, so it lies in one cluster under either connectivity;
+ *                 an element cut by a slab face is counted by the anchor's slab.  chi_6 of a cluster = CELLS - PAIRS + SQUARES - CUBES.
+ *   SUM_Z         the sum of the global plane numbers of the cluster's cells (the centroid along z, the axis that does not wrap)
+ *   MASS, MOM_a   fixed-point sums, added with integer atomics (no floating-point atomics: their order is not fixed).  Per cell
+ *                 rho = rho_R + rho_B (one rounded addition, as in the morphology) and p_a = rho * u_a (one rounded product, as in the
+ *                 integrals), each rounded to nearest-even to a multiple of its quantum: MASS in units of 2^-LBMPM_CP_MASS_BITS, MOM_a
+ *                 in units of 2^-LBMPM_CP_MOM_BITS.  Resolution: 6e-8 per cell for the mass, 9.3e-10 per cell for the momentum; the
+ *                 roundings are unbiased, so a ganglion's mean velocity is resolved far below that.
+ *   CLIPPED       cells where rho_R, rho_B or u is not finite, |rho| >= 64 or any |p_a| >= 1: they count here and in every integer
+ *                 column, and in none of MASS and MOM_a.  So |a cell's MASS| < 2^30 and |a cell's MOM_a| <= 2^30; with fewer than
+ *                 2^32 - 1 cells (the clusters' limit) neither sum can reach 2^62.
+ * Integer addition is associative: the table is the same bits under every order, launch and cut.  A slab's table is that of the slab
+ * alone, as the cluster table; merged rows are the sums of the slabs' rows.
+ * Device memory: (own planes + 2) * ny * nx bytes, allocated by the first call of either function, and 88 bytes per cluster of the
+ * largest count a lbmpm_*_cluster_props call has met (it grows only; a checkerboard has as many clusters as cells); both counted by
+ * lbmpm_*_device_bytes, nothing before the first call. */
+#define LBMPM_CLUSTER_PROP_COLS 14
+enum { LBMPM_CP_LABEL = 0, LBMPM_CP_CLASS, LBMPM_CP_CELLS, LBMPM_CP_FACES_FLUID, LBMPM_CP_FACES_SOLID,
+       LBMPM_CP_PAIRS, LBMPM_CP_SQUARES, LBMPM_CP_CUBES, LBMPM_CP_SUM_Z,
+       LBMPM_CP_MASS, LBMPM_CP_MOM_X, LBMPM_CP_MOM_Y, LBMPM_CP_MOM_Z, LBMPM_CP_CLIPPED };
+#define LBMPM_CP_MASS_BITS 24      /* MASS is in units of 2^-24 */
+#define LBMPM_CP_MOM_BITS  30      /* MOM_* are in units of 2^-30 */
+/* classes: host [2][ny][nx], the lowest and the highest own plane */
+int lbmpm_rk3d_cluster_props_face(lbmpm_rk3d *ctx, uint8_t *classes);
+/* below, above: host [ny][nx] or NULL; out: host [count][LBMPM_CLUSTER_PROP_COLS] */
+int lbmpm_rk3d_cluster_props(lbmpm_rk3d *ctx, const uint8_t *below, const uint8_t *above, int64_t *out);
 /* Phase morphology of the 3-D solvers: per own plane, counts over the 2 x 2 x 2 neighbourhoods of a class field plus two density sums,
  * reduced on the device (csrc/rk3d_morphology.h).  Interfacial and wetted areas, the Euler characteristic of each phase and a
  * phase-averaged pressure difference follow from them.
@@ -712,6 +752,10 @@ int lbmpm_rk3dcsf_clusters(lbmpm_rk3dcsf *ctx, const lbmpm_clusters_config *cfg,
 int lbmpm_rk3dcsf_clusters_table(lbmpm_rk3dcsf *ctx, int64_t *out);
 int lbmpm_rk3dcsf_clusters_labels(lbmpm_rk3dcsf *ctx, uint32_t *out);
 int lbmpm_rk3dcsf_clusters_faces(lbmpm_rk3dcsf *ctx, uint32_t *labels, uint8_t *classes);
+/* per-cluster properties of the last lbmpm_rk3dcsf_clusters, see lbmpm_rk3d_cluster_props: rho_R, rho_B and u are what
+ * LBMPM_RK3DCSF_REC_* hand out, from the populations in registers */
+int lbmpm_rk3dcsf_cluster_props_face(lbmpm_rk3dcsf *ctx, uint8_t *classes);
+int lbmpm_rk3dcsf_cluster_props(lbmpm_rk3dcsf *ctx, const uint8_t *below, const uint8_t *above, int64_t *out);
 /* phase morphology of the own planes, see lbmpm_rk3d_morphology: phi, rho_R and rho_B are what LBMPM_RK3DCSF_REC_* hand out, from the
  * populations in registers; out: host [own planes][LBMPM_MORPH_COLS].  LBMPM_ERR_STATE before set_macro / set_pdf */
 int lbmpm_rk3dcsf_morphology_face(lbmpm_rk3dcsf *ctx, const lbmpm_morphology_config *cfg, uint8_t *classes);

@@ -35,7 +35,10 @@ met with the nan_guard rule at that cadence.
 clusters_every = N > 0: at the same kind of cadence the connected clusters of each phase, labelled on the device (openlbmpm_amd/clusters.py;
 clusters_connectivity 6 or 18): /Clusters/TableAtStep<step> [n][5] int64 (label, class, cells, zmin, zmax; the whole lattice's, joined on
 rank 0 in a distributed run), /Clusters/Steps and /Clusters/Columns at the end; counts, the largest cluster, percolation and the trapped
-cells of each phase go to the log.
+cells of each phase go to the log.  clusters_props = True (only meaningful with clusters_every): the property table beside it, reduced on
+the device too: /Clusters/PropsAtStep<step> [n][14] int64 (label, class, cells, then faces towards the other phase and the solid, pairs,
+squares, cubes, the plane sum, mass and momentum in fixed point, clipped cells) and /Clusters/PropColumns; the ganglia of each phase and
+the mobile ones among them join the log line.
 
 morphology_every = N > 0: at the same kind of cadence the phase morphology, counted on the device (openlbmpm_amd/morphology.py;
 morphology_phi_cut: the band around phi = 0 that belongs to neither phase): /Morphology/PlanesAtStep<step> [nz][28] (cells, density
@@ -119,7 +122,7 @@ class RKColorGradient3D:
     def __init__(self, pathIniFile, output_dir=None, domain=None, device=0, record_every=None, num_buffering_layers=10,
                  structure_path=None, initial_dir=None, record_pdf=False, restart_from=None, checkpoint_every=0, csf_bulk_epsilon=0.0,
                  csf_transport=None, integrals_every=0, clusters_every=0, clusters_connectivity=6, morphology_every=0,
-                 morphology_phi_cut=0.0):
+                 morphology_phi_cut=0.0, clusters_props=False):
         self.pathIni = pathIniFile
         self.par = config.read_rk3d(pathIniFile)
         self.output_dir = output_dir or os.path.expanduser("~/LBMResults3D")       # main.py:28
@@ -137,6 +140,7 @@ class RKColorGradient3D:
         self.integrals_every = int(integrals_every)      # 0: no /Integrals group, no extra stop of the step loop
         # 0: no /Clusters group, no extra stop of the step loop; connectivity 6 (faces) or 18 (the D3Q19 links)
         self.clusters_every, self.clusters_connectivity = int(clusters_every), int(clusters_connectivity)
+        self.clusters_props = bool(clusters_props)       # with clusters_every: the property table beside every cluster table
         # 0: no /Morphology group, no extra stop of the step loop
         self.morphology_every, self.morphology_phi_cut = int(morphology_every), float(morphology_phi_cut)
         self.gather_records = True
@@ -338,6 +342,7 @@ class RKColorGradient3D:
         every = self.integrals_every
         # (the table is gathered: the whole lattice's on rank 0, whether the records are gathered or not)
         cevery = self.clusters_every
+        ckw = dict(props=True) if self.clusters_props else {}
         mevery = self.morphology_every
         more = ((("Integrals", "PlaneIntegrals"),) if every > 0 and rank == 0 else ()) + ((("Clusters", "PhaseClusters"),) if cevery > 0 and rank == 0 else ()) + \
             ((("Morphology", "PhaseMorphology"),) if mevery > 0 and rank == 0 else ())
@@ -354,7 +359,7 @@ class RKColorGradient3D:
             if every > 0 and done % every == 0:
                 self._integrals(integrals(), out, done)
             if cevery > 0 and done % cevery == 0:
-                self._clusters(clusters(connectivity=self.clusters_connectivity), out, done)
+                self._clusters(clusters(connectivity=self.clusters_connectivity, **ckw), out, done)
             if mevery > 0 and done % mevery == 0:
                 self._morphology(morphology(self.morphology_phi_cut), out, done)
             n = min(self.timeInterval - done % self.timeInterval, self.timeSteps - done)
@@ -382,11 +387,14 @@ class RKColorGradient3D:
                 out.write("Integrals", "Steps", np.array(self.integral_steps, dtype=np.int64))
                 out.write("Integrals", "Columns", column_bytes())
         if cevery > 0:
-            self._clusters(clusters(connectivity=self.clusters_connectivity), out, done)
+            self._clusters(clusters(connectivity=self.clusters_connectivity, **ckw), out, done)
             if rank == 0:
                 from .clusters import column_bytes as cluster_column_bytes
                 out.write("Clusters", "Steps", np.array(self.cluster_steps, dtype=np.int64))
                 out.write("Clusters", "Columns", cluster_column_bytes())
+                if self.clusters_props:
+                    from .clusters import prop_column_bytes
+                    out.write("Clusters", "PropColumns", prop_column_bytes())
         if mevery > 0:
             self._morphology(morphology(self.morphology_phi_cut), out, done)
             if rank == 0:
@@ -412,6 +420,8 @@ class RKColorGradient3D:
         if t is not None:
             if out is not None:
                 out.write("Clusters", "TableAtStep%d" % step, t.table)
+                if t.props is not None:
+                    out.write("Clusters", "PropsAtStep%d" % step, t.props)
             self._guard.log.info("rk3d clusters step %d: %s", step, " ".join("%s=%s" % kv for kv in t.summary().items()))
 
     def _morphology(self, t, out, step):

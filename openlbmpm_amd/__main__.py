@@ -12,6 +12,8 @@
                                                   ConcentrationResults)
         [--clusters-every N]                      rk3d: the connected clusters of each phase, labelled on the device, every N steps (/Clusters of the
         [--clusters-connectivity 6|18]            result file: label, class, cells, zmin, zmax per cluster); percolation and trapped cells to the log
+        [--clusters-props]                        rk3d, with --clusters-every: faces, pairs, squares, cubes, plane sum, mass and momentum per cluster
+                                                  (/Clusters/PropsAtStep<step>); ganglia and mobile ganglia to the log
         [--morphology-every N]                    rk3d: cells, class pairs, squares and cubes per plane, counted on the device, every N steps (/Morphology
         [--morphology-phi-cut c]                  of the result file); interfacial area, wetted fraction, Euler characteristics, capillary pressure to the log
 """
@@ -54,6 +56,9 @@ def main(argv=None):
     ap.add_argument("--clusters-every", type=int, default=0, metavar="N",
                     help="rk3d: every N steps the connected clusters of each phase (label, class, cells, zmin, zmax per cluster), labelled on the device, "
                          "to /Clusters of the result file; counts, the largest cluster, percolation and trapped cells to the log; 0: off")
+    ap.add_argument("--clusters-props", action="store_true",
+                    help="rk3d, with --clusters-every: the property table beside every cluster table (faces, pairs, squares, cubes, plane sum, mass and "
+                         "momentum per cluster, reduced on the device): /Clusters/PropsAtStep<step>; ganglia and mobile ganglia to the log")
     ap.add_argument("--clusters-connectivity", type=int, choices=[6, 18], default=6, help="rk3d: neighbours of a cell: 6 faces, or the 18 D3Q19 links")
     ap.add_argument("--morphology-every", type=int, default=0, metavar="N",
                     help="rk3d: every N steps the phase morphology (cells, density sums, class pairs, squares and cubes per plane), counted on the device, "
@@ -72,7 +77,7 @@ def main(argv=None):
         from .RKColorGradientD3Q19 import RKColorGradient3D
         device = _rank_device(a.device)
         sim = RKColorGradient3D(a.ini_dir, output_dir=a.out, device=device, csf_transport=a.csf_transport, integrals_every=a.integrals_every,
-                                clusters_every=a.clusters_every, clusters_connectivity=a.clusters_connectivity,
+                                clusters_every=a.clusters_every, clusters_connectivity=a.clusters_connectivity, clusters_props=a.clusters_props,
                                 morphology_every=a.morphology_every, morphology_phi_cut=a.morphology_phi_cut)
         if a.steps is not None:
             sim.timeSteps = a.steps

@@ -190,6 +190,8 @@ _SIGNATURES = {
     "lbmpm_rk3d_clusters_table": (C.c_int, [C.c_void_p, I64P]),
     "lbmpm_rk3d_clusters_labels": (C.c_int, [C.c_void_p, U32P]),
     "lbmpm_rk3d_clusters_faces": (C.c_int, [C.c_void_p, U32P, U8P]),
+    "lbmpm_rk3d_cluster_props_face": (C.c_int, [C.c_void_p, U8P]),
+    "lbmpm_rk3d_cluster_props": (C.c_int, [C.c_void_p, U8P, U8P, I64P]),
     "lbmpm_rk3d_morphology_face": (C.c_int, [C.c_void_p, C.POINTER(MorphologyConfig), U8P]),
     "lbmpm_rk3d_morphology": (C.c_int, [C.c_void_p, C.POINTER(MorphologyConfig), U8P, F64P]),
     "lbmpm_rk3d_num_fluid_nodes": (C.c_int64, [C.c_void_p]),
@@ -219,6 +221,8 @@ _SIGNATURES = {
     "lbmpm_rk3dcsf_clusters_table": (C.c_int, [C.c_void_p, I64P]),
     "lbmpm_rk3dcsf_clusters_labels": (C.c_int, [C.c_void_p, U32P]),
     "lbmpm_rk3dcsf_clusters_faces": (C.c_int, [C.c_void_p, U32P, U8P]),
+    "lbmpm_rk3dcsf_cluster_props_face": (C.c_int, [C.c_void_p, U8P]),
+    "lbmpm_rk3dcsf_cluster_props": (C.c_int, [C.c_void_p, U8P, U8P, I64P]),
     "lbmpm_rk3dcsf_morphology_face": (C.c_int, [C.c_void_p, C.POINTER(MorphologyConfig), U8P]),
     "lbmpm_rk3dcsf_morphology": (C.c_int, [C.c_void_p, C.POINTER(MorphologyConfig), U8P, F64P]),
     "lbmpm_rk3dcsf_tracer_integrals": (C.c_int, [C.c_void_p, F64P]),

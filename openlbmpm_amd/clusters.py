@@ -5,6 +5,11 @@ plane, how much is trapped in ganglia.
 The library labels the connected cells of each phase on the device; a label is the global cell number of a cluster's smallest cell,
 so a table is the same bit for bit however the lattice was cut into slabs.  A slab's table is that of the slab alone: `merge_slabs`
 joins the tables of consecutive slabs through the labels and classes of their face planes.
+
+Beside the table the library reduces a second one on request (lbmpm_*_cluster_props, `props=True`): per cluster the faces towards the
+other phase and towards the solid, the pairs, squares and cubes of its cells, the sum of its plane numbers, and mass and momentum as
+fixed-point integer sums -- interfacial and wetted area, Euler number, centre, mean density and velocity of every ganglion without a
+field leaving the device.  Integers throughout: `merge_props` adds the slabs' rows, and the result is the undivided lattice's bit for bit.
 """
 import numpy as np
 
@@ -13,6 +18,12 @@ COLUMNS = ("label", "class", "cells", "zmin", "zmax")
 LABEL, CLASS, CELLS, ZMIN, ZMAX = range(5)
 NONE = 0xFFFFFFFF                     # LBMPM_CLUSTER_NONE: a cell in no cluster
 PHASES = {"R": 1, "B": 2}
+# the columns of the property table, in the order of LBMPM_CP_* (include/lbmpm.h); the first three are the table's own
+PROP_COLUMNS = ("label", "class", "cells", "faces_fluid", "faces_solid", "pairs", "squares", "cubes", "sum_z", "mass", "mom_x", "mom_y", "mom_z",
+                "clipped")
+P_FACES_FLUID, P_FACES_SOLID, P_PAIRS, P_SQUARES, P_CUBES, P_SUM_Z, P_MASS, P_MOM_X, P_MOM_Y, P_MOM_Z, P_CLIPPED = range(3, 14)
+MASS_BITS, MOM_BITS = 24, 30          # LBMPM_CP_MASS_BITS, LBMPM_CP_MOM_BITS: MASS in units of 2^-24, MOM_* in units of 2^-30
+MOBILE_SPEED = 1e-6                   # summary(): a ganglion counts as mobile above this |velocity| (lattice units)
 
 # the neighbour offsets (dx, dy) of a cell in the plane above it: faces, and the D3Q19 links that cross z
 _UP = {6: ((0, 0),), 18: ((0, 0), (1, 0), (-1, 0), (0, 1), (0, -1))}
@@ -20,13 +31,21 @@ _UP = {6: ((0, 0),), 18: ((0, 0), (1, 0), (-1, 0), (0, 1), (0, -1))}
 
 class Clusters:
     """table: [n][5] int64, one row per cluster by ascending label (label, class 1 = R / 2 = B, cells, lowest and highest plane);
-    nx, ny, nz: the lattice; labels: [nz][ny][nx] uint32 or None (NONE: solid, interface band or not finite)"""
+    nx, ny, nz: the lattice; labels: [nz][ny][nx] uint32 or None (NONE: solid, interface band or not finite); props: [n][14] int64, the
+    property table row by row beside `table` (PROP_COLUMNS), or None"""
     COLUMNS = COLUMNS
+    PROP_COLUMNS = PROP_COLUMNS
 
-    def __init__(self, table, nx, ny, nz, labels=None):
+    def __init__(self, table, nx, ny, nz, labels=None, props=None):
         a = np.ascontiguousarray(table, dtype=np.int64).reshape(-1, len(COLUMNS)) if np.size(table) else np.zeros((0, len(COLUMNS)), dtype=np.int64)
         self.table, self.nx, self.ny, self.nz = a, int(nx), int(ny), int(nz)
         self.labels = labels
+        self.props = None
+        if props is not None:
+            b = np.ascontiguousarray(props, dtype=np.int64).reshape(-1, len(PROP_COLUMNS)) if np.size(props) else np.zeros((0, len(PROP_COLUMNS)), dtype=np.int64)
+            if b.shape[0] != a.shape[0] or not np.array_equal(b[:, :3], a[:, :3]):
+                raise ValueError("props and table are not row by row the same clusters (label, class, cells)")
+            self.props = b
 
     def rows(self, phase):
         """the rows of one phase ('R' or 'B')"""
@@ -78,13 +97,86 @@ class Clusters:
         n = self.cells(phase)
         return self.trapped_cells(phase, z_lo, z_hi) / n if n else float("nan")
 
-    def summary(self):
-        """the numbers a log line carries"""
+    def summary(self, speed=MOBILE_SPEED):
+        """the numbers a log line carries; with props also the ganglia of each phase and those of them faster than `speed`"""
         out = {}
         for p in ("R", "B"):
             out["clusters_" + p], out["largest_" + p] = self.count(p), self.largest(p)
             out["percolates_" + p], out["trapped_" + p] = self.percolates(p), self.trapped_cells(p)
+        if self.props is not None:
+            for p in ("R", "B"):
+                g = self.ganglia(p)
+                out["ganglia_" + p] = int(g.shape[0])
+                out["mobile_" + p] = int(np.count_nonzero(np.sqrt((g["velocity"] ** 2).sum(axis=1)) > speed)) if g.shape[0] else 0
         return out
+
+    # ---- the property table: every accessor returns an array row by row beside .table, or beside rows(phase) when a phase is given
+    def prop_rows(self, phase=None):
+        if self.props is None:
+            raise ValueError("no property table: ask for clusters(props=True)")
+        return self.props if phase is None else self.props[self.props[:, CLASS] == PHASES[phase]]
+
+    def interfacial_area(self, phase=None):
+        """2/3 of the faces towards the other phase: the three-direction Cauchy-Crofton estimate of morphology.Morphology.area"""
+        return 2.0 * self.prop_rows(phase)[:, P_FACES_FLUID] / 3.0
+
+    def wetted_area(self, phase=None):
+        """2/3 of the faces towards the solid, the same estimate"""
+        return 2.0 * self.prop_rows(phase)[:, P_FACES_SOLID] / 3.0
+
+    def euler(self, phase=None):
+        """chi_6 = cells - pairs + squares - cubes of every cluster (int64): 1 for a blob, 0 for a ring"""
+        r = self.prop_rows(phase)
+        return r[:, CELLS] - r[:, P_PAIRS] + r[:, P_SQUARES] - r[:, P_CUBES]
+
+    def centre_z(self, phase=None):
+        """the mean plane number of the cluster's cells"""
+        r = self.prop_rows(phase)
+        return r[:, P_SUM_Z] / r[:, CELLS]
+
+    def clipped(self, phase=None):
+        """cells that are in no mass or momentum sum (not finite, or out of the fixed-point range)"""
+        return self.prop_rows(phase)[:, P_CLIPPED]
+
+    def mass(self, phase=None):
+        """the sum of rho_R + rho_B over the cluster's cells that are not clipped"""
+        return self.prop_rows(phase)[:, P_MASS] * 2.0 ** -MASS_BITS
+
+    def mean_density(self, phase=None):
+        """mass per cell that is not clipped; NaN without one"""
+        r = self.prop_rows(phase)
+        n = (r[:, CELLS] - r[:, P_CLIPPED]).astype(np.float64)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return np.where(n > 0, self.mass(phase) / n, np.nan)
+
+    def momentum(self, phase=None):
+        """[n][3]: the sum of (rho_R + rho_B) u over the cluster's cells that are not clipped"""
+        return self.prop_rows(phase)[:, P_MOM_X:P_MOM_Z + 1] * 2.0 ** -MOM_BITS
+
+    def velocity(self, phase=None):
+        """[n][3]: momentum / mass, the mass-weighted mean velocity; NaN where the mass is 0"""
+        m = self.mass(phase)[:, None]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return np.where(m != 0, self.momentum(phase) / m, np.nan)
+
+    GANGLION = np.dtype([("label", np.int64), ("volume", np.int64), ("area", np.float64), ("wetted_area", np.float64), ("euler", np.int64),
+                         ("centre_z", np.float64), ("velocity", np.float64, (3,))])
+
+    def ganglia(self, phase, z_lo=None, z_hi=None):
+        """a structured array (GANGLION) of the clusters of the phase that touch neither open plane, by ascending label"""
+        lo, hi = self._planes(z_lo, z_hi)
+        r = self.rows(phase)
+        m = (r[:, ZMIN] > lo) & (r[:, ZMAX] < hi)
+        out = np.zeros(int(m.sum()), dtype=self.GANGLION)
+        out["label"], out["volume"] = r[m, LABEL], r[m, CELLS]
+        out["area"], out["wetted_area"] = self.interfacial_area(phase)[m], self.wetted_area(phase)[m]
+        out["euler"], out["centre_z"], out["velocity"] = self.euler(phase)[m], self.centre_z(phase)[m], self.velocity(phase)[m]
+        return out
+
+    def mobile_cells(self, phase, speed, z_lo=None, z_hi=None):
+        """the cells in ganglia whose |velocity| exceeds `speed`"""
+        g = self.ganglia(phase, z_lo, z_hi)
+        return int(g["volume"][np.sqrt((g["velocity"] ** 2).sum(axis=1)) > speed].sum()) if g.shape[0] else 0
 
 
 def _name_bytes():
@@ -95,6 +187,12 @@ def _name_bytes():
 def column_bytes():
     """COLUMNS as a [5][width] uint8 array, zero-padded: /Clusters/Columns of a result file (integrals.column_names reads it back)"""
     return _name_bytes()
+
+
+def prop_column_bytes():
+    """PROP_COLUMNS as a [14][width] uint8 array, zero-padded: /Clusters/PropColumns of a result file"""
+    width = max(len(c) for c in PROP_COLUMNS)
+    return np.array([list(c.encode().ljust(width, b"\0")) for c in PROP_COLUMNS], dtype=np.uint8)
 
 
 def merge_slabs(tables, face_labels, face_classes, nx, ny, connectivity=6):
@@ -161,17 +259,94 @@ def relabel(labels, mapping):
     return out
 
 
+def merge_props(props_parts, mapping):
+    """The property tables of consecutive slabs ([n_s][14] each) joined through merge_slabs' mapping: every row goes to its merged
+    label; the accumulated columns and the cells are summed (integers: the undivided lattice's bits), label and class are the merged
+    cluster's.  Returns [m][14] by ascending label, row by row beside merge_slabs' table."""
+    parts = [np.asarray(t, dtype=np.int64).reshape(-1, len(PROP_COLUMNS)) for t in props_parts]
+    rows = np.concatenate(parts, axis=0) if parts else np.zeros((0, len(PROP_COLUMNS)), dtype=np.int64)
+    rows = rows[np.argsort(rows[:, LABEL], kind="stable")]
+    mapping = np.asarray(mapping, dtype=np.int64).reshape(-1, 2)
+    if rows.shape[0] != mapping.shape[0] or not np.array_equal(rows[:, LABEL], mapping[:, 0]):
+        raise ValueError("the property tables and the mapping do not hold the same labels")
+    new, tgt = np.unique(mapping[:, 1], return_inverse=True)
+    out = np.zeros((new.shape[0], len(PROP_COLUMNS)), dtype=np.int64)
+    np.add.at(out, tgt.reshape(-1), rows)
+    out[:, LABEL] = new
+    keep = mapping[:, 0] == mapping[:, 1]                  # the row that gave the merged cluster its label: its class is the cluster's
+    out[:, CLASS] = rows[keep, CLASS]
+    return out
+
+
 def merged(parts, nx, ny, nz, connectivity, labels):
-    """Clusters of the whole lattice from the slabs' `take` results, lowest slab first"""
+    """Clusters of the whole lattice from the slabs' `take` results, lowest slab first (with the property table where every part has one)"""
     table, mapping = merge_slabs([p["table"] for p in parts], [p["face_labels"] for p in parts], [p["face_classes"] for p in parts],
                                  nx, ny, connectivity)
     field = relabel(np.concatenate([p["labels"] for p in parts], axis=0), mapping) if labels else None
-    return Clusters(table, nx, ny, nz, field)
+    props = merge_props([p["props"] for p in parts], mapping) if parts and all("props" in p for p in parts) else None
+    return Clusters(table, nx, ny, nz, field, props)
 
 
-def take(L, prefix, handle, planes, ny, nx, phi_cut=0.0, connectivity=6, labels=False, faces=False):
+def _class_plane(a, ny, nx, what):
+    if a is None:
+        return None
+    p = np.ascontiguousarray(a, dtype=np.uint8)
+    if p.shape != (int(ny), int(nx)):
+        raise TypeError("%s must have shape [ny][nx]" % what)
+    return p
+
+
+def props_face(L, prefix, handle, ny, nx):
+    """[2][ny][nx] uint8: the class bytes (0 S, 1 R, 2 B, 3 N) of the lowest and the highest own plane of one context, those of its last
+    lbmpm_<prefix>_clusters call -- what the slab below takes as `above` ([0]) and the slab above as `below` ([1])"""
+    from ._lib import U8P, check
+    out = np.empty((2, int(ny), int(nx)), dtype=np.uint8)
+    name = "lbmpm_%s_cluster_props_face" % prefix
+    check(getattr(L, name)(handle, out.ctypes.data_as(U8P)), name)
+    return out
+
+
+def props_table(L, prefix, handle, count, ny, nx, below=None, above=None):
+    """[count][14] int64 of one context through lbmpm_<prefix>_cluster_props: the properties of the clusters of its last
+    lbmpm_<prefix>_clusters call (count: that call's); below / above: [ny][nx] class planes of the neighbouring slabs, None at the
+    lattice's ends"""
+    from ._lib import I64P, U8P, check
+    dn, up = _class_plane(below, ny, nx, "below"), _class_plane(above, ny, nx, "above")
+    out = np.zeros((int(count), len(PROP_COLUMNS)), dtype=np.int64)
+    name = "lbmpm_%s_cluster_props" % prefix
+    check(getattr(L, name)(handle, None if dn is None else dn.ctypes.data_as(U8P), None if up is None else up.ctypes.data_as(U8P),
+                           out.ctypes.data_as(I64P)), name)
+    return out
+
+
+def stacked_props(slabs, parts):
+    """the slabs of one process, lowest first, after every one's clusters_part (parts): the slabs hand their face planes to each other
+    and every part gains its property table"""
+    faces = [s.cluster_props_face() for s in slabs]
+    for k, (s, part) in enumerate(zip(slabs, parts)):
+        part["props"] = s.cluster_props_part(part["table"].shape[0], faces[k - 1][1] if k else None, faces[k + 1][0] if k + 1 < len(slabs) else None)
+    return parts
+
+
+def faces_from_neighbours(mine, rank, world, group, device):
+    """collective: every rank gives the [2][ny][nx] class planes of its slab and takes (below, above): the highest plane of rank - 1 and
+    the lowest of rank + 1 (None at the ends).  One all_gather of 2 * ny * nx bytes, through device memory under nccl, host memory
+    under gloo"""
+    if world == 1:
+        return None, None
+    import torch
+    import torch.distributed as dist
+    dev = torch.device("cuda", device) if dist.get_backend(group) == "nccl" else torch.device("cpu")
+    t = torch.from_numpy(np.ascontiguousarray(mine, dtype=np.uint8)).to(dev)
+    every = [torch.empty_like(t) for _ in range(world)]
+    dist.all_gather(every, t, group=group)
+    return (every[rank - 1][1].cpu().numpy() if rank else None), (every[rank + 1][0].cpu().numpy() if rank + 1 < world else None)
+
+
+def take(L, prefix, handle, planes, ny, nx, phi_cut=0.0, connectivity=6, labels=False, faces=False, props=False, below=None, above=None):
     """One context through lbmpm_<prefix>_clusters*: dict(table [n][5] int64, labels [planes][ny][nx] uint32 when asked for, face_labels /
-    face_classes [2][ny][nx] when asked for)"""
+    face_classes [2][ny][nx] when asked for, props [n][14] int64 when asked for -- with below / above, the class planes of the
+    neighbouring slabs, where there are such)"""
     import ctypes as C
     from ._lib import I64P, U8P, U32P, ClustersConfig, check
     cfg = ClustersConfig(float(phi_cut), int(connectivity), 0)
@@ -188,6 +363,8 @@ def take(L, prefix, handle, planes, ny, nx, phi_cut=0.0, connectivity=6, labels=
         out["face_labels"] = np.empty((2, int(ny), int(nx)), dtype=np.uint32)
         out["face_classes"] = np.empty((2, int(ny), int(nx)), dtype=np.uint8)
         check(getattr(L, name + "_faces")(handle, out["face_labels"].ctypes.data_as(U32P), out["face_classes"].ctypes.data_as(U8P)), name + "_faces")
+    if props:
+        out["props"] = props_table(L, prefix, handle, n.value, ny, nx, below, above)
     return out
 
 

@@ -1166,6 +1166,7 @@ __global__ void rk3d_setup_solidnbr(RK3Dev p, uint32_t *solidnbr)
 #include "rk3d_integrals.h"
 #include "rk3d_clusters.h"
 #include "rk3d_morphology.h"
+#include "rk3d_cluster_props.h"
 
 // the fields of the last lbmpm_rk3d_phase_field(ctx, 1) (rhoR, rhoB, vx, vy, vz in `diag`, the phase field in `phi`; pitch, plane2 and
 // halo planes as lbmpm_rk3d_get_field reads them), the mask from the device's flags
@@ -1219,6 +1220,7 @@ struct lbmpm_rk3d {
     double *integ = nullptr;         // lbmpm_rk3d_integrals: chunk partials + the table (rk3d_integrals.h), allocated by the first call
     ClState cl;                      // lbmpm_rk3d_clusters: classes, labels, rows (rk3d_clusters.h), allocated by the first call
     uint8_t *morph = nullptr;        // lbmpm_rk3d_morphology: classes [nzl + 1][ny][nx] (rk3d_morphology.h), allocated by the first call
+    CpState cprops;                  // lbmpm_rk3d_cluster_props: classes [nzl + 2][ny][nx], accumulators (rk3d_cluster_props.h), allocated by the first call
     uint32_t *purA = nullptr, *purB = nullptr;       // row flags of the q23 storage, swapped with fA / fB
     double *send_up = nullptr, *send_dn = nullptr, *recv_below = nullptr, *recv_above = nullptr;
     std::vector<uint8_t> h_domain;   // owned planes only, [nzl][ny][nx]
@@ -2584,6 +2586,34 @@ extern "C" int lbmpm_rk3d_clusters_faces(lbmpm_rk3d *c, uint32_t *labels, uint8_
 {
     LBMPM_REQUIRE(c && labels && classes, "lbmpm_rk3d_clusters_faces: null argument");
     return clusters_faces("lbmpm_rk3d_clusters_faces", c->cl, c->steps, c->cfg.device, c->stream, labels, classes);
+}
+
+// Per-cluster properties beside the table of the last lbmpm_rk3d_clusters (rk3d_cluster_props.h; the definition: include/lbmpm.h), from
+// the fields of the last lbmpm_rk3d_phase_field(ctx, 1)
+static int cluster_props_ready(const char *who, lbmpm_rk3d *c)
+{
+    if (c->cl.valid && c->cl.at_step == c->steps && (c->observed_at != c->steps || !c->diag)) {
+        set_error("%s: the fields are stale: call lbmpm_rk3d_phase_field(ctx, 1) after the last step (observed at step %lld, now %lld)", who,
+                  (long long)c->observed_at, (long long)c->steps);
+        return LBMPM_ERR_STATE;
+    }
+    return LBMPM_OK;
+}
+
+extern "C" int lbmpm_rk3d_cluster_props_face(lbmpm_rk3d *c, uint8_t *classes)
+{
+    LBMPM_REQUIRE(c && classes, "lbmpm_rk3d_cluster_props_face: null argument");
+    { const int rc = cluster_props_ready("lbmpm_rk3d_cluster_props_face", c); if (rc) return rc; }
+    const Rk3dIntLoader load{c->flags, c->diag, c->phi, (unsigned)c->nx, (unsigned)c->pitch, c->plane2, c->vol};
+    return cluster_props_face("lbmpm_rk3d_cluster_props_face", load, c->cl, c->cprops, c->steps, c->cfg.device, c->mem, c->stream, c->stream, classes);
+}
+
+extern "C" int lbmpm_rk3d_cluster_props(lbmpm_rk3d *c, const uint8_t *below, const uint8_t *above, int64_t *out)
+{
+    LBMPM_REQUIRE(c && out, "lbmpm_rk3d_cluster_props: null argument");
+    { const int rc = cluster_props_ready("lbmpm_rk3d_cluster_props", c); if (rc) return rc; }
+    const Rk3dIntLoader load{c->flags, c->diag, c->phi, (unsigned)c->nx, (unsigned)c->pitch, c->plane2, c->vol};
+    return cluster_props_run("lbmpm_rk3d_cluster_props", load, c->cl, c->cprops, c->steps, c->cfg.device, c->mem, c->stream, c->stream, below, above, out);
 }
 
 // Phase morphology of the fields of the last lbmpm_rk3d_phase_field(ctx, 1) (rk3d_morphology.h; the definition: include/lbmpm.h).  The

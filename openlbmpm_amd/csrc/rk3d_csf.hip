@@ -1013,6 +1013,7 @@ __global__ __launch_bounds__(256) void csf3d_import(CsfDev p, double *f, const d
 #include "rk3d_tracer_integrals.h"
 #include "rk3d_clusters.h"
 #include "rk3d_morphology.h"
+#include "rk3d_cluster_props.h"
 
 // what LBMPM_RK3DCSF_REC_RHO_R .. _REC_PHI hand out, from the populations: cell_state<FIRST, true>, the velocity with half the force and
 // the phase field in the arithmetic of csf3d_observe<FIRST, true>; own planes only (plane 0 is lattice plane p.glo)
@@ -1083,6 +1084,7 @@ struct lbmpm_rk3dcsf {
     double *trinteg = nullptr;     // lbmpm_rk3dcsf_tracer_integrals: the same for the tracers' tables (rk3d_tracer_integrals.h)
     ClState cl;                    // lbmpm_rk3dcsf_clusters: classes, labels, rows (rk3d_clusters.h), allocated by the first call
     uint8_t *morph = nullptr;      // lbmpm_rk3dcsf_morphology: classes [own planes + 1][ny][nx] (rk3d_morphology.h), allocated by the first call
+    CpState cprops;                // lbmpm_rk3dcsf_cluster_props: classes [own planes + 2][ny][nx], accumulators (rk3d_cluster_props.h), allocated by the first call
     double *obs = nullptr;         // staging of the observe kernel: rho [2][N], u [3][N], phi [N] (the populations [2][N][19] come and go with the call)
     lbmpm::EventPool pool;
     size_t timed_steps = 0;
@@ -1846,6 +1848,26 @@ extern "C" int lbmpm_rk3dcsf_clusters_faces(lbmpm_rk3dcsf *c, uint32_t *labels, 
 {
     LBMPM_REQUIRE(c && labels && classes, "lbmpm_rk3dcsf_clusters_faces: null argument");
     return clusters_faces("lbmpm_rk3dcsf_clusters_faces", c->cl, c->steps, c->cfg.device, c->stream, labels, classes);
+}
+
+// Per-cluster properties beside the table of the last lbmpm_rk3dcsf_clusters (rk3d_cluster_props.h; the definition: include/lbmpm.h),
+// from the populations in registers.  (A context without a state has no clusters: clusters_current says LBMPM_ERR_STATE.)
+extern "C" int lbmpm_rk3dcsf_cluster_props_face(lbmpm_rk3dcsf *c, uint8_t *classes)
+{
+    LBMPM_REQUIRE(c && classes, "lbmpm_rk3dcsf_cluster_props_face: null argument");
+    const char *who = "lbmpm_rk3dcsf_cluster_props_face";
+    const CsfDev p = make_dev(c);
+    if (c->first) return cluster_props_face(who, CsfIntLoader<true>{p}, c->cl, c->cprops, c->steps, c->cfg.device, c->mem, nullptr, c->stream, classes);
+    return cluster_props_face(who, CsfIntLoader<false>{p}, c->cl, c->cprops, c->steps, c->cfg.device, c->mem, nullptr, c->stream, classes);
+}
+
+extern "C" int lbmpm_rk3dcsf_cluster_props(lbmpm_rk3dcsf *c, const uint8_t *below, const uint8_t *above, int64_t *out)
+{
+    LBMPM_REQUIRE(c && out, "lbmpm_rk3dcsf_cluster_props: null argument");
+    const char *who = "lbmpm_rk3dcsf_cluster_props";
+    const CsfDev p = make_dev(c);
+    if (c->first) return cluster_props_run(who, CsfIntLoader<true>{p}, c->cl, c->cprops, c->steps, c->cfg.device, c->mem, nullptr, c->stream, below, above, out);
+    return cluster_props_run(who, CsfIntLoader<false>{p}, c->cl, c->cprops, c->steps, c->cfg.device, c->mem, nullptr, c->stream, below, above, out);
 }
 
 // Phase morphology of the recorded state (rk3d_morphology.h; the definition: include/lbmpm.h), classified from the populations in registers.

@@ -217,12 +217,26 @@ class RK3DSlab(SlabTransportCalls):
         from .clusters import take
         return take(self._L, "rk3d", self._h, self.nzl, self.ny, self.nx, phi_cut, connectivity, labels, faces)
 
-    def clusters(self, phi_cut=0.0, connectivity=6, labels=False):
+    def cluster_props_face(self):
+        """[2][ny][nx] uint8: the class bytes of the slab's lowest and highest plane under its last clusters_part -- what the slabs
+        beside it pass to cluster_props_part"""
+        from .clusters import props_face
+        return props_face(self._L, "rk3d", self._h, self.ny, self.nx)
+
+    def cluster_props_part(self, count, below=None, above=None):
+        """[count][14] int64: the properties of the clusters of the slab's last clusters_part (count: its rows), reduced on the device
+        (lbmpm_rk3d_cluster_props); below / above: the class planes of the slabs beside it (None: the lattice ends there)"""
+        from .clusters import props_table
+        return props_table(self._L, "rk3d", self._h, count, self.ny, self.nx, below, above)
+
+    def clusters(self, phi_cut=0.0, connectivity=6, labels=False, props=False):
         """clusters.Clusters of the slab's own planes: the connected cells of each phase of phi of the last phase_field(diagnostics=True),
-        labelled on the device (lbmpm_rk3d_clusters); LbmpmError (LBMPM_ERR_STATE) when a step has been taken since"""
+        labelled on the device (lbmpm_rk3d_clusters); LbmpmError (LBMPM_ERR_STATE) when a step has been taken since.  props=True: with
+        the property table (faces, elements, plane sum, mass and momentum per cluster), reduced on the device"""
         from .clusters import Clusters
         got = self.clusters_part(phi_cut, connectivity, labels, faces=False)
-        return Clusters(got["table"], self.nx, self.ny, self.nz, got.get("labels"))
+        table = self.cluster_props_part(got["table"].shape[0]) if props else None
+        return Clusters(got["table"], self.nx, self.ny, self.nz, got.get("labels"), table)
 
     def morphology_face(self, phi_cut=0.0):
         """[ny][nx] uint8: the classes of the slab's lowest plane -- what the slab below passes to morphology_part as `above`"""
@@ -364,14 +378,18 @@ class RK3DCluster:
         s0 = self.slabs[0]
         return Integrals(fresh(lambda: np.concatenate([s.integrals().planes for s in self.slabs], axis=0), self.observe), s0.nx, s0.ny)
 
-    def clusters(self, phi_cut=0.0, connectivity=6, labels=False):
+    def clusters(self, phi_cut=0.0, connectivity=6, labels=False, props=False):
         """clusters.Clusters of the whole lattice: the slabs' tables joined through their face planes (equal to the undivided lattice's);
-        observe() first when the phase field is stale"""
-        from .clusters import merged
+        observe() first when the phase field is stale.  props=True: with the property table -- the slabs hand each other their class
+        planes, every slab reduces its own rows, the rows are added (bit-equal to the undivided lattice's)"""
+        from .clusters import merged, stacked_props
         from .integrals import fresh
         s0 = self.slabs[0]
-        parts = fresh(lambda: [s.clusters_part(phi_cut, connectivity, labels) for s in self.slabs], self.observe)
-        return merged(parts, s0.nx, s0.ny, s0.nz, connectivity, labels)
+
+        def take():
+            parts = [s.clusters_part(phi_cut, connectivity, labels) for s in self.slabs]
+            return stacked_props(self.slabs, parts) if props else parts
+        return merged(fresh(take, self.observe), s0.nx, s0.ny, s0.nz, connectivity, labels)
 
     def morphology(self, phi_cut=0.0):
         """morphology.Morphology of the whole lattice: every slab joins the lowest plane of the slab over it on its device (bit-equal to
@@ -572,12 +590,22 @@ class RK3DDistributed:
         t = self.gather(fresh(lambda: self.slab.integrals().planes, self.observe))
         return None if t is None else Integrals(t, self.slab.nx, self.slab.ny)
 
-    def clusters(self, phi_cut=0.0, connectivity=6, labels=False):
+    def clusters(self, phi_cut=0.0, connectivity=6, labels=False, props=False):
         """collective: rank 0 returns the clusters.Clusters of the whole lattice (the ranks' tables and face planes, joined there; with
-        labels=True the label planes too), the others None; observe() first when the phase field is stale"""
-        from .clusters import gather_merged
+        labels=True the label planes too), the others None; observe() first when the phase field is stale.  props=True: with the
+        property table -- one all_gather of 2 ny nx class bytes first, every rank reduces its own rows, rank 0 adds them"""
+        from .clusters import faces_from_neighbours, gather_merged
         from .integrals import fresh
-        part = fresh(lambda: self.slab.clusters_part(phi_cut, connectivity, labels), self.observe)
+
+        def take():
+            part = self.slab.clusters_part(phi_cut, connectivity, labels)
+            if props:
+                part["props_face"] = self.slab.cluster_props_face()
+            return part
+        part = fresh(take, self.observe)
+        if props:
+            below, above = faces_from_neighbours(part.pop("props_face"), self.rank, self.world, self.group, self.device)
+            part["props"] = self.slab.cluster_props_part(part["table"].shape[0], below, above)
         return gather_merged(part, self.rank, self.world, self.group, self.slab.nx, self.slab.ny, self.slab.nz, connectivity, labels)
 
     def morphology(self, phi_cut=0.0):

@@ -250,12 +250,26 @@ class RK3DCSFSolver(SlabTransportCalls):
         from .clusters import take
         return take(self._L, "rk3dcsf", self._h, self.nz - self.ghost[0] - self.ghost[1], self.ny, self.nx, phi_cut, connectivity, labels, faces)
 
-    def clusters(self, phi_cut=0.0, connectivity=6, labels=False):
+    def cluster_props_face(self):
+        """[2][ny][nx] uint8: the class bytes of the lowest and the highest own plane under the last clusters_part -- what the slabs
+        beside this one pass to cluster_props_part"""
+        from .clusters import props_face
+        return props_face(self._L, "rk3dcsf", self._h, self.ny, self.nx)
+
+    def cluster_props_part(self, count, below=None, above=None):
+        """[count][14] int64: the properties of the clusters of the last clusters_part (count: its rows), reduced on the device
+        (lbmpm_rk3dcsf_cluster_props); below / above: the class planes of the slabs beside this one (None: the lattice ends there)"""
+        from .clusters import props_table
+        return props_table(self._L, "rk3dcsf", self._h, count, self.ny, self.nx, below, above)
+
+    def clusters(self, phi_cut=0.0, connectivity=6, labels=False, props=False):
         """clusters.Clusters of the own planes: the connected cells of each phase of what get("rec_phi") hands out, classified from the
-        populations and labelled on the device (lbmpm_rk3dcsf_clusters) -- nothing staged, nothing to call beforehand"""
+        populations and labelled on the device (lbmpm_rk3dcsf_clusters) -- nothing staged, nothing to call beforehand.  props=True:
+        with the property table (faces, elements, plane sum, mass and momentum per cluster), reduced on the device"""
         from .clusters import Clusters
         got = self.clusters_part(phi_cut, connectivity, labels, faces=False)
-        return Clusters(got["table"], self.nx, self.ny, self.global_nz, got.get("labels"))
+        table = self.cluster_props_part(got["table"].shape[0]) if props else None
+        return Clusters(got["table"], self.nx, self.ny, self.global_nz, got.get("labels"), table)
 
     def morphology_face(self, phi_cut=0.0):
         """[ny][nx] uint8: the classes of the lowest own plane -- what the slab below passes to morphology_part as `above`"""
@@ -427,10 +441,13 @@ class RK3DCSFCluster:
         from .integrals import Integrals
         return Integrals(np.concatenate([s.integrals().planes for s in self.slabs], axis=0), self.nx, self.ny)
 
-    def clusters(self, phi_cut=0.0, connectivity=6, labels=False):
-        """clusters.Clusters of the whole lattice: the slabs' tables joined through their face planes (equal to the undivided lattice's)"""
-        from .clusters import merged
-        return merged([s.clusters_part(phi_cut, connectivity, labels) for s in self.slabs], self.nx, self.ny, self.nz, connectivity, labels)
+    def clusters(self, phi_cut=0.0, connectivity=6, labels=False, props=False):
+        """clusters.Clusters of the whole lattice: the slabs' tables joined through their face planes (equal to the undivided lattice's).
+        props=True: with the property table -- the slabs hand each other their class planes, every slab reduces its own rows, the rows
+        are added (bit-equal to the undivided lattice's)"""
+        from .clusters import merged, stacked_props
+        parts = [s.clusters_part(phi_cut, connectivity, labels) for s in self.slabs]
+        return merged(stacked_props(self.slabs, parts) if props else parts, self.nx, self.ny, self.nz, connectivity, labels)
 
     def morphology(self, phi_cut=0.0):
         """morphology.Morphology of the whole lattice: every slab joins the lowest own plane of the slab over it on its device, the top
@@ -652,11 +669,15 @@ class RK3DCSFDistributed:
         t = self.gather(self.slab.integrals().planes)
         return None if t is None else Integrals(t, self.shape[2], self.shape[1])
 
-    def clusters(self, phi_cut=0.0, connectivity=6, labels=False):
+    def clusters(self, phi_cut=0.0, connectivity=6, labels=False, props=False):
         """collective: rank 0 returns the clusters.Clusters of the whole lattice (the ranks' tables and face planes, joined there; with
-        labels=True the label planes too), the others None"""
-        from .clusters import gather_merged
+        labels=True the label planes too), the others None.  props=True: with the property table -- one all_gather of 2 ny nx class
+        bytes first, every rank reduces its own rows, rank 0 adds them"""
+        from .clusters import faces_from_neighbours, gather_merged
         part = self.slab.clusters_part(phi_cut, connectivity, labels)
+        if props:
+            below, above = faces_from_neighbours(self.slab.cluster_props_face(), self.rank, self.world, None, self._dev.index)
+            part["props"] = self.slab.cluster_props_part(part["table"].shape[0], below, above)
         return gather_merged(part, self.rank, self.world, None, self.shape[2], self.shape[1], self.nz, connectivity, labels)
 
     def morphology(self, phi_cut=0.0):
