@@ -499,6 +499,30 @@ enum { LBMPM_INT_CELLS = 0, LBMPM_INT_CELLS_R, LBMPM_INT_MASS_R, LBMPM_INT_MASS_
  * (never calls it itself: on slabs the halo exchange comes first, which is the caller's).  One stream synchronisation, nz_local * 96
  * bytes copied */
 int lbmpm_rk3d_integrals(lbmpm_rk3d *ctx, double *out);
+/* Steady-state monitor of the 3-D solvers: how far the recorded state -- the state, the planes and the mask of lbmpm_*_integrals -- has
+ * moved since a snapshot of it (csrc/rk3d_change.h).  change_mark stores ux, uy, uz, phi of every own cell on the device (32 bytes per
+ * own lattice cell, allocated by the first mark and counted by lbmpm_*_device_bytes) and the step counter; change reduces, for every plane
+ * z the context owns, LBMPM_CHANGE_COLS doubles over the plane's fluid cells, "now" against the snapshot "0", every term evaluated left to
+ * right with one rounding per operation and summed in the plane integrals' fixed order: the table is the same bit for bit however the
+ * lattice is cut into slabs (a snapshot belongs to its cell: slabs exchange nothing) and on every repeat of the call.
+ *   CELLS fluid cells | CELLS_R finite cells with phi > 0 | FLIPPED cells where (phi > 0) differs from (phi0 > 0) | U2_R, U2_B sum of
+ *   ux ux + uy uy + uz uz over the cells with phi > 0, phi <= 0 | DU2_R, DU2_B sum of dx dx + dy dy + dz dz, dx = ux - ux0 .., split by the
+ *   current phi | DPHI2 sum of d d, d = phi - phi0 | DUMAX2 max of the DU2 term | DPHIMAX max of |phi - phi0| | NONFINITE the cells that
+ *   are not finite
+ * A cell where any of rho_R, rho_B, u, phi or any of the four snapshot values is not finite counts in CELLS and NONFINITE and contributes
+ * to nothing else.  sqrt((DU2_R + DU2_B) / (U2_R + U2_B)) is the relative L2 change of the velocity, the criterion the reference wrote
+ * and never called (ShanChenD2Q9.py:831-850; it compares speeds, which never differ by more than the vectors do). */
+#define LBMPM_CHANGE_COLS 11
+enum { LBMPM_CH_CELLS = 0, LBMPM_CH_CELLS_R, LBMPM_CH_FLIPPED, LBMPM_CH_U2_R, LBMPM_CH_U2_B, LBMPM_CH_DU2_R, LBMPM_CH_DU2_B,
+       LBMPM_CH_DPHI2, LBMPM_CH_DUMAX2, LBMPM_CH_DPHIMAX, LBMPM_CH_NONFINITE };
+/* the snapshot of the recorded state and the step counter.  LBMPM_ERR_STATE where lbmpm_rk3d_integrals refuses (a step since the last
+ * lbmpm_rk3d_phase_field(ctx, 1)).  Enqueued on the context's stream: no synchronisation */
+int lbmpm_rk3d_change_mark(lbmpm_rk3d *ctx);
+/* out: host [nz_local][LBMPM_CHANGE_COLS]; *steps_between (may be null): steps now minus steps at the mark; remark != 0: the current state
+ * replaces the snapshot in the same pass (also where it is not finite).  LBMPM_ERR_STATE before a mark, where lbmpm_rk3d_integrals
+ * refuses, and after any lbmpm_rk3d_set_density / set_macro / set_pdf / set_state since the mark (they void the snapshot).  One stream
+ * synchronisation, nz_local * 88 bytes copied */
+int lbmpm_rk3d_change(lbmpm_rk3d *ctx, int remark, int64_t *steps_between, double *out);
 /* Phase clusters of the 3-D solvers: the connected components of each phase, labelled on the device (csrc/rk3d_clusters.h).
  *   Cells       the fluid cells of the planes the context owns -- the planes and the mask of lbmpm_*_integrals.  Perturbation model: phi
  *               of the last lbmpm_rk3d_phase_field(ctx, 1) (LBMPM_ERR_STATE when a step has been taken since, as for the integrals); CSF
@@ -746,6 +770,11 @@ int lbmpm_rk3dcsf_get_field(lbmpm_rk3dcsf *ctx, int field, double *out);
 /* out: host [own planes][LBMPM_INTEGRAL_COLS] (nz - ghost_lo - ghost_hi rows), see lbmpm_rk3d_integrals; reduced from the populations in
  * registers (no per-cell staging).  LBMPM_ERR_STATE before set_macro / set_pdf; valid wherever get_field(REC_*) is, slabs included */
 int lbmpm_rk3dcsf_integrals(lbmpm_rk3dcsf *ctx, double *out);
+/* steady-state monitor, see lbmpm_rk3d_change_mark / lbmpm_rk3d_change: u and phi of the snapshot are what LBMPM_RK3DCSF_REC_VX .. _REC_PHI
+ * hand out, from the populations in registers.  out: host [own planes][LBMPM_CHANGE_COLS].  LBMPM_ERR_STATE before set_macro / set_pdf,
+ * for change before a mark and after a set_macro / set_pdf since the mark; valid wherever lbmpm_rk3dcsf_integrals is, slabs included */
+int lbmpm_rk3dcsf_change_mark(lbmpm_rk3dcsf *ctx);
+int lbmpm_rk3dcsf_change(lbmpm_rk3dcsf *ctx, int remark, int64_t *steps_between, double *out);
 /* phase clusters of the own planes, see lbmpm_rk3d_clusters: phi is what LBMPM_RK3DCSF_REC_PHI hands out, from the populations in
  * registers (no dense phi staged); labels [own planes][ny][nx] */
 int lbmpm_rk3dcsf_clusters(lbmpm_rk3dcsf *ctx, const lbmpm_clusters_config *cfg, int64_t *count);

@@ -45,6 +45,16 @@ morphology_phi_cut: the band around phi = 0 that belongs to neither phase): /Mor
 sums, class pairs, squares and cubes per plane; the whole lattice's table on rank 0 in a distributed run), /Morphology/Steps and
 /Morphology/Columns at the end; the interfacial area, the wetted fraction, the Euler characteristics and the capillary pressure go to
 the log.
+
+steady_every = N > 0: the steady-state monitor (openlbmpm_amd/change.py; reduced on the device against a snapshot kept there, 32 bytes per
+lattice cell).  At every multiple of N the run reaches (step 0, the first one after a restart_from and the last step, where it is one,
+included; only multiples: rows over unequal intervals would not be comparable) the first visit marks and every later one takes the
+change since the visit before and marks again: /Steady/PlanesAtStep<step> [nz][11] (rank 0's in a distributed run: the whole lattice's
+table), and at the end /Steady/Steps (the steps with a table, not the marking one), /Steady/Columns, /Steady/Criteria [rows][8] (step,
+steps_between, velocity_change, velocity_change_R, velocity_change_B, phase_change, flipped, max_du) and /Steady/CriteriaColumns; the
+summary goes to the log.  steady_tol > 0 (needs steady_every): the run ends at the first visit where Change.is_steady(steady_tol,
+steady_phase_tol) holds -- its last record, tables and sync are taken at that step, which self.steady_step then names (None: never met;
+distributed: rank 0 decides and every rank hears of it before the next step is issued).  A checkpoint does not hold the snapshot.
 """
 import os
 
@@ -122,7 +132,7 @@ class RKColorGradient3D:
     def __init__(self, pathIniFile, output_dir=None, domain=None, device=0, record_every=None, num_buffering_layers=10,
                  structure_path=None, initial_dir=None, record_pdf=False, restart_from=None, checkpoint_every=0, csf_bulk_epsilon=0.0,
                  csf_transport=None, integrals_every=0, clusters_every=0, clusters_connectivity=6, morphology_every=0,
-                 morphology_phi_cut=0.0, clusters_props=False):
+                 morphology_phi_cut=0.0, clusters_props=False, steady_every=0, steady_tol=0.0, steady_phase_tol=None):
         self.pathIni = pathIniFile
         self.par = config.read_rk3d(pathIniFile)
         self.output_dir = output_dir or os.path.expanduser("~/LBMResults3D")       # main.py:28
@@ -143,6 +153,12 @@ class RKColorGradient3D:
         self.clusters_props = bool(clusters_props)       # with clusters_every: the property table beside every cluster table
         # 0: no /Morphology group, no extra stop of the step loop
         self.morphology_every, self.morphology_phi_cut = int(morphology_every), float(morphology_phi_cut)
+        # 0: no /Steady group, no extra stop of the step loop, nothing kept on the device; steady_tol 0: monitor only
+        self.steady_every, self.steady_tol = int(steady_every), float(steady_tol)
+        self.steady_phase_tol = None if steady_phase_tol is None else float(steady_phase_tol)
+        if self.steady_tol > 0 and self.steady_every <= 0:
+            raise config.ConfigError("steady_tol = %g needs steady_every > 0: the cadence at which the criterion is looked at" % self.steady_tol)
+        self.steady_step = None         # the step at which the criterion was met
         self.gather_records = True
         self.records = 0
         self.physicalVX = self.physicalVY = self.physicalVZ = None
@@ -292,6 +308,7 @@ class RKColorGradient3D:
             integrals = sim.solver.integrals
             clusters = sim.solver.clusters
             morphology = sim.solver.morphology
+            mark_change, change = sim.solver.mark_change, sim.solver.change
             self.z0, self.nzl = 0, self.zDomain
             if whole_arrays:
                 import torch.distributed as dist
@@ -317,6 +334,7 @@ class RKColorGradient3D:
             integrals = sim.integrals
             clusters = sim.clusters
             morphology = sim.morphology
+            mark_change, change = sim.mark_change, sim.change
             self.z0, self.nzl = sim.z0, sim.nzl
             if self.gather_records:
                 self._gather = sim.gather
@@ -329,6 +347,7 @@ class RKColorGradient3D:
             integrals = lambda: fresh(slab.integrals, observe)
             clusters = lambda **kw: fresh(lambda: slab.clusters(**kw), observe)
             morphology = lambda cut: fresh(lambda: slab.morphology(cut), observe)
+            mark_change, change = (lambda: fresh(slab.mark_change, observe)), (lambda: fresh(slab.change, observe))
             self.z0, self.nzl = 0, self.zDomain
         self._slab, self._observe = slab, observe
         done = 0
@@ -344,15 +363,29 @@ class RKColorGradient3D:
         cevery = self.clusters_every
         ckw = dict(props=True) if self.clusters_props else {}
         mevery = self.morphology_every
+        severy = self.steady_every
         more = ((("Integrals", "PlaneIntegrals"),) if every > 0 and rank == 0 else ()) + ((("Clusters", "PhaseClusters"),) if cevery > 0 and rank == 0 else ()) + \
-            ((("Morphology", "PhaseMorphology"),) if mevery > 0 and rank == 0 else ())
+            ((("Morphology", "PhaseMorphology"),) if mevery > 0 and rank == 0 else ()) + ((("Steady", "SteadyState"),) if severy > 0 and rank == 0 else ())
         out = ResultFile(self.output_dir, name, GROUPS + more) if writes else None
         self.integral_steps, self.cluster_steps, self.morphology_steps = [], [], []
+        self.steady_steps, self.steady_criteria, self.steady_step = [], [], None
+        marked = False
+
+        def steady_visit():
+            """the monitor's visit at `done`: the first one marks, the others take the table and mark again; True: the criterion is met"""
+            nonlocal marked
+            if not marked:
+                mark_change()
+                marked = True
+                return False
+            return self._steady(change(), out, done)
         self.result_path = out.path if out else None
         # distributed: every rank checks its own slab, the verdict is collective (all ranks raise together, none is left in an exchange)
         self._guard = RecordGuard("rk3d", slab.num_fluid_nodes, getattr(self, "nan_guard", "raise"), collective=self._distributed(), device=self.device)
         while done < self.timeSteps:
             self._step_now = done
+            if severy > 0 and done % severy == 0 and steady_visit() and self.steady_tol > 0:
+                break                              # (before this step's record: the tail below takes it, as at the end of a run of `done` steps)
             if done % self.timeInterval == 0:      # (a restarted run records its first step again: the counters of the checkpoint precede it)
                 observe()
                 self._record(slab, out)
@@ -369,6 +402,8 @@ class RKColorGradient3D:
                 n = min(n, cevery - done % cevery)
             if mevery > 0:
                 n = min(n, mevery - done % mevery)
+            if severy > 0:
+                n = min(n, severy - done % severy)
             if self.checkpoint_every > 0:
                 n = min(n, self.checkpoint_every - done % self.checkpoint_every)
             step(n)
@@ -401,6 +436,15 @@ class RKColorGradient3D:
                 from .morphology import column_bytes as morphology_column_bytes
                 out.write("Morphology", "Steps", np.array(self.morphology_steps, dtype=np.int64))
                 out.write("Morphology", "Columns", morphology_column_bytes())
+        if severy > 0:
+            if done % severy == 0 and (not self.steady_steps or self.steady_steps[-1] != done):
+                steady_visit()                   # the run's last step is a multiple
+            if rank == 0:
+                from .change import CRITERIA_COLUMNS, column_bytes as change_column_bytes, criteria_column_bytes
+                out.write("Steady", "Steps", np.array(self.steady_steps, dtype=np.int64))
+                out.write("Steady", "Columns", change_column_bytes())
+                out.write("Steady", "Criteria", np.array(self.steady_criteria, dtype=np.float64).reshape(-1, len(CRITERIA_COLUMNS)))
+                out.write("Steady", "CriteriaColumns", criteria_column_bytes())
         slab.sync()
         self.solver = sim
         return self.result_path
@@ -432,6 +476,24 @@ class RKColorGradient3D:
             if out is not None:
                 out.write("Morphology", "PlanesAtStep%d" % step, t.planes)
             self._guard.log.info("rk3d morphology step %d: %s", step, " ".join("%s=%s" % kv for kv in t.summary().items()))
+
+    def _steady(self, t, out, step):
+        """t: the Change of the whole lattice at `step` (None on the other ranks of a distributed run); True when the criterion is met --
+        rank 0's verdict, which every rank hears of here (one all-reduce of a flag) before anybody issues the next step"""
+        self.change = t
+        self.steady_steps.append(int(step))
+        met = False
+        if t is not None:
+            self.steady_criteria.append(t.criteria(step))
+            if out is not None:
+                out.write("Steady", "PlanesAtStep%d" % step, t.planes)
+            self._guard.log.info("rk3d steady step %d: %s", step, " ".join("%s=%s" % kv for kv in t.summary().items()))
+            met = self.steady_tol > 0 and t.is_steady(self.steady_tol, self.steady_phase_tol)
+        if self.steady_tol > 0 and self._guard.anyone(met):
+            if self.steady_step is None:
+                self.steady_step = int(step)
+            return True
+        return False
 
     def _record(self, slab, out):
         k = self.records

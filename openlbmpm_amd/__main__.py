@@ -16,6 +16,8 @@
                                                   (/Clusters/PropsAtStep<step>); ganglia and mobile ganglia to the log
         [--morphology-every N]                    rk3d: cells, class pairs, squares and cubes per plane, counted on the device, every N steps (/Morphology
         [--morphology-phi-cut c]                  of the result file); interfacial area, wetted fraction, Euler characteristics, capillary pressure to the log
+        [--steady-every N]                        rk3d: the change of velocity and phase field between multiples of N steps, reduced on the device (/Steady of
+        [--steady-tol t] [--steady-phase-tol p]   the result file); with a tolerance the run ends at the first multiple where the change is within it
 """
 import argparse
 import sys
@@ -39,7 +41,7 @@ def _rank_device(device):
     return device
 
 
-def main(argv=None):
+def parser():
     ap = argparse.ArgumentParser(prog="python -m openlbmpm_amd")
     ap.add_argument("model", choices=["rk", "sc", "tr", "rk3d", "tr3d"], help="rk = colour gradient (RKtwophasesetup2D.ini); "
                                                        "sc = Shan-Chen / EFS (twophasesetup.ini + efs2D.ini|shanchen2D.ini)")
@@ -64,7 +66,19 @@ def main(argv=None):
                     help="rk3d: every N steps the phase morphology (cells, density sums, class pairs, squares and cubes per plane), counted on the device, "
                          "to /Morphology of the result file; interfacial area, wetted fraction, Euler characteristics and capillary pressure to the log; 0: off")
     ap.add_argument("--morphology-phi-cut", type=float, default=0.0, metavar="c", help="rk3d: cells with |phi| within c of 0 belong to neither phase")
-    a = ap.parse_args(argv)
+    ap.add_argument("--steady-every", type=int, default=0, metavar="N",
+                    help="rk3d: at every multiple of N steps the change of the velocity and the phase field since the multiple before (per plane: squared "
+                         "changes by phase, cells that changed colour, largest changes), reduced on the device against a snapshot kept there, to /Steady "
+                         "of the result file and the log; 0: off")
+    ap.add_argument("--steady-tol", type=float, default=0.0, metavar="t",
+                    help="rk3d, with --steady-every: end the run at the first multiple where the relative L2 change of the velocity is <= t (and that of the "
+                         "phase field <= --steady-phase-tol); 0: monitor only")
+    ap.add_argument("--steady-phase-tol", type=float, default=None, metavar="p", help="rk3d: the bound on the rms change of phi (default: --steady-tol)")
+    return ap
+
+
+def main(argv=None):
+    a = parser().parse_args(argv)
     t0 = time.time()
     if a.model == "rk":
         from .RKD2Q9 import RKColorGradientLBM
@@ -78,11 +92,14 @@ def main(argv=None):
         device = _rank_device(a.device)
         sim = RKColorGradient3D(a.ini_dir, output_dir=a.out, device=device, csf_transport=a.csf_transport, integrals_every=a.integrals_every,
                                 clusters_every=a.clusters_every, clusters_connectivity=a.clusters_connectivity, clusters_props=a.clusters_props,
-                                morphology_every=a.morphology_every, morphology_phi_cut=a.morphology_phi_cut)
+                                morphology_every=a.morphology_every, morphology_phi_cut=a.morphology_phi_cut, steady_every=a.steady_every,
+                                steady_tol=a.steady_tol, steady_phase_tol=a.steady_phase_tol)
         if a.steps is not None:
             sim.timeSteps = a.steps
         path = sim.runRKColorGradient3D()
-        steps, nodes = sim.timeSteps, sim.voidSpace
+        steps, nodes = sim.timeSteps if sim.steady_step is None else sim.steady_step, sim.voidSpace
+        if sim.steady_step is not None:
+            print("steady at step %d" % sim.steady_step)
     elif a.model == "tr3d":
         from .Transport3DRK import Transport3DRK
         sim = Transport3DRK(a.ini_dir, output_dir=a.out, device=_rank_device(a.device), csf_transport=a.csf_transport,

@@ -186,6 +186,8 @@ _SIGNATURES = {
     "lbmpm_rk3d_buffer": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), I64P]),
     "lbmpm_rk3d_get_field": (C.c_int, [C.c_void_p, C.c_int, F64P]),
     "lbmpm_rk3d_integrals": (C.c_int, [C.c_void_p, F64P]),
+    "lbmpm_rk3d_change_mark": (C.c_int, [C.c_void_p]),
+    "lbmpm_rk3d_change": (C.c_int, [C.c_void_p, C.c_int, I64P, F64P]),
     "lbmpm_rk3d_clusters": (C.c_int, [C.c_void_p, C.POINTER(ClustersConfig), I64P]),
     "lbmpm_rk3d_clusters_table": (C.c_int, [C.c_void_p, I64P]),
     "lbmpm_rk3d_clusters_labels": (C.c_int, [C.c_void_p, U32P]),
@@ -217,6 +219,8 @@ _SIGNATURES = {
     "lbmpm_rk3dcsf_enable_diagnostics": (C.c_int, [C.c_void_p, C.c_int]),
     "lbmpm_rk3dcsf_get_field": (C.c_int, [C.c_void_p, C.c_int, F64P]),
     "lbmpm_rk3dcsf_integrals": (C.c_int, [C.c_void_p, F64P]),
+    "lbmpm_rk3dcsf_change_mark": (C.c_int, [C.c_void_p]),
+    "lbmpm_rk3dcsf_change": (C.c_int, [C.c_void_p, C.c_int, I64P, F64P]),
     "lbmpm_rk3dcsf_clusters": (C.c_int, [C.c_void_p, C.POINTER(ClustersConfig), I64P]),
     "lbmpm_rk3dcsf_clusters_table": (C.c_int, [C.c_void_p, I64P]),
     "lbmpm_rk3dcsf_clusters_labels": (C.c_int, [C.c_void_p, U32P]),

@@ -1167,6 +1167,7 @@ __global__ void rk3d_setup_solidnbr(RK3Dev p, uint32_t *solidnbr)
 #include "rk3d_clusters.h"
 #include "rk3d_morphology.h"
 #include "rk3d_cluster_props.h"
+#include "rk3d_change.h"
 
 // the fields of the last lbmpm_rk3d_phase_field(ctx, 1) (rhoR, rhoB, vx, vy, vz in `diag`, the phase field in `phi`; pitch, plane2 and
 // halo planes as lbmpm_rk3d_get_field reads them), the mask from the device's flags
@@ -1221,6 +1222,7 @@ struct lbmpm_rk3d {
     ClState cl;                      // lbmpm_rk3d_clusters: classes, labels, rows (rk3d_clusters.h), allocated by the first call
     uint8_t *morph = nullptr;        // lbmpm_rk3d_morphology: classes [nzl + 1][ny][nx] (rk3d_morphology.h), allocated by the first call
     CpState cprops;                  // lbmpm_rk3d_cluster_props: classes [nzl + 2][ny][nx], accumulators (rk3d_cluster_props.h), allocated by the first call
+    ChState chg;                     // lbmpm_rk3d_change: the snapshot [4][nzl][ny][nx], partials + the table (rk3d_change.h), allocated by the first mark
     uint32_t *purA = nullptr, *purB = nullptr;       // row flags of the q23 storage, swapped with fA / fB
     double *send_up = nullptr, *send_dn = nullptr, *recv_below = nullptr, *recv_above = nullptr;
     std::vector<uint8_t> h_domain;   // owned planes only, [nzl][ny][nx]
@@ -1572,6 +1574,7 @@ extern "C" int lbmpm_rk3d_set_density(lbmpm_rk3d *c, const double *rho_r, const 
     c->steps = 0;
     c->observed_at = -1;
     c->cl.valid = false;
+    c->chg.valid = false;
     return LBMPM_OK;
 }
 
@@ -1659,6 +1662,7 @@ void state_was_set(lbmpm_rk3d *c, int64_t steps, bool streamed)
     c->steps = steps;
     c->observed_at = -1;
     c->cl.valid = false;
+    c->chg.valid = false;
 }
 }  // namespace
 
@@ -2549,6 +2553,34 @@ extern "C" int lbmpm_rk3d_integrals(lbmpm_rk3d *c, double *out)
     const Rk3dIntLoader load{c->flags, c->diag, c->phi, (unsigned)c->nx, (unsigned)c->pitch, c->plane2, c->vol};
     LBMPM_HIP_TRY(integrals_run(load, planes, plane_cells, c->integ, out, c->stream));
     return LBMPM_OK;
+}
+
+// Steady-state monitor over the fields of the last lbmpm_rk3d_phase_field(ctx, 1) (rk3d_change.h; the definition: include/lbmpm.h)
+static int change_ready(const char *who, lbmpm_rk3d *c)
+{
+    LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
+    if (c->observed_at != c->steps || !c->diag) {
+        set_error("%s: the fields are stale: call lbmpm_rk3d_phase_field(ctx, 1) after the last step (the monitor compares the fields of the "
+                  "streamed, boundary-corrected lattice at that call; observed at step %lld, now %lld)", who, (long long)c->observed_at, (long long)c->steps);
+        return LBMPM_ERR_STATE;
+    }
+    return LBMPM_OK;
+}
+
+extern "C" int lbmpm_rk3d_change_mark(lbmpm_rk3d *c)
+{
+    LBMPM_REQUIRE(c, "lbmpm_rk3d_change_mark: null argument");
+    { const int rc = change_ready("lbmpm_rk3d_change_mark", c); if (rc) return rc; }
+    const Rk3dIntLoader load{c->flags, c->diag, c->phi, (unsigned)c->nx, (unsigned)c->pitch, c->plane2, c->vol};
+    return change_mark(load, c->chg, c->steps, (unsigned)c->nzl, (unsigned)c->nx * (unsigned)c->ny, c->mem, c->stream);
+}
+
+extern "C" int lbmpm_rk3d_change(lbmpm_rk3d *c, int remark, int64_t *steps_between, double *out)
+{
+    LBMPM_REQUIRE(c && out, "lbmpm_rk3d_change: null argument");
+    { const int rc = change_ready("lbmpm_rk3d_change", c); if (rc) return rc; }
+    const Rk3dIntLoader load{c->flags, c->diag, c->phi, (unsigned)c->nx, (unsigned)c->pitch, c->plane2, c->vol};
+    return change_run("lbmpm_rk3d_change", load, c->chg, remark, c->steps, steps_between, (unsigned)c->nzl, (unsigned)c->nx * (unsigned)c->ny, out, c->stream);
 }
 
 // Phase clusters of phi of the last lbmpm_rk3d_phase_field(ctx, 1) (rk3d_clusters.h; the definition: include/lbmpm.h)

@@ -1014,6 +1014,7 @@ __global__ __launch_bounds__(256) void csf3d_import(CsfDev p, double *f, const d
 #include "rk3d_clusters.h"
 #include "rk3d_morphology.h"
 #include "rk3d_cluster_props.h"
+#include "rk3d_change.h"
 
 // what LBMPM_RK3DCSF_REC_RHO_R .. _REC_PHI hand out, from the populations: cell_state<FIRST, true>, the velocity with half the force and
 // the phase field in the arithmetic of csf3d_observe<FIRST, true>; own planes only (plane 0 is lattice plane p.glo)
@@ -1085,6 +1086,7 @@ struct lbmpm_rk3dcsf {
     ClState cl;                    // lbmpm_rk3dcsf_clusters: classes, labels, rows (rk3d_clusters.h), allocated by the first call
     uint8_t *morph = nullptr;      // lbmpm_rk3dcsf_morphology: classes [own planes + 1][ny][nx] (rk3d_morphology.h), allocated by the first call
     CpState cprops;                // lbmpm_rk3dcsf_cluster_props: classes [own planes + 2][ny][nx], accumulators (rk3d_cluster_props.h), allocated by the first call
+    ChState chg;                   // lbmpm_rk3dcsf_change: the snapshot [4][own planes][ny][nx], partials + the table (rk3d_change.h), allocated by the first mark
     double *obs = nullptr;         // staging of the observe kernel: rho [2][N], u [3][N], phi [N] (the populations [2][N][19] come and go with the call)
     lbmpm::EventPool pool;
     size_t timed_steps = 0;
@@ -1471,6 +1473,7 @@ static int reset_state(lbmpm_rk3dcsf *c, const double *fx, const double *fy, con
     LBMPM_HIP_TRY(hipStreamSynchronize(c->stream));
     c->first = true; c->have_state = true; c->steps = 0; c->diag_valid = false; c->next_stage = 0;
     c->cl.valid = false;
+    c->chg.valid = false;
     return LBMPM_OK;
 }
 
@@ -1812,6 +1815,30 @@ extern "C" int lbmpm_rk3dcsf_integrals(lbmpm_rk3dcsf *c, double *out)
     if (c->first) LBMPM_HIP_TRY(integrals_run(CsfIntLoader<true>{p}, planes, plane_cells, c->integ, out, c->stream));
     else LBMPM_HIP_TRY(integrals_run(CsfIntLoader<false>{p}, planes, plane_cells, c->integ, out, c->stream));
     return LBMPM_OK;
+}
+
+// Steady-state monitor over the recorded state (rk3d_change.h; the definition: include/lbmpm.h): u and phi of a cell from the populations
+// in registers, as the integrals take them.  Valid wherever lbmpm_rk3dcsf_integrals is, slabs included.
+extern "C" int lbmpm_rk3dcsf_change_mark(lbmpm_rk3dcsf *c)
+{
+    LBMPM_REQUIRE(c, "lbmpm_rk3dcsf_change_mark: null argument");
+    if (!c->have_state) { set_error("lbmpm_rk3dcsf_change_mark before set_macro / set_pdf"); return LBMPM_ERR_STATE; }
+    LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
+    const unsigned planes = (unsigned)(c->nz - c->cfg.ghost_lo - c->cfg.ghost_hi), plane_cells = (unsigned)c->nx * (unsigned)c->ny;
+    const CsfDev p = make_dev(c);
+    if (c->first) return change_mark(CsfIntLoader<true>{p}, c->chg, c->steps, planes, plane_cells, c->mem, c->stream);
+    return change_mark(CsfIntLoader<false>{p}, c->chg, c->steps, planes, plane_cells, c->mem, c->stream);
+}
+
+extern "C" int lbmpm_rk3dcsf_change(lbmpm_rk3dcsf *c, int remark, int64_t *steps_between, double *out)
+{
+    LBMPM_REQUIRE(c && out, "lbmpm_rk3dcsf_change: null argument");
+    if (!c->have_state) { set_error("lbmpm_rk3dcsf_change before set_macro / set_pdf"); return LBMPM_ERR_STATE; }
+    LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
+    const unsigned planes = (unsigned)(c->nz - c->cfg.ghost_lo - c->cfg.ghost_hi), plane_cells = (unsigned)c->nx * (unsigned)c->ny;
+    const CsfDev p = make_dev(c);
+    if (c->first) return change_run("lbmpm_rk3dcsf_change", CsfIntLoader<true>{p}, c->chg, remark, c->steps, steps_between, planes, plane_cells, out, c->stream);
+    return change_run("lbmpm_rk3dcsf_change", CsfIntLoader<false>{p}, c->chg, remark, c->steps, steps_between, planes, plane_cells, out, c->stream);
 }
 
 // Phase clusters of the recorded phase field (rk3d_clusters.h; the definition: include/lbmpm.h), classified from the populations in

@@ -195,6 +195,10 @@ class RecordGuard:
         dist.all_reduce(t, op=dist.ReduceOp.MAX, group=self.group)
         return bool(int(t.item()))
 
+    def anyone(self, flag):
+        """MAX over the ranks of a flag (a run on one process: the flag): how a verdict that one rank holds reaches all of them"""
+        return self._anyone_bad(bool(flag))
+
     def integrals(self, step, nonfinite, sums=None):
         """The same rule at the cadence of the plane integrals (openlbmpm_amd/integrals.py): `nonfinite` is the number of fluid cells
         the device counted as not finite, `sums` what the log line carries; both None on a rank of a distributed run that does not hold

@@ -212,6 +212,25 @@ class RK3DSlab(SlabTransportCalls):
         from .integrals import Integrals, table
         return Integrals(table(self._L, "lbmpm_rk3d_integrals", self._h, self.nzl), self.nx, self.ny)
 
+    def mark_change(self):
+        """the snapshot change() compares with: u and phi of the last phase_field(diagnostics=True), kept on the device (32 bytes per own
+        lattice cell, allocated by the first call); LbmpmError (LBMPM_ERR_STATE) when a step has been taken since that phase_field"""
+        from .change import mark
+        mark(self._L, "rk3d", self._h)
+
+    def change_part(self, remark=True):
+        """([nzl][11], steps since the mark): the change table of the slab's own planes"""
+        from .change import table
+        return table(self._L, "rk3d", self._h, self.nzl, remark)
+
+    def change(self, remark=True):
+        """change.Change of the slab's own planes: the fields of the last phase_field(diagnostics=True) against the snapshot, reduced on
+        the device (lbmpm_rk3d_change); remark: they replace the snapshot in the same pass.  LbmpmError (LBMPM_ERR_STATE) before
+        mark_change(), when a step has been taken since that phase_field, and after a set_* since the mark"""
+        from .change import Change
+        t, steps = self.change_part(remark)
+        return Change(t, self.nx, self.ny, steps)
+
     def clusters_part(self, phi_cut=0.0, connectivity=6, labels=False, faces=True):
         """clusters.take of the slab's own planes: the table (and labels, faces) of this slab alone, for clusters.merge_slabs"""
         from .clusters import take
@@ -377,6 +396,20 @@ class RK3DCluster:
         from .integrals import Integrals, fresh
         s0 = self.slabs[0]
         return Integrals(fresh(lambda: np.concatenate([s.integrals().planes for s in self.slabs], axis=0), self.observe), s0.nx, s0.ny)
+
+    def mark_change(self):
+        """every slab's snapshot for change(); observe() first when the diagnostics are stale"""
+        from .integrals import fresh
+        fresh(lambda: [s.mark_change() for s in self.slabs], self.observe)
+
+    def change(self, remark=True):
+        """change.Change of the whole lattice: the slabs' tables in plane order, each against its own snapshot (bit-equal to the undivided
+        lattice's); observe() first when the diagnostics are stale"""
+        from .change import Change, stacked
+        from .integrals import fresh
+        s0 = self.slabs[0]
+        t, steps = fresh(lambda: stacked(self.slabs, remark), self.observe)
+        return Change(t, s0.nx, s0.ny, steps)
 
     def clusters(self, phi_cut=0.0, connectivity=6, labels=False, props=False):
         """clusters.Clusters of the whole lattice: the slabs' tables joined through their face planes (equal to the undivided lattice's);
@@ -589,6 +622,20 @@ class RK3DDistributed:
         from .integrals import Integrals, fresh
         t = self.gather(fresh(lambda: self.slab.integrals().planes, self.observe))
         return None if t is None else Integrals(t, self.slab.nx, self.slab.ny)
+
+    def mark_change(self):
+        """every rank: the snapshot of its slab for change(); observe() first when the diagnostics are stale"""
+        from .integrals import fresh
+        fresh(self.slab.mark_change, self.observe)
+
+    def change(self, remark=True):
+        """collective: rank 0 returns the change.Change of the whole lattice (every rank against its own snapshot, the tables through
+        gather()), the others None; observe() first when the diagnostics are stale"""
+        from .change import Change
+        from .integrals import fresh
+        part, steps = fresh(lambda: self.slab.change_part(remark), self.observe)
+        t = self.gather(part)
+        return None if t is None else Change(t, self.slab.nx, self.slab.ny, steps)
 
     def clusters(self, phi_cut=0.0, connectivity=6, labels=False, props=False):
         """collective: rank 0 returns the clusters.Clusters of the whole lattice (the ranks' tables and face planes, joined there; with

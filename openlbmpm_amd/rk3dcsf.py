@@ -245,6 +245,25 @@ class RK3DCSFSolver(SlabTransportCalls):
         from .integrals import Integrals, table
         return Integrals(table(self._L, "lbmpm_rk3dcsf_integrals", self._h, self.nz - self.ghost[0] - self.ghost[1]), self.nx, self.ny)
 
+    def mark_change(self):
+        """the snapshot change() compares with: what get("rec_vx" .. "rec_phi") hand out for the own planes, taken from the populations
+        and kept on the device (32 bytes per own lattice cell, allocated by the first call)"""
+        from .change import mark
+        mark(self._L, "rk3dcsf", self._h)
+
+    def change_part(self, remark=True):
+        """([own planes][11], steps since the mark): the change table of this lattice or slab alone"""
+        from .change import table
+        return table(self._L, "rk3dcsf", self._h, self.nz - self.ghost[0] - self.ghost[1], remark)
+
+    def change(self, remark=True):
+        """change.Change of the own planes: the recorded state against the snapshot, reduced from the populations on the device
+        (lbmpm_rk3dcsf_change); remark: it replaces the snapshot in the same pass.  LbmpmError (LBMPM_ERR_STATE) before mark_change()
+        and after a set_macro / set_pdf since the mark"""
+        from .change import Change
+        t, steps = self.change_part(remark)
+        return Change(t, self.nx, self.ny, steps)
+
     def clusters_part(self, phi_cut=0.0, connectivity=6, labels=False, faces=True):
         """clusters.take of the own planes: the table (and labels, faces) of this lattice or slab alone, for clusters.merge_slabs"""
         from .clusters import take
@@ -440,6 +459,18 @@ class RK3DCSFCluster:
         """the slabs' tables in plane order: bit-equal to the undivided lattice's"""
         from .integrals import Integrals
         return Integrals(np.concatenate([s.integrals().planes for s in self.slabs], axis=0), self.nx, self.ny)
+
+    def mark_change(self):
+        """every slab's snapshot for change()"""
+        for s in self.slabs:
+            s.mark_change()
+
+    def change(self, remark=True):
+        """change.Change of the whole lattice: the slabs' tables in plane order, each against its own snapshot (bit-equal to the undivided
+        lattice's)"""
+        from .change import Change, stacked
+        t, steps = stacked(self.slabs, remark)
+        return Change(t, self.nx, self.ny, steps)
 
     def clusters(self, phi_cut=0.0, connectivity=6, labels=False, props=False):
         """clusters.Clusters of the whole lattice: the slabs' tables joined through their face planes (equal to the undivided lattice's).
@@ -668,6 +699,18 @@ class RK3DCSFDistributed:
         from .integrals import Integrals
         t = self.gather(self.slab.integrals().planes)
         return None if t is None else Integrals(t, self.shape[2], self.shape[1])
+
+    def mark_change(self):
+        """every rank: the snapshot of its slab for change()"""
+        self.slab.mark_change()
+
+    def change(self, remark=True):
+        """collective: rank 0 returns the change.Change of the whole lattice (every rank against its own snapshot, the tables through
+        gather()), the others None"""
+        from .change import Change
+        part, steps = self.slab.change_part(remark)
+        t = self.gather(part)
+        return None if t is None else Change(t, self.shape[2], self.shape[1], steps)
 
     def clusters(self, phi_cut=0.0, connectivity=6, labels=False, props=False):
         """collective: rank 0 returns the clusters.Clusters of the whole lattice (the ranks' tables and face planes, joined there; with
