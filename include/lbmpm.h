@@ -676,6 +676,10 @@ int64_t lbmpm_rk3d_device_bytes(const lbmpm_rk3d *ctx);
  * the caller sends (RCCL / MPI / torch.distributed), or -- opt-in, see the end of this block -- the library's own IPC / RCCL transport
  * moves all three and lbmpm_rk3dcsf_step_slab runs whole steps behind one call.  Bit-equal to the undivided lattice (tests/test_rk3d_csf_gpu.py,
  * tests/test_rk3d_csf_transport_gpu.py).
+ * Mixed wettability: lbmpm_rk3dcsf_set_contact_angles gives every fluid cell next to solid (kind 3) a contact angle of its own, which takes
+ * the place of contact_angle_deg in the wetting rule and nowhere else; the rule is local to the cell, so the slabs' messages stay as they
+ * are (LBMPM_CSF_MSG_NORMAL carries the sender's corrected normal).  A uniform map equals the scalar run bit for bit
+ * (tests/test_rk3d_csf_wettability_gpu.py).
  * ---------------------------------------------------------------------------------- */
 typedef struct lbmpm_rk3dcsf_config {
     int64_t nx, ny, nz;        /* xDomain, yDomain, zDomain (incl. the ghost planes 0 and nz-1); nz >= 8 */
@@ -726,6 +730,8 @@ typedef enum lbmpm_rk3dcsf_field {
     LBMPM_RK3DCSF_K = 14,                                                     /* needs enable_diagnostics */
     LBMPM_RK3DCSF_NSX = 15, LBMPM_RK3DCSF_NSY = 16, LBMPM_RK3DCSF_NSZ = 17,   /* solid normal at the fluid cells next to solid */
     LBMPM_RK3DCSF_KIND = 18,   /* 0 solid, 1 fluid, 2 wetting solid, 3 fluid next to solid */
+    LBMPM_RK3DCSF_THETA = 19,  /* the contact angle in force at the fluid cells next to solid, degrees (the map of lbmpm_rk3dcsf_set_contact_angles,
+                                * else contact_angle_deg); 0 elsewhere.  Like KIND not part of the state: valid before set_macro / set_pdf too */
     LBMPM_RK3DCSF_REC_PDF_R = 30, LBMPM_RK3DCSF_REC_PDF_B = 31, LBMPM_RK3DCSF_REC_RHO_R = 32, LBMPM_RK3DCSF_REC_RHO_B = 33,
     LBMPM_RK3DCSF_REC_VX = 34, LBMPM_RK3DCSF_REC_VY = 35, LBMPM_RK3DCSF_REC_VZ = 36, LBMPM_RK3DCSF_REC_PHI = 37
 } lbmpm_rk3dcsf_field;
@@ -740,6 +746,17 @@ int lbmpm_rk3dcsf_set_macro(lbmpm_rk3dcsf *ctx, const double *rho_r, const doubl
 /* restart ([CyclesSetup] IsCycle, RKD2Q9.py:491-559): streamed populations [nz][ny][nx][19] per colour as LBMPM_RK3DCSF_PDF_* returns
  * them, and the force of the last step (LBMPM_RK3DCSF_F*; NULL = 0): a run continued from them equals the uninterrupted run bit for bit */
 int lbmpm_rk3dcsf_set_pdf(lbmpm_rk3dcsf *ctx, const double *pdf_r, const double *pdf_b, const double *fx, const double *fy, const double *fz);
+/* Per-cell contact angles (mixed wettability).  theta_deg: host [nz][ny][nx], the context's whole lattice, ghost planes included (a slab:
+ * cut from the undivided lattice like is_domain).  Read at kind-3 cells only (LBMPM_RK3DCSF_KIND); other entries are ignored and may be
+ * NaN.  At a kind-3 cell the value must be finite and in [0, 180], else LBMPM_ERR_INVALID with the first offending cell in the error text
+ * and nothing changed (a slab's outermost ghost planes, whose kind depends on planes the slab does not hold and which nothing reads, are
+ * not looked at); LBMPM_ERR_INVALID too with wetting_type 0, where no rule would use the angles.  NULL: back to cfg.contact_angle_deg, and
+ * the map's device memory is released.  May be called whenever the context is idle -- before set_macro, between steps, repeatedly
+ * (wettability alteration) -- and touches neither the state nor the step counter nor the snapshot of lbmpm_rk3dcsf_change; set_macro and
+ * set_pdf keep the map.  cos and sin are taken on the host by the expression that serves contact_angle_deg, so a uniform map reproduces
+ * the scalar run bit for bit.  Device memory: 24 bytes per fluid cell (theta, cos, sin numbered by fluid cell), allocated by the first
+ * call and counted by lbmpm_rk3dcsf_device_bytes. */
+int lbmpm_rk3dcsf_set_contact_angles(lbmpm_rk3dcsf *ctx, const double *theta_deg);
 int lbmpm_rk3dcsf_step(lbmpm_rk3dcsf *ctx, int64_t nsteps);          /* undivided lattices only (ghost_lo = ghost_hi = 0) */
 /* One third of a time step, in order 0, 1, 2: (0) the blocks' lists, the bulk's collision on its own stream, the phase field;
  * (1) phi on the wetting solids, gradient, n; (2) the collision of the full path, buffers swapped.  Between them the face messages:

@@ -55,13 +55,22 @@ steps_between, velocity_change, velocity_change_R, velocity_change_B, phase_chan
 summary goes to the log.  steady_tol > 0 (needs steady_every): the run ends at the first visit where Change.is_steady(steady_tol,
 steady_phase_tol) holds -- its last record, tables and sync are taken at that step, which self.steady_step then names (None: never met;
 distributed: rank 0 decides and every rank hears of it before the next step is issued).  A checkpoint does not hold the snapshot.
+
+contact_angle_solids = array or path of a .npy file (also [SurfaceTension] ContactAngleFile = '...' of the ini, --contact-angles FILE of the
+command line; 3-D CSF only, ConfigError on the perturbation model, whose wetting is SolidRhoR / SolidRhoB): mixed wettability.  Contact
+angles in degrees per SOLID voxel, in the shape of the lattice -- with a voxel file ([ImageSetup], framed by geometry.voxel_domain) in the
+shape of that file, framed the same way.  Solids it does not cover -- NaN entries, the forced side walls, the buffer planes -- take the
+ini's ContactAngle.  geometry.wall_contact_angles turns it into the angle of every fluid cell next to solid (Cassie average over the
+cell's solid neighbours), set_contact_angles hands that to the solver (under torchrun every rank cuts its planes), and the result file
+gets /Wettability/ContactAngle once: the angles in force, get("theta") of the whole lattice (rank 0 writes).  A checkpoint does not hold
+the map: restart_from= applies it again from the same argument.
 """
 import os
 
 import numpy as np
 
 from . import config
-from .geometry import initial_densities_rk3d, voxel_domain
+from .geometry import initial_densities_rk3d, voxel_domain, wall_contact_angles
 from .integrals import column_bytes, fresh
 from .results import RecordGuard, ResultFile, find_result_file, read_planes
 from .rk3d import RK3DSlab, RK3DDistributed
@@ -132,9 +141,13 @@ class RKColorGradient3D:
     def __init__(self, pathIniFile, output_dir=None, domain=None, device=0, record_every=None, num_buffering_layers=10,
                  structure_path=None, initial_dir=None, record_pdf=False, restart_from=None, checkpoint_every=0, csf_bulk_epsilon=0.0,
                  csf_transport=None, integrals_every=0, clusters_every=0, clusters_connectivity=6, morphology_every=0,
-                 morphology_phi_cut=0.0, clusters_props=False, steady_every=0, steady_tol=0.0, steady_phase_tol=None):
+                 morphology_phi_cut=0.0, clusters_props=False, steady_every=0, steady_tol=0.0, steady_phase_tol=None, contact_angle_solids=None):
         self.pathIni = pathIniFile
         self.par = config.read_rk3d(pathIniFile)
+        # mixed wettability (3-D CSF only): contact angles per solid voxel, an array or the path of a .npy file; None: the ini's ContactAngleFile, if any
+        self.contact_angle_solids = contact_angle_solids if contact_angle_solids is not None else self.par.get("contact_angle_file")
+        if self.contact_angle_solids is not None and self.par["tension_type"] != "CSF":
+            raise config.ConfigError("contact_angle_solids belongs to SurfaceTensionType = 'CSF': the perturbation model's wetting is SolidRhoR / SolidRhoB")
         self.output_dir = output_dir or os.path.expanduser("~/LBMResults3D")       # main.py:28
         self.initial_dir = initial_dir or os.path.expanduser("~/LBMInitial")       # RKD2Q9.py:492
         self.device, self._domain, self.nbuf = device, domain, int(num_buffering_layers)
@@ -176,7 +189,8 @@ class RKColorGradient3D:
             path = self.structure_path or os.path.expanduser("~/StructureImage/structure3D.npy")
             if not os.path.isfile(path):
                 raise config.ConfigError("[ImageSetup] Existance = 'yes': voxel file %s not found (or pass `domain=`)" % path)
-            self.isDomain = voxel_domain(np.load(path), self.nbuf)
+            self._voxels = np.load(path)
+            self.isDomain = voxel_domain(self._voxels, self.nbuf)
         else:
             self.isDomain = duct(p["nx"], p["ny"], p["nz"])
         self.zDomain, self.yDomain, self.xDomain = self.isDomain.shape
@@ -185,6 +199,44 @@ class RKColorGradient3D:
     @property
     def _is_image(self):
         return self._domain is not None or self.par["image"]
+
+    def solid_contact_angles(self):
+        """contact_angle_solids on the lattice [nz][ny][nx] (NaN: the ini's ContactAngle), or None; after initializeDomainBorder"""
+        a = self.contact_angle_solids
+        if a is None:
+            return None
+        if isinstance(a, (str, os.PathLike)):
+            if not os.path.isfile(a):
+                raise config.ConfigError("contact angles: file %s not found" % a)
+            a = np.load(a)
+        a = np.array(a, dtype=np.float64)
+        voxels = getattr(self, "_voxels", None) if self._domain is None else None
+        if voxels is not None:
+            # framed like the voxel file (geometry.voxel_domain): buffer planes below and above; what the file calls pore is not covered --
+            # the side walls forced solid there take the ini's angle
+            if a.shape != np.shape(voxels):
+                raise config.ConfigError("contact angles have shape %s, the voxel file %s" % (a.shape, np.shape(voxels)))
+            a[np.asarray(voxels) != 0] = np.nan
+            buf = np.full((self.nbuf,) + a.shape[1:], np.nan)
+            a = np.concatenate([buf, a, buf], axis=0)
+        if a.shape != self.isDomain.shape:
+            raise config.ConfigError("contact angles have shape %s, the lattice %s" % (a.shape, self.isDomain.shape))
+        return a
+
+    def _apply_contact_angles(self, solver, out):
+        """the wall angles of contact_angle_solids into the solver (the undivided array: a distributed solver cuts its planes), and the
+        angles in force into /Wettability/ContactAngle (collective: rank 0, or everyone ungathered, writes)"""
+        solids = self.solid_contact_angles()
+        if solids is None:
+            return
+        try:
+            self.wallContactAngle = wall_contact_angles(self.isDomain, solids, self.par["theta"])
+        except ValueError as e:
+            raise config.ConfigError("contact angles: %s" % e)
+        solver.set_contact_angles(self.wallContactAngle)
+        a = self._gather(solver.get("theta"))
+        if out is not None and a is not None:
+            out.write("Wettability", "ContactAngle", a)
 
     def initializeDomainCondition(self, z0=0, nzl=None):
         """initial fields of the planes [z0, z0 + nzl) (a rank's slab; default: the whole lattice)"""
@@ -365,8 +417,11 @@ class RKColorGradient3D:
         mevery = self.morphology_every
         severy = self.steady_every
         more = ((("Integrals", "PlaneIntegrals"),) if every > 0 and rank == 0 else ()) + ((("Clusters", "PhaseClusters"),) if cevery > 0 and rank == 0 else ()) + \
-            ((("Morphology", "PhaseMorphology"),) if mevery > 0 and rank == 0 else ()) + ((("Steady", "SteadyState"),) if severy > 0 and rank == 0 else ())
+            ((("Morphology", "PhaseMorphology"),) if mevery > 0 and rank == 0 else ()) + ((("Steady", "SteadyState"),) if severy > 0 and rank == 0 else ()) + \
+            ((("Wettability", "ContactAngles"),) if self.contact_angle_solids is not None else ())
         out = ResultFile(self.output_dir, name, GROUPS + more) if writes else None
+        if self.contact_angle_solids is not None:
+            self._apply_contact_angles(sim.solver, out)          # (after a restart_from too: a checkpoint does not hold the map)
         self.integral_steps, self.cluster_steps, self.morphology_steps = [], [], []
         self.steady_steps, self.steady_criteria, self.steady_step = [], [], None
         marked = False

@@ -15,6 +15,8 @@ g_i = w_i C, one tracer sub-step inside every flow step after the wetting-correc
 record holds two views: the flow arrays at the START of step iStep, the concentrations AFTER the tracer update of that step; the
 record the 3-D driver writes after the last step holds the concentrations as they stand.  The inlet concentrations are the file's.
 checkpoint() / restart_from= carry the tracers' populations behind the flow's (41 + 7 per tracer doubles per cell): bit for bit.
+contact_angle_solids= / [SurfaceTension] ContactAngleFile: mixed wettability exactly as in the flow's driver (RKColorGradientD3Q19.py),
+/Wettability/ContactAngle in SimulationResultsRK3D.h5; a checkpoint does not hold the map, restart_from= applies it again.
 
 integrals_every = N > 0: every N steps (step 0 and the last step included; the step loop's runs are cut there as at the record and
 checkpoint cadences) two tables, both reduced on the device and the same bit for bit on any number of ranks: the flow's plane integrals
@@ -110,7 +112,10 @@ class Transport3DRK(RKColorGradient3D):
                 slab.solver.set_concentration(k, self.tracerConc[k])
         every = self.integrals_every
         more = lambda group: ((group, "PlaneIntegrals"),) if every > 0 else ()
-        flow = ResultFile(self.output_dir, "SimulationResultsRK3D", GROUPS + more("Integrals")) if rank == 0 else None
+        wett = (("Wettability", "ContactAngles"),) if self.contact_angle_solids is not None else ()
+        flow = ResultFile(self.output_dir, "SimulationResultsRK3D", GROUPS + more("Integrals") + wett) if rank == 0 else None
+        if self.contact_angle_solids is not None:
+            self._apply_contact_angles(slab.solver, flow)        # mixed wettability, as in the flow's driver (after a restart_from too)
         conc = ResultFile(self.output_dir, "ConcentrationResults", (("TransportMacro", "MacroData"),) + more("TracerIntegrals")) if rank == 0 else None
         self.integral_steps = []
         self.result_path, self.concentration_path = (flow.path, conc.path) if rank == 0 else (None, None)

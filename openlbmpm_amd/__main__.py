@@ -16,6 +16,8 @@
                                                   (/Clusters/PropsAtStep<step>); ganglia and mobile ganglia to the log
         [--morphology-every N]                    rk3d: cells, class pairs, squares and cubes per plane, counted on the device, every N steps (/Morphology
         [--morphology-phi-cut c]                  of the result file); interfacial area, wetted fraction, Euler characteristics, capillary pressure to the log
+        [--contact-angles FILE]                   rk3d with SurfaceTensionType = 'CSF', tr3d: mixed wettability -- a .npy of contact angles per solid voxel
+                                                  (the lattice's shape, or the voxel file's; NaN = the ini's ContactAngle); /Wettability/ContactAngle
         [--steady-every N]                        rk3d: the change of velocity and phase field between multiples of N steps, reduced on the device (/Steady of
         [--steady-tol t] [--steady-phase-tol p]   the result file); with a tolerance the run ends at the first multiple where the change is within it
 """
@@ -51,6 +53,10 @@ def parser():
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--csf-transport", choices=["auto", "ipc", "rccl"], default=None,
                     help="rk3d with SurfaceTensionType = 'CSF', tr3d; under torchrun: move the slabs' face messages over the library's own transport")
+    ap.add_argument("--contact-angles", default=None, metavar="FILE",
+                    help="rk3d with SurfaceTensionType = 'CSF', tr3d: contact angles in degrees per solid voxel (.npy in the shape of the lattice, or of the "
+                         "voxel file; NaN: the ini's ContactAngle) -- every fluid cell next to solid takes the Cassie average over its solid neighbours; "
+                         "the angles in force go to /Wettability/ContactAngle of the result file.  The same as [SurfaceTension] ContactAngleFile")
     ap.add_argument("--integrals-every", type=int, default=0, metavar="N",
                     help="rk3d, tr3d: every N steps the plane integrals (saturation, masses, fluxes, largest speed, non-finite cells), reduced on the device, "
                          "to /Integrals of the result file and the log; tr3d also the tracers' (cells, mass, flux_x, flux_y, flux_z, sum_c2, cmin, cmax, "
@@ -93,7 +99,7 @@ def main(argv=None):
         sim = RKColorGradient3D(a.ini_dir, output_dir=a.out, device=device, csf_transport=a.csf_transport, integrals_every=a.integrals_every,
                                 clusters_every=a.clusters_every, clusters_connectivity=a.clusters_connectivity, clusters_props=a.clusters_props,
                                 morphology_every=a.morphology_every, morphology_phi_cut=a.morphology_phi_cut, steady_every=a.steady_every,
-                                steady_tol=a.steady_tol, steady_phase_tol=a.steady_phase_tol)
+                                steady_tol=a.steady_tol, steady_phase_tol=a.steady_phase_tol, contact_angle_solids=a.contact_angles)
         if a.steps is not None:
             sim.timeSteps = a.steps
         path = sim.runRKColorGradient3D()
@@ -103,7 +109,7 @@ def main(argv=None):
     elif a.model == "tr3d":
         from .Transport3DRK import Transport3DRK
         sim = Transport3DRK(a.ini_dir, output_dir=a.out, device=_rank_device(a.device), csf_transport=a.csf_transport,
-                            integrals_every=a.integrals_every)
+                            integrals_every=a.integrals_every, contact_angle_solids=a.contact_angles)
         if a.steps is not None:
             sim.timeSteps = a.steps
         path = " and ".join(str(f) for f in sim.runTransport3DMPMCRK())        # (under torchrun rank 0 writes both files)

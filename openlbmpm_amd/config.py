@@ -147,12 +147,16 @@ def read_rk3d(ini_dir):
         if p["wetting"] != 2:
             raise ConfigError("3-D CSF: WettingType 2 (Akai et al. 2018); WettingType 1 (AcceleratedRKGPU2D.py:1639-1679) rotates the normal in the plane "
                               "and has no 3-D form")
+        # optional: a .npy of contact angles per SOLID voxel (mixed wettability; RKColorGradientD3Q19.py), ContactAngle where it says NaN
+        p["contact_angle_file"] = c.str("SurfaceTension", "ContactAngleFile", default="''") or None
         p["delta"] = c.float("RKParameters", "DeltaValue")
         p["tautype"] = c.int("FluidParameters", "TauType", default=2)
         if p["tautype"] not in (1, 2):
             raise ConfigError("[FluidParameters] TauType must be 1 or 2")
         p["AkR"] = c.float("RKParameters", "AkR", default=0.0); p["AkB"] = c.float("RKParameters", "AkB", default=0.0)      # read, unused by the CSF loop
     else:
+        if c.str("SurfaceTension", "ContactAngleFile", default="''"):
+            raise ConfigError("[SurfaceTension] ContactAngleFile belongs to SurfaceTensionType = 'CSF': the perturbation model's wetting is SolidRhoR / SolidRhoB")
         p["AkR"] = c.float("RKParameters", "AkR"); p["AkB"] = c.float("RKParameters", "AkB")
     p["beta"] = c.float("RKParameters", "BetaThickness")
     p["tauR"] = c.float("FluidParameters", "TauR"); p["tauB"] = c.float("FluidParameters", "TauB")

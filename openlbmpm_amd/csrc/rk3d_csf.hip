@@ -8,7 +8,8 @@
 //   f_tot, u with the lagged force, phi   A:1414-1424, A:2634-2654, A:1348-1357
 //   phi on the wetting solids       A:1560-1581            gradient   A:1584-1634
 //   wetting rule 2 (Akai 2018)      A:2430-2492, solid normals from the 3-D E8 stencil (Sbragaglia et al. 2007) whose sums along one axis
-//                                   are the reference's 24-point weights (RKD2Q9.py:811-885)
+//                                   are the reference's 24-point weights (RKD2Q9.py:811-885); the contact angle is the configuration's, or
+//                                   the cell's own after lbmpm_rk3dcsf_set_contact_angles (mixed wettability: CsfDev.wang)
 //   curvature, force                A:2499-2551: K = -(I - n n) : grad n, F = -1/2 sigma K G
 //   BGK / MRT + Guo source          A:1804-1848 + A:1743-1798 | A:1938-2017 + A:2027-2113 (D3Q19 basis of d'Humieres et al. 2002)
 //   recolouring, streaming          A:1857-1899, A:340-417 (as a pull)
@@ -84,6 +85,8 @@ struct CsfDev {
                                  // have something to do in (not deep, or deep since this step), L_FULL the blocks that are not deep, L_DEEP those that are
     const uint32_t *src;         // [18][FS] number of the fluid cell x - e_i (the cell direction i is pulled from), SRC_WALL off a solid
     double *trflow;              // [4][FS] tracers configured: rho_R, u of the step per fluid cell, for tr3d_step (rk3d_tracer.h); else null
+    const double *wang;          // [3][NF] after lbmpm_rk3dcsf_set_contact_angles: theta in degrees, cos, sin of the fluid cells next to solid (kind 3),
+                                 // numbered by fluid cell; the wetting rule takes them in the place of cosT, sinT.  Else null
 };
 
 struct Nb { unsigned xo[3], yo[3], zo[3]; };
@@ -244,6 +247,8 @@ __device__ __forceinline__ unsigned block_of()
 // last one that holds a cell within two cells of this block's (`rng`, a whole stretch of the lattice order: conservative) all `pure` of one
 // colour -- a difference of two prefix counts.  Such a block skips the phase-field pull, the gradient and the curvature: bit-equal to
 // the full path (tests/test_rk3d_csf_gpu.py), 79 instead of 136 doubles per cell and step.  The open planes always take the full path.
+// The contact angle has no part in this, whether one for the lattice or one per cell (CsfDev.wang): where |G| = 0 the wetting rule scales
+// either candidate by |G| and returns zeros for any angle, so a deep block's zeros stand under every map and under a map that changes.
 __device__ __forceinline__ int deep_colour(const CsfDev &p, unsigned b)
 {
     if (!p.skip || b >= p.nblk || p.bcblk[b]) return 0;
@@ -322,7 +327,10 @@ __global__ __launch_bounds__(256) void csf3d_solid_phi(CsfDev p, const uint32_t 
     p.phi[n] = sum / sw;
 }
 
-// A:1584-1634 gradient, A:2430-2492 wetting rule, and the unit normal n = -G / |G| (threshold 1e-8, A:2512-2520) the curvature reads
+// A:1584-1634 gradient, A:2430-2492 wetting rule, and the unit normal n = -G / |G| (threshold 1e-8, A:2512-2520) the curvature reads.
+// The rule's angle: p.cosT, p.sinT, or (MAP: a map is set, p.wang) the cell's own -- two loads inside the kind-3 branch.  Two instances:
+// without a map the kernel is the one it was (80 VGPRs, 6 waves per SIMD; the map's two values held across the rule cost 4 more and a wave).
+template <bool MAP>
 __global__ __launch_bounds__(256) void csf3d_gradient(CsfDev p)
 {
     constexpr int CX[Q] = CSF_CX, CY[Q] = CSF_CY, CZ[Q] = CSF_CZ;
@@ -354,15 +362,17 @@ __global__ __launch_bounds__(256) void csf3d_gradient(CsfDev p)
         const double sx = p.ns[n], sy = p.ns[p.NS + n], sz = p.ns[2 * p.NS + n];
         const double ang = ux * sx + uy * sy + uz * sz;
         const double th = acos(ang);
+        double cosT = p.cosT, sinT = p.sinT;
+        if (MAP) { cosT = p.wang[(size_t)p.NF + j]; sinT = p.wang[2 * (size_t)p.NF + j]; }
         double c1 = 0., c2 = 0., c3 = 0., c4 = 0.;
         if (fabs(sin(th)) > 1.0e-9) {
-            c1 = p.sinT * cos(th) / sin(th);
-            c2 = p.sinT / sin(th);
-            c3 = -p.sinT * cos(th) / sin(th);
-            c4 = -p.sinT / sin(th);
+            c1 = sinT * cos(th) / sin(th);
+            c2 = sinT / sin(th);
+            c3 = -sinT * cos(th) / sin(th);
+            c4 = -sinT / sin(th);
         }
-        const double ax = (p.cosT - c1) * sx + c2 * ux, ay = (p.cosT - c1) * sy + c2 * uy, az = (p.cosT - c1) * sz + c2 * uz;
-        const double bx = (p.cosT - c3) * sx + c4 * ux, by = (p.cosT - c3) * sy + c4 * uy, bz = (p.cosT - c3) * sz + c4 * uz;
+        const double ax = (cosT - c1) * sx + c2 * ux, ay = (cosT - c1) * sy + c2 * uy, az = (cosT - c1) * sz + c2 * uz;
+        const double bx = (cosT - c3) * sx + c4 * ux, by = (cosT - c3) * sy + c4 * uy, bz = (cosT - c3) * sz + c4 * uz;
         const double d1 = sqrt((ax - ux) * (ax - ux) + (ay - uy) * (ay - uy) + (az - uz) * (az - uz));
         const double d2 = sqrt((bx - ux) * (bx - ux) + (by - uy) * (by - uy) + (bz - uz) * (bz - uz));
         if (d1 < d2) { gx = -nrm * ax; gy = -nrm * ay; gz = -nrm * az; }
@@ -1104,6 +1114,7 @@ struct lbmpm_rk3dcsf {
     double *gA = nullptr, *gB = nullptr, *trflow = nullptr;      // [ntr][7][FS] x 2, [4][FS]
     uint32_t *trsrc = nullptr;                                   // [6][FS] when the context has no table of source cells of its own
     double trB[4][9];
+    double *wang = nullptr;        // lbmpm_rk3dcsf_set_contact_angles: [3][nfluid] theta, cos, sin per fluid cell (CsfDev.wang), allocated by the first call
 };
 
 namespace {
@@ -1129,6 +1140,7 @@ CsfDev make_dev(const lbmpm_rk3dcsf *c)
     p.eps = c->cfg.bulk_epsilon > 0. ? c->cfg.bulk_epsilon : 0x1p-51;
     p.nblk = c->nblk; p.skip = c->skip ? 1 : 0; p.pure = c->pure; p.deep_prev = c->deep_prev; p.bcblk = c->bcblk; p.rng = c->rng; p.pfx = c->pfx; p.deep_now = c->deep_now; p.work = c->work; p.src = c->src;
     p.trflow = c->trflow;
+    p.wang = c->wang;
     return p;
 }
 
@@ -1197,7 +1209,7 @@ int launch_step(lbmpm_rk3dcsf *c, const CsfDev &p, hipEvent_t e0, hipEvent_t e1,
     if (stages & 1) csf3d_phase<FIRST><<<gw, 256, 0, c->stream>>>(p);
     if (stages & 2) {
         if (c->nwet) csf3d_solid_phi<<<blocks_of(c->nwet), 256, 0, c->stream>>>(p, c->wetlist, c->wethome);
-        csf3d_gradient<<<gw, 256, 0, c->stream>>>(p);
+        if (p.wang) csf3d_gradient<true><<<gw, 256, 0, c->stream>>>(p); else csf3d_gradient<false><<<gw, 256, 0, c->stream>>>(p);
     }
     if (stages & 4) {
         if (tr) {
@@ -1510,6 +1522,55 @@ extern "C" int lbmpm_rk3dcsf_set_pdf(lbmpm_rk3dcsf *c, const double *pdf_r, cons
     return rc;
 }
 
+// Per-cell contact angles: see include/lbmpm.h.  Stored per fluid cell (the gradient kernel has the cell's number at hand): theta as given
+// for LBMPM_RK3DCSF_THETA, cos and sin by make_dev's expression.  Fluid cells that are not kind 3 hold zeros nobody reads.
+extern "C" int lbmpm_rk3dcsf_set_contact_angles(lbmpm_rk3dcsf *c, const double *theta_deg)
+{
+    LBMPM_REQUIRE(c, "lbmpm_rk3dcsf_set_contact_angles: null context");
+    LBMPM_REQUIRE(c->cfg.wetting_type != 0, "lbmpm_rk3dcsf_set_contact_angles: wetting_type 0 has no rule to apply the angles to");
+    LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
+    if (!theta_deg) {
+        if (c->wang) {           // no launch of either stream may still read the map
+            LBMPM_HIP_TRY(hipStreamSynchronize(c->stream));
+            LBMPM_HIP_TRY(hipStreamSynchronize(c->stream2));
+            c->mem.release(&c->wang);
+        }
+        return LBMPM_OK;
+    }
+    const size_t N = c->N, NF = (size_t)c->nfluid, pl = (size_t)c->nx * c->ny;
+    std::vector<uint32_t> m;
+    std::vector<double> h;
+    try { m.resize(N); h.assign(3 * NF, 0.); }
+    catch (const std::bad_alloc &) { set_error("lbmpm_rk3dcsf_set_contact_angles: out of host memory"); return LBMPM_ERR_NOMEM; }
+    LBMPM_HIP_TRY(hipMemcpy(m.data(), c->meta, N * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    // (a slab's outermost ghost planes: kind there is taken with neighbours the slab does not hold, and no kernel computes those cells)
+    const size_t zlo = c->cfg.ghost_lo ? 1 : 0, zhi = (size_t)c->nz - (c->cfg.ghost_hi ? 1 : 0);
+    size_t j = 0;
+    for (size_t k = 0; k < N; ++k) {
+        if (!(m[k] & 1u)) continue;
+        const size_t z = k / pl;
+        if (((m[k] >> KIND_SHIFT) & 3u) == 3u) {
+            double t = theta_deg[k];
+            const bool ok = std::isfinite(t) && t >= 0. && t <= 180.;
+            if (!ok && z >= zlo && z < zhi) {
+                const size_t r = k - z * pl;
+                set_error("lbmpm_rk3dcsf_set_contact_angles: contact angle %g at the cell (z, y, x) = (%zu, %zu, %zu), a fluid cell next to solid: finite and within [0, 180] degrees",
+                          t, z, r / (size_t)c->nx, r % (size_t)c->nx);
+                return LBMPM_ERR_INVALID;
+            }
+            if (!ok) t = c->cfg.contact_angle_deg;
+            const double th = t / 180. * M_PI;
+            h[j] = t; h[NF + j] = cos(th); h[2 * NF + j] = sin(th);
+        }
+        ++j;
+    }
+    LBMPM_HIP_TRY(hipStreamSynchronize(c->stream));
+    LBMPM_HIP_TRY(hipStreamSynchronize(c->stream2));
+    if (!c->wang) { const int rc = c->mem.alloc(&c->wang, 3 * NF, nullptr); if (rc) return rc; }
+    LBMPM_HIP_TRY(hipMemcpy(c->wang, h.data(), 3 * NF * sizeof(double), hipMemcpyHostToDevice));
+    return LBMPM_OK;
+}
+
 extern "C" int lbmpm_rk3dcsf_step(lbmpm_rk3dcsf *c, int64_t nsteps)
 {
     LBMPM_REQUIRE(c && nsteps >= 0, "lbmpm_rk3dcsf_step: bad argument");
@@ -1759,7 +1820,7 @@ static int observe(lbmpm_rk3dcsf *c, bool rec, double *pdf)
 extern "C" int lbmpm_rk3dcsf_get_field(lbmpm_rk3dcsf *c, int field, double *out)
 {
     LBMPM_REQUIRE(c && out, "lbmpm_rk3dcsf_get_field: null argument");
-    LBMPM_REQUIRE(c->have_state, "lbmpm_rk3dcsf_get_field before set_macro / set_pdf");
+    LBMPM_REQUIRE(c->have_state || field == LBMPM_RK3DCSF_THETA || field == LBMPM_RK3DCSF_KIND, "lbmpm_rk3dcsf_get_field before set_macro / set_pdf");   // (those two: the geometry's)
     LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
     LBMPM_HIP_TRY(hipStreamSynchronize(c->stream));
     const size_t N = c->N, NS = c->NS;
@@ -1794,6 +1855,19 @@ extern "C" int lbmpm_rk3dcsf_get_field(lbmpm_rk3dcsf *c, int field, double *out)
         std::vector<uint32_t> m(N);
         LBMPM_HIP_TRY(hipMemcpy(m.data(), c->meta, N * sizeof(uint32_t), hipMemcpyDeviceToHost));
         for (size_t k = 0; k < N; ++k) out[k] = (double)((m[k] >> KIND_SHIFT) & 3u);
+        return LBMPM_OK;
+    }
+    case LBMPM_RK3DCSF_THETA: {
+        std::vector<uint32_t> m(N);
+        std::vector<double> t;
+        LBMPM_HIP_TRY(hipMemcpy(m.data(), c->meta, N * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        if (c->wang) { t.resize((size_t)c->nfluid); LBMPM_HIP_TRY(hipMemcpy(t.data(), c->wang, t.size() * sizeof(double), hipMemcpyDeviceToHost)); }
+        size_t j = 0;
+        for (size_t k = 0; k < N; ++k) {
+            const bool wall = ((m[k] >> KIND_SHIFT) & 3u) == 3u;
+            out[k] = wall ? (c->wang ? t[j] : c->cfg.contact_angle_deg) : 0.;
+            if (m[k] & 1u) ++j;
+        }
         return LBMPM_OK;
     }
     default:

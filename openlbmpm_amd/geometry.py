@@ -138,6 +138,47 @@ def voxel_domain(voxels, nbuf=10, walls=True):
     return np.ascontiguousarray(np.concatenate([buf, core, buf], axis=0))
 
 
+# the 18 links of D3Q19 as (dz, dy, dx): six along the axes (weight 1/18), twelve diagonal (1/36)
+D3Q19_LINKS = [(dz, dy, dx) for dz in (-1, 0, 1) for dy in (-1, 0, 1) for dx in (-1, 0, 1) if 1 <= dz * dz + dy * dy + dx * dx <= 2]
+
+
+def wall_contact_angles(is_domain, solid_theta, default):
+    """From a mineral map to the contact angles of the fluid cells next to solid (mixed wettability; what
+    RK3DCSFSolver.set_contact_angles takes).  is_domain [nz][ny][nx], 1 = fluid; solid_theta [nz][ny][nx]: degrees, read at the SOLID
+    voxels, NaN = `default`.  Every fluid cell with at least one solid among its 18 neighbours (the solver's kind 3; x, y and z wrap as
+    in the solver) gets the Cassie average over those neighbours, theta = acos(sum w_i cos theta_i / sum w_i) with w = 1/18 along the
+    axes and 1/36 on the diagonals; where they all carry one value, that value as it stands (no acos(cos()) round trip: a uniform
+    mineral map gives a uniform wall map bit for bit).  NaN off those cells."""
+    dom = np.asarray(is_domain)
+    if dom.ndim != 3:
+        raise TypeError("is_domain must be a [nz][ny][nx] array")
+    th = np.array(solid_theta, dtype=np.float64)
+    if th.shape != dom.shape:
+        raise ValueError("solid_theta has shape %s, the domain %s" % (th.shape, dom.shape))
+    solid = dom != 1
+    th[np.isnan(th)] = float(default)
+    bad = solid & ~(np.isfinite(th) & (th >= 0.0) & (th <= 180.0))
+    if bad.any():
+        raise ValueError("solid_theta: contact angle %r at the solid voxel (z, y, x) = %s, not within [0, 180] degrees"
+                         % (float(th[bad][0]), tuple(int(i[0]) for i in np.nonzero(bad))))
+    cos = np.cos(th / 180.0 * np.pi)
+    sw, sc = np.zeros(dom.shape), np.zeros(dom.shape)
+    lo, hi = np.full(dom.shape, np.inf), np.full(dom.shape, -np.inf)
+    for dz, dy, dx in D3Q19_LINKS:
+        w = 1.0 / 18.0 if dz * dz + dy * dy + dx * dx == 1 else 1.0 / 36.0
+        s = np.roll(solid, (-dz, -dy, -dx), axis=(0, 1, 2))          # s[z, y, x] = solid[z + dz, y + dy, x + dx], wrapped
+        t = np.roll(th, (-dz, -dy, -dx), axis=(0, 1, 2))
+        sw += np.where(s, w, 0.0)
+        sc += np.where(s, w * np.roll(cos, (-dz, -dy, -dx), axis=(0, 1, 2)), 0.0)
+        lo, hi = np.where(s, np.minimum(lo, t), lo), np.where(s, np.maximum(hi, t), hi)
+    wall = ~solid & (sw > 0.0)
+    out = np.full(dom.shape, np.nan)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        mixed = np.degrees(np.arccos(np.clip(sc / sw, -1.0, 1.0)))
+    out[wall] = np.where(lo == hi, lo, mixed)[wall]
+    return out
+
+
 def initial_densities_rk3d(is_domain, nbuf, rho_r=1.0, rho_b=1.0):
     """3-D analogue of RKD2Q9.py:511-531: red below the top buffer planes, blue in them."""
     nz = is_domain.shape[0]

@@ -12,7 +12,7 @@ from ._lib import F64P, U8P, RK3DCSFConfig, SlabTransportCalls, check
 from .slab import connect_in_library
 
 FIELDS = dict(fR=0, fB=1, rhoR=2, rhoB=3, vx=4, vy=5, vz=6, phi=7, Gx=8, Gy=9, Gz=10, Fx=11, Fy=12, Fz=13, K=14, nsx=15, nsy=16, nsz=17,
-              kind=18, rec_fR=30, rec_fB=31, rec_rhoR=32, rec_rhoB=33, rec_vx=34, rec_vy=35, rec_vz=36, rec_phi=37)
+              kind=18, theta=19, rec_fR=30, rec_fB=31, rec_rhoR=32, rec_rhoB=33, rec_vx=34, rec_vy=35, rec_vz=36, rec_phi=37)
 _PDF_FIELDS = {"fR", "fB", "rec_fR", "rec_fB"}
 
 # the 2-D ini's parameters (IniFiles/RKtwophasesetup2D.ini) under the 3-D ini's key names for the flow axis (RKtwophasesetup3D.ini:27-38)
@@ -154,6 +154,21 @@ class RK3DCSFSolver(SlabTransportCalls):
         ptr += [self._ptr(a, self.shape, "force") for a in (force or (None, None, None))]
         check(self._L.lbmpm_rk3dcsf_set_pdf(self._h, *ptr), "lbmpm_rk3dcsf_set_pdf")
         self._keep = []
+
+    def set_contact_angles(self, theta):
+        """mixed wettability: theta [nz][ny][nx] in degrees (a slab: with its ghost planes, like set_macro), read at the fluid cells next
+        to solid (get("kind") == 3) and ignored elsewhere, where it may be NaN -- what geometry.wall_contact_angles returns.  It takes
+        the place of params["theta"] in the wetting rule from the next step on; None: back to params["theta"].  Whenever the solver is
+        idle, repeatedly; the state, the step counter and the snapshot of change() stay, and set_macro / set_pdf keep the map.
+        get("theta") returns the angles in force.  ValueError: a wrong shape; LbmpmError (LBMPM_ERR_INVALID): an angle at such a cell
+        that is not finite or not within [0, 180], or params["wetting"] == 0"""
+        if theta is None:
+            check(self._L.lbmpm_rk3dcsf_set_contact_angles(self._h, None), "lbmpm_rk3dcsf_set_contact_angles")
+            return
+        a = _f64(theta)
+        if a.shape != self.shape:
+            raise ValueError("contact angles must have shape %s, not %s" % (self.shape, a.shape))
+        check(self._L.lbmpm_rk3dcsf_set_contact_angles(self._h, a.ctypes.data_as(F64P)), "lbmpm_rk3dcsf_set_contact_angles")
 
     def enable_diagnostics(self, on=True):
         check(self._L.lbmpm_rk3dcsf_enable_diagnostics(self._h, 1 if on else 0), "enable_diagnostics")
@@ -379,6 +394,29 @@ class _SlabGeometry:
         return a[self.ghost[0]:a.shape[0] - self.ghost[1]]
 
 
+def _undivided_angles(theta, shape):
+    if theta is None:
+        return None
+    a = _f64(theta)
+    if a.shape != tuple(shape):
+        raise ValueError("contact angles must have the shape of the undivided lattice %s, not %s" % (tuple(shape), a.shape))
+    return a
+
+
+def _angles_valid(slab, a):
+    """what lbmpm_rk3dcsf_set_contact_angles checks, ahead of the call: RK3DCSFCluster changes no slab when another would refuse"""
+    wall = slab.get("kind") == 3
+    if slab.ghost[0]:
+        wall[0] = False
+    if slab.ghost[1]:
+        wall[-1] = False
+    v = a[wall]
+    if not bool(np.all(np.isfinite(v) & (v >= 0.0) & (v <= 180.0))):
+        z, y, x = [int(i[0]) for i in np.nonzero(wall & ~(np.isfinite(a) & (a >= 0.0) & (a <= 180.0)))]
+        raise _lib.LbmpmError("contact angle %r at the cell (z, y, x) = (%d, %d, %d) of a slab, a fluid cell next to solid: finite and "
+                              "within [0, 180] degrees" % (float(a[z, y, x]), z, y, x), _lib.ERR_INVALID)
+
+
 _TRACERS_AT_CONSTRUCTION = ("tracers on z-slabs are part of the slabs' population message, which is sized when the ring is set up: "
                             "give them to %s at construction (tracers=dict(...)), not afterwards")
 
@@ -412,6 +450,17 @@ class RK3DCSFCluster:
     def set_pdf(self, fR, fB, force=None):
         for s, g in zip(self.slabs, self.geo):
             s.set_pdf(g.cut(np.asarray(fR)), g.cut(np.asarray(fB)), None if force is None else tuple(g.cut(np.asarray(c)) for c in force))
+
+    def set_contact_angles(self, theta):
+        """the undivided array [nz][ny][nx] (RK3DCSFSolver.set_contact_angles; None: the scalar angle again); every slab takes its
+        planes and the images of its neighbours'.  Checked on every slab before any is changed"""
+        theta = _undivided_angles(theta, self.shape)
+        cut = [g.cut(theta) for g in self.geo]
+        if theta is not None:
+            for s, a in zip(self.slabs, cut):
+                _angles_valid(s, a)
+        for s, a in zip(self.slabs, cut):
+            s.set_contact_angles(a)
 
     def configure_tracers(self, *args, **kwargs):
         """refused: on slabs the tracers change the size of the population message, so they are given at construction (tracers=)"""
@@ -570,6 +619,11 @@ class RK3DCSFDistributed:
     def configure_tracers(self, *args, **kwargs):
         """refused: on slabs the tracers change the size of the population message, so they are given at construction (tracers=)"""
         raise _lib.LbmpmError(_TRACERS_AT_CONSTRUCTION % type(self).__name__, _lib.ERR_UNSUPPORTED)
+
+    def set_contact_angles(self, theta):
+        """the undivided array [nz][ny][nx], the same on every rank (RK3DCSFSolver.set_contact_angles; None: the scalar angle again);
+        every rank takes its planes and the images of its neighbours'.  Call it after sync(): the slab must be idle"""
+        self.slab.set_contact_angles(self.geo.cut(_undivided_angles(theta, self.shape)))
 
     def set_concentration(self, t, conc):
         """the undivided array [nz][ny][nx]; every rank takes its planes (and the images of its neighbours')"""
