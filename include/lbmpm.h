@@ -680,6 +680,14 @@ int64_t lbmpm_rk3d_device_bytes(const lbmpm_rk3d *ctx);
  * the place of contact_angle_deg in the wetting rule and nowhere else; the rule is local to the cell, so the slabs' messages stay as they
  * are (LBMPM_CSF_MSG_NORMAL carries the sender's corrected normal).  A uniform map equals the scalar run bit for bit
  * (tests/test_rk3d_csf_wettability_gpu.py).
+ * Body force (gravity, force-driven flow): lbmpm_rk3dcsf_set_body_force gives each colour an acceleration g_R, g_B in lattice units.  In
+ * every fluid cell the step computes, the force density is F_b = rho_R g_R + rho_B g_B with the densities the cell has after the step's
+ * boundary-plane rules.  The velocity is u = ((sum e f_tot + F_csf / 2) + F_b / 2) / rho, evaluated in that order: the CSF force stays the
+ * one of the step before, F_b is the step's own, so nothing new is stored per cell.  The Guo source (SRT :1743-1798, MRT :2027-2113 in
+ * moment space) takes F_csf + F_b in the place of F_csf.  LBMPM_RK3DCSF_F*, the force of lbmpm_rk3dcsf_set_pdf, restart data and the
+ * slabs' messages stay the CSF force alone; LBMPM_RK3DCSF_V* / _REC_V*, the integrals, lbmpm_rk3dcsf_change, the cluster properties and
+ * the tracers' flow all carry the u above.  The force is not a configuration field: a context without one runs the kernels it always ran,
+ * and the bulk path (`variant` 0) stays bit-equal to the full path with one (tests/test_rk3d_csf_body_force_gpu.py).
  * ---------------------------------------------------------------------------------- */
 typedef struct lbmpm_rk3dcsf_config {
     int64_t nx, ny, nz;        /* xDomain, yDomain, zDomain (incl. the ghost planes 0 and nz-1); nz >= 8 */
@@ -757,6 +765,13 @@ int lbmpm_rk3dcsf_set_pdf(lbmpm_rk3dcsf *ctx, const double *pdf_r, const double 
  * the scalar run bit for bit.  Device memory: 24 bytes per fluid cell (theta, cos, sin numbered by fluid cell), allocated by the first
  * call and counted by lbmpm_rk3dcsf_device_bytes. */
 int lbmpm_rk3dcsf_set_contact_angles(lbmpm_rk3dcsf *ctx, const double *theta_deg);
+/* Body force per colour.  accel_r, accel_b: three doubles each (x, y, z), lattice units.  Both NULL, or all six zero: no body force -- the
+ * step runs the kernels it ran before.  Any time the solver is idle, repeatedly; the state, the step counter, the contact-angle map and
+ * the snapshot of lbmpm_rk3dcsf_change stay; set_macro / set_pdf keep it.  On slabs: the same call on every slab.  LBMPM_ERR_INVALID
+ * (nothing changed): one pointer NULL, a value not finite.  LBMPM_ERR_STATE (nothing changed): between the stages of a step. */
+int lbmpm_rk3dcsf_set_body_force(lbmpm_rk3dcsf *ctx, const double *accel_r, const double *accel_b);
+/* the accelerations in force (zeros without a body force) */
+int lbmpm_rk3dcsf_get_body_force(const lbmpm_rk3dcsf *ctx, double *accel_r, double *accel_b);
 int lbmpm_rk3dcsf_step(lbmpm_rk3dcsf *ctx, int64_t nsteps);          /* undivided lattices only (ghost_lo = ghost_hi = 0) */
 /* One third of a time step, in order 0, 1, 2: (0) the blocks' lists, the bulk's collision on its own stream, the phase field;
  * (1) phi on the wetting solids, gradient, n; (2) the collision of the full path, buffers swapped.  Between them the face messages:

@@ -64,6 +64,13 @@ ini's ContactAngle.  geometry.wall_contact_angles turns it into the angle of eve
 cell's solid neighbours), set_contact_angles hands that to the solver (under torchrun every rank cuts its planes), and the result file
 gets /Wettability/ContactAngle once: the angles in force, get("theta") of the whole lattice (rank 0 writes).  A checkpoint does not hold
 the map: restart_from= applies it again from the same argument.
+
+body_force = (gx, gy, gz) for both colours | dict(red=(gx, gy, gz), blue=(gx, gy, gz)) (also [BodyForce] isBodyForce = 'yes' with
+bodyForceX / Y / Z and the optional bodyForce{X,Y,Z}R / ...B of the ini, --body-force GX GY GZ [--body-force-blue GX GY GZ] of the command
+line; 3-D CSF only, ConfigError on the perturbation model, whose solver has no force term): an acceleration per colour in lattice units --
+gravity, or the drive of a force-driven flow between open planes at equal pressure (set_body_force; the model: include/lbmpm.h).  The
+result file gets /BodyForce/Acceleration [2][3] once: red, blue as the solver holds them.  A checkpoint does not hold the force:
+restart_from= applies it again from the same argument.
 """
 import os
 
@@ -141,9 +148,14 @@ class RKColorGradient3D:
     def __init__(self, pathIniFile, output_dir=None, domain=None, device=0, record_every=None, num_buffering_layers=10,
                  structure_path=None, initial_dir=None, record_pdf=False, restart_from=None, checkpoint_every=0, csf_bulk_epsilon=0.0,
                  csf_transport=None, integrals_every=0, clusters_every=0, clusters_connectivity=6, morphology_every=0,
-                 morphology_phi_cut=0.0, clusters_props=False, steady_every=0, steady_tol=0.0, steady_phase_tol=None, contact_angle_solids=None):
+                 morphology_phi_cut=0.0, clusters_props=False, steady_every=0, steady_tol=0.0, steady_phase_tol=None, contact_angle_solids=None,
+                 body_force=None):
         self.pathIni = pathIniFile
         self.par = config.read_rk3d(pathIniFile)
+        # an acceleration per colour (3-D CSF only): (gx, gy, gz) for both, or dict(red=, blue=); None: the ini's [BodyForce], if any
+        self.body_force = self._body_force_arg(body_force if body_force is not None else self.par.get("body_force"))
+        if self.body_force is not None and self.par["tension_type"] != "CSF":
+            raise config.ConfigError("body_force belongs to SurfaceTensionType = 'CSF': the perturbation model's solver has no force term")
         # mixed wettability (3-D CSF only): contact angles per solid voxel, an array or the path of a .npy file; None: the ini's ContactAngleFile, if any
         self.contact_angle_solids = contact_angle_solids if contact_angle_solids is not None else self.par.get("contact_angle_file")
         if self.contact_angle_solids is not None and self.par["tension_type"] != "CSF":
@@ -222,6 +234,28 @@ class RKColorGradient3D:
         if a.shape != self.isDomain.shape:
             raise config.ConfigError("contact angles have shape %s, the lattice %s" % (a.shape, self.isDomain.shape))
         return a
+
+    @staticmethod
+    def _body_force_arg(bf):
+        """body_force= as the keyword arguments of set_body_force, or None"""
+        if bf is None:
+            return None
+        kw = dict(bf) if isinstance(bf, dict) else dict(g=bf)
+        if set(kw) - {"g", "red", "blue"}:
+            raise config.ConfigError("body_force = (gx, gy, gz) or dict(red=(gx, gy, gz), blue=(gx, gy, gz)), not %r" % (bf,))
+        try:
+            from .rk3dcsf import body_force_pair
+            body_force_pair(kw.get("g"), kw.get("red"), kw.get("blue"))
+        except (ValueError, TypeError) as e:
+            raise config.ConfigError("body_force: %s" % e)
+        return kw
+
+    def _apply_body_force(self, solver, out):
+        """body_force into the solver (every rank makes the same call) and the accelerations in force into /BodyForce/Acceleration"""
+        kw = dict(self.body_force)
+        solver.set_body_force(kw.pop("g", None), **kw)
+        if out is not None:
+            out.write("BodyForce", "Acceleration", np.array(solver.body_force, dtype=np.float64))
 
     def _apply_contact_angles(self, solver, out):
         """the wall angles of contact_angle_solids into the solver (the undivided array: a distributed solver cuts its planes), and the
@@ -418,10 +452,13 @@ class RKColorGradient3D:
         severy = self.steady_every
         more = ((("Integrals", "PlaneIntegrals"),) if every > 0 and rank == 0 else ()) + ((("Clusters", "PhaseClusters"),) if cevery > 0 and rank == 0 else ()) + \
             ((("Morphology", "PhaseMorphology"),) if mevery > 0 and rank == 0 else ()) + ((("Steady", "SteadyState"),) if severy > 0 and rank == 0 else ()) + \
-            ((("Wettability", "ContactAngles"),) if self.contact_angle_solids is not None else ())
+            ((("Wettability", "ContactAngles"),) if self.contact_angle_solids is not None else ()) + \
+            ((("BodyForce", "Acceleration"),) if self.body_force is not None else ())
         out = ResultFile(self.output_dir, name, GROUPS + more) if writes else None
         if self.contact_angle_solids is not None:
             self._apply_contact_angles(sim.solver, out)          # (after a restart_from too: a checkpoint does not hold the map)
+        if self.body_force is not None:
+            self._apply_body_force(sim.solver, out)              # (likewise)
         self.integral_steps, self.cluster_steps, self.morphology_steps = [], [], []
         self.steady_steps, self.steady_criteria, self.steady_step = [], [], None
         marked = False

@@ -17,6 +17,8 @@ record the 3-D driver writes after the last step holds the concentrations as the
 checkpoint() / restart_from= carry the tracers' populations behind the flow's (41 + 7 per tracer doubles per cell): bit for bit.
 contact_angle_solids= / [SurfaceTension] ContactAngleFile: mixed wettability exactly as in the flow's driver (RKColorGradientD3Q19.py),
 /Wettability/ContactAngle in SimulationResultsRK3D.h5; a checkpoint does not hold the map, restart_from= applies it again.
+body_force= / [BodyForce] isBodyForce = 'yes': an acceleration per colour exactly as in the flow's driver; the tracers are advected by the
+velocity that holds half of it.  /BodyForce/Acceleration in SimulationResultsRK3D.h5; restart_from= applies it again.
 
 integrals_every = N > 0: every N steps (step 0 and the last step included; the step loop's runs are cut there as at the record and
 checkpoint cadences) two tables, both reduced on the device and the same bit for bit on any number of ranks: the flow's plane integrals
@@ -113,9 +115,12 @@ class Transport3DRK(RKColorGradient3D):
         every = self.integrals_every
         more = lambda group: ((group, "PlaneIntegrals"),) if every > 0 else ()
         wett = (("Wettability", "ContactAngles"),) if self.contact_angle_solids is not None else ()
-        flow = ResultFile(self.output_dir, "SimulationResultsRK3D", GROUPS + more("Integrals") + wett) if rank == 0 else None
+        force = (("BodyForce", "Acceleration"),) if self.body_force is not None else ()
+        flow = ResultFile(self.output_dir, "SimulationResultsRK3D", GROUPS + more("Integrals") + wett + force) if rank == 0 else None
         if self.contact_angle_solids is not None:
             self._apply_contact_angles(slab.solver, flow)        # mixed wettability, as in the flow's driver (after a restart_from too)
+        if self.body_force is not None:
+            self._apply_body_force(slab.solver, flow)            # likewise
         conc = ResultFile(self.output_dir, "ConcentrationResults", (("TransportMacro", "MacroData"),) + more("TracerIntegrals")) if rank == 0 else None
         self.integral_steps = []
         self.result_path, self.concentration_path = (flow.path, conc.path) if rank == 0 else (None, None)

@@ -18,6 +18,8 @@
         [--morphology-phi-cut c]                  of the result file); interfacial area, wetted fraction, Euler characteristics, capillary pressure to the log
         [--contact-angles FILE]                   rk3d with SurfaceTensionType = 'CSF', tr3d: mixed wettability -- a .npy of contact angles per solid voxel
                                                   (the lattice's shape, or the voxel file's; NaN = the ini's ContactAngle); /Wettability/ContactAngle
+        [--body-force GX GY GZ]                   rk3d with SurfaceTensionType = 'CSF', tr3d: an acceleration in lattice units for both colours (gravity,
+        [--body-force-blue GX GY GZ]              force-driven flow), the second option: another one for blue; /BodyForce/Acceleration of the result file
         [--steady-every N]                        rk3d: the change of velocity and phase field between multiples of N steps, reduced on the device (/Steady of
         [--steady-tol t] [--steady-phase-tol p]   the result file); with a tolerance the run ends at the first multiple where the change is within it
 """
@@ -45,6 +47,9 @@ def _rank_device(device):
 
 def parser():
     ap = argparse.ArgumentParser(prog="python -m openlbmpm_amd")
+    # (argparse takes -1e-6 for an option: its pattern of a negative number knows no exponent; --body-force 0 0 -1e-6 is gravity)
+    import re
+    ap._negative_number_matcher = re.compile(r"^-(\d+\.?\d*|\.\d+)([eE][-+]?\d+)?$")
     ap.add_argument("model", choices=["rk", "sc", "tr", "rk3d", "tr3d"], help="rk = colour gradient (RKtwophasesetup2D.ini); "
                                                        "sc = Shan-Chen / EFS (twophasesetup.ini + efs2D.ini|shanchen2D.ini)")
     ap.add_argument("ini_dir")
@@ -57,6 +62,12 @@ def parser():
                     help="rk3d with SurfaceTensionType = 'CSF', tr3d: contact angles in degrees per solid voxel (.npy in the shape of the lattice, or of the "
                          "voxel file; NaN: the ini's ContactAngle) -- every fluid cell next to solid takes the Cassie average over its solid neighbours; "
                          "the angles in force go to /Wettability/ContactAngle of the result file.  The same as [SurfaceTension] ContactAngleFile")
+    ap.add_argument("--body-force", type=float, nargs=3, default=None, metavar=("GX", "GY", "GZ"),
+                    help="rk3d with SurfaceTensionType = 'CSF', tr3d: an acceleration in lattice units on both colours (force density rho_R g + rho_B g): "
+                         "gravity, or the drive of a flow between open planes at equal pressure.  The same as [BodyForce] isBodyForce = 'yes' with "
+                         "bodyForceX / Y / Z; /BodyForce/Acceleration of the result file")
+    ap.add_argument("--body-force-blue", type=float, nargs=3, default=None, metavar=("GX", "GY", "GZ"),
+                    help="... the blue fluid's acceleration where it differs (--body-force is then the red one's; alone: red has none)")
     ap.add_argument("--integrals-every", type=int, default=0, metavar="N",
                     help="rk3d, tr3d: every N steps the plane integrals (saturation, masses, fluxes, largest speed, non-finite cells), reduced on the device, "
                          "to /Integrals of the result file and the log; tr3d also the tracers' (cells, mass, flux_x, flux_y, flux_z, sum_c2, cmin, cmax, "
@@ -83,9 +94,20 @@ def parser():
     return ap
 
 
+def _body_force(a):
+    """--body-force / --body-force-blue as the drivers' body_force=, or None"""
+    if a.body_force is None and a.body_force_blue is None:
+        return None
+    if a.body_force_blue is None:
+        return tuple(a.body_force)
+    return dict(red=tuple(a.body_force or (0.0, 0.0, 0.0)), blue=tuple(a.body_force_blue))
+
+
 def main(argv=None):
     a = parser().parse_args(argv)
     t0 = time.time()
+    if a.model not in ("rk3d", "tr3d") and _body_force(a) is not None:
+        raise SystemExit("--body-force belongs to rk3d (SurfaceTensionType = 'CSF') and tr3d: the 2-D solvers have no body force")
     if a.model == "rk":
         from .RKD2Q9 import RKColorGradientLBM
         sim = RKColorGradientLBM(a.ini_dir, output_dir=a.out, device=a.device)
@@ -99,7 +121,8 @@ def main(argv=None):
         sim = RKColorGradient3D(a.ini_dir, output_dir=a.out, device=device, csf_transport=a.csf_transport, integrals_every=a.integrals_every,
                                 clusters_every=a.clusters_every, clusters_connectivity=a.clusters_connectivity, clusters_props=a.clusters_props,
                                 morphology_every=a.morphology_every, morphology_phi_cut=a.morphology_phi_cut, steady_every=a.steady_every,
-                                steady_tol=a.steady_tol, steady_phase_tol=a.steady_phase_tol, contact_angle_solids=a.contact_angles)
+                                steady_tol=a.steady_tol, steady_phase_tol=a.steady_phase_tol, contact_angle_solids=a.contact_angles,
+                                body_force=_body_force(a))
         if a.steps is not None:
             sim.timeSteps = a.steps
         path = sim.runRKColorGradient3D()
@@ -109,7 +132,7 @@ def main(argv=None):
     elif a.model == "tr3d":
         from .Transport3DRK import Transport3DRK
         sim = Transport3DRK(a.ini_dir, output_dir=a.out, device=_rank_device(a.device), csf_transport=a.csf_transport,
-                            integrals_every=a.integrals_every, contact_angle_solids=a.contact_angles)
+                            integrals_every=a.integrals_every, contact_angle_solids=a.contact_angles, body_force=_body_force(a))
         if a.steps is not None:
             sim.timeSteps = a.steps
         path = " and ".join(str(f) for f in sim.runTransport3DMPMCRK())        # (under torchrun rank 0 writes both files)

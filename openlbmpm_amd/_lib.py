@@ -208,6 +208,8 @@ _SIGNATURES = {
     "lbmpm_rk3dcsf_set_macro": (C.c_int, [C.c_void_p, F64P, F64P, F64P, F64P, F64P]),
     "lbmpm_rk3dcsf_set_pdf": (C.c_int, [C.c_void_p, F64P, F64P, F64P, F64P, F64P]),
     "lbmpm_rk3dcsf_set_contact_angles": (C.c_int, [C.c_void_p, F64P]),
+    "lbmpm_rk3dcsf_set_body_force": (C.c_int, [C.c_void_p, F64P, F64P]),
+    "lbmpm_rk3dcsf_get_body_force": (C.c_int, [C.c_void_p, F64P, F64P]),
     "lbmpm_rk3dcsf_step": (C.c_int, [C.c_void_p, C.c_int64]),
     "lbmpm_rk3dcsf_step_timed": (C.c_int, [C.c_void_p, C.c_int64, F64P, F64P]),
     "lbmpm_rk3dcsf_stage": (C.c_int, [C.c_void_p, C.c_int]),

@@ -183,6 +183,15 @@ def read_rk3d(ini_dir):
     p["densityRL"] = c.float("BoundaryCondition", "densityRL", default=1.0)
     if c.str("GradientType", "Type", default="'Isotropic'") != "Isotropic":
         raise ConfigError("[GradientType] Type: only 'Isotropic'")
+    # [BodyForce] isBodyForce = 'yes' (the section of RKtwophasesetup2D.ini, with a z component): an acceleration per colour for the 3-D CSF
+    # loop -- bodyForceX / Y / Z for both colours, bodyForce{X,Y,Z}R / ...B in their place for one (rk3dcsf.RK3DCSFSolver.set_body_force)
+    p["body_force"] = None
+    if c.str("BodyForce", "isBodyForce", default="'no'") == "yes":
+        if not csf:
+            raise ConfigError("[BodyForce] isBodyForce = 'yes' belongs to SurfaceTensionType = 'CSF': the perturbation model's solver has no force term")
+        both = [c.float("BodyForce", "bodyForce" + a, default=0.0) for a in "XYZ"]
+        p["body_force"] = dict((name, tuple(c.float("BodyForce", "bodyForce" + a + tag, default=both[i]) for i, a in enumerate("XYZ")))
+                               for name, tag in (("red", "R"), ("blue", "B")))
     p["steps"] = c.int("TimeSteps", "TimeSteps")
     p["interval"] = c.int("TimeSteps", "TimeInterval", default=0)       # not in the shipped file
     p["relax"] = c.str("RelaxationType", "Type", default="'SRT'")

@@ -87,6 +87,8 @@ struct CsfDev {
     double *trflow;              // [4][FS] tracers configured: rho_R, u of the step per fluid cell, for tr3d_step (rk3d_tracer.h); else null
     const double *wang;          // [3][NF] after lbmpm_rk3dcsf_set_contact_angles: theta in degrees, cos, sin of the fluid cells next to solid (kind 3),
                                  // numbered by fluid cell; the wetting rule takes them in the place of cosT, sinT.  Else null
+    double gacc[6];              // lbmpm_rk3dcsf_set_body_force: the accelerations g_R (x, y, z), g_B (x, y, z); zeros without one
+    int bf;                      // a body force is set (the collisions are told by their template parameter BF, the observers look here)
 };
 
 struct Nb { unsigned xo[3], yo[3], zo[3]; };
@@ -124,6 +126,20 @@ __device__ __forceinline__ double feq(double rho, int i, int cx, int cy, int cz,
     return rho * wq(i) * (1 + (3. * eu + 4.5 * eu * eu - 1.5 * (vx * vx + vy * vy + vz * vz)));
 }
 __device__ __forceinline__ double sum_inplane(const double f[Q]) { return f[0] + f[1] + f[2] + f[3] + f[4] + f[7] + f[8] + f[9] + f[10]; }
+
+// Body force (lbmpm_rk3dcsf_set_body_force; the model: include/lbmpm.h).  Its density F_b = rho_R g_R + rho_B g_B is taken from the
+// densities cell_state<., true> returns, so it is known within the step and never stored: p.F stays the CSF force alone.
+__device__ __forceinline__ void body_force(const CsfDev &p, double rR, double rB, double &bx, double &by, double &bz)
+{
+    bx = rR * p.gacc[0] + rB * p.gacc[3]; by = rR * p.gacc[1] + rB * p.gacc[4]; bz = rR * p.gacc[2] + rB * p.gacc[5];
+}
+// one component of u = ((sum e f_tot + F_csf / 2) + F_b / 2) / rho, in that order (A:2634-2654 with the CSF force of the step before);
+// every place that forms u goes through here: the two collisions (bf their BF), csf3d_observe and CsfIntLoader (bf = p.bf)
+__device__ __forceinline__ double velocity_of(double m, double fcsf, double fb, double rho, bool bf)
+{
+    const double h = m + 0.5 * fcsf;
+    return (bf ? h + 0.5 * fb : h) / rho;
+}
 
 // The populations, densities of one fluid cell as the loop's first half leaves them: pulled (FIRST: taken where they stand -- the state
 // given by set_macro / set_pdf has been streamed already), then the boundary-plane rule of the cell's plane.  BC = false: the pull alone
@@ -470,12 +486,42 @@ __device__ __forceinline__ double tau_of(const CsfDev &p, double Phi, double rR,
     return tau;
 }
 
+// Guo source of the force f added to the relaxed f_tot, SRT: A:1743-1798
+__device__ __forceinline__ void add_guo_srt(double t[Q], double tau, double vx, double vy, double vz, double fx, double fy, double fz)
+{
+    constexpr int CX[Q] = CSF_CX, CY[Q] = CSF_CY, CZ[Q] = CSF_CZ;
+#pragma unroll
+    for (int i = 0; i < Q; ++i) {
+        const double eu = edotv(CX[i], CY[i], CZ[i], vx, vy, vz);
+        const double src = wq(i) * ((3. * ((double)CX[i] - vx) + 9. * (double)CX[i] * eu) * fx + (3. * ((double)CY[i] - vy) + 9. * (double)CY[i] * eu) * fy +
+                                    (3. * ((double)CZ[i] - vz) + 9. * (double)CZ[i] * eu) * fz) * (1. - 1. / (2. * tau));
+        t[i] = t[i] + src;
+    }
+}
+// ... MRT, in moment space M^-1 (I - S/2) M: A:2027-2113.  S: the collision's rates on entry, I - S/2 on return
+__device__ __forceinline__ void add_guo_mrt(double t[Q], double S[Q], double vx, double vy, double vz, double fx, double fy, double fz)
+{
+    constexpr int CX[Q] = CSF_CX, CY[Q] = CSF_CY, CZ[Q] = CSF_CZ;
+    double d[Q];
+    const double uf = vx * fx + vy * fy + vz * fz;
+#pragma unroll
+    for (int i = 0; i < Q; ++i) {
+        const double ef = edotv(CX[i], CY[i], CZ[i], fx, fy, fz), eu = edotv(CX[i], CY[i], CZ[i], vx, vy, vz);
+        d[i] = wq(i) * (3. * ef + 9. * eu * ef - 3. * uf);
+        S[i] = 1. - 0.5 * S[i];
+    }
+    mrt_apply(S, d);
+#pragma unroll
+    for (int i = 0; i < Q; ++i) t[i] = t[i] + d[i];
+}
+
 // second half of the loop for one cell: curvature and force, collision with the Guo source, recolouring; stores the post-collision
 // populations (the next step pulls them).  DIAG: also keep u and K of the step.  TR: keep rho_R and u per fluid cell for the tracers.
+// BF: a body force is set -- u takes half of it, the Guo source takes F_csf + F_b; the force stored for the next step stays F_csf.
 #ifndef CSF_MRT_WAVES
 #define CSF_MRT_WAVES 2
 #endif
-template <bool FIRST, bool MRT, bool DIAG, bool TR>
+template <bool FIRST, bool MRT, bool DIAG, bool TR, bool BF>
 __global__ __launch_bounds__(256, MRT ? CSF_MRT_WAVES : 3) void csf3d_collide(CsfDev p)
 {
     constexpr int CX[Q] = CSF_CX, CY[Q] = CSF_CY, CZ[Q] = CSF_CZ;
@@ -503,7 +549,9 @@ __global__ __launch_bounds__(256, MRT ? CSF_MRT_WAVES : 3) void csf3d_collide(Cs
     for (int i = 1; i < Q; ++i) { addc(mx, CX[i], t[i]); addc(my, CY[i], t[i]); addc(mz, CZ[i], t[i]); }
     const double rs = rB + rR;
     const double pfx_ = was_deep ? 0. : p.F[n], pfy_ = was_deep ? 0. : p.F[p.NS + n], pfz_ = was_deep ? 0. : p.F[2 * p.NS + n];
-    const double vx = (mx + 0.5 * pfx_) / rs, vy = (my + 0.5 * pfy_) / rs, vz = (mz + 0.5 * pfz_) / rs;
+    double bx = 0., by = 0., bz = 0.;
+    if (BF) body_force(p, rR, rB, bx, by, bz);
+    const double vx = velocity_of(mx, pfx_, bx, rs, BF), vy = velocity_of(my, pfy_, by, rs, BF), vz = velocity_of(mz, pfz_, bz, rs, BF);
     const double phi = (rR - rB) / (rR + rB);
     // A:2499-2551: derivatives of n over the fluid neighbours, K = -(I - n n) : grad n
     double gx = 0., gy = 0., gz = 0., k = 0., fx = 0., fy = 0., fz = 0.;
@@ -529,19 +577,14 @@ __global__ __launch_bounds__(256, MRT ? CSF_MRT_WAVES : 3) void csf3d_collide(Cs
     if (DIAG) { p.K[n] = k; p.U[n] = vx; p.U[p.NS + n] = vy; p.U[2 * p.NS + n] = vz; }
     if (TR) { p.trflow[j] = rR; p.trflow[p.FS + j] = vx; p.trflow[2 * p.FS + j] = vy; p.trflow[3 * p.FS + j] = vz; }
     const double tau = tau_of(p, phi, rR, rB);
+    const double gfx = BF ? fx + bx : fx, gfy = BF ? fy + by : fy, gfz = BF ? fz + bz : fz;       // what the Guo source takes
     if (!MRT) {
 #pragma unroll
         for (int i = 0; i < Q; ++i) {                    // A:1804-1848
             const double eT = feq(rR, i, CX[i], CY[i], CZ[i], vx, vy, vz) + feq(rB, i, CX[i], CY[i], CZ[i], vx, vy, vz);
             t[i] = -1. / tau * (t[i] - eT) + t[i];
         }
-#pragma unroll
-        for (int i = 0; i < Q; ++i) {                    // A:1743-1798
-            const double eu = edotv(CX[i], CY[i], CZ[i], vx, vy, vz);
-            const double src = wq(i) * ((3. * ((double)CX[i] - vx) + 9. * (double)CX[i] * eu) * fx + (3. * ((double)CY[i] - vy) + 9. * (double)CY[i] * eu) * fy +
-                                        (3. * ((double)CZ[i] - vz) + 9. * (double)CZ[i] * eu) * fz) * (1. - 1. / (2. * tau));
-            t[i] = t[i] + src;
-        }
+        add_guo_srt(t, tau, vx, vy, vz, gfx, gfy, gfz);
     } else {
         const double it = 1. / tau;
         double S[Q] = {p.rate[5], p.rate[0], p.rate[1], p.rate[5], p.rate[2], p.rate[5], p.rate[2], p.rate[5], p.rate[2], it, p.rate[3], it, p.rate[3],
@@ -552,16 +595,7 @@ __global__ __launch_bounds__(256, MRT ? CSF_MRT_WAVES : 3) void csf3d_collide(Cs
         mrt_apply(S, d);                                 // A:1938-2017
 #pragma unroll
         for (int i = 0; i < Q; ++i) t[i] = -d[i] + t[i];
-        const double uf = vx * fx + vy * fy + vz * fz;
-#pragma unroll
-        for (int i = 0; i < Q; ++i) {                    // A:2027-2113
-            const double ef = edotv(CX[i], CY[i], CZ[i], fx, fy, fz), eu = edotv(CX[i], CY[i], CZ[i], vx, vy, vz);
-            d[i] = wq(i) * (3. * ef + 9. * eu * ef - 3. * uf);
-            S[i] = 1. - 0.5 * S[i];
-        }
-        mrt_apply(S, d);
-#pragma unroll
-        for (int i = 0; i < Q; ++i) t[i] = t[i] + d[i];
+        add_guo_mrt(t, S, vx, vy, vz, gfx, gfy, gfz);
     }
     // A:1857-1899 calRecoloringProcessM
     const double gn = sqrt(gx * gx + gy * gy + gz * gz), tot = rR + rB;
@@ -591,13 +625,16 @@ __global__ __launch_bounds__(256, MRT ? CSF_MRT_WAVES : 3) void csf3d_collide(Cs
     }   // blocks of the list
 }
 
-// The deep blocks' collision (deep_colour): one colour alone, no gradient, no force.  What the full path computes then, term by term --
-// the absent colour's populations and equilibrium are exact zeros, the Guo source is a sum of products by F = 0, cos(theta_i) = 0,
-// rho_c / rho = 1 exactly -- so the present colour's populations are the relaxed f_tot and the other colour's are zeros, bit for bit
-// (tests: variant 1 runs every block through csf3d_collide).  19 loads through the table of source cells (no lattice coordinates, no
+// The deep blocks' collision (deep_colour): one colour alone, no gradient, no CSF force.  What the full path computes then, term by term --
+// the absent colour's populations and equilibrium are exact zeros, the Guo source of the CSF force is a sum of products by F = 0,
+// cos(theta_i) = 0, rho_c / rho = 1 exactly -- so the present colour's populations are the relaxed f_tot and the other colour's are zeros,
+// bit for bit (tests: variant 1 runs every block through csf3d_collide).  BF: the body force is there all the same, F_b = rho_c g_c + 0 g
+// by the full path's own expression (body_force with the absent density an exact zero), half of it in u and its Guo source -- the full
+// path's F_csf + F_b with F_csf = -+0, which adds nothing to a sum (F_b is +0, never -0, where it vanishes: set_body_force hands on no -0).
+// 19 loads through the table of source cells (no lattice coordinates, no
 // meta words: the open planes are never deep), 19 stores; the absent colour is not read, and not written again once its zeros are in
 // place (a block deep since the step before: this buffer was written two steps ago, when the block held that colour alone already).
-template <bool MRT, bool DIAG, bool TR>
+template <bool MRT, bool DIAG, bool TR, bool BF>
 __global__ __launch_bounds__(256) void csf3d_collide_deep(CsfDev p)
 {
     constexpr int CX[Q] = CSF_CX, CY[Q] = CSF_CY, CZ[Q] = CSF_CZ, OPP[Q] = CSF_OPP;
@@ -627,7 +664,9 @@ __global__ __launch_bounds__(256) void csf3d_collide_deep(CsfDev p)
             unsigned n = 0;
             if (!was_deep || DIAG) n = p.cells[j];
             const double pfx_ = was_deep ? 0. : p.F[n], pfy_ = was_deep ? 0. : p.F[p.NS + n], pfz_ = was_deep ? 0. : p.F[2 * p.NS + n];
-            const double vx = (mx + 0.5 * pfx_) / rs, vy = (my + 0.5 * pfy_) / rs, vz = (mz + 0.5 * pfz_) / rs;
+            double bx = 0., by = 0., bz = 0.;
+            if (BF) body_force(p, rR, rB, bx, by, bz);
+            const double vx = velocity_of(mx, pfx_, bx, rs, BF), vy = velocity_of(my, pfy_, by, rs, BF), vz = velocity_of(mz, pfz_, bz, rs, BF);
             const double phi = (rR - rB) / (rR + rB);
             if (!was_deep) { p.F[n] = 0.; p.F[p.NS + n] = 0.; p.F[2 * p.NS + n] = 0.; }
             if (DIAG) { p.K[n] = 0.; p.U[n] = vx; p.U[p.NS + n] = vy; p.U[2 * p.NS + n] = vz; }
@@ -639,9 +678,10 @@ __global__ __launch_bounds__(256) void csf3d_collide_deep(CsfDev p)
                     const double eT = feq(rc, i, CX[i], CY[i], CZ[i], vx, vy, vz);      // (+ the absent colour's 0 * ... = +0)
                     t[i] = -1. / tau * (t[i] - eT) + t[i];
                 }
+                if (BF) add_guo_srt(t, tau, vx, vy, vz, bx, by, bz);
             } else {
                 const double it = 1. / tau;
-                const double S[Q] = {p.rate[5], p.rate[0], p.rate[1], p.rate[5], p.rate[2], p.rate[5], p.rate[2], p.rate[5], p.rate[2], it, p.rate[3], it, p.rate[3],
+                double S[Q] = {p.rate[5], p.rate[0], p.rate[1], p.rate[5], p.rate[2], p.rate[5], p.rate[2], p.rate[5], p.rate[2], it, p.rate[3], it, p.rate[3],
                                      it, it, it, p.rate[4], p.rate[4], p.rate[4]};
                 double d[Q];
 #pragma unroll
@@ -649,6 +689,7 @@ __global__ __launch_bounds__(256) void csf3d_collide_deep(CsfDev p)
                 mrt_apply(S, d);
 #pragma unroll
                 for (int i = 0; i < Q; ++i) t[i] = -d[i] + t[i];
+                if (BF) add_guo_mrt(t, S, vx, vy, vz, bx, by, bz);
             }
             double *present = p.fout + colour + j, *absent = p.fout + ((size_t)Q * p.FS - colour) + j;
 #pragma unroll
@@ -880,7 +921,9 @@ __global__ __launch_bounds__(256) void csf3d_observe(CsfDev p, double *out_pdf, 
 #pragma unroll
             for (int i = 1; i < Q; ++i) { const double t = fR[i] + fB[i]; addc(mx, CX[i], t); addc(my, CY[i], t); addc(mz, CZ[i], t); }
             const double rs = rB + rR;
-            mx = (mx + 0.5 * p.F[n]) / rs; my = (my + 0.5 * p.F[p.NS + n]) / rs; mz = (mz + 0.5 * p.F[2 * p.NS + n]) / rs;
+            double bx, by, bz;
+            body_force(p, rR, rB, bx, by, bz);
+            mx = velocity_of(mx, p.F[n], bx, rs, p.bf); my = velocity_of(my, p.F[p.NS + n], by, rs, p.bf); mz = velocity_of(mz, p.F[2 * p.NS + n], bz, rs, p.bf);
         }
         out_u[n] = mx; out_u[(size_t)p.N + n] = my; out_u[2 * (size_t)p.N + n] = mz;
         out_phi[n] = fluid ? (rR - rB) / (rR + rB) : 0.;
@@ -1045,7 +1088,9 @@ struct CsfIntLoader {
         for (int i = 1; i < Q; ++i) { const double t = fR[i] + fB[i]; addc(mx, CX[i], t); addc(my, CY[i], t); addc(mz, CZ[i], t); }
         const double rs = rB + rR;
         c.rR = rR; c.rB = rB;
-        c.ux = (mx + 0.5 * p.F[n]) / rs; c.uy = (my + 0.5 * p.F[p.NS + n]) / rs; c.uz = (mz + 0.5 * p.F[2 * p.NS + n]) / rs;
+        double bx, by, bz;
+        body_force(p, rR, rB, bx, by, bz);
+        c.ux = velocity_of(mx, p.F[n], bx, rs, p.bf); c.uy = velocity_of(my, p.F[p.NS + n], by, rs, p.bf); c.uz = velocity_of(mz, p.F[2 * p.NS + n], bz, rs, p.bf);
         c.phi = (rR - rB) / (rR + rB);
         return true;
     }
@@ -1115,6 +1160,8 @@ struct lbmpm_rk3dcsf {
     uint32_t *trsrc = nullptr;                                   // [6][FS] when the context has no table of source cells of its own
     double trB[4][9];
     double *wang = nullptr;        // lbmpm_rk3dcsf_set_contact_angles: [3][nfluid] theta, cos, sin per fluid cell (CsfDev.wang), allocated by the first call
+    double gacc[6] = {0., 0., 0., 0., 0., 0.};      // lbmpm_rk3dcsf_set_body_force: g_R, g_B (CsfDev.gacc)
+    bool bf = false;               // ... one of them is not zero: the step launches the BF instances of the two collisions
 };
 
 namespace {
@@ -1141,6 +1188,8 @@ CsfDev make_dev(const lbmpm_rk3dcsf *c)
     p.nblk = c->nblk; p.skip = c->skip ? 1 : 0; p.pure = c->pure; p.deep_prev = c->deep_prev; p.bcblk = c->bcblk; p.rng = c->rng; p.pfx = c->pfx; p.deep_now = c->deep_now; p.work = c->work; p.src = c->src;
     p.trflow = c->trflow;
     p.wang = c->wang;
+    for (int i = 0; i < 6; ++i) p.gacc[i] = c->gacc[i];
+    p.bf = c->bf ? 1 : 0;
     return p;
 }
 
@@ -1197,13 +1246,17 @@ int launch_step(lbmpm_rk3dcsf *c, const CsfDev &p, hipEvent_t e0, hipEvent_t e1,
         // second stream beside the four launches of the full path (small, latency-bound launches when most of the lattice is bulk)
         LBMPM_HIP_TRY(hipEventRecord(c->ev_lists, c->stream));
         LBMPM_HIP_TRY(hipStreamWaitEvent(c->stream2, c->ev_lists, 0));
-        if (tr) {
-            if (mrt) { if (c->diag) csf3d_collide_deep<true, true, true><<<gw, 256, 0, c->stream2>>>(p); else csf3d_collide_deep<true, false, true><<<gw, 256, 0, c->stream2>>>(p); }
-            else { if (c->diag) csf3d_collide_deep<false, true, true><<<gw, 256, 0, c->stream2>>>(p); else csf3d_collide_deep<false, false, true><<<gw, 256, 0, c->stream2>>>(p); }
-        } else {
-            if (mrt) { if (c->diag) csf3d_collide_deep<true, true, false><<<gw, 256, 0, c->stream2>>>(p); else csf3d_collide_deep<true, false, false><<<gw, 256, 0, c->stream2>>>(p); }
-            else { if (c->diag) csf3d_collide_deep<false, true, false><<<gw, 256, 0, c->stream2>>>(p); else csf3d_collide_deep<false, false, false><<<gw, 256, 0, c->stream2>>>(p); }
-        }
+#define CSF_DEEP(BF) do { \
+        if (tr) { \
+            if (mrt) { if (c->diag) csf3d_collide_deep<true, true, true, BF><<<gw, 256, 0, c->stream2>>>(p); else csf3d_collide_deep<true, false, true, BF><<<gw, 256, 0, c->stream2>>>(p); } \
+            else { if (c->diag) csf3d_collide_deep<false, true, true, BF><<<gw, 256, 0, c->stream2>>>(p); else csf3d_collide_deep<false, false, true, BF><<<gw, 256, 0, c->stream2>>>(p); } \
+        } else { \
+            if (mrt) { if (c->diag) csf3d_collide_deep<true, true, false, BF><<<gw, 256, 0, c->stream2>>>(p); else csf3d_collide_deep<true, false, false, BF><<<gw, 256, 0, c->stream2>>>(p); } \
+            else { if (c->diag) csf3d_collide_deep<false, true, false, BF><<<gw, 256, 0, c->stream2>>>(p); else csf3d_collide_deep<false, false, false, BF><<<gw, 256, 0, c->stream2>>>(p); } \
+        } \
+    } while (0)
+        if (c->bf) CSF_DEEP(true); else CSF_DEEP(false);
+#undef CSF_DEEP
         LBMPM_HIP_TRY(hipEventRecord(c->ev_deep, c->stream2));
     }
     if (stages & 1) csf3d_phase<FIRST><<<gw, 256, 0, c->stream>>>(p);
@@ -1212,13 +1265,17 @@ int launch_step(lbmpm_rk3dcsf *c, const CsfDev &p, hipEvent_t e0, hipEvent_t e1,
         if (p.wang) csf3d_gradient<true><<<gw, 256, 0, c->stream>>>(p); else csf3d_gradient<false><<<gw, 256, 0, c->stream>>>(p);
     }
     if (stages & 4) {
-        if (tr) {
-            if (mrt) { if (c->diag) csf3d_collide<FIRST, true, true, true><<<gw, 256, 0, c->stream>>>(p); else csf3d_collide<FIRST, true, false, true><<<gw, 256, 0, c->stream>>>(p); }
-            else { if (c->diag) csf3d_collide<FIRST, false, true, true><<<gw, 256, 0, c->stream>>>(p); else csf3d_collide<FIRST, false, false, true><<<gw, 256, 0, c->stream>>>(p); }
-        } else {
-            if (mrt) { if (c->diag) csf3d_collide<FIRST, true, true, false><<<gw, 256, 0, c->stream>>>(p); else csf3d_collide<FIRST, true, false, false><<<gw, 256, 0, c->stream>>>(p); }
-            else { if (c->diag) csf3d_collide<FIRST, false, true, false><<<gw, 256, 0, c->stream>>>(p); else csf3d_collide<FIRST, false, false, false><<<gw, 256, 0, c->stream>>>(p); }
-        }
+#define CSF_FULL(BF) do { \
+        if (tr) { \
+            if (mrt) { if (c->diag) csf3d_collide<FIRST, true, true, true, BF><<<gw, 256, 0, c->stream>>>(p); else csf3d_collide<FIRST, true, false, true, BF><<<gw, 256, 0, c->stream>>>(p); } \
+            else { if (c->diag) csf3d_collide<FIRST, false, true, true, BF><<<gw, 256, 0, c->stream>>>(p); else csf3d_collide<FIRST, false, false, true, BF><<<gw, 256, 0, c->stream>>>(p); } \
+        } else { \
+            if (mrt) { if (c->diag) csf3d_collide<FIRST, true, true, false, BF><<<gw, 256, 0, c->stream>>>(p); else csf3d_collide<FIRST, true, false, false, BF><<<gw, 256, 0, c->stream>>>(p); } \
+            else { if (c->diag) csf3d_collide<FIRST, false, true, false, BF><<<gw, 256, 0, c->stream>>>(p); else csf3d_collide<FIRST, false, false, false, BF><<<gw, 256, 0, c->stream>>>(p); } \
+        } \
+    } while (0)
+        if (c->bf) CSF_FULL(true); else CSF_FULL(false);
+#undef CSF_FULL
         if (deep_launch) LBMPM_HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_deep, 0));
         // the tracers' sub-step of this flow step: rho_R, u as both collisions left them, G of csf3d_gradient (rk3d_tracer.h)
         if (tr) { const int rc = launch_tracers(c, p, g); if (rc != LBMPM_OK) return rc; }
@@ -1568,6 +1625,31 @@ extern "C" int lbmpm_rk3dcsf_set_contact_angles(lbmpm_rk3dcsf *c, const double *
     LBMPM_HIP_TRY(hipStreamSynchronize(c->stream2));
     if (!c->wang) { const int rc = c->mem.alloc(&c->wang, 3 * NF, nullptr); if (rc) return rc; }
     LBMPM_HIP_TRY(hipMemcpy(c->wang, h.data(), 3 * NF * sizeof(double), hipMemcpyHostToDevice));
+    return LBMPM_OK;
+}
+
+// Body force: see include/lbmpm.h.  Six doubles that travel as kernel arguments (make_dev): nothing on the device changes here.
+extern "C" int lbmpm_rk3dcsf_set_body_force(lbmpm_rk3dcsf *c, const double *accel_r, const double *accel_b)
+{
+    LBMPM_REQUIRE(c, "lbmpm_rk3dcsf_set_body_force: null context");
+    LBMPM_REQUIRE((accel_r == nullptr) == (accel_b == nullptr), "lbmpm_rk3dcsf_set_body_force: accel_r and accel_b are both given or both NULL");
+    if (c->next_stage != 0) { set_error("lbmpm_rk3dcsf_set_body_force: stage %d of a step begun with lbmpm_rk3dcsf_stage is next", c->next_stage); return LBMPM_ERR_STATE; }
+    double g[6] = {0., 0., 0., 0., 0., 0.};
+    if (accel_r) {
+        for (int i = 0; i < 3; ++i) { g[i] = accel_r[i]; g[3 + i] = accel_b[i]; }
+        for (int i = 0; i < 6; ++i) LBMPM_REQUIRE(std::isfinite(g[i]), "lbmpm_rk3dcsf_set_body_force: the acceleration's component %d of %s is %g", i % 3, i < 3 ? "red" : "blue", g[i]);
+    }
+    bool any = false;
+    for (int i = 0; i < 6; ++i) { g[i] += 0.; any = any || g[i] != 0.; }        // (-0 -> +0: csf3d_collide_deep)
+    for (int i = 0; i < 6; ++i) c->gacc[i] = g[i];
+    c->bf = any;
+    return LBMPM_OK;
+}
+
+extern "C" int lbmpm_rk3dcsf_get_body_force(const lbmpm_rk3dcsf *c, double *accel_r, double *accel_b)
+{
+    LBMPM_REQUIRE(c && accel_r && accel_b, "lbmpm_rk3dcsf_get_body_force: null argument");
+    for (int i = 0; i < 3; ++i) { accel_r[i] = c->gacc[i]; accel_b[i] = c->gacc[3 + i]; }
     return LBMPM_OK;
 }
 

@@ -55,6 +55,19 @@ def tracer_config(num_tracers=1, diffusion_x=1. / 6., diffusion_y=None, diffusio
     return cfg
 
 
+def body_force_pair(g=None, red=None, blue=None):
+    """the arguments of set_body_force as ((gx, gy, gz) of red, ... of blue): g for both colours, red / blue in its place for one;
+    a colour nobody names is zero.  ValueError: not three numbers"""
+    def three(v, what):
+        if v is None:
+            return (0.0, 0.0, 0.0)
+        a = np.asarray(v, dtype=np.float64)
+        if a.shape != (3,):
+            raise ValueError("body force %s = (gx, gy, gz), not %r" % (what, v))
+        return tuple(float(x) for x in a)
+    return three(g if red is None else red, "red"), three(g if blue is None else blue, "blue")
+
+
 class RK3DCSFSolver(SlabTransportCalls):
     _C_PREFIX, _NO_TRANSPORT = "lbmpm_rk3dcsf", "none"
 
@@ -169,6 +182,26 @@ class RK3DCSFSolver(SlabTransportCalls):
         if a.shape != self.shape:
             raise ValueError("contact angles must have shape %s, not %s" % (self.shape, a.shape))
         check(self._L.lbmpm_rk3dcsf_set_contact_angles(self._h, a.ctypes.data_as(F64P)), "lbmpm_rk3dcsf_set_contact_angles")
+
+    def set_body_force(self, g=None, *, red=None, blue=None):
+        """an acceleration per colour in lattice units (gravity, force-driven flow): g = (gx, gy, gz) for both colours, red= / blue= in
+        its place for one; all None (or all zeros): no body force, the step runs the kernels it ran before.  The force density of a cell
+        is rho_R g_R + rho_B g_B; half of it enters u, the Guo source takes it beside the CSF force (include/lbmpm.h).  get("Fx" ...) and
+        the force= of set_pdf stay the CSF force alone.  Whenever the solver is idle, repeatedly; the state, the step counter, the
+        contact angles and the snapshot of change() stay, and set_macro / set_pdf keep it.  ValueError: not three numbers; LbmpmError:
+        a value that is not finite (LBMPM_ERR_INVALID), a call between the stages of a step (LBMPM_ERR_STATE)"""
+        if g is None and red is None and blue is None:
+            check(self._L.lbmpm_rk3dcsf_set_body_force(self._h, None, None), "lbmpm_rk3dcsf_set_body_force")
+            return
+        gr, gb = body_force_pair(g, red, blue)
+        check(self._L.lbmpm_rk3dcsf_set_body_force(self._h, (C.c_double * 3)(*gr), (C.c_double * 3)(*gb)), "lbmpm_rk3dcsf_set_body_force")
+
+    @property
+    def body_force(self):
+        """((gx, gy, gz) of red, (gx, gy, gz) of blue) in force; zeros without a body force"""
+        gr, gb = (C.c_double * 3)(), (C.c_double * 3)()
+        check(self._L.lbmpm_rk3dcsf_get_body_force(self._h, gr, gb), "lbmpm_rk3dcsf_get_body_force")
+        return tuple(gr), tuple(gb)
 
     def enable_diagnostics(self, on=True):
         check(self._L.lbmpm_rk3dcsf_enable_diagnostics(self._h, 1 if on else 0), "enable_diagnostics")
@@ -462,6 +495,18 @@ class RK3DCSFCluster:
         for s, a in zip(self.slabs, cut):
             s.set_contact_angles(a)
 
+    def set_body_force(self, g=None, *, red=None, blue=None):
+        """RK3DCSFSolver.set_body_force on every slab (the force is local to a cell: no message changes).  Checked before any slab is changed"""
+        if not (g is None and red is None and blue is None):
+            if not np.all(np.isfinite(body_force_pair(g, red, blue))):
+                raise _lib.LbmpmError("set_body_force: an acceleration that is not finite", _lib.ERR_INVALID)
+        for s in self.slabs:
+            s.set_body_force(g, red=red, blue=blue)
+
+    @property
+    def body_force(self):
+        return self.slabs[0].body_force
+
     def configure_tracers(self, *args, **kwargs):
         """refused: on slabs the tracers change the size of the population message, so they are given at construction (tracers=)"""
         raise _lib.LbmpmError(_TRACERS_AT_CONSTRUCTION % type(self).__name__, _lib.ERR_UNSUPPORTED)
@@ -624,6 +669,14 @@ class RK3DCSFDistributed:
         """the undivided array [nz][ny][nx], the same on every rank (RK3DCSFSolver.set_contact_angles; None: the scalar angle again);
         every rank takes its planes and the images of its neighbours'.  Call it after sync(): the slab must be idle"""
         self.slab.set_contact_angles(self.geo.cut(_undivided_angles(theta, self.shape)))
+
+    def set_body_force(self, g=None, *, red=None, blue=None):
+        """RK3DCSFSolver.set_body_force, the same call on every rank (the force is local to a cell: no message changes)"""
+        self.slab.set_body_force(g, red=red, blue=blue)
+
+    @property
+    def body_force(self):
+        return self.slab.body_force
 
     def set_concentration(self, t, conc):
         """the undivided array [nz][ny][nx]; every rank takes its planes (and the images of its neighbours')"""
