@@ -125,19 +125,19 @@ def criteria_column_bytes():
 
 
 def mark(L, prefix, handle):
-    """the snapshot of one context through lbmpm_<prefix>_change_mark"""
+    """the snapshot of one context through <prefix>_change_mark"""
     from ._lib import check
-    name = "lbmpm_%s_change_mark" % prefix
+    name = prefix + "_change_mark"
     check(getattr(L, name)(handle), name)
 
 
 def table(L, prefix, handle, planes, remark):
-    """([planes][11], steps since the mark) of one context through lbmpm_<prefix>_change"""
+    """([planes][11], steps since the mark) of one context through <prefix>_change"""
     import ctypes as C
     from ._lib import F64P, check
     out = np.empty((int(planes), len(COLUMNS)), dtype=np.float64)
     steps = C.c_int64(0)
-    name = "lbmpm_%s_change" % prefix
+    name = prefix + "_change"
     check(getattr(L, name)(handle, 1 if remark else 0, C.byref(steps), out.ctypes.data_as(F64P)), name)
     return out, int(steps.value)
 

@@ -298,22 +298,22 @@ def _class_plane(a, ny, nx, what):
 
 def props_face(L, prefix, handle, ny, nx):
     """[2][ny][nx] uint8: the class bytes (0 S, 1 R, 2 B, 3 N) of the lowest and the highest own plane of one context, those of its last
-    lbmpm_<prefix>_clusters call -- what the slab below takes as `above` ([0]) and the slab above as `below` ([1])"""
+    <prefix>_clusters call -- what the slab below takes as `above` ([0]) and the slab above as `below` ([1])"""
     from ._lib import U8P, check
     out = np.empty((2, int(ny), int(nx)), dtype=np.uint8)
-    name = "lbmpm_%s_cluster_props_face" % prefix
+    name = prefix + "_cluster_props_face"
     check(getattr(L, name)(handle, out.ctypes.data_as(U8P)), name)
     return out
 
 
 def props_table(L, prefix, handle, count, ny, nx, below=None, above=None):
-    """[count][14] int64 of one context through lbmpm_<prefix>_cluster_props: the properties of the clusters of its last
-    lbmpm_<prefix>_clusters call (count: that call's); below / above: [ny][nx] class planes of the neighbouring slabs, None at the
+    """[count][14] int64 of one context through <prefix>_cluster_props: the properties of the clusters of its last
+    <prefix>_clusters call (count: that call's); below / above: [ny][nx] class planes of the neighbouring slabs, None at the
     lattice's ends"""
     from ._lib import I64P, U8P, check
     dn, up = _class_plane(below, ny, nx, "below"), _class_plane(above, ny, nx, "above")
     out = np.zeros((int(count), len(PROP_COLUMNS)), dtype=np.int64)
-    name = "lbmpm_%s_cluster_props" % prefix
+    name = prefix + "_cluster_props"
     check(getattr(L, name)(handle, None if dn is None else dn.ctypes.data_as(U8P), None if up is None else up.ctypes.data_as(U8P),
                            out.ctypes.data_as(I64P)), name)
     return out
@@ -344,14 +344,14 @@ def faces_from_neighbours(mine, rank, world, group, device):
 
 
 def take(L, prefix, handle, planes, ny, nx, phi_cut=0.0, connectivity=6, labels=False, faces=False, props=False, below=None, above=None):
-    """One context through lbmpm_<prefix>_clusters*: dict(table [n][5] int64, labels [planes][ny][nx] uint32 when asked for, face_labels /
+    """One context through <prefix>_clusters*: dict(table [n][5] int64, labels [planes][ny][nx] uint32 when asked for, face_labels /
     face_classes [2][ny][nx] when asked for, props [n][14] int64 when asked for -- with below / above, the class planes of the
     neighbouring slabs, where there are such)"""
     import ctypes as C
     from ._lib import I64P, U8P, U32P, ClustersConfig, check
     cfg = ClustersConfig(float(phi_cut), int(connectivity), 0)
     n = C.c_int64(0)
-    name = "lbmpm_%s_clusters" % prefix
+    name = prefix + "_clusters"
     check(getattr(L, name)(handle, C.byref(cfg), C.byref(n)), name)
     out = dict(table=np.zeros((n.value, len(COLUMNS)), dtype=np.int64))
     if n.value:

@@ -1301,6 +1301,61 @@ dim3 grid3(const lbmpm_rk3d *c, int planes) { return dim3((c->nx + BX3 - 1) / BX
 
 }  // namespace
 
+#include "rk3d_analysis.h"
+
+namespace {
+
+// The analyses read the fields of the last lbmpm_rk3d_phase_field(ctx, 1): phi, and `diag` where one reads more than phi.  They never
+// call phase_field themselves: on slabs that needs the halo exchange first, which is the caller's job.
+template <>
+struct AnalysisModel<lbmpm_rk3d> {
+    static AnalysisView view(const lbmpm_rk3d *c)
+    {
+        return {c->cfg.device, c->stream, c->stream, (unsigned)c->nx, (unsigned)c->ny, (unsigned)c->nzl, (unsigned)c->cfg.z_offset, (unsigned)c->cfg.nz_global};
+    }
+    static int enter(const char *, lbmpm_rk3d *c)
+    {
+        LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
+        return LBMPM_OK;
+    }
+    static int fresh(const char *who, lbmpm_rk3d *c, Analysis a)
+    {
+        bool stale = c->observed_at != c->steps || (a != Analysis::Clusters && !c->diag);
+        // (the properties go with a table: without a current one clusters_current refuses, in its own words)
+        if (a == Analysis::ClusterProps && !(c->cl.valid && c->cl.at_step == c->steps)) stale = false;
+        if (!stale) return LBMPM_OK;
+        const long long at = (long long)c->observed_at, now = (long long)c->steps;
+        switch (a) {
+        case Analysis::Integrals:
+            set_error("the integrals are stale: call lbmpm_rk3d_phase_field(ctx, 1) after the last step (they are sums over the fields of the streamed, "
+                      "boundary-corrected lattice at that call; observed at step %lld, now %lld)", at, now);
+            break;
+        case Analysis::Change:
+            set_error("%s: the fields are stale: call lbmpm_rk3d_phase_field(ctx, 1) after the last step (the monitor compares the fields of the "
+                      "streamed, boundary-corrected lattice at that call; observed at step %lld, now %lld)", who, at, now);
+            break;
+        case Analysis::Clusters:
+            set_error("the phase field is stale: call lbmpm_rk3d_phase_field(ctx, 1) after the last step (clusters are those of phi at that call; "
+                      "observed at step %lld, now %lld)", at, now);
+            break;
+        case Analysis::ClusterProps:
+            set_error("%s: the fields are stale: call lbmpm_rk3d_phase_field(ctx, 1) after the last step (observed at step %lld, now %lld)", who, at, now);
+            break;
+        case Analysis::Morphology:
+            set_error("the phase field is stale: call lbmpm_rk3d_phase_field(ctx, 1) after the last step (the morphology is that of the fields at that "
+                      "call; observed at step %lld, now %lld)", at, now);
+            break;
+        }
+        return LBMPM_ERR_STATE;
+    }
+    template <typename F>
+    static int with_flow(lbmpm_rk3d *c, F &&f) { return f(Rk3dIntLoader{c->flags, c->diag, c->phi, (unsigned)c->nx, (unsigned)c->pitch, c->plane2, c->vol}); }
+    template <typename F>
+    static int with_phi(lbmpm_rk3d *c, F &&f) { return f(Rk3dPhiLoader{c->flags, c->phi, (unsigned)c->nx, (unsigned)c->pitch, c->plane2}); }
+};
+
+}  // namespace
+
 extern "C" int lbmpm_rk3d_create(const lbmpm_rk3d_config *cfg, const uint8_t *is_domain_with_halo, lbmpm_rk3d **out)
 {
     LBMPM_REQUIRE(cfg && is_domain_with_halo && out, "lbmpm_rk3d_create: null argument");
@@ -1794,14 +1849,6 @@ extern "C" int lbmpm_rk3d_phase_field(lbmpm_rk3d *c, int with_diagnostics)
 }
 
 namespace {
-// run f(bool_constant<a>, bool_constant<b>): two run-time switches -> template arguments
-template <typename F>
-void dispatch2(bool a, bool b, F &&f)
-{
-    if (a) { if (b) f(std::true_type{}, std::true_type{}); else f(std::true_type{}, std::false_type{}); }
-    else   { if (b) f(std::false_type{}, std::true_type{}); else f(std::false_type{}, std::false_type{}); }
-}
-
 template <int TX, int TY>
 void launch_fused(lbmpm_rk3d *c, const RK3Dev &p, hipStream_t st, int z_first, int z_last)
 {
@@ -1811,7 +1858,7 @@ void launch_fused(lbmpm_rk3d *c, const RK3Dev &p, hipStream_t st, int z_first, i
     auto go = [&](auto first, auto mrt) {
         rk3d_fused<TX, TY, decltype(first)::value, decltype(mrt)::value><<<grid, block, 0, st>>>(p, tilesX, tilesY, rpx, c->chunk_len, z_first, z_last);
     };
-    dispatch2(p.first != 0, p.mrt != 0, go);
+    lbmpm::dispatch(go, p.first != 0, p.mrt != 0);
 }
 
 template <int TY>
@@ -1823,7 +1870,7 @@ void launch_fused_c(lbmpm_rk3d *c, const RK3Dev &p, hipStream_t st, int z_first,
     auto go = [&](auto first, auto mrt) {
         rk3dc_fused<TY, decltype(first)::value, decltype(mrt)::value><<<grid, block, 0, st>>>(p, tilesX, tilesY, rpx, c->chunk_len, z_first, z_last);
     };
-    dispatch2(p.first != 0, p.mrt != 0, go);
+    lbmpm::dispatch(go, p.first != 0, p.mrt != 0);
 }
 
 // q23 storage: planes z_first..z_last and (if z_last2 >= z_first2) z_first2..z_last2 in ONE launch
@@ -1862,15 +1909,10 @@ void launch_q23(lbmpm_rk3d *c, const RK3Dev &p, hipStream_t st, int z_first, int
         if (i == 2048u) (void)hipMemsetAsync(c->slotq + (size_t)(ring ^ 1u) * 4096u * 8u, 0, 4096u * 8u * sizeof(unsigned), st);
         q = c->slotq + ((size_t)ring * 4096u + i) * 8u;
     }
-    auto go = [&](auto first, auto mrt) {
-        constexpr bool F = decltype(first)::value, M = decltype(mrt)::value;
-        auto launch = [&](auto ragged, auto pin) {
-            rk3dq_fused<F, M, decltype(ragged)::value, decltype(pin)::value><<<grid, block, 0, st>>>(p, tilesX, tilesY, rpx, chunk_len, z_first, z_last,
-                                                                                                     nchunks1, z_first2, z_last2, q);
-        };
-        dispatch2(c->nx % 64 != 0, p.inletP != 0, launch);
-    };
-    dispatch2(p.first != 0, p.mrt != 0, go);
+    lbmpm::dispatch([&](auto first, auto mrt, auto ragged, auto pin) {
+        rk3dq_fused<decltype(first)::value, decltype(mrt)::value, decltype(ragged)::value, decltype(pin)::value><<<grid, block, 0, st>>>(
+            p, tilesX, tilesY, rpx, chunk_len, z_first, z_last, nchunks1, z_first2, z_last2, q);
+    }, p.first != 0, p.mrt != 0, c->nx % 64 != 0, p.inletP != 0);
 }
 
 // planes z_first..z_last of the time step on stream st
@@ -1891,9 +1933,9 @@ void launch_step_range(lbmpm_rk3d *c, const RK3Dev &p, hipStream_t st, int z_fir
             RK3Dev m = p;
             m.halo_lo = c->conv_lo;
             launch_q23(c, m, st, zs, z_last, 1, 0);
-            dispatch2(p.first != 0, p.mrt != 0, [&](auto first, auto mrt) {
+            lbmpm::dispatch([&](auto first, auto mrt) {
                 rk3dq_conv_collide<decltype(first)::value, decltype(mrt)::value><<<dim3(c->nseg, gy, 2), block, 0, st>>>(p, zs);
-            });
+            }, p.first != 0, p.mrt != 0);
             return;
         }
     }
@@ -2537,148 +2579,19 @@ extern "C" int lbmpm_rk3d_get_field(lbmpm_rk3d *c, int field, double *out)
     return LBMPM_OK;
 }
 
-// Plane integrals of the fields of the last lbmpm_rk3d_phase_field(ctx, 1) (rk3d_integrals.h): out [nz_local][LBMPM_INTEGRAL_COLS].  Never
-// calls phase_field itself: on slabs that needs the halo exchange first, which is the caller's job.
-extern "C" int lbmpm_rk3d_integrals(lbmpm_rk3d *c, double *out)
-{
-    LBMPM_REQUIRE(c && out, "lbmpm_rk3d_integrals: null argument");
-    LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
-    if (c->observed_at != c->steps || !c->diag) {
-        set_error("the integrals are stale: call lbmpm_rk3d_phase_field(ctx, 1) after the last step (they are sums over the fields of the streamed, "
-                  "boundary-corrected lattice at that call; observed at step %lld, now %lld)", (long long)c->observed_at, (long long)c->steps);
-        return LBMPM_ERR_STATE;
-    }
-    const unsigned planes = (unsigned)c->nzl, plane_cells = (unsigned)c->nx * (unsigned)c->ny;
-    { const int rc = integral_buffer<FlowCols>(c->mem, &c->integ, planes, plane_cells, 1, c->stream); if (rc) return rc; }
-    const Rk3dIntLoader load{c->flags, c->diag, c->phi, (unsigned)c->nx, (unsigned)c->pitch, c->plane2, c->vol};
-    LBMPM_HIP_TRY(integrals_run(load, planes, plane_cells, c->integ, out, c->stream));
-    return LBMPM_OK;
-}
-
-// Steady-state monitor over the fields of the last lbmpm_rk3d_phase_field(ctx, 1) (rk3d_change.h; the definition: include/lbmpm.h)
-static int change_ready(const char *who, lbmpm_rk3d *c)
-{
-    LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
-    if (c->observed_at != c->steps || !c->diag) {
-        set_error("%s: the fields are stale: call lbmpm_rk3d_phase_field(ctx, 1) after the last step (the monitor compares the fields of the "
-                  "streamed, boundary-corrected lattice at that call; observed at step %lld, now %lld)", who, (long long)c->observed_at, (long long)c->steps);
-        return LBMPM_ERR_STATE;
-    }
-    return LBMPM_OK;
-}
-
-extern "C" int lbmpm_rk3d_change_mark(lbmpm_rk3d *c)
-{
-    LBMPM_REQUIRE(c, "lbmpm_rk3d_change_mark: null argument");
-    { const int rc = change_ready("lbmpm_rk3d_change_mark", c); if (rc) return rc; }
-    const Rk3dIntLoader load{c->flags, c->diag, c->phi, (unsigned)c->nx, (unsigned)c->pitch, c->plane2, c->vol};
-    return change_mark(load, c->chg, c->steps, (unsigned)c->nzl, (unsigned)c->nx * (unsigned)c->ny, c->mem, c->stream);
-}
-
-extern "C" int lbmpm_rk3d_change(lbmpm_rk3d *c, int remark, int64_t *steps_between, double *out)
-{
-    LBMPM_REQUIRE(c && out, "lbmpm_rk3d_change: null argument");
-    { const int rc = change_ready("lbmpm_rk3d_change", c); if (rc) return rc; }
-    const Rk3dIntLoader load{c->flags, c->diag, c->phi, (unsigned)c->nx, (unsigned)c->pitch, c->plane2, c->vol};
-    return change_run("lbmpm_rk3d_change", load, c->chg, remark, c->steps, steps_between, (unsigned)c->nzl, (unsigned)c->nx * (unsigned)c->ny, out, c->stream);
-}
-
-// Phase clusters of phi of the last lbmpm_rk3d_phase_field(ctx, 1) (rk3d_clusters.h; the definition: include/lbmpm.h)
-extern "C" int lbmpm_rk3d_clusters(lbmpm_rk3d *c, const lbmpm_clusters_config *cfg, int64_t *count)
-{
-    LBMPM_REQUIRE(c && count, "lbmpm_rk3d_clusters: null argument");
-    LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
-    double cut = 0.;
-    ClGeom g{};
-    { const int rc = clusters_configure("lbmpm_rk3d_clusters", cfg, (unsigned long long)c->nx * c->ny * (unsigned long long)c->cfg.nz_global, &cut, &g); if (rc) return rc; }
-    if (c->observed_at != c->steps) {
-        set_error("the phase field is stale: call lbmpm_rk3d_phase_field(ctx, 1) after the last step (clusters are those of phi at that call; "
-                  "observed at step %lld, now %lld)", (long long)c->observed_at, (long long)c->steps);
-        return LBMPM_ERR_STATE;
-    }
-    g.nx = (unsigned)c->nx; g.ny = (unsigned)c->ny; g.planes = (unsigned)c->nzl; g.plane_cells = g.nx * g.ny; g.n = g.planes * g.plane_cells;
-    g.z0 = (unsigned)c->cfg.z_offset; g.base = g.z0 * g.plane_cells;
-    const Rk3dPhiLoader load{c->flags, c->phi, (unsigned)c->nx, (unsigned)c->pitch, c->plane2};
-    return clusters_label(load, c->cl, g, cut, c->steps, c->mem, c->stream, c->stream, count);
-}
-
-extern "C" int lbmpm_rk3d_clusters_table(lbmpm_rk3d *c, int64_t *out)
-{
-    LBMPM_REQUIRE(c && out, "lbmpm_rk3d_clusters_table: null argument");
-    return clusters_table("lbmpm_rk3d_clusters_table", c->cl, c->steps, c->cfg.device, c->stream, out);
-}
-
-extern "C" int lbmpm_rk3d_clusters_labels(lbmpm_rk3d *c, uint32_t *out)
-{
-    LBMPM_REQUIRE(c && out, "lbmpm_rk3d_clusters_labels: null argument");
-    return clusters_labels("lbmpm_rk3d_clusters_labels", c->cl, c->steps, c->cfg.device, c->stream, out);
-}
-
-extern "C" int lbmpm_rk3d_clusters_faces(lbmpm_rk3d *c, uint32_t *labels, uint8_t *classes)
-{
-    LBMPM_REQUIRE(c && labels && classes, "lbmpm_rk3d_clusters_faces: null argument");
-    return clusters_faces("lbmpm_rk3d_clusters_faces", c->cl, c->steps, c->cfg.device, c->stream, labels, classes);
-}
-
-// Per-cluster properties beside the table of the last lbmpm_rk3d_clusters (rk3d_cluster_props.h; the definition: include/lbmpm.h), from
-// the fields of the last lbmpm_rk3d_phase_field(ctx, 1)
-static int cluster_props_ready(const char *who, lbmpm_rk3d *c)
-{
-    if (c->cl.valid && c->cl.at_step == c->steps && (c->observed_at != c->steps || !c->diag)) {
-        set_error("%s: the fields are stale: call lbmpm_rk3d_phase_field(ctx, 1) after the last step (observed at step %lld, now %lld)", who,
-                  (long long)c->observed_at, (long long)c->steps);
-        return LBMPM_ERR_STATE;
-    }
-    return LBMPM_OK;
-}
-
-extern "C" int lbmpm_rk3d_cluster_props_face(lbmpm_rk3d *c, uint8_t *classes)
-{
-    LBMPM_REQUIRE(c && classes, "lbmpm_rk3d_cluster_props_face: null argument");
-    { const int rc = cluster_props_ready("lbmpm_rk3d_cluster_props_face", c); if (rc) return rc; }
-    const Rk3dIntLoader load{c->flags, c->diag, c->phi, (unsigned)c->nx, (unsigned)c->pitch, c->plane2, c->vol};
-    return cluster_props_face("lbmpm_rk3d_cluster_props_face", load, c->cl, c->cprops, c->steps, c->cfg.device, c->mem, c->stream, c->stream, classes);
-}
-
-extern "C" int lbmpm_rk3d_cluster_props(lbmpm_rk3d *c, const uint8_t *below, const uint8_t *above, int64_t *out)
-{
-    LBMPM_REQUIRE(c && out, "lbmpm_rk3d_cluster_props: null argument");
-    { const int rc = cluster_props_ready("lbmpm_rk3d_cluster_props", c); if (rc) return rc; }
-    const Rk3dIntLoader load{c->flags, c->diag, c->phi, (unsigned)c->nx, (unsigned)c->pitch, c->plane2, c->vol};
-    return cluster_props_run("lbmpm_rk3d_cluster_props", load, c->cl, c->cprops, c->steps, c->cfg.device, c->mem, c->stream, c->stream, below, above, out);
-}
-
-// Phase morphology of the fields of the last lbmpm_rk3d_phase_field(ctx, 1) (rk3d_morphology.h; the definition: include/lbmpm.h).  The
-// checks and the class array of both entry points; then the context's device is the current one.
-static int morphology_ready(const char *who, lbmpm_rk3d *c, const lbmpm_morphology_config *cfg, double *cut)
-{
-    LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
-    { const int rc = morphology_configure(who, cfg, (unsigned long long)(c->nzl + 1) * c->nx * c->ny, cut); if (rc) return rc; }
-    if (c->observed_at != c->steps || !c->diag) {
-        set_error("the phase field is stale: call lbmpm_rk3d_phase_field(ctx, 1) after the last step (the morphology is that of the fields at that "
-                  "call; observed at step %lld, now %lld)", (long long)c->observed_at, (long long)c->steps);
-        return LBMPM_ERR_STATE;
-    }
-    return morphology_classes(c->mem, &c->morph, (unsigned)c->nzl, (unsigned)c->nx * (unsigned)c->ny, c->stream);
-}
-
-extern "C" int lbmpm_rk3d_morphology_face(lbmpm_rk3d *c, const lbmpm_morphology_config *cfg, uint8_t *classes)
-{
-    LBMPM_REQUIRE(c && classes, "lbmpm_rk3d_morphology_face: null argument");
-    double cut = 0.;
-    { const int rc = morphology_ready("lbmpm_rk3d_morphology_face", c, cfg, &cut); if (rc) return rc; }
-    const Rk3dIntLoader load{c->flags, c->diag, c->phi, (unsigned)c->nx, (unsigned)c->pitch, c->plane2, c->vol};
-    return morphology_face(load, c->morph, (unsigned)c->nx * (unsigned)c->ny, cut, classes, c->stream);
-}
-
-extern "C" int lbmpm_rk3d_morphology(lbmpm_rk3d *c, const lbmpm_morphology_config *cfg, const uint8_t *above, double *out)
-{
-    LBMPM_REQUIRE(c && out, "lbmpm_rk3d_morphology: null argument");
-    double cut = 0.;
-    { const int rc = morphology_ready("lbmpm_rk3d_morphology", c, cfg, &cut); if (rc) return rc; }
-    const Rk3dIntLoader load{c->flags, c->diag, c->phi, (unsigned)c->nx, (unsigned)c->pitch, c->plane2, c->vol};
-    return morphology_run("lbmpm_rk3d_morphology", load, c->morph, (unsigned)c->nzl, (unsigned)c->nx, (unsigned)c->ny, cut, above, out, c->stream);
-}
+// The analyses over the fields of the last lbmpm_rk3d_phase_field(ctx, 1) (rk3d_analysis.h holds the bodies, AnalysisModel<lbmpm_rk3d>
+// above what they read and when it is stale; the definitions: include/lbmpm.h).  integrals: out [nz_local][LBMPM_INTEGRAL_COLS].
+extern "C" int lbmpm_rk3d_integrals(lbmpm_rk3d *c, double *out) { LBMPM_REQUIRE(c && out, "lbmpm_rk3d_integrals: null argument"); return analysis_integrals("lbmpm_rk3d_integrals", c, out); }
+extern "C" int lbmpm_rk3d_change_mark(lbmpm_rk3d *c) { LBMPM_REQUIRE(c, "lbmpm_rk3d_change_mark: null argument"); return analysis_change_mark("lbmpm_rk3d_change_mark", c); }
+extern "C" int lbmpm_rk3d_change(lbmpm_rk3d *c, int remark, int64_t *steps_between, double *out) { LBMPM_REQUIRE(c && out, "lbmpm_rk3d_change: null argument"); return analysis_change("lbmpm_rk3d_change", c, remark, steps_between, out); }
+extern "C" int lbmpm_rk3d_clusters(lbmpm_rk3d *c, const lbmpm_clusters_config *cfg, int64_t *count) { LBMPM_REQUIRE(c && count, "lbmpm_rk3d_clusters: null argument"); return analysis_clusters("lbmpm_rk3d_clusters", c, cfg, count); }
+extern "C" int lbmpm_rk3d_clusters_table(lbmpm_rk3d *c, int64_t *out) { LBMPM_REQUIRE(c && out, "lbmpm_rk3d_clusters_table: null argument"); return analysis_clusters_table("lbmpm_rk3d_clusters_table", c, out); }
+extern "C" int lbmpm_rk3d_clusters_labels(lbmpm_rk3d *c, uint32_t *out) { LBMPM_REQUIRE(c && out, "lbmpm_rk3d_clusters_labels: null argument"); return analysis_clusters_labels("lbmpm_rk3d_clusters_labels", c, out); }
+extern "C" int lbmpm_rk3d_clusters_faces(lbmpm_rk3d *c, uint32_t *labels, uint8_t *classes) { LBMPM_REQUIRE(c && labels && classes, "lbmpm_rk3d_clusters_faces: null argument"); return analysis_clusters_faces("lbmpm_rk3d_clusters_faces", c, labels, classes); }
+extern "C" int lbmpm_rk3d_cluster_props_face(lbmpm_rk3d *c, uint8_t *classes) { LBMPM_REQUIRE(c && classes, "lbmpm_rk3d_cluster_props_face: null argument"); return analysis_cluster_props_face("lbmpm_rk3d_cluster_props_face", c, classes); }
+extern "C" int lbmpm_rk3d_cluster_props(lbmpm_rk3d *c, const uint8_t *below, const uint8_t *above, int64_t *out) { LBMPM_REQUIRE(c && out, "lbmpm_rk3d_cluster_props: null argument"); return analysis_cluster_props("lbmpm_rk3d_cluster_props", c, below, above, out); }
+extern "C" int lbmpm_rk3d_morphology_face(lbmpm_rk3d *c, const lbmpm_morphology_config *cfg, uint8_t *classes) { LBMPM_REQUIRE(c && classes, "lbmpm_rk3d_morphology_face: null argument"); return analysis_morphology_face("lbmpm_rk3d_morphology_face", c, cfg, classes); }
+extern "C" int lbmpm_rk3d_morphology(lbmpm_rk3d *c, const lbmpm_morphology_config *cfg, const uint8_t *above, double *out) { LBMPM_REQUIRE(c && out, "lbmpm_rk3d_morphology: null argument"); return analysis_morphology("lbmpm_rk3d_morphology", c, cfg, above, out); }
 
 // What the storage moves, by its own count (bench.py's "bytes moved" beside the algorithmic 608 B): out[0] doubles stored per fluid
 // cell, out[1] fluid cells of the owned planes, out[2] those of them in row segments that carry a single-colour flag instead of records

@@ -1193,6 +1193,41 @@ CsfDev make_dev(const lbmpm_rk3dcsf *c)
     return p;
 }
 
+}  // namespace
+
+#include "rk3d_analysis.h"
+
+namespace {
+
+// The analyses read the recorded state (what LBMPM_RK3DCSF_REC_* hand out) from the populations in registers: no staging array, nothing
+// to call beforehand, valid wherever lbmpm_rk3dcsf_get_field(REC_*) is, slabs included (own planes only).  First-use allocations are
+// zeroed on the null stream.
+template <>
+struct AnalysisModel<lbmpm_rk3dcsf> {
+    static AnalysisView view(const lbmpm_rk3dcsf *c)
+    {
+        return {c->cfg.device, c->stream, nullptr, (unsigned)c->nx, (unsigned)c->ny, (unsigned)(c->nz - c->cfg.ghost_lo - c->cfg.ghost_hi),
+                (unsigned)(c->zoff + c->cfg.ghost_lo), (unsigned)c->nzg};
+    }
+    static int enter(const char *who, lbmpm_rk3dcsf *c)
+    {
+        if (!c->have_state) { set_error("%s before set_macro / set_pdf", who); return LBMPM_ERR_STATE; }
+        LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
+        return LBMPM_OK;
+    }
+    static int fresh(const char *, lbmpm_rk3dcsf *, Analysis) { return LBMPM_OK; }      // (the populations are the state: never stale)
+    template <typename F>
+    static int with_flow(lbmpm_rk3dcsf *c, F &&f)
+    {
+        return lbmpm::dispatch([&](auto first) { return f(CsfIntLoader<decltype(first)::value>{make_dev(c)}); }, c->first);
+    }
+    template <typename F>
+    static int with_phi(lbmpm_rk3dcsf *c, F &&f)
+    {
+        return lbmpm::dispatch([&](auto first) { return f(CsfPhiLoader<decltype(first)::value>{make_dev(c)}); }, c->first);
+    }
+};
+
 unsigned blocks_of(size_t n) { return (unsigned)((n + 255) / 256); }
 unsigned blocks8(size_t n) { return (blocks_of(n) + 7u) / 8u * 8u; }      // fluid_cell(): eight XCDs
 
@@ -1215,11 +1250,9 @@ int launch_tracers(lbmpm_rk3dcsf *c, const CsfDev &p, unsigned g)
 {
     const TrDev t = make_trdev(c);
     // (SLAB: a context with ghost planes; the undivided lattice keeps the instance without the ghost and global-plane tests)
-#define TR3D_GO(NT, SLAB) do { if (c->tr_first) tr3d_step<true, NT, SLAB><<<g, 256, 0, c->stream>>>(p, t); else tr3d_step<false, NT, SLAB><<<g, 256, 0, c->stream>>>(p, t); } while (0)
-#define TR3D_NT(SLAB) switch (c->ntr) { case 1: TR3D_GO(1, SLAB); break; case 2: TR3D_GO(2, SLAB); break; case 3: TR3D_GO(3, SLAB); break; default: TR3D_GO(4, SLAB); break; }
-    if (c->cfg.ghost_lo || c->cfg.ghost_hi) { TR3D_NT(true) } else { TR3D_NT(false) }
-#undef TR3D_NT
-#undef TR3D_GO
+    lbmpm::dispatch([&](auto first, auto slab) {
+        lbmpm::dispatch_int<1, 4>([&](auto nt) { tr3d_step<decltype(first)::value, decltype(nt)::value, decltype(slab)::value><<<g, 256, 0, c->stream>>>(p, t); }, c->ntr);
+    }, c->tr_first, c->cfg.ghost_lo || c->cfg.ghost_hi);
     LBMPM_HIP_TRY(hipGetLastError());
     std::swap(c->gA, c->gB);
     c->tr_first = false;
@@ -1246,17 +1279,9 @@ int launch_step(lbmpm_rk3dcsf *c, const CsfDev &p, hipEvent_t e0, hipEvent_t e1,
         // second stream beside the four launches of the full path (small, latency-bound launches when most of the lattice is bulk)
         LBMPM_HIP_TRY(hipEventRecord(c->ev_lists, c->stream));
         LBMPM_HIP_TRY(hipStreamWaitEvent(c->stream2, c->ev_lists, 0));
-#define CSF_DEEP(BF) do { \
-        if (tr) { \
-            if (mrt) { if (c->diag) csf3d_collide_deep<true, true, true, BF><<<gw, 256, 0, c->stream2>>>(p); else csf3d_collide_deep<true, false, true, BF><<<gw, 256, 0, c->stream2>>>(p); } \
-            else { if (c->diag) csf3d_collide_deep<false, true, true, BF><<<gw, 256, 0, c->stream2>>>(p); else csf3d_collide_deep<false, false, true, BF><<<gw, 256, 0, c->stream2>>>(p); } \
-        } else { \
-            if (mrt) { if (c->diag) csf3d_collide_deep<true, true, false, BF><<<gw, 256, 0, c->stream2>>>(p); else csf3d_collide_deep<true, false, false, BF><<<gw, 256, 0, c->stream2>>>(p); } \
-            else { if (c->diag) csf3d_collide_deep<false, true, false, BF><<<gw, 256, 0, c->stream2>>>(p); else csf3d_collide_deep<false, false, false, BF><<<gw, 256, 0, c->stream2>>>(p); } \
-        } \
-    } while (0)
-        if (c->bf) CSF_DEEP(true); else CSF_DEEP(false);
-#undef CSF_DEEP
+        lbmpm::dispatch([&](auto m, auto d, auto t, auto b) {
+            csf3d_collide_deep<decltype(m)::value, decltype(d)::value, decltype(t)::value, decltype(b)::value><<<gw, 256, 0, c->stream2>>>(p);
+        }, mrt, c->diag, tr, c->bf);
         LBMPM_HIP_TRY(hipEventRecord(c->ev_deep, c->stream2));
     }
     if (stages & 1) csf3d_phase<FIRST><<<gw, 256, 0, c->stream>>>(p);
@@ -1265,17 +1290,9 @@ int launch_step(lbmpm_rk3dcsf *c, const CsfDev &p, hipEvent_t e0, hipEvent_t e1,
         if (p.wang) csf3d_gradient<true><<<gw, 256, 0, c->stream>>>(p); else csf3d_gradient<false><<<gw, 256, 0, c->stream>>>(p);
     }
     if (stages & 4) {
-#define CSF_FULL(BF) do { \
-        if (tr) { \
-            if (mrt) { if (c->diag) csf3d_collide<FIRST, true, true, true, BF><<<gw, 256, 0, c->stream>>>(p); else csf3d_collide<FIRST, true, false, true, BF><<<gw, 256, 0, c->stream>>>(p); } \
-            else { if (c->diag) csf3d_collide<FIRST, false, true, true, BF><<<gw, 256, 0, c->stream>>>(p); else csf3d_collide<FIRST, false, false, true, BF><<<gw, 256, 0, c->stream>>>(p); } \
-        } else { \
-            if (mrt) { if (c->diag) csf3d_collide<FIRST, true, true, false, BF><<<gw, 256, 0, c->stream>>>(p); else csf3d_collide<FIRST, true, false, false, BF><<<gw, 256, 0, c->stream>>>(p); } \
-            else { if (c->diag) csf3d_collide<FIRST, false, true, false, BF><<<gw, 256, 0, c->stream>>>(p); else csf3d_collide<FIRST, false, false, false, BF><<<gw, 256, 0, c->stream>>>(p); } \
-        } \
-    } while (0)
-        if (c->bf) CSF_FULL(true); else CSF_FULL(false);
-#undef CSF_FULL
+        lbmpm::dispatch([&](auto m, auto d, auto t, auto b) {
+            csf3d_collide<FIRST, decltype(m)::value, decltype(d)::value, decltype(t)::value, decltype(b)::value><<<gw, 256, 0, c->stream>>>(p);
+        }, mrt, c->diag, tr, c->bf);
         if (deep_launch) LBMPM_HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_deep, 0));
         // the tracers' sub-step of this flow step: rho_R, u as both collisions left them, G of csf3d_gradient (rk3d_tracer.h)
         if (tr) { const int rc = launch_tracers(c, p, g); if (rc != LBMPM_OK) return rc; }
@@ -1958,136 +1975,19 @@ extern "C" int lbmpm_rk3dcsf_get_field(lbmpm_rk3dcsf *c, int field, double *out)
     }
 }
 
-// Plane integrals of the recorded state (rk3d_integrals.h), reduced from the populations in registers: no staging array.  out: [own
-// planes][LBMPM_INTEGRAL_COLS]; valid wherever lbmpm_rk3dcsf_get_field(REC_*) is, slabs included.
-extern "C" int lbmpm_rk3dcsf_integrals(lbmpm_rk3dcsf *c, double *out)
-{
-    LBMPM_REQUIRE(c && out, "lbmpm_rk3dcsf_integrals: null argument");
-    if (!c->have_state) { set_error("lbmpm_rk3dcsf_integrals before set_macro / set_pdf"); return LBMPM_ERR_STATE; }
-    LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
-    const unsigned planes = (unsigned)(c->nz - c->cfg.ghost_lo - c->cfg.ghost_hi), plane_cells = (unsigned)c->nx * (unsigned)c->ny;
-    { const int rc = integral_buffer<FlowCols>(c->mem, &c->integ, planes, plane_cells, 1, nullptr); if (rc) return rc; }
-    const CsfDev p = make_dev(c);
-    if (c->first) LBMPM_HIP_TRY(integrals_run(CsfIntLoader<true>{p}, planes, plane_cells, c->integ, out, c->stream));
-    else LBMPM_HIP_TRY(integrals_run(CsfIntLoader<false>{p}, planes, plane_cells, c->integ, out, c->stream));
-    return LBMPM_OK;
-}
-
-// Steady-state monitor over the recorded state (rk3d_change.h; the definition: include/lbmpm.h): u and phi of a cell from the populations
-// in registers, as the integrals take them.  Valid wherever lbmpm_rk3dcsf_integrals is, slabs included.
-extern "C" int lbmpm_rk3dcsf_change_mark(lbmpm_rk3dcsf *c)
-{
-    LBMPM_REQUIRE(c, "lbmpm_rk3dcsf_change_mark: null argument");
-    if (!c->have_state) { set_error("lbmpm_rk3dcsf_change_mark before set_macro / set_pdf"); return LBMPM_ERR_STATE; }
-    LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
-    const unsigned planes = (unsigned)(c->nz - c->cfg.ghost_lo - c->cfg.ghost_hi), plane_cells = (unsigned)c->nx * (unsigned)c->ny;
-    const CsfDev p = make_dev(c);
-    if (c->first) return change_mark(CsfIntLoader<true>{p}, c->chg, c->steps, planes, plane_cells, c->mem, c->stream);
-    return change_mark(CsfIntLoader<false>{p}, c->chg, c->steps, planes, plane_cells, c->mem, c->stream);
-}
-
-extern "C" int lbmpm_rk3dcsf_change(lbmpm_rk3dcsf *c, int remark, int64_t *steps_between, double *out)
-{
-    LBMPM_REQUIRE(c && out, "lbmpm_rk3dcsf_change: null argument");
-    if (!c->have_state) { set_error("lbmpm_rk3dcsf_change before set_macro / set_pdf"); return LBMPM_ERR_STATE; }
-    LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
-    const unsigned planes = (unsigned)(c->nz - c->cfg.ghost_lo - c->cfg.ghost_hi), plane_cells = (unsigned)c->nx * (unsigned)c->ny;
-    const CsfDev p = make_dev(c);
-    if (c->first) return change_run("lbmpm_rk3dcsf_change", CsfIntLoader<true>{p}, c->chg, remark, c->steps, steps_between, planes, plane_cells, out, c->stream);
-    return change_run("lbmpm_rk3dcsf_change", CsfIntLoader<false>{p}, c->chg, remark, c->steps, steps_between, planes, plane_cells, out, c->stream);
-}
-
-// Phase clusters of the recorded phase field (rk3d_clusters.h; the definition: include/lbmpm.h), classified from the populations in
-// registers: no dense phi is staged.  Valid wherever lbmpm_rk3dcsf_integrals is, slabs included.
-extern "C" int lbmpm_rk3dcsf_clusters(lbmpm_rk3dcsf *c, const lbmpm_clusters_config *cfg, int64_t *count)
-{
-    LBMPM_REQUIRE(c && count, "lbmpm_rk3dcsf_clusters: null argument");
-    if (!c->have_state) { set_error("lbmpm_rk3dcsf_clusters before set_macro / set_pdf"); return LBMPM_ERR_STATE; }
-    LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
-    double cut = 0.;
-    ClGeom g{};
-    { const int rc = clusters_configure("lbmpm_rk3dcsf_clusters", cfg, (unsigned long long)c->nx * c->ny * (unsigned long long)c->nzg, &cut, &g); if (rc) return rc; }
-    g.nx = (unsigned)c->nx; g.ny = (unsigned)c->ny; g.planes = (unsigned)(c->nz - c->cfg.ghost_lo - c->cfg.ghost_hi);
-    g.plane_cells = g.nx * g.ny; g.n = g.planes * g.plane_cells;
-    g.z0 = (unsigned)(c->zoff + c->cfg.ghost_lo); g.base = g.z0 * g.plane_cells;
-    const CsfDev p = make_dev(c);
-    if (c->first) return clusters_label(CsfPhiLoader<true>{p}, c->cl, g, cut, c->steps, c->mem, nullptr, c->stream, count);
-    return clusters_label(CsfPhiLoader<false>{p}, c->cl, g, cut, c->steps, c->mem, nullptr, c->stream, count);
-}
-
-extern "C" int lbmpm_rk3dcsf_clusters_table(lbmpm_rk3dcsf *c, int64_t *out)
-{
-    LBMPM_REQUIRE(c && out, "lbmpm_rk3dcsf_clusters_table: null argument");
-    return clusters_table("lbmpm_rk3dcsf_clusters_table", c->cl, c->steps, c->cfg.device, c->stream, out);
-}
-
-extern "C" int lbmpm_rk3dcsf_clusters_labels(lbmpm_rk3dcsf *c, uint32_t *out)
-{
-    LBMPM_REQUIRE(c && out, "lbmpm_rk3dcsf_clusters_labels: null argument");
-    return clusters_labels("lbmpm_rk3dcsf_clusters_labels", c->cl, c->steps, c->cfg.device, c->stream, out);
-}
-
-extern "C" int lbmpm_rk3dcsf_clusters_faces(lbmpm_rk3dcsf *c, uint32_t *labels, uint8_t *classes)
-{
-    LBMPM_REQUIRE(c && labels && classes, "lbmpm_rk3dcsf_clusters_faces: null argument");
-    return clusters_faces("lbmpm_rk3dcsf_clusters_faces", c->cl, c->steps, c->cfg.device, c->stream, labels, classes);
-}
-
-// Per-cluster properties beside the table of the last lbmpm_rk3dcsf_clusters (rk3d_cluster_props.h; the definition: include/lbmpm.h),
-// from the populations in registers.  (A context without a state has no clusters: clusters_current says LBMPM_ERR_STATE.)
-extern "C" int lbmpm_rk3dcsf_cluster_props_face(lbmpm_rk3dcsf *c, uint8_t *classes)
-{
-    LBMPM_REQUIRE(c && classes, "lbmpm_rk3dcsf_cluster_props_face: null argument");
-    const char *who = "lbmpm_rk3dcsf_cluster_props_face";
-    const CsfDev p = make_dev(c);
-    if (c->first) return cluster_props_face(who, CsfIntLoader<true>{p}, c->cl, c->cprops, c->steps, c->cfg.device, c->mem, nullptr, c->stream, classes);
-    return cluster_props_face(who, CsfIntLoader<false>{p}, c->cl, c->cprops, c->steps, c->cfg.device, c->mem, nullptr, c->stream, classes);
-}
-
-extern "C" int lbmpm_rk3dcsf_cluster_props(lbmpm_rk3dcsf *c, const uint8_t *below, const uint8_t *above, int64_t *out)
-{
-    LBMPM_REQUIRE(c && out, "lbmpm_rk3dcsf_cluster_props: null argument");
-    const char *who = "lbmpm_rk3dcsf_cluster_props";
-    const CsfDev p = make_dev(c);
-    if (c->first) return cluster_props_run(who, CsfIntLoader<true>{p}, c->cl, c->cprops, c->steps, c->cfg.device, c->mem, nullptr, c->stream, below, above, out);
-    return cluster_props_run(who, CsfIntLoader<false>{p}, c->cl, c->cprops, c->steps, c->cfg.device, c->mem, nullptr, c->stream, below, above, out);
-}
-
-// Phase morphology of the recorded state (rk3d_morphology.h; the definition: include/lbmpm.h), classified from the populations in registers.
-// The checks and the class array of both entry points; then the context's device is the current one.  Valid wherever
-// lbmpm_rk3dcsf_integrals is, slabs included.
-static int morphology_ready(const char *who, lbmpm_rk3dcsf *c, const lbmpm_morphology_config *cfg, double *cut, unsigned *planes)
-{
-    if (!c->have_state) { set_error("%s before set_macro / set_pdf", who); return LBMPM_ERR_STATE; }
-    LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
-    *planes = (unsigned)(c->nz - c->cfg.ghost_lo - c->cfg.ghost_hi);
-    { const int rc = morphology_configure(who, cfg, (unsigned long long)(*planes + 1u) * c->nx * c->ny, cut); if (rc) return rc; }
-    return morphology_classes(c->mem, &c->morph, *planes, (unsigned)c->nx * (unsigned)c->ny, nullptr);
-}
-
-extern "C" int lbmpm_rk3dcsf_morphology_face(lbmpm_rk3dcsf *c, const lbmpm_morphology_config *cfg, uint8_t *classes)
-{
-    LBMPM_REQUIRE(c && classes, "lbmpm_rk3dcsf_morphology_face: null argument");
-    double cut = 0.;
-    unsigned planes = 0;
-    { const int rc = morphology_ready("lbmpm_rk3dcsf_morphology_face", c, cfg, &cut, &planes); if (rc) return rc; }
-    const CsfDev p = make_dev(c);
-    const unsigned plane_cells = (unsigned)c->nx * (unsigned)c->ny;
-    if (c->first) return morphology_face(CsfIntLoader<true>{p}, c->morph, plane_cells, cut, classes, c->stream);
-    return morphology_face(CsfIntLoader<false>{p}, c->morph, plane_cells, cut, classes, c->stream);
-}
-
-extern "C" int lbmpm_rk3dcsf_morphology(lbmpm_rk3dcsf *c, const lbmpm_morphology_config *cfg, const uint8_t *above, double *out)
-{
-    LBMPM_REQUIRE(c && out, "lbmpm_rk3dcsf_morphology: null argument");
-    double cut = 0.;
-    unsigned planes = 0;
-    { const int rc = morphology_ready("lbmpm_rk3dcsf_morphology", c, cfg, &cut, &planes); if (rc) return rc; }
-    const CsfDev p = make_dev(c);
-    const unsigned nx = (unsigned)c->nx, ny = (unsigned)c->ny;
-    if (c->first) return morphology_run("lbmpm_rk3dcsf_morphology", CsfIntLoader<true>{p}, c->morph, planes, nx, ny, cut, above, out, c->stream);
-    return morphology_run("lbmpm_rk3dcsf_morphology", CsfIntLoader<false>{p}, c->morph, planes, nx, ny, cut, above, out, c->stream);
-}
+// The analyses over the recorded state (rk3d_analysis.h holds the bodies, AnalysisModel<lbmpm_rk3dcsf> above what they read; the
+// definitions: include/lbmpm.h).  integrals: out [own planes][LBMPM_INTEGRAL_COLS].
+extern "C" int lbmpm_rk3dcsf_integrals(lbmpm_rk3dcsf *c, double *out) { LBMPM_REQUIRE(c && out, "lbmpm_rk3dcsf_integrals: null argument"); return analysis_integrals("lbmpm_rk3dcsf_integrals", c, out); }
+extern "C" int lbmpm_rk3dcsf_change_mark(lbmpm_rk3dcsf *c) { LBMPM_REQUIRE(c, "lbmpm_rk3dcsf_change_mark: null argument"); return analysis_change_mark("lbmpm_rk3dcsf_change_mark", c); }
+extern "C" int lbmpm_rk3dcsf_change(lbmpm_rk3dcsf *c, int remark, int64_t *steps_between, double *out) { LBMPM_REQUIRE(c && out, "lbmpm_rk3dcsf_change: null argument"); return analysis_change("lbmpm_rk3dcsf_change", c, remark, steps_between, out); }
+extern "C" int lbmpm_rk3dcsf_clusters(lbmpm_rk3dcsf *c, const lbmpm_clusters_config *cfg, int64_t *count) { LBMPM_REQUIRE(c && count, "lbmpm_rk3dcsf_clusters: null argument"); return analysis_clusters("lbmpm_rk3dcsf_clusters", c, cfg, count); }
+extern "C" int lbmpm_rk3dcsf_clusters_table(lbmpm_rk3dcsf *c, int64_t *out) { LBMPM_REQUIRE(c && out, "lbmpm_rk3dcsf_clusters_table: null argument"); return analysis_clusters_table("lbmpm_rk3dcsf_clusters_table", c, out); }
+extern "C" int lbmpm_rk3dcsf_clusters_labels(lbmpm_rk3dcsf *c, uint32_t *out) { LBMPM_REQUIRE(c && out, "lbmpm_rk3dcsf_clusters_labels: null argument"); return analysis_clusters_labels("lbmpm_rk3dcsf_clusters_labels", c, out); }
+extern "C" int lbmpm_rk3dcsf_clusters_faces(lbmpm_rk3dcsf *c, uint32_t *labels, uint8_t *classes) { LBMPM_REQUIRE(c && labels && classes, "lbmpm_rk3dcsf_clusters_faces: null argument"); return analysis_clusters_faces("lbmpm_rk3dcsf_clusters_faces", c, labels, classes); }
+extern "C" int lbmpm_rk3dcsf_cluster_props_face(lbmpm_rk3dcsf *c, uint8_t *classes) { LBMPM_REQUIRE(c && classes, "lbmpm_rk3dcsf_cluster_props_face: null argument"); return analysis_cluster_props_face("lbmpm_rk3dcsf_cluster_props_face", c, classes); }
+extern "C" int lbmpm_rk3dcsf_cluster_props(lbmpm_rk3dcsf *c, const uint8_t *below, const uint8_t *above, int64_t *out) { LBMPM_REQUIRE(c && out, "lbmpm_rk3dcsf_cluster_props: null argument"); return analysis_cluster_props("lbmpm_rk3dcsf_cluster_props", c, below, above, out); }
+extern "C" int lbmpm_rk3dcsf_morphology_face(lbmpm_rk3dcsf *c, const lbmpm_morphology_config *cfg, uint8_t *classes) { LBMPM_REQUIRE(c && classes, "lbmpm_rk3dcsf_morphology_face: null argument"); return analysis_morphology_face("lbmpm_rk3dcsf_morphology_face", c, cfg, classes); }
+extern "C" int lbmpm_rk3dcsf_morphology(lbmpm_rk3dcsf *c, const lbmpm_morphology_config *cfg, const uint8_t *above, double *out) { LBMPM_REQUIRE(c && out, "lbmpm_rk3dcsf_morphology: null argument"); return analysis_morphology("lbmpm_rk3dcsf_morphology", c, cfg, above, out); }
 
 extern "C" int64_t lbmpm_rk3dcsf_num_fluid_nodes(const lbmpm_rk3dcsf *c) { return c ? c->nfluid : 0; }
 extern "C" int64_t lbmpm_rk3dcsf_num_wetting_solids(const lbmpm_rk3dcsf *c) { return c ? (int64_t)c->nwet : 0; }

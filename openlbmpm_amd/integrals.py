@@ -229,8 +229,11 @@ def column_names(a):
 
 
 def fresh(take, observe):
-    """take(), after observe() when the perturbation model's diagnostics are stale (LBMPM_ERR_STATE: a step since the last observe)"""
+    """take(), after observe() when the perturbation model's diagnostics are stale (LBMPM_ERR_STATE: a step since the last observe);
+    observe = None (a model whose analyses are never stale): just take()"""
     from ._lib import ERR_STATE, LbmpmError
+    if observe is None:
+        return take()
     try:
         return take()
     except LbmpmError as e:
@@ -240,11 +243,12 @@ def fresh(take, observe):
     return take()
 
 
-def table(L, fn_name, handle, planes):
-    """[planes][12] of one context through lbmpm_*_integrals"""
+def table(L, prefix, handle, planes):
+    """[planes][12] of one context through <prefix>_integrals (prefix: the class's _C_PREFIX, here and in change, clusters, morphology)"""
     from ._lib import F64P, check
     out = np.empty((int(planes), len(COLUMNS)), dtype=np.float64)
-    check(getattr(L, fn_name)(handle, out.ctypes.data_as(F64P)), fn_name)
+    name = prefix + "_integrals"
+    check(getattr(L, name)(handle, out.ctypes.data_as(F64P)), name)
     return out
 
 

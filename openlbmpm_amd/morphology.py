@@ -115,17 +115,17 @@ def _config(phi_cut):
 
 
 def face(L, prefix, handle, ny, nx, phi_cut=0.0):
-    """[ny][nx] uint8: the classes of the lowest own plane of one context through lbmpm_<prefix>_morphology_face"""
+    """[ny][nx] uint8: the classes of the lowest own plane of one context through <prefix>_morphology_face"""
     import ctypes as C
     from ._lib import U8P, check
     out = np.empty((int(ny), int(nx)), dtype=np.uint8)
-    name = "lbmpm_%s_morphology_face" % prefix
+    name = prefix + "_morphology_face"
     check(getattr(L, name)(handle, C.byref(_config(phi_cut)), out.ctypes.data_as(U8P)), name)
     return out
 
 
 def table(L, prefix, handle, planes, ny, nx, phi_cut=0.0, above=None):
-    """[planes][28] of one context through lbmpm_<prefix>_morphology; above: [ny][nx] classes of the plane over the highest own plane
+    """[planes][28] of one context through <prefix>_morphology; above: [ny][nx] classes of the plane over the highest own plane
     (the `face` of the slab above), None at the lattice's end"""
     import ctypes as C
     from ._lib import F64P, U8P, check
@@ -135,7 +135,7 @@ def table(L, prefix, handle, planes, ny, nx, phi_cut=0.0, above=None):
         up = np.ascontiguousarray(above, dtype=np.uint8)
         if up.shape != (int(ny), int(nx)):
             raise TypeError("above must have shape [ny][nx]")
-    name = "lbmpm_%s_morphology" % prefix
+    name = prefix + "_morphology"
     check(getattr(L, name)(handle, C.byref(_config(phi_cut)), None if up is None else up.ctypes.data_as(U8P), out.ctypes.data_as(F64P)), name)
     return out
 

@@ -7,6 +7,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import F64P, U8P, RK3DConfig, SlabTransportCalls, check
+from .analysis import GatheredAnalysis, SlabAnalysisCalls, StackedAnalysis
 from .slab import partition_z, partition_z_balanced, neighbour_exchange, local_exchange, connect_in_library, DeviceBuffer
 from .slab import _torch_librccl        # noqa: F401 -- its earlier home: importable from here as before
 
@@ -22,7 +23,7 @@ DEFAULT_PARAMS = dict(AkR=7.0e-3, AkB=7.0e-3, beta=1.0, tauR=1.0, tauB=1.0, Soli
                       outlet="Dirichlet")                                    # BoundaryTypeOutlet 'Convective': planes 0 .. 2 copy plane 3
 
 
-class RK3DSlab(SlabTransportCalls):
+class RK3DSlab(SlabTransportCalls, SlabAnalysisCalls):
     """One slab: planes [z0, z0+nzl) of a global [nz, ny, nx] lattice.  The exchange's transport inside the library (ipc_init ..
     sync(deadline_s)): SlabTransportCalls; `transport` says 'callback' when none is connected -- the caller's exchange function."""
     _C_PREFIX, _NO_TRANSPORT = "lbmpm_rk3d", "callback"
@@ -206,74 +207,10 @@ class RK3DSlab(SlabTransportCalls):
         check(self._L.lbmpm_rk3d_get_field(self._h, FIELDS[name], out.ctypes.data_as(F64P)), "get_field(%s)" % name)
         return out
 
-    def integrals(self):
-        """integrals.Integrals of the slab's own planes: sums over the fields of the last phase_field(diagnostics=True), reduced on the
-        device (lbmpm_rk3d_integrals); LbmpmError (LBMPM_ERR_STATE) when a step has been taken since"""
-        from .integrals import Integrals, table
-        return Integrals(table(self._L, "lbmpm_rk3d_integrals", self._h, self.nzl), self.nx, self.ny)
-
-    def mark_change(self):
-        """the snapshot change() compares with: u and phi of the last phase_field(diagnostics=True), kept on the device (32 bytes per own
-        lattice cell, allocated by the first call); LbmpmError (LBMPM_ERR_STATE) when a step has been taken since that phase_field"""
-        from .change import mark
-        mark(self._L, "rk3d", self._h)
-
-    def change_part(self, remark=True):
-        """([nzl][11], steps since the mark): the change table of the slab's own planes"""
-        from .change import table
-        return table(self._L, "rk3d", self._h, self.nzl, remark)
-
-    def change(self, remark=True):
-        """change.Change of the slab's own planes: the fields of the last phase_field(diagnostics=True) against the snapshot, reduced on
-        the device (lbmpm_rk3d_change); remark: they replace the snapshot in the same pass.  LbmpmError (LBMPM_ERR_STATE) before
-        mark_change(), when a step has been taken since that phase_field, and after a set_* since the mark"""
-        from .change import Change
-        t, steps = self.change_part(remark)
-        return Change(t, self.nx, self.ny, steps)
-
-    def clusters_part(self, phi_cut=0.0, connectivity=6, labels=False, faces=True):
-        """clusters.take of the slab's own planes: the table (and labels, faces) of this slab alone, for clusters.merge_slabs"""
-        from .clusters import take
-        return take(self._L, "rk3d", self._h, self.nzl, self.ny, self.nx, phi_cut, connectivity, labels, faces)
-
-    def cluster_props_face(self):
-        """[2][ny][nx] uint8: the class bytes of the slab's lowest and highest plane under its last clusters_part -- what the slabs
-        beside it pass to cluster_props_part"""
-        from .clusters import props_face
-        return props_face(self._L, "rk3d", self._h, self.ny, self.nx)
-
-    def cluster_props_part(self, count, below=None, above=None):
-        """[count][14] int64: the properties of the clusters of the slab's last clusters_part (count: its rows), reduced on the device
-        (lbmpm_rk3d_cluster_props); below / above: the class planes of the slabs beside it (None: the lattice ends there)"""
-        from .clusters import props_table
-        return props_table(self._L, "rk3d", self._h, count, self.ny, self.nx, below, above)
-
-    def clusters(self, phi_cut=0.0, connectivity=6, labels=False, props=False):
-        """clusters.Clusters of the slab's own planes: the connected cells of each phase of phi of the last phase_field(diagnostics=True),
-        labelled on the device (lbmpm_rk3d_clusters); LbmpmError (LBMPM_ERR_STATE) when a step has been taken since.  props=True: with
-        the property table (faces, elements, plane sum, mass and momentum per cluster), reduced on the device"""
-        from .clusters import Clusters
-        got = self.clusters_part(phi_cut, connectivity, labels, faces=False)
-        table = self.cluster_props_part(got["table"].shape[0]) if props else None
-        return Clusters(got["table"], self.nx, self.ny, self.nz, got.get("labels"), table)
-
-    def morphology_face(self, phi_cut=0.0):
-        """[ny][nx] uint8: the classes of the slab's lowest plane -- what the slab below passes to morphology_part as `above`"""
-        from .morphology import face
-        return face(self._L, "rk3d", self._h, self.ny, self.nx, phi_cut)
-
-    def morphology_part(self, phi_cut=0.0, above=None):
-        """[nzl][28]: the morphology table of the slab's own planes; above: the morphology_face of the slab over it (None: the highest
-        plane anchors nothing that reaches upwards)"""
-        from .morphology import table
-        return table(self._L, "rk3d", self._h, self.nzl, self.ny, self.nx, phi_cut, above)
-
-    def morphology(self, phi_cut=0.0):
-        """morphology.Morphology of the slab's own planes: cells, class pairs, squares and cubes of the fields of the last
-        phase_field(diagnostics=True), counted on the device (lbmpm_rk3d_morphology); LbmpmError (LBMPM_ERR_STATE) when a step has been
-        taken since"""
-        from .morphology import Morphology
-        return Morphology(self.morphology_part(phi_cut), self.nx, self.ny)
+    # ---- integrals() .. morphology(): analysis.SlabAnalysisCalls, here over the fields of the last phase_field(diagnostics=True) --
+    # LbmpmError (LBMPM_ERR_STATE) when a step has been taken since
+    own_planes = property(lambda self: self.nzl)
+    lattice_nz = property(lambda self: self.nz)
 
     @property
     def num_fluid_nodes(self):
@@ -313,13 +250,14 @@ class RK3DSlab(SlabTransportCalls):
         return self.dominant_kernel == "rk3dq_fused"
 
 
-class RK3DCluster:
+class RK3DCluster(StackedAnalysis):
     """k slabs ('virtual ranks') in ONE process on one GPU, halos moved by device copies.
-    Exists to prove that the slab-decomposed time step equals the single-domain one."""
+    Exists to prove that the slab-decomposed time step equals the single-domain one.
+    integrals() .. morphology(): analysis.StackedAnalysis, with observe() first when the diagnostics are stale."""
 
     def __init__(self, is_domain_global, k, params=None, device=0):
-        nz = is_domain_global.shape[0]
-        self.parts = partition_z(nz, k)
+        self.nz, self.ny, self.nx = is_domain_global.shape
+        self.parts = partition_z(self.nz, k)
         import torch
         self.slabs = [RK3DSlab(is_domain_global, z0, n, params, device) for z0, n in self.parts]
         self.stream = torch.cuda.Stream(device)
@@ -388,60 +326,22 @@ class RK3DCluster:
             for s in self.slabs:
                 s.phase_field(diagnostics=True)
 
+    _refresh = observe
+
     def get(self, name):
         return np.concatenate([s.get(name) for s in self.slabs], axis=0)
-
-    def integrals(self):
-        """the slabs' tables in plane order (bit-equal to the undivided lattice's); observe() first when the diagnostics are stale"""
-        from .integrals import Integrals, fresh
-        s0 = self.slabs[0]
-        return Integrals(fresh(lambda: np.concatenate([s.integrals().planes for s in self.slabs], axis=0), self.observe), s0.nx, s0.ny)
-
-    def mark_change(self):
-        """every slab's snapshot for change(); observe() first when the diagnostics are stale"""
-        from .integrals import fresh
-        fresh(lambda: [s.mark_change() for s in self.slabs], self.observe)
-
-    def change(self, remark=True):
-        """change.Change of the whole lattice: the slabs' tables in plane order, each against its own snapshot (bit-equal to the undivided
-        lattice's); observe() first when the diagnostics are stale"""
-        from .change import Change, stacked
-        from .integrals import fresh
-        s0 = self.slabs[0]
-        t, steps = fresh(lambda: stacked(self.slabs, remark), self.observe)
-        return Change(t, s0.nx, s0.ny, steps)
-
-    def clusters(self, phi_cut=0.0, connectivity=6, labels=False, props=False):
-        """clusters.Clusters of the whole lattice: the slabs' tables joined through their face planes (equal to the undivided lattice's);
-        observe() first when the phase field is stale.  props=True: with the property table -- the slabs hand each other their class
-        planes, every slab reduces its own rows, the rows are added (bit-equal to the undivided lattice's)"""
-        from .clusters import merged, stacked_props
-        from .integrals import fresh
-        s0 = self.slabs[0]
-
-        def take():
-            parts = [s.clusters_part(phi_cut, connectivity, labels) for s in self.slabs]
-            return stacked_props(self.slabs, parts) if props else parts
-        return merged(fresh(take, self.observe), s0.nx, s0.ny, s0.nz, connectivity, labels)
-
-    def morphology(self, phi_cut=0.0):
-        """morphology.Morphology of the whole lattice: every slab joins the lowest plane of the slab over it on its device (bit-equal to
-        the undivided lattice's); observe() first when the diagnostics are stale"""
-        from .integrals import fresh
-        from .morphology import Morphology, stacked
-        s0 = self.slabs[0]
-        return Morphology(fresh(lambda: stacked(self.slabs, phi_cut), self.observe), s0.nx, s0.ny)
 
     def close(self):
         for s in self.slabs:
             s.close()
 
 
-class RK3DDistributed:
+class RK3DDistributed(GatheredAnalysis):
     """One slab per process/GPU.  The face messages travel over a transport INSIDE the library where one connects -- 'ipc' (landing
     areas mapped with hipIpcOpenMemHandle, one copy-engine transfer + a stream value operation per message: no CU, no host work per
     step) or 'rccl' (ncclSend / ncclRecv of a communicator the library makes itself) -- else through the 'callback': torch.distributed
-    P2P enqueued from Python once per step.  torch.distributed is used for set-up (handles, unique id, agreement) either way."""
+    P2P enqueued from Python once per step.  torch.distributed is used for set-up (handles, unique id, agreement) either way.
+    integrals() .. morphology(): analysis.GatheredAnalysis, with observe() first when the diagnostics are stale."""
 
     def __init__(self, is_domain_global, params=None, device=0, group=None, balance=True, plane_cost=None, transport=None):
         """plane_cost: measured cost per lattice plane (`calibrated_plane_cost` of an earlier instance); the cuts then equalise it
@@ -453,6 +353,7 @@ class RK3DDistributed:
         self.parts = self.partition(is_domain_global, self.world, balance, plane_cost)      # every rank's (z0, planes)
         z0, n = self.parts[self.rank]
         self.z0, self.nzl = z0, n
+        self.nz, self.ny, self.nx = is_domain_global.shape
         import os
         import torch
         self._torch = torch
@@ -460,7 +361,7 @@ class RK3DDistributed:
         # CURRENT device under NCCL: make that the slab's GPU, whoever constructed us
         if torch.cuda.is_available():
             torch.cuda.set_device(device)
-        self.device = device
+        self.device = self.device_index = device
         self.slab = RK3DSlab(is_domain_global, z0, n, params, device)
         self.stream = torch.cuda.Stream(device)
         self.slab.use_torch_stream(self.stream)
@@ -616,55 +517,7 @@ class RK3DDistributed:
             self.slab.phase_field(diagnostics=True)
         self.sync()
 
-    def integrals(self):
-        """collective: rank 0 returns the integrals.Integrals of the whole lattice (the ranks' tables through gather()), the others None;
-        observe() first when the diagnostics are stale (every rank is, or none: they step together)"""
-        from .integrals import Integrals, fresh
-        t = self.gather(fresh(lambda: self.slab.integrals().planes, self.observe))
-        return None if t is None else Integrals(t, self.slab.nx, self.slab.ny)
-
-    def mark_change(self):
-        """every rank: the snapshot of its slab for change(); observe() first when the diagnostics are stale"""
-        from .integrals import fresh
-        fresh(self.slab.mark_change, self.observe)
-
-    def change(self, remark=True):
-        """collective: rank 0 returns the change.Change of the whole lattice (every rank against its own snapshot, the tables through
-        gather()), the others None; observe() first when the diagnostics are stale"""
-        from .change import Change
-        from .integrals import fresh
-        part, steps = fresh(lambda: self.slab.change_part(remark), self.observe)
-        t = self.gather(part)
-        return None if t is None else Change(t, self.slab.nx, self.slab.ny, steps)
-
-    def clusters(self, phi_cut=0.0, connectivity=6, labels=False, props=False):
-        """collective: rank 0 returns the clusters.Clusters of the whole lattice (the ranks' tables and face planes, joined there; with
-        labels=True the label planes too), the others None; observe() first when the phase field is stale.  props=True: with the
-        property table -- one all_gather of 2 ny nx class bytes first, every rank reduces its own rows, rank 0 adds them"""
-        from .clusters import faces_from_neighbours, gather_merged
-        from .integrals import fresh
-
-        def take():
-            part = self.slab.clusters_part(phi_cut, connectivity, labels)
-            if props:
-                part["props_face"] = self.slab.cluster_props_face()
-            return part
-        part = fresh(take, self.observe)
-        if props:
-            below, above = faces_from_neighbours(part.pop("props_face"), self.rank, self.world, self.group, self.device)
-            part["props"] = self.slab.cluster_props_part(part["table"].shape[0], below, above)
-        return gather_merged(part, self.rank, self.world, self.group, self.slab.nx, self.slab.ny, self.slab.nz, connectivity, labels)
-
-    def morphology(self, phi_cut=0.0):
-        """collective: rank 0 returns the morphology.Morphology of the whole lattice (every rank takes the lowest class plane of the rank
-        above it, one all_gather of [ny][nx] bytes, and joins on its device; the tables through gather()), the others None; observe()
-        first when the diagnostics are stale"""
-        from .integrals import fresh
-        from .morphology import Morphology, face_from_above
-        mine = fresh(lambda: self.slab.morphology_face(phi_cut), self.observe)
-        above = face_from_above(mine, self.rank, self.world, self.group, self.device)
-        t = self.gather(self.slab.morphology_part(phi_cut, above))
-        return None if t is None else Morphology(t, self.slab.nx, self.slab.ny)
+    _refresh = observe
 
     def sync(self, deadline_s=None):
         """Wait for this rank's work.  With an in-library transport the wait is the library's watchdog (lbmpm_rk3d_sync_deadline,

@@ -9,6 +9,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import F64P, U8P, RK3DCSFConfig, SlabTransportCalls, check
+from .analysis import GatheredAnalysis, SlabAnalysisCalls, StackedAnalysis
 from .slab import connect_in_library
 
 FIELDS = dict(fR=0, fB=1, rhoR=2, rhoB=3, vx=4, vy=5, vz=6, phi=7, Gx=8, Gy=9, Gz=10, Fx=11, Fy=12, Fz=13, K=14, nsx=15, nsy=16, nsz=17,
@@ -68,7 +69,7 @@ def body_force_pair(g=None, red=None, blue=None):
     return three(g if red is None else red, "red"), three(g if blue is None else blue, "blue")
 
 
-class RK3DCSFSolver(SlabTransportCalls):
+class RK3DCSFSolver(SlabTransportCalls, SlabAnalysisCalls):
     _C_PREFIX, _NO_TRANSPORT = "lbmpm_rk3dcsf", "none"
 
     def __init__(self, is_domain, params=None, device=0, diagnostics=False, slab=None, tracers=None):
@@ -287,74 +288,10 @@ class RK3DCSFSolver(SlabTransportCalls):
         check(self._L.lbmpm_rk3dcsf_get_field(self._h, FIELDS[name], out.ctypes.data_as(F64P)), "get_field(%s)" % name)
         return out
 
-    def integrals(self):
-        """integrals.Integrals of the own planes (a slab: without its ghost planes): sums over what get("rec_*") hands out, reduced from
-        the populations on the device (lbmpm_rk3dcsf_integrals) -- no per-cell staging, nothing to call beforehand"""
-        from .integrals import Integrals, table
-        return Integrals(table(self._L, "lbmpm_rk3dcsf_integrals", self._h, self.nz - self.ghost[0] - self.ghost[1]), self.nx, self.ny)
-
-    def mark_change(self):
-        """the snapshot change() compares with: what get("rec_vx" .. "rec_phi") hand out for the own planes, taken from the populations
-        and kept on the device (32 bytes per own lattice cell, allocated by the first call)"""
-        from .change import mark
-        mark(self._L, "rk3dcsf", self._h)
-
-    def change_part(self, remark=True):
-        """([own planes][11], steps since the mark): the change table of this lattice or slab alone"""
-        from .change import table
-        return table(self._L, "rk3dcsf", self._h, self.nz - self.ghost[0] - self.ghost[1], remark)
-
-    def change(self, remark=True):
-        """change.Change of the own planes: the recorded state against the snapshot, reduced from the populations on the device
-        (lbmpm_rk3dcsf_change); remark: it replaces the snapshot in the same pass.  LbmpmError (LBMPM_ERR_STATE) before mark_change()
-        and after a set_macro / set_pdf since the mark"""
-        from .change import Change
-        t, steps = self.change_part(remark)
-        return Change(t, self.nx, self.ny, steps)
-
-    def clusters_part(self, phi_cut=0.0, connectivity=6, labels=False, faces=True):
-        """clusters.take of the own planes: the table (and labels, faces) of this lattice or slab alone, for clusters.merge_slabs"""
-        from .clusters import take
-        return take(self._L, "rk3dcsf", self._h, self.nz - self.ghost[0] - self.ghost[1], self.ny, self.nx, phi_cut, connectivity, labels, faces)
-
-    def cluster_props_face(self):
-        """[2][ny][nx] uint8: the class bytes of the lowest and the highest own plane under the last clusters_part -- what the slabs
-        beside this one pass to cluster_props_part"""
-        from .clusters import props_face
-        return props_face(self._L, "rk3dcsf", self._h, self.ny, self.nx)
-
-    def cluster_props_part(self, count, below=None, above=None):
-        """[count][14] int64: the properties of the clusters of the last clusters_part (count: its rows), reduced on the device
-        (lbmpm_rk3dcsf_cluster_props); below / above: the class planes of the slabs beside this one (None: the lattice ends there)"""
-        from .clusters import props_table
-        return props_table(self._L, "rk3dcsf", self._h, count, self.ny, self.nx, below, above)
-
-    def clusters(self, phi_cut=0.0, connectivity=6, labels=False, props=False):
-        """clusters.Clusters of the own planes: the connected cells of each phase of what get("rec_phi") hands out, classified from the
-        populations and labelled on the device (lbmpm_rk3dcsf_clusters) -- nothing staged, nothing to call beforehand.  props=True:
-        with the property table (faces, elements, plane sum, mass and momentum per cluster), reduced on the device"""
-        from .clusters import Clusters
-        got = self.clusters_part(phi_cut, connectivity, labels, faces=False)
-        table = self.cluster_props_part(got["table"].shape[0]) if props else None
-        return Clusters(got["table"], self.nx, self.ny, self.global_nz, got.get("labels"), table)
-
-    def morphology_face(self, phi_cut=0.0):
-        """[ny][nx] uint8: the classes of the lowest own plane -- what the slab below passes to morphology_part as `above`"""
-        from .morphology import face
-        return face(self._L, "rk3dcsf", self._h, self.ny, self.nx, phi_cut)
-
-    def morphology_part(self, phi_cut=0.0, above=None):
-        """[own planes][28]: the morphology table of this lattice or slab alone; above: the morphology_face of the slab over it (None:
-        the highest own plane anchors nothing that reaches upwards)"""
-        from .morphology import table
-        return table(self._L, "rk3dcsf", self._h, self.nz - self.ghost[0] - self.ghost[1], self.ny, self.nx, phi_cut, above)
-
-    def morphology(self, phi_cut=0.0):
-        """morphology.Morphology of the own planes: cells, class pairs, squares and cubes of what get("rec_phi") and get("rec_rho*") hand
-        out, classified from the populations and counted on the device (lbmpm_rk3dcsf_morphology) -- nothing staged, nothing to call
-        beforehand"""
-        from .morphology import Morphology
-        return Morphology(self.morphology_part(phi_cut), self.nx, self.ny)
+    # ---- integrals() .. morphology(): analysis.SlabAnalysisCalls, here over what get("rec_*") hands out for the own planes (a slab:
+    # without its ghost planes), taken from the populations in registers -- no per-cell staging, nothing to call beforehand
+    own_planes = property(lambda self: self.nz - self.ghost[0] - self.ghost[1])
+    lattice_nz = property(lambda self: self.global_nz)
 
     def tracer_integrals(self):
         """integrals.TracerIntegrals of the own planes, [planes][nT][9]: cells, mass, the first moments g(+a) - g(-a) per axis, sum C^2,
@@ -362,7 +299,7 @@ class RK3DCSFSolver(SlabTransportCalls):
         device for all tracers at once (lbmpm_rk3dcsf_tracer_integrals), no dense field staged or copied"""
         from .integrals import TracerIntegrals, tracer_table
         n = max(1, getattr(self, "num_tracers", 0))          # (without tracers the library refuses before it writes)
-        return TracerIntegrals(tracer_table(self._L, self._h, self.nz - self.ghost[0] - self.ghost[1], n), self.nx, self.ny)
+        return TracerIntegrals(tracer_table(self._L, self._h, self.own_planes, n), self.nx, self.ny)
 
     @property
     def num_fluid_nodes(self):
@@ -454,10 +391,11 @@ _TRACERS_AT_CONSTRUCTION = ("tracers on z-slabs are part of the slabs' populatio
                             "give them to %s at construction (tracers=dict(...)), not afterwards")
 
 
-class RK3DCSFCluster:
+class RK3DCSFCluster(StackedAnalysis):
     """The 3-D CSF model cut into slabs along z, every slab a context of its own (devices[k]; all on one GPU: a rehearsal of the
     decomposition, bit-equal to the undivided lattice).  One time step = three stages with a face message after each: phi (two planes),
-    n (one plane), the populations crossing the face (lbmpm_rk3dcsf_stage / _face_copy)."""
+    n (one plane), the populations crossing the face (lbmpm_rk3dcsf_stage / _face_copy).
+    integrals() .. morphology(): analysis.StackedAnalysis; nothing can be stale, so nothing is refreshed."""
 
     def __init__(self, is_domain, params=None, nslabs=2, devices=None, cuts=None, diagnostics=False, tracers=None):
         """tracers = dict(<the keyword arguments of RK3DCSFSolver.configure_tracers>): D3Q7 tracers on every slab"""
@@ -549,37 +487,6 @@ class RK3DCSFCluster:
     def get(self, name):
         return np.concatenate([g.own(s.get(name)) for s, g in zip(self.slabs, self.geo)], axis=0)
 
-    def integrals(self):
-        """the slabs' tables in plane order: bit-equal to the undivided lattice's"""
-        from .integrals import Integrals
-        return Integrals(np.concatenate([s.integrals().planes for s in self.slabs], axis=0), self.nx, self.ny)
-
-    def mark_change(self):
-        """every slab's snapshot for change()"""
-        for s in self.slabs:
-            s.mark_change()
-
-    def change(self, remark=True):
-        """change.Change of the whole lattice: the slabs' tables in plane order, each against its own snapshot (bit-equal to the undivided
-        lattice's)"""
-        from .change import Change, stacked
-        t, steps = stacked(self.slabs, remark)
-        return Change(t, self.nx, self.ny, steps)
-
-    def clusters(self, phi_cut=0.0, connectivity=6, labels=False, props=False):
-        """clusters.Clusters of the whole lattice: the slabs' tables joined through their face planes (equal to the undivided lattice's).
-        props=True: with the property table -- the slabs hand each other their class planes, every slab reduces its own rows, the rows
-        are added (bit-equal to the undivided lattice's)"""
-        from .clusters import merged, stacked_props
-        parts = [s.clusters_part(phi_cut, connectivity, labels) for s in self.slabs]
-        return merged(stacked_props(self.slabs, parts) if props else parts, self.nx, self.ny, self.nz, connectivity, labels)
-
-    def morphology(self, phi_cut=0.0):
-        """morphology.Morphology of the whole lattice: every slab joins the lowest own plane of the slab over it on its device, the top
-        slab nothing -- z does not wrap here, whatever the ring of the flow does (bit-equal to the undivided lattice's)"""
-        from .morphology import Morphology, stacked
-        return Morphology(stacked(self.slabs, phi_cut), self.nx, self.ny)
-
     def tracer_integrals(self):
         """the slabs' tracer tables in plane order: bit-equal to the undivided lattice's"""
         from .integrals import TracerIntegrals
@@ -598,12 +505,13 @@ class RK3DCSFCluster:
         return sum(s.bulk_cells for s in self.slabs)
 
 
-class RK3DCSFDistributed:
+class RK3DCSFDistributed(GatheredAnalysis):
     """One slab of the 3-D CSF model per rank of torch.distributed (launch: one process per GPU).  The face messages travel as device
     tensors under the nccl (= RCCL) backend and through host memory under gloo; three per step and face (phi, n, populations: 2 + 3 +
     10 doubles per cell of a plane, + 1 per tracer), batched per stage.  Opt-in (transport='ipc' | 'rccl' | 'auto'): the messages travel over a transport
     inside the library instead, and a call to step() is one lbmpm_rk3dcsf_step_slab -- no Python and no host synchronisation between the
-    stages; torch.distributed then only carries the set-up (blobs, unique id, agreement)."""
+    stages; torch.distributed then only carries the set-up (blobs, unique id, agreement).
+    integrals() .. morphology(): analysis.GatheredAnalysis over the default group; nothing can be stale, so nothing is refreshed."""
 
     def __init__(self, is_domain, params=None, device=0, cuts=None, diagnostics=False, slab_factory=None, transport=None, tracers=None):
         """tracers = dict(<the keyword arguments of RK3DCSFSolver.configure_tracers>), the same on every rank: D3Q7 tracers, one more
@@ -621,6 +529,7 @@ class RK3DCSFDistributed:
         dom = np.ascontiguousarray(is_domain, dtype=np.uint8)
         self.shape = dom.shape
         self.nz = dom.shape[0]
+        self.group = None
         # (default: equal shares of the fluid cells -- the same cuts on every rank, they hold the same mask)
         self.cuts = list(cuts) if cuts is not None else slab_cuts(self.nz, self.world, weights=(dom.reshape(self.nz, -1) == 1).sum(axis=1) + 1.0e-3)
         if len(self.cuts) != self.world + 1:
@@ -801,43 +710,6 @@ class RK3DCSFDistributed:
         """this rank's own planes"""
         return np.ascontiguousarray(self.geo.own(self.slab.get(name)))
 
-    def integrals(self):
-        """collective: rank 0 returns the integrals.Integrals of the whole lattice (the ranks' tables through gather()), the others None"""
-        from .integrals import Integrals
-        t = self.gather(self.slab.integrals().planes)
-        return None if t is None else Integrals(t, self.shape[2], self.shape[1])
-
-    def mark_change(self):
-        """every rank: the snapshot of its slab for change()"""
-        self.slab.mark_change()
-
-    def change(self, remark=True):
-        """collective: rank 0 returns the change.Change of the whole lattice (every rank against its own snapshot, the tables through
-        gather()), the others None"""
-        from .change import Change
-        part, steps = self.slab.change_part(remark)
-        t = self.gather(part)
-        return None if t is None else Change(t, self.shape[2], self.shape[1], steps)
-
-    def clusters(self, phi_cut=0.0, connectivity=6, labels=False, props=False):
-        """collective: rank 0 returns the clusters.Clusters of the whole lattice (the ranks' tables and face planes, joined there; with
-        labels=True the label planes too), the others None.  props=True: with the property table -- one all_gather of 2 ny nx class
-        bytes first, every rank reduces its own rows, rank 0 adds them"""
-        from .clusters import faces_from_neighbours, gather_merged
-        part = self.slab.clusters_part(phi_cut, connectivity, labels)
-        if props:
-            below, above = faces_from_neighbours(self.slab.cluster_props_face(), self.rank, self.world, None, self._dev.index)
-            part["props"] = self.slab.cluster_props_part(part["table"].shape[0], below, above)
-        return gather_merged(part, self.rank, self.world, None, self.shape[2], self.shape[1], self.nz, connectivity, labels)
-
-    def morphology(self, phi_cut=0.0):
-        """collective: rank 0 returns the morphology.Morphology of the whole lattice (every rank takes the lowest class plane of the rank
-        above it, one all_gather of [ny][nx] bytes, and joins on its device; the tables through gather()), the others None"""
-        from .morphology import Morphology, face_from_above
-        above = face_from_above(self.slab.morphology_face(phi_cut), self.rank, self.world, None, self._dev.index)
-        t = self.gather(self.slab.morphology_part(phi_cut, above))
-        return None if t is None else Morphology(t, self.shape[2], self.shape[1])
-
     def tracer_integrals(self):
         """collective: rank 0 returns the integrals.TracerIntegrals of the whole lattice ([nz][nT][9]: axis 0 is z, so gather() stacks the
         ranks' tables), the others None"""
@@ -849,7 +721,11 @@ class RK3DCSFDistributed:
         """rank 0: the ranks' planes stacked along z (None elsewhere); slab.gather_planes"""
         from .slab import gather_planes
         parts = [(self.cuts[r], self.cuts[r + 1] - self.cuts[r]) for r in range(self.world)]
-        return gather_planes(a, parts, self.rank, self.world, device=self._dev.index)
+        return gather_planes(a, parts, self.rank, self.world, device=self.device_index)
+
+    device_index = property(lambda self: self._dev.index)
+    ny = property(lambda self: self.shape[1])
+    nx = property(lambda self: self.shape[2])
 
     num_fluid_nodes = property(lambda self: int((self.geo.own(self.slab.is_domain) == 1).sum()))
     steps_done = property(lambda self: self.slab.steps_done)
