@@ -77,20 +77,65 @@ import os
 import numpy as np
 
 from . import config
+from .change import CRITERIA_COLUMNS, column_bytes as change_column_bytes, criteria_column_bytes
+from .clusters import column_bytes as cluster_column_bytes, prop_column_bytes
 from .geometry import initial_densities_rk3d, voxel_domain, wall_contact_angles
 from .integrals import column_bytes, fresh
+from .morphology import column_bytes as morphology_column_bytes
 from .results import RecordGuard, ResultFile, find_result_file, read_planes
 from .rk3d import RK3DSlab, RK3DDistributed
+from . import runloop
+from .runloop import PeriodicTask
 
 PARAM_KEYS = ("AkR", "AkB", "beta", "tauR", "tauB", "SolidRhoR", "SolidRhoB", "velocityZR", "velocityZB",
               "densityRL", "densityBL", "relax", "inlet", "densityRH", "densityBH", "outlet")
 GROUPS = (("FluidMacro", "MacroData"), ("FluidPDF", "MicroData"), ("FluidVelocity", "MacroVelocity"))
+ANALYSES =("integrals", "clusters", "morphology", "mark_change", "change")
 
 
-class _CSFSlab:
-    """RK3DCSFSolver behind the calls this driver makes on a slab of the perturbation model"""
+class _SolverHandle:
+    """What a driver's run talks to, whichever solver the ini chose:
+      step(n), observe() (refreshes what a record or an analysis reads; nothing for CSF), the calls of ANALYSES,
+      slab   the calls of a slab of the perturbation model: set_density / set_macro / set_pdf, get, get_pdf, get_state / set_state, sync
+      sim    what the driver keeps as self.solver after the run;  solver: the CSF solver (contact angles, body force)
+      rank, z0 / nzl (this rank's planes), gather (a rank's planes -> the whole lattice's on the writing rank, None on the others),
+      suffix of the result file's name, whole_arrays (set_* take the undivided arrays and cut this rank's planes out themselves)"""
+    whole_arrays = False
 
-    def __init__(self, dom, par, device, bulk_epsilon=0.0, distributed=False, transport=None, tracers=None):
+    def _place(self, s, nz, distributed, gather_records):
+        self.rank, self.z0, self.nzl, self.gather, self.suffix = 0, 0, nz, (lambda a: a), ""
+        if distributed:
+            import torch.distributed as dist
+            self.rank, self.z0, self.nzl = dist.get_rank(), s.z0, s.nzl
+            if gather_records:
+                self.gather = s.gather
+            else:
+                self.suffix = "_rank%d" % self.rank          # every rank its own planes in its own file
+
+
+class _PerturbationSlab(_SolverHandle):
+    """RK3DSlab, or RK3DDistributed (one slab per rank), behind the handle's calls"""
+
+    def __init__(self, sim, nz, gather_records=True):
+        many = isinstance(sim, RK3DDistributed)
+        self.sim, self.slab, self.close = sim, (sim.slab if many else sim), sim.close
+        self._place(sim, nz, many, gather_records)
+        if many:
+            self.step, self.observe = sim.step, sim.observe
+            checked = lambda call: call
+        else:
+            # a single slab's diagnostics are stale after a step: an analysis that finds them so observes and asks again
+            observe = lambda: sim.phase_field(diagnostics=True)
+            self.step, self.observe = sim.step_single, observe
+            checked = lambda call: (lambda *a, **kw: fresh(lambda: call(*a, **kw), observe))
+        for name in ANALYSES:
+            setattr(self, name, checked(getattr(sim, name)))
+
+
+class _CSFSlab(_SolverHandle):
+    """RK3DCSFSolver (under torchrun RK3DCSFDistributed, one slab per rank) behind the handle's calls; it is its own `slab` and `sim`"""
+
+    def __init__(self, dom, par, device, bulk_epsilon=0.0, distributed=False, transport=None, tracers=None, gather_records=True):
         from .rk3dcsf import RK3DCSFSolver, RK3DCSFDistributed
         q = dict(sigma=par["sigma"], theta=par["theta"], wetting=par["wetting"], beta=par["beta"], delta=par["delta"], tauR=par["tauR"], tauB=par["tauB"],
                  tautype=par["tautype"], relax=par["relax"], inlet=par["inlet"], outlet=par["outlet"], velocityZR=par["velocityZR"],
@@ -102,8 +147,18 @@ class _CSFSlab:
         # part of the population message, which is sized before the transport connects
         more = {} if tracers is None else dict(tracers=tracers)
         self.solver = RK3DCSFDistributed(dom, q, device=device, transport=transport, **more) if distributed else RK3DCSFSolver(dom, q, device=device, **more)
-        self.step_single, self.sync, self.close = self.solver.step, self.solver.sync, self.solver.close
+        self.step = self.step_single = self.solver.step
+        self.sync, self.close = self.solver.sync, self.solver.close
         self.base_steps = 0          # the steps a restored checkpoint had behind it (set_pdf starts the solver's own counter again)
+        self.whole_arrays = bool(distributed)        # the slabs carry images of their neighbours' planes and cut them out of the undivided arrays
+        self._place(self.solver, np.shape(dom)[0], distributed, gather_records)
+        for name in ANALYSES:                        # (never stale: the CSF loop keeps what they read)
+            setattr(self, name, getattr(self.solver, name))
+
+    slab = sim = property(lambda self: self)
+
+    def observe(self):
+        pass
 
     num_fluid_nodes = property(lambda self: self.solver.num_fluid_nodes)
     dominant_kernel = property(lambda self: self.solver.dominant_kernel)
@@ -380,212 +435,119 @@ class RKColorGradient3D:
             out.write("FluidVelocity", "FluidVelocity" + ax, got[ax])
         return out.path
 
-    def runRKColorGradient3D(self, progress=None):
+    # ---- the pieces of a run (Transport3DRK runs on the same ones)
+    def _open_solver(self):
+        """the handle of the solver the ini chooses, on this process's share of the lattice"""
         p = self.par
-        self.initializeDomainBorder()
-        par = {k: p[k] for k in PARAM_KEYS}
-        name, rank = "SimulationResultsRK3D", 0
-        self._gather = lambda a: a
-        whole_arrays = False          # distributed 3-D CSF: the slabs carry images of their neighbours' planes and cut them out of the undivided arrays
         if p["tension_type"] == "CSF":
-            whole_arrays = self._distributed()
-            slab = sim = _CSFSlab(self.isDomain, p, self.device, self.csf_bulk_epsilon, distributed=whole_arrays, transport=self.csf_transport)
-            step, observe = slab.step_single, (lambda: None)
-            integrals = sim.solver.integrals
-            clusters = sim.solver.clusters
-            morphology = sim.solver.morphology
-            mark_change, change = sim.solver.mark_change, sim.solver.change
-            self.z0, self.nzl = 0, self.zDomain
-            if whole_arrays:
-                import torch.distributed as dist
-                rank = dist.get_rank()
-                self.z0, self.nzl = sim.solver.z0, sim.solver.nzl
-                if self.gather_records:
-                    self._gather = sim.solver.gather
-                else:
-                    name += "_rank%d" % rank
-        elif self._distributed():
-            import torch.distributed as dist
-            rank = dist.get_rank()
-            sim = RK3DDistributed(self.isDomain, par, device=self.device)
-            if getattr(self, "calibrate_partition", self.timeSteps >= 1000):
-                # long runs: one measured re-cut of the slabs (rk3d.RK3DDistributed.calibrated_plane_cost) from the plain initial
-                # state -- the rank that holds the colour interface otherwise runs ~10 % behind the others
-                rR, rB = initial_densities_rk3d(self.isDomain, min(self.nbuf, self.zDomain // 4), p["rho0R"], p["rho0B"])
-                sim.set_density(rR, rB)
-                cost = sim.calibrated_plane_cost(8)
-                sim.close()
-                sim = RK3DDistributed(self.isDomain, par, device=self.device, plane_cost=cost)
-            step, observe, slab = sim.step, sim.observe, sim.slab
-            integrals = sim.integrals
-            clusters = sim.clusters
-            morphology = sim.morphology
-            mark_change, change = sim.mark_change, sim.change
-            self.z0, self.nzl = sim.z0, sim.nzl
-            if self.gather_records:
-                self._gather = sim.gather
-            else:
-                name += "_rank%d" % rank
-        else:
-            slab = sim = RK3DSlab(self.isDomain, 0, self.zDomain, par, self.device)
-            step = slab.step_single
-            observe = lambda: slab.phase_field(diagnostics=True)
-            integrals = lambda: fresh(slab.integrals, observe)
-            clusters = lambda **kw: fresh(lambda: slab.clusters(**kw), observe)
-            morphology = lambda cut: fresh(lambda: slab.morphology(cut), observe)
-            mark_change, change = (lambda: fresh(slab.mark_change, observe)), (lambda: fresh(slab.change, observe))
-            self.z0, self.nzl = 0, self.zDomain
-        self._slab, self._observe = slab, observe
-        done = 0
-        z0, nzl = (0, self.zDomain) if whole_arrays else (self.z0, self.nzl)
+            return _CSFSlab(self.isDomain, p, self.device, self.csf_bulk_epsilon, distributed=self._distributed(), transport=self.csf_transport,
+                            gather_records=self.gather_records)
+        par = {k: p[k] for k in PARAM_KEYS}
+        if not self._distributed():
+            return _PerturbationSlab(RK3DSlab(self.isDomain, 0, self.zDomain, par, self.device), self.zDomain)
+        sim = RK3DDistributed(self.isDomain, par, device=self.device)
+        if getattr(self, "calibrate_partition", self.timeSteps >= 1000):
+            # long runs: one measured re-cut of the slabs (rk3d.RK3DDistributed.calibrated_plane_cost) from the plain initial
+            # state -- the rank that holds the colour interface otherwise runs ~10 % behind the others
+            rR, rB = initial_densities_rk3d(self.isDomain, min(self.nbuf, self.zDomain // 4), p["rho0R"], p["rho0B"])
+            sim.set_density(rR, rB)
+            cost = sim.calibrated_plane_cost(8)
+            sim.close()
+            sim = RK3DDistributed(self.isDomain, par, device=self.device, plane_cost=cost)
+        return _PerturbationSlab(sim, self.zDomain, self.gather_records)
+
+    def _start(self, h):
+        """the handle becomes this run's solver and takes the initial state or the checkpoint's; -> the steps behind it"""
+        self._slab, self._observe, self._gather, self.z0, self.nzl = h.slab, h.observe, h.gather, h.z0, h.nzl
+        z0, nzl = (0, self.zDomain) if h.whole_arrays else (h.z0, h.nzl)
         if self.restart_from:
-            done, self.records = self._load_checkpoint(slab, z0, nzl)
-        else:
-            self.initializeDomainCondition(z0, nzl)
-            self._upload_initial_state(slab)
-        writes = rank == 0 or not (self._distributed() and self.gather_records)
-        every = self.integrals_every
-        # (the table is gathered: the whole lattice's on rank 0, whether the records are gathered or not)
-        cevery = self.clusters_every
-        ckw = dict(props=True) if self.clusters_props else {}
-        mevery = self.morphology_every
-        severy = self.steady_every
-        more = ((("Integrals", "PlaneIntegrals"),) if every > 0 and rank == 0 else ()) + ((("Clusters", "PhaseClusters"),) if cevery > 0 and rank == 0 else ()) + \
-            ((("Morphology", "PhaseMorphology"),) if mevery > 0 and rank == 0 else ()) + ((("Steady", "SteadyState"),) if severy > 0 and rank == 0 else ()) + \
-            ((("Wettability", "ContactAngles"),) if self.contact_angle_solids is not None else ()) + \
+            done, self.records = self._load_checkpoint(h.slab, z0, nzl)
+            return done
+        self.initializeDomainCondition(z0, nzl)
+        self._upload_initial_state(h.slab)
+        return 0
+
+    def _integrals_task(self, h, **kw):
+        def report(step, t):
+            self._guard.integrals(step, None if t is None else t.nonfinite, None if t is None else t.summary())
+        return PeriodicTask(self, self.integrals_every, ("Integrals", "PlaneIntegrals"), h.rank == 0, h.integrals, "integrals", "integral_steps",
+                            report=report, closing=lambda: [("Columns", column_bytes())], **kw)
+
+    def _tasks(self, h):
+        """The periodic analyses of a run, in the order a stop visits them: the one place that names them.  Another analysis is a
+        constructor argument for its cadence and an entry here.  (Their tables are gathered: the whole lattice's on rank 0, whether the
+        records are gathered or not.)"""
+        def log(name):
+            def report(step, t):
+                if t is not None:
+                    self._guard.log.info("rk3d %s step %d: %s", name, step, " ".join("%s=%s" % kv for kv in t.summary().items()))
+            return report
+
+        def steady(step, t):
+            """true when the criterion is met -- rank 0's verdict, which every rank hears of here (one all-reduce of a flag) before
+            anybody issues the next step"""
+            met = False
+            if t is not None:
+                self.steady_criteria.append(t.criteria(step))
+                log("steady")(step, t)
+                met = self.steady_tol > 0 and t.is_steady(self.steady_tol, self.steady_phase_tol)
+            if self.steady_tol > 0 and self._guard.anyone(met):
+                if self.steady_step is None:
+                    self.steady_step = int(step)
+                return True
+            return False
+        self.steady_criteria, self.steady_step = [], None
+        here, ckw = h.rank == 0, (dict(props=True) if self.clusters_props else {})
+        return [
+            self._integrals_task(h),
+            PeriodicTask(self, self.clusters_every, ("Clusters", "PhaseClusters"), here, lambda: h.clusters(connectivity=self.clusters_connectivity, **ckw),
+                         "clusters", "cluster_steps", datasets=(("TableAtStep%d", "table"), ("PropsAtStep%d", "props")), report=log("clusters"),
+                         closing=lambda: [("Columns", cluster_column_bytes())] + ([("PropColumns", prop_column_bytes())] if self.clusters_props else [])),
+            PeriodicTask(self, self.morphology_every, ("Morphology", "PhaseMorphology"), here, lambda: h.morphology(self.morphology_phi_cut),
+                         "morphology", "morphology_steps", report=log("morphology"), closing=lambda: [("Columns", morphology_column_bytes())]),
+            # the steady-state monitor: only multiples of its cadence, the first visit marks, its verdict ends the run before that step's record
+            PeriodicTask(self, self.steady_every, ("Steady", "SteadyState"), here, h.change, "change", "steady_steps", report=steady, mark=h.mark_change,
+                         before_record=True, only_multiples=True,
+                         closing=lambda: [("Columns", change_column_bytes()),
+                                          ("Criteria", np.array(self.steady_criteria, dtype=np.float64).reshape(-1, len(CRITERIA_COLUMNS))),
+                                          ("CriteriaColumns", criteria_column_bytes())])]
+
+    def _open_flow_file(self, h, tasks, writes):
+        """SimulationResultsRK3D with the tasks' groups (None on a rank that writes none); contact angles and body force go into the solver
+        (after a restart_from too: a checkpoint holds neither) and, once, into the file"""
+        more = runloop.groups(tasks) + ((("Wettability", "ContactAngles"),) if self.contact_angle_solids is not None else ()) + \
             ((("BodyForce", "Acceleration"),) if self.body_force is not None else ())
-        out = ResultFile(self.output_dir, name, GROUPS + more) if writes else None
+        out = ResultFile(self.output_dir, "SimulationResultsRK3D" + h.suffix, GROUPS + more) if writes else None
+        runloop.attach(tasks, out)
         if self.contact_angle_solids is not None:
-            self._apply_contact_angles(sim.solver, out)          # (after a restart_from too: a checkpoint does not hold the map)
+            self._apply_contact_angles(h.solver, out)
         if self.body_force is not None:
-            self._apply_body_force(sim.solver, out)              # (likewise)
-        self.integral_steps, self.cluster_steps, self.morphology_steps = [], [], []
-        self.steady_steps, self.steady_criteria, self.steady_step = [], [], None
-        marked = False
-
-        def steady_visit():
-            """the monitor's visit at `done`: the first one marks, the others take the table and mark again; True: the criterion is met"""
-            nonlocal marked
-            if not marked:
-                mark_change()
-                marked = True
-                return False
-            return self._steady(change(), out, done)
+            self._apply_body_force(h.solver, out)
         self.result_path = out.path if out else None
+        return out
+
+    def _synced_checkpoint(self):
+        self._slab.sync()
+        self.checkpoint_path = self.checkpoint()
+
+    def runRKColorGradient3D(self, progress=None):
+        self.initializeDomainBorder()
+        h = self._open_solver()
+        done = self._start(h)
+        tasks = self._tasks(h)
+        out = self._open_flow_file(h, tasks, h.rank == 0 or not (self._distributed() and self.gather_records))
         # distributed: every rank checks its own slab, the verdict is collective (all ranks raise together, none is left in an exchange)
-        self._guard = RecordGuard("rk3d", slab.num_fluid_nodes, getattr(self, "nan_guard", "raise"), collective=self._distributed(), device=self.device)
-        while done < self.timeSteps:
+        self._guard = RecordGuard("rk3d", h.slab.num_fluid_nodes, getattr(self, "nan_guard", "raise"), collective=self._distributed(), device=self.device)
+
+        def record(done, tail):
+            h.observe()
             self._step_now = done
-            if severy > 0 and done % severy == 0 and steady_visit() and self.steady_tol > 0:
-                break                              # (before this step's record: the tail below takes it, as at the end of a run of `done` steps)
-            if done % self.timeInterval == 0:      # (a restarted run records its first step again: the counters of the checkpoint precede it)
-                observe()
-                self._record(slab, out)
-            if every > 0 and done % every == 0:
-                self._integrals(integrals(), out, done)
-            if cevery > 0 and done % cevery == 0:
-                self._clusters(clusters(connectivity=self.clusters_connectivity, **ckw), out, done)
-            if mevery > 0 and done % mevery == 0:
-                self._morphology(morphology(self.morphology_phi_cut), out, done)
-            n = min(self.timeInterval - done % self.timeInterval, self.timeSteps - done)
-            if every > 0:
-                n = min(n, every - done % every)
-            if cevery > 0:
-                n = min(n, cevery - done % cevery)
-            if mevery > 0:
-                n = min(n, mevery - done % mevery)
-            if severy > 0:
-                n = min(n, severy - done % severy)
-            if self.checkpoint_every > 0:
-                n = min(n, self.checkpoint_every - done % self.checkpoint_every)
-            step(n)
-            done += n
-            if self.checkpoint_every > 0 and done % self.checkpoint_every == 0 and done < self.timeSteps:
-                slab.sync()
-                self.checkpoint_path = self.checkpoint()
-            if progress:
-                progress(done)
-        observe()
-        self._step_now = done
-        self._record(slab, out)
-        if every > 0:
-            self._integrals(integrals(), out, done)
-            if rank == 0:
-                out.write("Integrals", "Steps", np.array(self.integral_steps, dtype=np.int64))
-                out.write("Integrals", "Columns", column_bytes())
-        if cevery > 0:
-            self._clusters(clusters(connectivity=self.clusters_connectivity, **ckw), out, done)
-            if rank == 0:
-                from .clusters import column_bytes as cluster_column_bytes
-                out.write("Clusters", "Steps", np.array(self.cluster_steps, dtype=np.int64))
-                out.write("Clusters", "Columns", cluster_column_bytes())
-                if self.clusters_props:
-                    from .clusters import prop_column_bytes
-                    out.write("Clusters", "PropColumns", prop_column_bytes())
-        if mevery > 0:
-            self._morphology(morphology(self.morphology_phi_cut), out, done)
-            if rank == 0:
-                from .morphology import column_bytes as morphology_column_bytes
-                out.write("Morphology", "Steps", np.array(self.morphology_steps, dtype=np.int64))
-                out.write("Morphology", "Columns", morphology_column_bytes())
-        if severy > 0:
-            if done % severy == 0 and (not self.steady_steps or self.steady_steps[-1] != done):
-                steady_visit()                   # the run's last step is a multiple
-            if rank == 0:
-                from .change import CRITERIA_COLUMNS, column_bytes as change_column_bytes, criteria_column_bytes
-                out.write("Steady", "Steps", np.array(self.steady_steps, dtype=np.int64))
-                out.write("Steady", "Columns", change_column_bytes())
-                out.write("Steady", "Criteria", np.array(self.steady_criteria, dtype=np.float64).reshape(-1, len(CRITERIA_COLUMNS)))
-                out.write("Steady", "CriteriaColumns", criteria_column_bytes())
-        slab.sync()
-        self.solver = sim
+            self._record(h.slab, out)
+            return done
+        runloop.run(tasks, done, self.timeSteps, self.timeInterval, self.checkpoint_every, record, h.step, self._synced_checkpoint, progress)
+        h.slab.sync()
+        self.solver = h.sim
         return self.result_path
-
-    def _integrals(self, t, out, step):
-        """t: the Integrals of the whole lattice at `step` (None on the other ranks of a distributed run)"""
-        self.integrals = t
-        self.integral_steps.append(int(step))
-        if t is not None and out is not None:
-            out.write("Integrals", "PlanesAtStep%d" % step, t.planes)
-        self._guard.integrals(step, None if t is None else t.nonfinite, None if t is None else t.summary())
-
-    def _clusters(self, t, out, step):
-        """t: the Clusters of the whole lattice at `step` (None on the other ranks of a distributed run)"""
-        self.clusters = t
-        self.cluster_steps.append(int(step))
-        if t is not None:
-            if out is not None:
-                out.write("Clusters", "TableAtStep%d" % step, t.table)
-                if t.props is not None:
-                    out.write("Clusters", "PropsAtStep%d" % step, t.props)
-            self._guard.log.info("rk3d clusters step %d: %s", step, " ".join("%s=%s" % kv for kv in t.summary().items()))
-
-    def _morphology(self, t, out, step):
-        """t: the Morphology of the whole lattice at `step` (None on the other ranks of a distributed run)"""
-        self.morphology = t
-        self.morphology_steps.append(int(step))
-        if t is not None:
-            if out is not None:
-                out.write("Morphology", "PlanesAtStep%d" % step, t.planes)
-            self._guard.log.info("rk3d morphology step %d: %s", step, " ".join("%s=%s" % kv for kv in t.summary().items()))
-
-    def _steady(self, t, out, step):
-        """t: the Change of the whole lattice at `step` (None on the other ranks of a distributed run); True when the criterion is met --
-        rank 0's verdict, which every rank hears of here (one all-reduce of a flag) before anybody issues the next step"""
-        self.change = t
-        self.steady_steps.append(int(step))
-        met = False
-        if t is not None:
-            self.steady_criteria.append(t.criteria(step))
-            if out is not None:
-                out.write("Steady", "PlanesAtStep%d" % step, t.planes)
-            self._guard.log.info("rk3d steady step %d: %s", step, " ".join("%s=%s" % kv for kv in t.summary().items()))
-            met = self.steady_tol > 0 and t.is_steady(self.steady_tol, self.steady_phase_tol)
-        if self.steady_tol > 0 and self._guard.anyone(met):
-            if self.steady_step is None:
-                self.steady_step = int(step)
-            return True
-        return False
 
     def _record(self, slab, out):
         k = self.records

@@ -27,14 +27,16 @@ driver writes them, the tracers' (integrals.TracerIntegrals: cells, mass, flux_x
 and tracer -- mass balances, the breakthrough -flux_z at the outlet, the plume's moments along z) to /TracerIntegrals/PlanesAtStep<step>
 [nz][nT][9], /TracerIntegrals/Steps and /TracerIntegrals/Columns of ConcentrationResults.h5.  Both counts of non-finite cells meet the
 nan_guard rule at that cadence (collective under torchrun; rank 0 writes), masses and extrema go to the log.  N = 0 writes no group and
-adds no stop; the records and checkpoints of a run do not depend on N.
+adds no stop; the records and checkpoints of a run do not depend on N.  The flow driver's other cadences (clusters_every,
+morphology_every, steady_every) are accepted by the constructor and not acted on: this driver runs the two integrals tasks only.
 """
 import numpy as np
 
-from . import config
-from .RKColorGradientD3Q19 import GROUPS, RKColorGradient3D, _CSFSlab
-from .integrals import column_bytes, tracer_column_bytes
+from . import config, runloop
+from .RKColorGradientD3Q19 import RKColorGradient3D, _CSFSlab
+from .integrals import tracer_column_bytes
 from .results import RecordGuard, ResultFile
+from .runloop import PeriodicTask
 
 
 class _CSFTracerSlab(_CSFSlab):
@@ -47,6 +49,7 @@ class _CSFTracerSlab(_CSFSlab):
                        inlet_concentration=tuple(t["inlet_conc"]), dirichlet_inlet=t["inlet_type"] == "Dirichlet",
                        free_outlet=t["outlet_type"] == "Freeflow", reaction_rate=t["reaction_rate"], diffusion_j=tuple(t["diffJ3"]))
         _CSFSlab.__init__(self, dom, par, device, bulk_epsilon, distributed=distributed, transport=transport, tracers=tracers)
+        self.tracer_integrals = self.solver.tracer_integrals
 
     def get_state(self):
         st, info = _CSFSlab.get_state(self)
@@ -87,101 +90,61 @@ class Transport3DRK(RKColorGradient3D):
                 conc[0, fluid & (planes <= nz - self.nbuf)] = 1.0
         self.tracerConc = conc
 
+    def _open_solver(self):
+        # distributed: one slab per rank; set_* take the undivided arrays, get* return the rank's own planes, rank 0 writes what it gathers
+        return _CSFTracerSlab(self.isDomain, self.par, self.tr, self.device, self.csf_bulk_epsilon, distributed=self._distributed(), transport=self.csf_transport)
+
+    def _start(self, h):
+        done = RKColorGradient3D._start(self, h)
+        if not self.restart_from:
+            self.initializeTransportDomain()
+            for k in range(self.numTracers):
+                h.solver.set_concentration(k, self.tracerConc[k])
+        return done
+
+    def _tasks(self, h):
+        """Both tables at one cadence, looked at before a stop's record (which steps): the flow's as the flow's driver writes them,
+        the tracers' into ConcentrationResults and past the tracers' guard.  clusters_every, morphology_every and steady_every are not
+        among them."""
+        def report(step, t):
+            self._tracer_guard.integrals(step, None if t is None else t.nonfinite, None if t is None else t.summary())
+        return [self._integrals_task(h, before_record=True),
+                PeriodicTask(self, self.integrals_every, ("TracerIntegrals", "PlaneIntegrals"), h.rank == 0, h.tracer_integrals, "tracer_integrals", file="conc",
+                             report=report, closing=lambda: [("Columns", tracer_column_bytes())], before_record=True, joined=True)]
+
     def runTransport3DMPMCRK(self, progress=None):
-        p, t = self.par, self.tr
-        if p["tension_type"] != "CSF":
+        if self.par["tension_type"] != "CSF":
             raise config.ConfigError("the tracers are coupled to the CSF colour-gradient flow: [SurfaceTension] SurfaceTensionType = 'CSF'")
         self.initializeDomainBorder()
-        # distributed: one slab per rank; set_* take the undivided arrays, get* return the rank's own planes, rank 0 writes what it gathers
-        shared = self._distributed()
-        slab = _CSFTracerSlab(self.isDomain, p, t, self.device, self.csf_bulk_epsilon, distributed=shared, transport=self.csf_transport)
-        self._slab, self._observe, self._gather = slab, (lambda: None), (lambda a: a)
-        self.z0, self.nzl = 0, self.zDomain
-        rank = 0
-        if shared:
-            import torch.distributed as dist
-            rank = dist.get_rank()
-            self.z0, self.nzl = slab.solver.z0, slab.solver.nzl
-            self._gather = slab.solver.gather
-        n, done = self.numTracers, 0
-        if self.restart_from:
-            done, self.records = self._load_checkpoint(slab, 0, self.zDomain)
-        else:
-            self.initializeDomainCondition(0, self.zDomain)
-            self._upload_initial_state(slab)
-            self.initializeTransportDomain()
-            for k in range(n):
-                slab.solver.set_concentration(k, self.tracerConc[k])
-        every = self.integrals_every
-        more = lambda group: ((group, "PlaneIntegrals"),) if every > 0 else ()
-        wett = (("Wettability", "ContactAngles"),) if self.contact_angle_solids is not None else ()
-        force = (("BodyForce", "Acceleration"),) if self.body_force is not None else ()
-        flow = ResultFile(self.output_dir, "SimulationResultsRK3D", GROUPS + more("Integrals") + wett + force) if rank == 0 else None
-        if self.contact_angle_solids is not None:
-            self._apply_contact_angles(slab.solver, flow)        # mixed wettability, as in the flow's driver (after a restart_from too)
-        if self.body_force is not None:
-            self._apply_body_force(slab.solver, flow)            # likewise
-        conc = ResultFile(self.output_dir, "ConcentrationResults", (("TransportMacro", "MacroData"),) + more("TracerIntegrals")) if rank == 0 else None
-        self.integral_steps = []
-        self.result_path, self.concentration_path = (flow.path, conc.path) if rank == 0 else (None, None)
+        h = self._open_solver()
+        done = self._start(h)
+        tasks = self._tasks(h)
+        flow = self._open_flow_file(h, tasks, h.rank == 0)
+        conc = ResultFile(self.output_dir, "ConcentrationResults", (("TransportMacro", "MacroData"),) + runloop.groups(tasks, "conc")) if h.rank == 0 else None
+        runloop.attach(tasks, conc, "conc")
+        self.concentration_path = conc.path if conc else None
         # distributed: every rank checks its own planes, the verdict is collective (all ranks raise together, none is left in an exchange)
-        self._guard = RecordGuard("rk3d+tracers", slab.num_fluid_nodes, getattr(self, "nan_guard", "raise"), collective=shared, device=self.device)
-        tracer_guard = RecordGuard("tracers", slab.num_fluid_nodes, getattr(self, "nan_guard", "raise"), collective=shared, device=self.device)
+        guard = dict(nan_guard=getattr(self, "nan_guard", "raise"), collective=self._distributed(), device=self.device)
+        self._guard = RecordGuard("rk3d+tracers", h.num_fluid_nodes, **guard)
+        self._tracer_guard = RecordGuard("tracers", h.num_fluid_nodes, **guard)
+        n = self.numTracers
 
-        def record_tracers(k, step):
-            self.tracerConc = np.array([slab.solver.get_concentration(i) for i in range(n)])      # (distributed: this rank's planes)
+        def record(done, tail):
+            """the flow at the start of step done + 1 and the concentrations after the tracer update of that step, under one record
+            number; in the tail: both as they stand"""
+            self._step_now, k = done, self.records
+            self._record(h, flow)
+            if not tail:
+                h.step(1)
+                done += 1
+            self.tracerConc = np.array([h.solver.get_concentration(i) for i in range(n)])      # (distributed: this rank's planes)
             for i in range(n):
                 whole = self._gather(self.tracerConc[i])
                 if conc is not None and whole is not None:
                     conc.write("TransportMacro", "TracerConcType%gin%g" % (i, k), whole)
-            tracer_guard(k, step, {"tracer%d" % i: self.tracerConc[i] for i in range(n)}, {"tracer%d" % i: float(self.tracerConc[i].sum()) for i in range(n)})
-
-        def maybe_checkpoint():
-            if self.checkpoint_every > 0 and done % self.checkpoint_every == 0 and done < self.timeSteps:
-                slab.sync()
-                self.checkpoint_path = self.checkpoint()
-
-        def maybe_integrals(last=False):
-            """both tables of the state after `done` steps (collective: rank 0 holds the whole lattice's and writes)"""
-            if every <= 0 or (done % every and not last) or (self.integral_steps and self.integral_steps[-1] == done):
-                return
-            self._integrals(slab.solver.integrals(), flow, done)
-            t = self.tracer_integrals = slab.solver.tracer_integrals()
-            if t is not None and conc is not None:
-                conc.write("TracerIntegrals", "PlanesAtStep%d" % done, t.planes)
-            tracer_guard.integrals(done, None if t is None else t.nonfinite, None if t is None else t.summary())
-
-        while done < self.timeSteps:
-            self._step_now = done
-            maybe_integrals()
-            if done % self.timeInterval == 0:
-                k = self.records
-                self._record(slab, flow)                # the flow at the start of step done + 1
-                slab.step_single(1)
-                done += 1
-                record_tracers(k, done)                 # the concentrations after the tracer update of that step
-                maybe_checkpoint()
-                maybe_integrals()
-            m = min(self.timeInterval - done % self.timeInterval, self.timeSteps - done) if done % self.timeInterval else 0
-            if self.checkpoint_every > 0 and m:
-                m = min(m, self.checkpoint_every - done % self.checkpoint_every)
-            if every > 0 and m:
-                m = min(m, every - done % every)
-            if m:
-                slab.step_single(m)
-                done += m
-                maybe_checkpoint()
-            if progress:
-                progress(done)
-        self._step_now = done
-        k = self.records
-        self._record(slab, flow)
-        record_tracers(k, done)
-        maybe_integrals(last=True)
-        if every > 0 and rank == 0:
-            steps = np.array(self.integral_steps, dtype=np.int64)
-            flow.write("Integrals", "Steps", steps); flow.write("Integrals", "Columns", column_bytes())
-            conc.write("TracerIntegrals", "Steps", steps); conc.write("TracerIntegrals", "Columns", tracer_column_bytes())
-        slab.sync()
-        self.solver = slab
+            self._tracer_guard(k, done, {"tracer%d" % i: self.tracerConc[i] for i in range(n)}, {"tracer%d" % i: float(self.tracerConc[i].sum()) for i in range(n)})
+            return done
+        runloop.run(tasks, done, self.timeSteps, self.timeInterval, self.checkpoint_every, record, h.step, self._synced_checkpoint, progress)
+        h.sync()
+        self.solver = h
         return self.result_path, self.concentration_path
