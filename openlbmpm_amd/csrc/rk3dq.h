@@ -444,7 +444,7 @@ __global__ __launch_bounds__(512, 1) void rk3dq_fused(RK3Dev p, int tilesX, int 
     const int zl_gb = 1 - p.z0, zl_gt = p.nzg - p.z0;          // local index of the ghost planes z = 0 and z = nz-1 (when owned)
     auto is_ghost = [&](int zl) { return zl == zl_gb || zl == zl_gt; };
     // one record per lane (72 lanes) + the row flags that ride in its spare words: .z this segment's, .w (centre record) the three
-    // segments' combined.  fetch_rows only LOADS (its results are consumed a march step later, no wait in between); put_rows combines
+    // segments' combined, .w (left record) those of the rows y - 1 .. y + 1 combined (combine_rows).  fetch_rows only LOADS (its results are consumed a march step later, no wait in between); put_rows combines
     struct RowRec { u32x4 v; unsigned f0, f1, f2; };
     auto fetch_rows = [&](int zl) -> RowRec {
         RowRec q;
@@ -472,6 +472,15 @@ __global__ __launch_bounds__(512, 1) void rk3dq_fused(RK3Dev p, int tilesX, int 
             u32x4 v = q.v;
             if (tid & 1) { v.z = q.f0; v.w = q.f0 & q.f1 & q.f2; }       // k = tid % 6 is odd exactly when tid is
             const_cast<u32x4 &>(srow[zl & (TR::SLOTS - 1)][tid / 6][tid % 6]) = v;
+        }
+    };
+    // ... and one step later, when the barrier has made them visible, the three segments' combined flags of the rows y - 1 .. y + 1 are
+    // combined once more, into the spare word .w of the left segment's second record: purity() then reads one word per plane
+    auto combine_rows = [&](int zl) {
+        if (wave == 0 && tid < TR::ROWS) {
+            auto *pl = srow[zl & (TR::SLOTS - 1)];
+            const unsigned c = pl[tid > 0 ? tid - 1 : 0][3].w & pl[tid][3].w & pl[tid < TR::ROWS - 1 ? tid + 1 : tid][3].w;
+            const_cast<u32x4 &>(pl[tid][1]).w = c;
         }
     };
     auto row_flag = [&](int zl, int lrow, int k) -> unsigned { return srow[zl & (TR::SLOTS - 1)][lrow][2 * k + 1].z; };   // segment k = 0, 1, 2
@@ -524,10 +533,17 @@ __global__ __launch_bounds__(512, 1) void rk3dq_fused(RK3Dev p, int tilesX, int 
         }
     };
     // colour of everything the cells of the tile rows row_lo .. row_hi of plane zp pull from: 1 red, 2 blue, 0 mixed
-    auto purity = [&](int zp, int row_lo, int row_hi) -> int {
+    // (purity: around one tile row; purity_tile: around the rows -1 .. TY, i.e. of the staged rows 0 .. 11 = the rows around 1, 4, 7, 10)
+    auto purity = [&](int zp, int row) -> int {
+        unsigned c = 3u;
+        for (int dz = -1; dz <= 1; ++dz) c &= srow[(zp + dz) & (TR::SLOTS - 1)][row + 2][1].w;
+        return __builtin_amdgcn_readfirstlane((int)c);
+    };
+    auto purity_tile = [&](int zp) -> int {
+        static_assert(TR::ROWS == 12, "the staged rows in four groups of three");
         unsigned c = 3u;
         for (int dz = -1; dz <= 1; ++dz)
-            for (int rr = row_lo - 1; rr <= row_hi + 1; ++rr) c &= srow[(zp + dz) & (TR::SLOTS - 1)][rr + 2][3].w;
+            for (int lrow = 1; lrow < TR::ROWS; lrow += 3) c &= srow[(zp + dz) & (TR::SLOTS - 1)][lrow][1].w;
         return __builtin_amdgcn_readfirstlane((int)c);
     };
     auto lds_scal = [&](int zp, int row, int col) {       // accessor for the node at tile coordinates (col, row) pulled around plane zp
@@ -548,6 +564,7 @@ __global__ __launch_bounds__(512, 1) void rk3dq_fused(RK3Dev p, int tilesX, int 
     }
     RowRec staged = fetch_rows(za + 3);
     __syncthreads();
+    for (int k = 0; k < 5; ++k) combine_rows(za - 3 + k);      // (plane za + 2: the first march step)
     {
         SRec e0[3], e1[3];
 #pragma unroll
@@ -621,10 +638,17 @@ __global__ __launch_bounds__(512, 1) void rk3dq_fused(RK3Dev p, int tilesX, int 
         // s_waitcnt vmcnt(0) in front of its use drains the pulls in flight (the collision then overlaps nothing)
         const unsigned long long pz0 = pstart_of(p, z > 0 ? z : 0), pz1 = pstart_of(p, z > 0 ? z + 1 : 1);
         put_rows(z + 5, staged);
+        combine_rows(z + 4);
         SRec e0, e1;
         fetch_s(z + 3, e0, e1);                 // in LDS before this step's barrier, read from the next step on
         const bool halo_n = zn <= p.halo_lo || zn >= p.nzl + 1, ghost_n = !halo_n && is_ghost(zn);
         const bool fill_gb = !halo_n && !ghost_n && zn - 1 == zl_gb && zn - 1 >= 1;     // the bottom ghost's phase field = this plane's
+        // plane z + 1 carries no boundary rule of its own (scalar): not a halo, ghost or fill_gb plane, not a Zou-He plane -- source_plane(zn)
+        // = zn off the ghost planes, and the convective outlet's planes are halo planes here (halo_lo).  Where, on such a plane, everything
+        // a wave's cells pull from is of one colour as well (purity), the wave is STEADY: rho_R = rho or 0 and phi = +-1 are constants of the
+        // colour -- bit for bit what bc_q and phi_q return there (k + a = t + 0, x / x = 1) -- and nothing may rewrite a pulled population
+        const int zsg_n = p.z0 + zn - 1;
+        const bool plain_n = !halo_n && !ghost_n && !fill_gb && zsg_n != 1 && zsg_n != p.nzg - 2;
         // ---- plane z + 1, rim cells: phase field only
         if (wave < 3) {
             if (has_rim) {
@@ -635,14 +659,17 @@ __global__ __launch_bounds__(512, 1) void rk3dq_fused(RK3Dev p, int tilesX, int 
                     double g[Q], a, c;
                     unsigned j;
                     Sums S;
-                    const int pc = wave < 2 ? purity(zn, hly - 1, hly - 1) : purity(zn, -1, TY);
+                    const int pc = wave < 2 ? purity(zn, hly - 1) : purity_tile(zn);
                     const unsigned hb = RAGGED ? (hlx == 0 ? (unsigned)(twl - 1) : 0u) : (unsigned)(hx & 63);      // a rim column's bit in its segment
                     const bool fl = wave < 2 ? bit_of<true>(rows_rimrow(zn, 0).m, (unsigned)lx) : bit_of<false>(rows_rimcol(zn, 0).m, hb);
-                    if (pc != 0) {          // single colour around: phi = +-1 (or the planes' boundary values) without a pull
+                    if (pc != 0) {          // single colour around: no pull
                         if (fl) {
-                            S.t0 = 1.; S.tp = S.tm = 0.; S.k0 = (pc & 1) ? 1. : 0.; S.kp = S.km = S.a0 = S.ap = S.am = 0.;
-                            bc_q<false, PIN ? 1 : 0>(p, zn, S, nullptr, a, c);
-                            ph = phi_q(a, c);
+                            if (plain_n) ph = (pc & 1) ? 1. : -1.;       // steady: from the mask bit and the combined flag alone
+                            else {                                       // the boundary planes' values
+                                S.t0 = 1.; S.tp = S.tm = 0.; S.k0 = (pc & 1) ? 1. : 0.; S.kp = S.km = S.a0 = S.ap = S.am = 0.;
+                                bc_q<false, PIN ? 1 : 0>(p, zn, S, nullptr, a, c);
+                                ph = phi_q(a, c);
+                            }
                         }
                     } else if (wave < 2) {
                         if (fl) {
@@ -675,14 +702,28 @@ __global__ __launch_bounds__(512, 1) void rk3dq_fused(RK3Dev p, int tilesX, int 
             double rRn = 1., rhon = 2., ph = p.solidPhi;
             if (halo_n) { if (has_own) ph = (p.phi + (size_t)zn * p.plane2)[(size_t)yo * p.pitch + x]; }
             else if (ghost_n) { if (has_own && zn == zl_gt) ph = sphi[z & (M::RING - 1)][ly + 1][lx + 1]; }
-            else if (fl_raw) {
-                Sums S;
-                const int pc = purity(zn, ly, ly);
+            else {
+                const int pc = purity(zn, ly);             // (a wave = a tile row: the same for every lane)
                 mixed_n = pc == 0;
-                if (pc != 0) class_sums_pure(raw, (pc & 1) != 0, S);
-                else class_sums<FIRST, true>(p, rows_own, lds_scal(zn, ly, lx), zn, (unsigned)lx, raw, S);
-                bc_q<true, PIN ? 1 : 0>(p, zn, S, raw, rRn, rhon);
-                ph = phi_q(rRn, rhon);
+                if (pc != 0 && plain_n) {                  // steady: straight line, every lane (only a fluid lane's densities are ever used)
+                    Sums S;
+                    const bool red = (pc & 1) != 0;
+                    class_sums_pure(raw, red, S);
+                    rhon = (S.t0 + S.tp) + S.tm;
+                    rRn = red ? rhon : 0.;
+                    if (fl_raw) ph = red ? 1. : -1.;
+                } else if (fl_raw) {
+                    Sums S;
+                    if (pc != 0) class_sums_pure(raw, (pc & 1) != 0, S);
+                    else class_sums<FIRST, true>(p, rows_own, lds_scal(zn, ly, lx), zn, (unsigned)lx, raw, S);
+                    // the Zou-He closures -- the only writers of a pulled population -- behind a scalar branch of their own
+                    if (!plain_n) bc_q<true, PIN ? 1 : 0>(p, zn, S, raw, rRn, rhon);
+                    else {                                 // bc_q away from the Zou-He planes
+                        rRn = ((S.k0 + S.a0) + (S.kp + S.ap)) + (S.km + S.am);
+                        rhon = (S.t0 + S.tp) + S.tm;
+                    }
+                    ph = phi_q(rRn, rhon);
+                }
             }
             if (has_own) {
                 sphi[zn & (M::RING - 1)][ly + 1][lx + 1] = ph;
