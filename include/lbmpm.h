@@ -73,11 +73,13 @@ int lbmpm_hbm_stream_test(int device, int64_t bytes_per_buffer, int reps, double
 
 enum { LBMPM_RELAX_SRT = 0, LBMPM_RELAX_MRT = 1 };
 enum { LBMPM_INLET_VELOCITY = 0,      /* BoundaryTypeInlet 'Neumann'   */
-       LBMPM_INLET_PRESSURE = 1 };    /* BoundaryTypeInlet 'Dirichlet' */
+       LBMPM_INLET_PRESSURE = 1,      /* BoundaryTypeInlet 'Dirichlet' */
+       LBMPM_INLET_PERIODIC = 2 };    /* rk3dcsf only, together with LBMPM_OUTLET_NONE: BoundaryTypeInlet 'Periodic' -- periodic z */
 enum { LBMPM_OUTLET_PRESSURE = 0,     /* BoundaryTypeOutlet 'Dirichlet'  */
        LBMPM_OUTLET_CONVECTIVE = 1,   /* BoundaryTypeOutlet 'Convective' */
-       LBMPM_OUTLET_NONE = 2,         /* sc2d only: no boundary kernels at all, inlet included: fully periodic box
-                                         (the static-droplet Laplace case of the reference's CPU path SimpleD2Q9) */
+       LBMPM_OUTLET_NONE = 2,         /* sc2d: no boundary kernels at all, inlet included: fully periodic box
+                                         (the static-droplet Laplace case of the reference's CPU path SimpleD2Q9);
+                                         rk3dcsf, together with LBMPM_INLET_PERIODIC: BoundaryTypeOutlet 'Periodic' -- periodic z */
        LBMPM_OUTLET_FREEFLOW = 3 };   /* sc2d, explicit forcing, SRT (any ExplicitScheme): BoundaryTypeOutlet 'Freeflow'
                                          (ShanChenD2Q9.py:1865-1884, ExplicitD2Q9GPU.py:1476-1563): before every collision
                                          rows 2, 1, 0 take f-bar, F_i and f_eq of the row above, i.e. they leave the
@@ -688,9 +690,22 @@ int64_t lbmpm_rk3d_device_bytes(const lbmpm_rk3d *ctx);
  * slabs' messages stay the CSF force alone; LBMPM_RK3DCSF_V* / _REC_V*, the integrals, lbmpm_rk3dcsf_change, the cluster properties and
  * the tracers' flow all carry the u above.  The force is not a configuration field: a context without one runs the kernels it always ran,
  * and the bulk path (`variant` 0) stays bit-equal to the full path with one (tests/test_rk3d_csf_body_force_gpu.py).
+ * Periodic z (force-driven flow without open planes): inlet_type LBMPM_INLET_PERIODIC together with outlet_type LBMPM_OUTLET_NONE; one
+ * without the other is LBMPM_ERR_INVALID.  All nz planes are then ordinary planes that wrap like x and y: no plane copies another, no
+ * Zou-He or convective rule runs, inlet_velocity_z, inlet_rho_* and outlet_rho_total are not read, the mask need not repeat itself at the
+ * ends, and nz >= 4 is enough (an undivided lattice; smaller ones would meet themselves inside the two-cell reach of the wetting walls).
+ * The REC_* fields, lbmpm_rk3dcsf_integrals, _change, _clusters, _cluster_props and _morphology read the pulled state with no plane rule.
+ * Colour mass is conserved to rounding and a body force along z is the only drive -- the relative-permeability set-up.  Slabs stay as they
+ * are (ghost_lo = ghost_hi = 2, slab_z0, global_nz, >= 4 own planes; the ring's seam is one more face between two slabs), and so do the
+ * messages, the transports and the watchdog.  The bulk path runs across the seam: a block's stretch of the lattice order is an arc of the
+ * ring there (tests/test_rk3d_csf_periodic_gpu.py: a lattice rolled along z gives the rolled fields bit for bit and the same bulk count).
+ * The tracers' dirichlet_inlet and free_outlet name planes that are not special any more: lbmpm_rk3dcsf_tracer_configure / _configure_slab
+ * refuse them (LBMPM_ERR_INVALID); with both 0 the tracers are periodic in z as they always were.  The analyses keep their documented z
+ * behaviour whatever the flow does: clusters, cluster properties and morphology do NOT wrap z -- a ganglion that sits across the seam counts
+ * as two, touching the first and the last plane.
  * ---------------------------------------------------------------------------------- */
 typedef struct lbmpm_rk3dcsf_config {
-    int64_t nx, ny, nz;        /* xDomain, yDomain, zDomain (incl. the ghost planes 0 and nz-1); nz >= 8 */
+    int64_t nx, ny, nz;        /* xDomain, yDomain, zDomain (incl. the ghost planes 0 and nz-1); nz >= 8 (periodic z: nz >= 4) */
     double surface_tension;    /* [SurfaceTension] SurfaceTensionValue                      */
     double contact_angle_deg;  /* [SurfaceTension] ContactAngle (measured through the blue fluid with rule 2; at exactly 0 or 180 the rule's two
                                 * candidates coincide and its choice -- AcceleratedRKGPU2D.py:2488-2492 -- is decided by rounding, as in the reference) */
@@ -702,8 +717,8 @@ typedef struct lbmpm_rk3dcsf_config {
     int32_t wetting_type;      /* 2 (Akai 2018) | 0: no correction of the gradient at walls */
     int32_t tau_type;          /* [FluidParameters] TauType 1 | 2                           */
     int32_t relaxation;        /* LBMPM_RELAX_*                                             */
-    int32_t inlet_type;        /* LBMPM_INLET_VELOCITY | LBMPM_INLET_PRESSURE               */
-    int32_t outlet_type;       /* LBMPM_OUTLET_PRESSURE | LBMPM_OUTLET_CONVECTIVE           */
+    int32_t inlet_type;        /* LBMPM_INLET_VELOCITY | LBMPM_INLET_PRESSURE | LBMPM_INLET_PERIODIC (with LBMPM_OUTLET_NONE: periodic z) */
+    int32_t outlet_type;       /* LBMPM_OUTLET_PRESSURE | LBMPM_OUTLET_CONVECTIVE | LBMPM_OUTLET_NONE (with LBMPM_INLET_PERIODIC) */
     int32_t device;
     int32_t variant;           /* 0: blocks of 256 fluid cells deep inside one colour skip the phase-field pull, the gradient and the curvature
                                 * (exact: phi = +-1, G = n = K = F = 0 there, bit for bit); 1: every cell takes the full path (cross-check) */
@@ -720,7 +735,8 @@ typedef struct lbmpm_rk3dcsf_config {
                                 * other plane (cut from the undivided lattice).  The slabs form a RING: the loop wraps z like x and y (the walls of
                                 * the ghost plane 0 average phi over the plane nz-1), so the first slab's low face is the last slab's high face */
     int64_t slab_z0, global_nz; /* a slab: its first own plane (this context's plane 2) and the number of planes of the undivided lattice; the open
-                                * planes are the undivided lattice's 0, 1 (0 .. 3 convective) and nz-2, nz-1; >= 4 own planes per slab */
+                                * planes are the undivided lattice's 0, 1 (0 .. 3 convective) and nz-2, nz-1, which lie in one slab each (periodic z:
+                                * there are none, a cut may fall anywhere); >= 4 own planes per slab */
 } lbmpm_rk3dcsf_config;
 
 typedef struct lbmpm_rk3dcsf lbmpm_rk3dcsf;
@@ -745,7 +761,7 @@ typedef enum lbmpm_rk3dcsf_field {
 } lbmpm_rk3dcsf_field;
 
 /* is_domain: host [nz][ny][nx] uint8, 1 = fluid.  The ghost planes must carry the mask of the plane they copy (nz-1 <- nz-2; 0 <- 1,
- * or 0, 1, 2 <- 3 with the convective outlet). */
+ * or 0, 1, 2 <- 3 with the convective outlet); with periodic z the mask is taken as given. */
 int lbmpm_rk3dcsf_create(const lbmpm_rk3dcsf_config *cfg, const uint8_t *is_domain, lbmpm_rk3dcsf **out);
 void lbmpm_rk3dcsf_destroy(lbmpm_rk3dcsf *ctx);
 /* f_c,i = rho_c w_i (1 + 3 e_i.u + 4.5 (e_i.u)^2 - 1.5 u^2) (RKD2Q9.py:577-601); vx, vy, vz may be NULL (= 0); the force of "the step

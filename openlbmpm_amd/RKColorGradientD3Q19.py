@@ -68,9 +68,17 @@ the map: restart_from= applies it again from the same argument.
 body_force = (gx, gy, gz) for both colours | dict(red=(gx, gy, gz), blue=(gx, gy, gz)) (also [BodyForce] isBodyForce = 'yes' with
 bodyForceX / Y / Z and the optional bodyForce{X,Y,Z}R / ...B of the ini, --body-force GX GY GZ [--body-force-blue GX GY GZ] of the command
 line; 3-D CSF only, ConfigError on the perturbation model, whose solver has no force term): an acceleration per colour in lattice units --
-gravity, or the drive of a force-driven flow between open planes at equal pressure (set_body_force; the model: include/lbmpm.h).  The
+gravity, or the drive of a force-driven flow, between open planes at equal pressure or with periodic z (set_body_force; the model:
+include/lbmpm.h).  The
 result file gets /BodyForce/Acceleration [2][3] once: red, blue as the solver holds them.  A checkpoint does not hold the force:
 restart_from= applies it again from the same argument.
+
+[BoundaryCondition] BoundaryTypeInlet = 'Periodic' with BoundaryTypeOutlet = 'Periodic' (3-D CSF only; one without the other and the
+perturbation model are a ConfigError): periodic z -- no inlet, no outlet, every plane wraps like x and y, so a body force is the only
+drive and the saturation is conserved (the relative-permeability set-up; README).  The mask is taken as given: duct() keeps its four side
+walls, a voxel file gets its side walls and NO buffer planes (num_buffering_layers is not applied), the planes at the ends need not
+repeat.  NeumannType, velocityZ*, density* are not used.  The result file gets /BoundaryCondition/PeriodicZ = 1; IsCycle, checkpoints
+and restart_from= work unchanged.  clusters_every / morphology_every tables do not wrap z.
 """
 import os
 
@@ -207,6 +215,8 @@ class RKColorGradient3D:
                  body_force=None):
         self.pathIni = pathIniFile
         self.par = config.read_rk3d(pathIniFile)
+        # periodic z (3-D CSF only; BoundaryTypeInlet = BoundaryTypeOutlet = 'Periodic'): no open planes -- the mask is taken as given
+        self.periodic_z = bool(self.par.get("periodic_z"))
         # an acceleration per colour (3-D CSF only): (gx, gy, gz) for both, or dict(red=, blue=); None: the ini's [BodyForce], if any
         self.body_force = self._body_force_arg(body_force if body_force is not None else self.par.get("body_force"))
         if self.body_force is not None and self.par["tension_type"] != "CSF":
@@ -257,7 +267,7 @@ class RKColorGradient3D:
             if not os.path.isfile(path):
                 raise config.ConfigError("[ImageSetup] Existance = 'yes': voxel file %s not found (or pass `domain=`)" % path)
             self._voxels = np.load(path)
-            self.isDomain = voxel_domain(self._voxels, self.nbuf)
+            self.isDomain = voxel_domain(self._voxels, self._image_buffer)
         else:
             self.isDomain = duct(p["nx"], p["ny"], p["nz"])
         self.zDomain, self.yDomain, self.xDomain = self.isDomain.shape
@@ -266,6 +276,12 @@ class RKColorGradient3D:
     @property
     def _is_image(self):
         return self._domain is not None or self.par["image"]
+
+    @property
+    def _image_buffer(self):
+        """the all-fluid planes a voxel file gets below and above: num_buffering_layers between open planes, none with periodic z
+        (the sample is its own neighbour there; the side walls stay, as duct() keeps its four)"""
+        return 0 if self.periodic_z else self.nbuf
 
     def solid_contact_angles(self):
         """contact_angle_solids on the lattice [nz][ny][nx] (NaN: the ini's ContactAngle), or None; after initializeDomainBorder"""
@@ -284,7 +300,7 @@ class RKColorGradient3D:
             if a.shape != np.shape(voxels):
                 raise config.ConfigError("contact angles have shape %s, the voxel file %s" % (a.shape, np.shape(voxels)))
             a[np.asarray(voxels) != 0] = np.nan
-            buf = np.full((self.nbuf,) + a.shape[1:], np.nan)
+            buf = np.full((self._image_buffer,) + a.shape[1:], np.nan)
             a = np.concatenate([buf, a, buf], axis=0)
         if a.shape != self.isDomain.shape:
             raise config.ConfigError("contact angles have shape %s, the lattice %s" % (a.shape, self.isDomain.shape))
@@ -516,9 +532,12 @@ class RKColorGradient3D:
         """SimulationResultsRK3D with the tasks' groups (None on a rank that writes none); contact angles and body force go into the solver
         (after a restart_from too: a checkpoint holds neither) and, once, into the file"""
         more = runloop.groups(tasks) + ((("Wettability", "ContactAngles"),) if self.contact_angle_solids is not None else ()) + \
-            ((("BodyForce", "Acceleration"),) if self.body_force is not None else ())
+            ((("BodyForce", "Acceleration"),) if self.body_force is not None else ()) + \
+            ((("BoundaryCondition", "OpenPlanes"),) if self.periodic_z else ())
         out = ResultFile(self.output_dir, "SimulationResultsRK3D" + h.suffix, GROUPS + more) if writes else None
         runloop.attach(tasks, out)
+        if self.periodic_z and out is not None:
+            out.write("BoundaryCondition", "PeriodicZ", np.array([1], dtype=np.int64))     # (only a periodic run has the group)
         if self.contact_angle_solids is not None:
             self._apply_contact_angles(h.solver, out)
         if self.body_force is not None:

@@ -69,7 +69,7 @@ class _CSFTracerSlab(_CSFSlab):
 class Transport3DRK(RKColorGradient3D):
     def __init__(self, pathIniFile, initial_concentration=None, **kw):
         RKColorGradient3D.__init__(self, pathIniFile, **kw)
-        self.tr = config.read_transport3d(pathIniFile)
+        self.tr = config.read_transport3d(pathIniFile, periodic_z=self.periodic_z)      # (periodic z: no Dirichlet inlet, no Freeflow outlet)
         self.numTracers = self.tr["num_tracers"]
         self._initial_concentration = initial_concentration
 

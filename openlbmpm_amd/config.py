@@ -167,15 +167,23 @@ def read_rk3d(ini_dir):
     if p["SolidRhoR"] + p["SolidRhoB"] == 0.0:
         raise ConfigError("[BoundariesSetup] SolidRhoR + SolidRhoB must not be zero")
     p["inlet"] = c.str("BoundaryCondition", "BoundaryTypeInlet")
-    if p["inlet"] not in ("Neumann", "Dirichlet") or (p["inlet"] == "Neumann" and c.str("BoundaryCondition", "NeumannType", default="'ZouHe'") != "ZouHe"):
+    p["outlet"] = c.str("BoundaryCondition", "BoundaryTypeOutlet")
+    # periodic z (3-D CSF only): BoundaryTypeInlet = 'Periodic' with BoundaryTypeOutlet = 'Periodic' -- no open planes, the mask taken as
+    # given; NeumannType is not looked at, the velocity and density keys below are read with their defaults and ignored
+    p["periodic_z"] = p["inlet"] == "Periodic" or p["outlet"] == "Periodic"
+    if p["periodic_z"]:
+        if p["inlet"] != p["outlet"]:
+            raise ConfigError("periodic z: BoundaryTypeInlet = 'Periodic' together with BoundaryTypeOutlet = 'Periodic', not %r with %r" % (p["inlet"], p["outlet"]))
+        if not csf:
+            raise ConfigError("BoundaryTypeInlet / BoundaryTypeOutlet = 'Periodic' belong to SurfaceTensionType = 'CSF': the perturbation model keeps its open planes")
+    elif p["inlet"] not in ("Neumann", "Dirichlet") or (p["inlet"] == "Neumann" and c.str("BoundaryCondition", "NeumannType", default="'ZouHe'") != "ZouHe"):
         raise ConfigError("3-D inlet: BoundaryTypeInlet = 'Neumann' with NeumannType = 'ZouHe' (velocityZR / velocityZB) or 'Dirichlet' "
                           "(densityRH / densityBH: Zou-He pressure per colour, the keys of RKtwophasesetup2D.ini)")
     p["densityRH"] = c.float("BoundaryCondition", "densityRH", default=1.0)
     p["densityBH"] = c.float("BoundaryCondition", "densityBH", default=1.0)
     if p["inlet"] == "Dirichlet" and not (p["densityRH"] > 0.0 and p["densityBH"] > 0.0):
         raise ConfigError("3-D pressure inlet: densityRH and densityBH must be positive (the closure divides by them; the absent colour gets e.g. 1e-8)")
-    p["outlet"] = c.str("BoundaryCondition", "BoundaryTypeOutlet")
-    if p["outlet"] not in ("Dirichlet", "Convective"):
+    if not p["periodic_z"] and p["outlet"] not in ("Dirichlet", "Convective"):
         raise ConfigError("3-D outlet: BoundaryTypeOutlet = 'Dirichlet' (densityRL / densityBL) or 'Convective' (the planes 0 .. 2 copy plane 3)")
     p["velocityZR"] = c.float("BoundaryCondition", "velocityZR", default=0.0)
     p["velocityZB"] = c.float("BoundaryCondition", "velocityZB", default=0.0)
@@ -318,14 +326,19 @@ def read_transport(ini_dir):
     return p
 
 
-def read_transport3d(ini_dir):
+def read_transport3d(ini_dir, periodic_z=False):
     """transportsetup.ini for the D3Q7 tracers of the 3-D CSF flow: the keys of read_transport plus the z entries of [TransportMRT] --
     DiffusionZ (per tracer), DiffusionXZ, DiffusionZX, DiffusionYZ, DiffusionZY.  A missing z entry defaults to the y entry of the 2-D
     file (DiffusionZ <- DiffusionY, DiffusionXZ <- DiffusionXY, DiffusionZX <- DiffusionYX; DiffusionYZ, DiffusionZY <- 0), so a 2-D file
     with DiffusionX = DiffusionY describes an isotropic 3-D case.  z is the flow axis: the inlet / outlet rules act on its end planes.
     diffJ3 is the rest weight of the reaction source on the D3Q7 lattice: the moving weights must agree with the 2-D model's,
-    (1 - J0') / 6 = (1 - J0) / 4, so J0' = (3 J0 - 1) / 2 (the 2-D default J0 = 1/3 gives 0)."""
+    (1 - J0') / 6 = (1 - J0) / 4, so J0' = (3 J0 - 1) / 2 (the 2-D default J0 = 1/3 gives 0).
+    periodic_z: the flow is periodic in z (read_rk3d: BoundaryTypeInlet = BoundaryTypeOutlet = 'Periodic') -- the planes nz-1 and 0 are
+    ordinary planes, so InletType = 'Dirichlet' and the OutletType the loop acts on, 'Freeflow', are a ConfigError."""
     p = read_transport(ini_dir)
+    if periodic_z and (p["inlet_type"] == "Dirichlet" or p["outlet_type"] == "Freeflow"):
+        raise ConfigError("[BoundaryCondition] InletType = %r, OutletType = %r on a flow that is periodic in z: the inlet and outlet planes they act on "
+                          "are ordinary planes there (neither 'Dirichlet' nor 'Freeflow')" % (p["inlet_type"], p["outlet_type"]))
     c = Ini(os.path.join(ini_dir, "transportsetup.ini"))
     n = p["num_tracers"]
     sec = c.cp["TransportMRT"] if "TransportMRT" in c.cp else {}

@@ -70,6 +70,7 @@ struct CsfDev {
     const double *ns;
     double sigma, cosT, sinT, beta, delta, tauR, tauB, vzIn, pInB, pInR, pOut;
     int tauType, inletP, conv, wetting, nwet;
+    int perz;                    // periodic z (LBMPM_INLET_PERIODIC with LBMPM_OUTLET_NONE): no open planes, every plane pulls like any other
     double rate[6];
     double eps;                  // a colour below eps * rho is absent (0x1p-51 unless the caller asks for more)
     // bulk skip (see deep_colour): per block of 256 fluid cells
@@ -151,7 +152,7 @@ __device__ __forceinline__ void cell_state(const CsfDev &p, int x, int y, int z,
     constexpr int UP[5] = {5, 11, 14, 15, 18}, DN[5] = {6, 12, 13, 16, 17};
     int zs = z;                                   // the plane whose streamed populations this cell takes
     bool top = false, bot = false;                // the inlet's / the pressure outlet's rule applies
-    if (BC && z >= p.glo && z < p.nz - p.ghi) {   // (a slab's own planes; the open planes are planes of the undivided lattice)
+    if (BC && !p.perz && z >= p.glo && z < p.nz - p.ghi) {   // (a slab's own planes; the open planes are planes of the undivided lattice)
         const int zg = z + p.zoff;
         int zsg = zg;
         if (zg == p.nzg - 1) zsg = p.nzg - 2;
@@ -263,6 +264,8 @@ __device__ __forceinline__ unsigned block_of()
 // last one that holds a cell within two cells of this block's (`rng`, a whole stretch of the lattice order: conservative) all `pure` of one
 // colour -- a difference of two prefix counts.  Such a block skips the phase-field pull, the gradient and the curvature: bit-equal to
 // the full path (tests/test_rk3d_csf_gpu.py), 79 instead of 136 doubles per cell and step.  The open planes always take the full path.
+// Periodic z has no open planes and the lattice order is a ring: a block next to the seam reads across it, so its stretch is an arc of the
+// ring, stored lo > hi where it runs over the seam (csf3d_setup_ranges) and counted from the same two prefix arrays.
 // The contact angle has no part in this, whether one for the lattice or one per cell (CsfDev.wang): where |G| = 0 the wetting rule scales
 // either candidate by |G| and returns zeros for any angle, so a deep block's zeros stand under every map and under a map that changes.
 __device__ __forceinline__ int deep_colour(const CsfDev &p, unsigned b)
@@ -270,6 +273,11 @@ __device__ __forceinline__ int deep_colour(const CsfDev &p, unsigned b)
     if (!p.skip || b >= p.nblk || p.bcblk[b]) return 0;
     const unsigned lo = p.rng[b], hi = p.rng[p.nblk + b];
     const uint32_t *pr = p.pfx, *pb = p.pfx + (p.nblk + 1u);
+    if (lo > hi) {                               // periodic z: the stretch runs across the seam, lo .. nblk - 1 and 0 .. hi -- all but hi + 1 .. lo - 1
+        if (pr[p.nblk] - (pr[lo] - pr[hi + 1u]) == 0u) return 1;
+        if (pb[p.nblk] - (pb[lo] - pb[hi + 1u]) == 0u) return 2;
+        return 0;
+    }
     if (pr[hi + 1u] - pr[lo] == 0u) return 1;
     if (pb[hi + 1u] - pb[lo] == 0u) return 2;
     return 0;
@@ -839,7 +847,17 @@ __global__ __launch_bounds__(1024) void csf3d_tile_rank(CsfDev p, const uint8_t 
 }
 
 // set-up of the bulk skip: first / last fluid cell any cell of a block reads its state from (pass 0), then first / last block over the
-// blocks of those cells' own ranges (pass 1: covers two cells around); blocks that hold cells of the open planes or their ghosts
+// blocks of those cells' own ranges (pass 1: covers two cells around); blocks that hold cells of the open planes or their ghosts.
+// Periodic z on the undivided lattice (ring): the fluid cells in lattice order are a ring of NF cells and a cell of plane 0 reads plane
+// nz - 1, so the stretch is an arc: lo / hi collect how far it reaches behind / ahead of the block's FIRST cell, each cell taken the
+// shorter way round (either way round reaches it, so either is conservative; the choice only decides how long the arc gets).  Pass 1
+// adds the arcs of the blocks reached, each shifted by the way to that block's first cell -- exact.  An arc of NF cells or more is the
+// whole lattice (ring_blocks).  A slab keeps the stretch: its seam lies between two slabs, beyond its ghost planes.
+__device__ __forceinline__ long long ring_way(unsigned from, unsigned to, unsigned n)
+{
+    const unsigned u = to >= from ? to - from : to + (n - from);
+    return u <= n / 2u ? (long long)u : (long long)u - (long long)n;
+}
 __global__ __launch_bounds__(256) void csf3d_setup_ranges(CsfDev p, int pass, uint32_t *lo, uint32_t *hi, const uint32_t *lo0, const uint32_t *hi0, uint8_t *bcblk)
 {
     constexpr int CX[Q] = CSF_CX, CY[Q] = CSF_CY, CZ[Q] = CSF_CZ;
@@ -851,7 +869,7 @@ __global__ __launch_bounds__(256) void csf3d_setup_ranges(CsfDev p, int pass, ui
     int zs = z;
     const bool ghost = z < p.glo || z >= p.nz - p.ghi;
     bool open = false;
-    if (!ghost) {
+    if (!ghost && !p.perz) {
         const int zg = z + p.zoff;
         int zsg = zg;
         open = zg >= p.nzg - 2 || zg <= 1;
@@ -864,8 +882,18 @@ __global__ __launch_bounds__(256) void csf3d_setup_ranges(CsfDev p, int pass, ui
     const unsigned own = at(nb, 0, 0, 0);
     const uint32_t m = p.meta[own];
     unsigned mn = j, mx = j;
+    const bool ring = p.perz && !p.glo && !p.ghi;
+    long long behind = 0, ahead = 0;
     auto take = [&](unsigned q) {
-        if (pass == 0) { mn = min(mn, q); mx = max(mx, q); }
+        if (ring) {
+            const long long way = (long long)(j & 255u) + ring_way(j, q, p.NF);       // from the block's first cell to q
+            if (pass == 0) { behind = max(behind, -way); ahead = max(ahead, way); }
+            else {
+                const long long w0 = way - (long long)(q & 255u);                      // ... to the first cell of q's block
+                behind = max(behind, (long long)lo0[q >> 8] - w0); ahead = max(ahead, w0 + (long long)hi0[q >> 8]);
+            }
+        }
+        else if (pass == 0) { mn = min(mn, q); mx = max(mx, q); }
         else { mn = min(mn, lo0[q >> 8]); mx = max(mx, hi0[q >> 8]); }
     };
     take(j);
@@ -887,6 +915,11 @@ __global__ __launch_bounds__(256) void csf3d_setup_ranges(CsfDev p, int pass, ui
         const Nb nq = make_nb(p, qx, qy, qz);
         for (int k = 1; k < Q; ++k)
             if ((ms >> k) & 1u) take(p.cidx[at(nq, CX[k], CY[k], CZ[k])]);
+    }
+    if (ring) {
+        atomicMax(&lo[b], (unsigned)min(behind, (long long)p.NF));
+        atomicMax(&hi[b], (unsigned)min(ahead, (long long)p.NF));
+        return;
     }
     atomicMin(&lo[b], mn);
     atomicMax(&hi[b], mx);
@@ -1180,6 +1213,7 @@ CsfDev make_dev(const lbmpm_rk3dcsf *c)
     p.vzIn = c->cfg.inlet_velocity_z; p.pInB = c->cfg.inlet_rho_b; p.pInR = c->cfg.inlet_rho_r; p.pOut = c->cfg.outlet_rho_total;
     p.tauType = c->cfg.tau_type; p.inletP = c->cfg.inlet_type == LBMPM_INLET_PRESSURE; p.conv = c->cfg.outlet_type == LBMPM_OUTLET_CONVECTIVE;
     p.wetting = c->cfg.wetting_type; p.nwet = (int)c->nwet;
+    p.perz = c->cfg.inlet_type == LBMPM_INLET_PERIODIC;
     bool any = false;
     for (int i = 0; i < 6; ++i) any = any || c->cfg.mrt_rates[i] != 0.;
     const double own[6] = {1.19, 1.4, 1.2, 1.4, 1.2, 0.};
@@ -1230,6 +1264,24 @@ struct AnalysisModel<lbmpm_rk3dcsf> {
 
 unsigned blocks_of(size_t n) { return (unsigned)((n + 255) / 256); }
 unsigned blocks8(size_t n) { return (blocks_of(n) + 7u) / 8u * 8u; }      // fluid_cell(): eight XCDs
+
+// periodic z: the arcs csf3d_setup_ranges collected -- h[b] cells behind, h[nb + b] cells ahead of block b's first cell on the ring of nf
+// fluid cells -- as CsfDev.rng: first / last block, first > last where the arc runs over the seam (deep_colour).  An arc that leaves no
+// whole block out is the whole lattice.
+void ring_blocks(uint32_t *h, unsigned nb, uint64_t nf)
+{
+    for (unsigned b = 0; b < nb; ++b) {
+        const uint64_t c0 = (uint64_t)b << 8, behind = h[b], ahead = h[nb + b];
+        uint32_t lo = 0, hi = nb - 1u;
+        if (behind + ahead + 1u < nf) {
+            const uint64_t first = (c0 + nf - behind) % nf, last = (c0 + ahead) % nf;
+            const uint32_t fb = (uint32_t)(first >> 8), lb = (uint32_t)(last >> 8);
+            if (first <= last) { lo = fb; hi = lb; }
+            else if (lb + 1u < fb) { lo = fb; hi = lb; }
+        }
+        h[b] = lo; h[nb + b] = hi;
+    }
+}
 
 TrDev make_trdev(const lbmpm_rk3dcsf *c)
 {
@@ -1350,12 +1402,17 @@ extern "C" void lbmpm_rk3dcsf_destroy(lbmpm_rk3dcsf *c)
 extern "C" int lbmpm_rk3dcsf_create(const lbmpm_rk3dcsf_config *cfg, const uint8_t *is_domain, lbmpm_rk3dcsf **out)
 {
     LBMPM_REQUIRE(cfg && is_domain && out, "lbmpm_rk3dcsf_create: null argument");
-    LBMPM_REQUIRE(cfg->nx >= 1 && cfg->ny >= 1 && cfg->nz >= 8, "lbmpm_rk3dcsf_create: lattice %lld x %lld x %lld out of range (nz >= 8: two open planes and their ghosts at each end)",
+    // periodic z: the pair LBMPM_INLET_PERIODIC + LBMPM_OUTLET_NONE, never one of them alone
+    const bool perz = cfg->inlet_type == LBMPM_INLET_PERIODIC;
+    LBMPM_REQUIRE(perz == (cfg->outlet_type == LBMPM_OUTLET_NONE),
+                  "lbmpm_rk3dcsf_create: inlet_type %d with outlet_type %d: periodic z is inlet_type LBMPM_INLET_PERIODIC together with outlet_type LBMPM_OUTLET_NONE, neither without the other",
+                  cfg->inlet_type, cfg->outlet_type);
+    LBMPM_REQUIRE(cfg->nx >= 1 && cfg->ny >= 1 && cfg->nz >= (perz ? 4 : 8), "lbmpm_rk3dcsf_create: lattice %lld x %lld x %lld out of range (nz >= 8: two open planes and their ghosts at each end; periodic z: nz >= 4)",
                   (long long)cfg->nx, (long long)cfg->ny, (long long)cfg->nz);
     LBMPM_REQUIRE((double)cfg->nx * (double)cfg->ny * (double)cfg->nz < 2147483648., "lbmpm_rk3dcsf_create: more than 2^31 cells");
     LBMPM_REQUIRE(cfg->relaxation == LBMPM_RELAX_SRT || cfg->relaxation == LBMPM_RELAX_MRT, "bad relaxation %d", cfg->relaxation);
-    LBMPM_REQUIRE(cfg->inlet_type == LBMPM_INLET_VELOCITY || cfg->inlet_type == LBMPM_INLET_PRESSURE, "bad inlet_type %d", cfg->inlet_type);
-    LBMPM_REQUIRE(cfg->outlet_type == LBMPM_OUTLET_PRESSURE || cfg->outlet_type == LBMPM_OUTLET_CONVECTIVE, "bad outlet_type %d", cfg->outlet_type);
+    LBMPM_REQUIRE(perz || cfg->inlet_type == LBMPM_INLET_VELOCITY || cfg->inlet_type == LBMPM_INLET_PRESSURE, "bad inlet_type %d", cfg->inlet_type);
+    LBMPM_REQUIRE(perz || cfg->outlet_type == LBMPM_OUTLET_PRESSURE || cfg->outlet_type == LBMPM_OUTLET_CONVECTIVE, "bad outlet_type %d", cfg->outlet_type);
     LBMPM_REQUIRE(cfg->tau_type == 1 || cfg->tau_type == 2, "TauType must be 1 or 2");
     LBMPM_REQUIRE(cfg->tau_r > 0.5 && cfg->tau_b > 0.5, "TauR, TauB must exceed 0.5");
     if (cfg->wetting_type == 1) {
@@ -1381,11 +1438,12 @@ extern "C" int lbmpm_rk3dcsf_create(const lbmpm_rk3dcsf_config *cfg, const uint8
     };
     // (planes of the undivided lattice; a slab checks the ones it owns: the open planes and the planes they copy lie in one slab, >= 4 planes)
     auto owns = [&](int64_t zg) { return zg - zoff >= cfg->ghost_lo && zg - zoff < cfg->nz - cfg->ghost_hi; };
-    if (owns(nzg - 1)) {
+    // (periodic z: no plane copies another, the mask is taken as it is)
+    if (!perz && owns(nzg - 1)) {
         LBMPM_REQUIRE(owns(nzg - 2), "lbmpm_rk3dcsf_create: the inlet plane and its ghost plane belong to one slab");
         LBMPM_REQUIRE(same(nzg - 1 - zoff, nzg - 2 - zoff), "lbmpm_rk3dcsf_create: the ghost plane nz-1 must have the mask of the inlet plane nz-2");
     }
-    if (owns(0)) {
+    if (!perz && owns(0)) {
         if (cfg->outlet_type == LBMPM_OUTLET_CONVECTIVE) {
             LBMPM_REQUIRE(owns(3), "lbmpm_rk3dcsf_create: the planes 0 .. 3 of the convective outlet belong to one slab");
             LBMPM_REQUIRE(same(0 - zoff, 3 - zoff) && same(1 - zoff, 3 - zoff) && same(2 - zoff, 3 - zoff), "lbmpm_rk3dcsf_create: the convective outlet copies plane 3 onto the planes 2, 1, 0: their masks must coincide");
@@ -1500,9 +1558,10 @@ extern "C" int lbmpm_rk3dcsf_create(const lbmpm_rk3dcsf_config *cfg, const uint8
         if (rc == LBMPM_OK) {
             uint32_t *const lo0 = ranges.get(), *const hi0 = lo0 + nb, *const lo1 = hi0 + nb, *const hi1 = lo1 + nb;
             const CsfDev p = make_dev(c);
-            e = hipMemsetAsync(lo0, 0xFF, nb * sizeof(uint32_t), c->stream);
+            const bool ring = p.perz && !slab;       // (csf3d_setup_ranges: lo collects a reach behind the block, a maximum like hi)
+            e = hipMemsetAsync(lo0, ring ? 0 : 0xFF, nb * sizeof(uint32_t), c->stream);
             if (e == hipSuccess) e = hipMemsetAsync(hi0, 0, nb * sizeof(uint32_t), c->stream);
-            if (e == hipSuccess) e = hipMemsetAsync(lo1, 0xFF, nb * sizeof(uint32_t), c->stream);
+            if (e == hipSuccess) e = hipMemsetAsync(lo1, ring ? 0 : 0xFF, nb * sizeof(uint32_t), c->stream);
             if (e == hipSuccess) e = hipMemsetAsync(hi1, 0, nb * sizeof(uint32_t), c->stream);
             for (uint8_t *q : {c->pure, c->deep_prev, c->bcblk}) if (e == hipSuccess) e = hipMemsetAsync(q, 0, nb, c->stream);
             if (e == hipSuccess) {
@@ -1513,7 +1572,8 @@ extern "C" int lbmpm_rk3dcsf_create(const lbmpm_rk3dcsf_config *cfg, const uint8
                 std::vector<uint32_t> h(2 * (size_t)nb);
                 e = hipMemcpyAsync(h.data(), lo1, 2 * (size_t)nb * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
                 if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-                for (uint32_t &v : h) v >>= 8;          // cells -> blocks
+                if (ring) ring_blocks(h.data(), nb, (uint64_t)c->nfluid);
+                else for (uint32_t &v : h) v >>= 8;     // cells -> blocks
                 if (e == hipSuccess) e = hipMemcpyAsync(c->rng, h.data(), 2 * (size_t)nb * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
                 if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
                 if (e == hipSuccess) e = hipGetLastError();
@@ -2310,6 +2370,9 @@ static int tracer_configure(lbmpm_rk3dcsf *c, const lbmpm_tracer3d_config *k, co
 {
     LBMPM_REQUIRE(k->num_tracers >= 1 && k->num_tracers <= 4, "%s: NumberTracers %d, 1 .. 4 are built", who, (int)k->num_tracers);
     LBMPM_REQUIRE(k->reaction_rate == 0. || k->num_tracers == 3, "%s: the reaction A + B -> C couples exactly three tracers, not %d", who, (int)k->num_tracers);
+    LBMPM_REQUIRE(c->cfg.inlet_type != LBMPM_INLET_PERIODIC || (!k->dirichlet_inlet && !k->free_outlet),
+                  "%s: dirichlet_inlet %d, free_outlet %d on a flow that is periodic in z: the planes nz-1 and 0 they name are ordinary planes there, both must be 0",
+                  who, (int)k->dirichlet_inlet, (int)k->free_outlet);
     if (c->steps > 0 || !c->first) { set_error("%s after stepping: configure the tracers before the first step", who); return LBMPM_ERR_STATE; }
     if (c->ntr) { set_error("%s: the tracers of this context are configured already", who); return LBMPM_ERR_STATE; }
     double B[4][9];

@@ -22,6 +22,20 @@ DEFAULT_PARAMS = dict(sigma=0.1, theta=60.0, wetting=2, beta=0.7, delta=0.98, ta
                       densityBL=1.0, densityRL=5e-8, rates=None, variant=0, bulk_epsilon=0.0)
 
 
+_INLETS = dict(Neumann=0, Dirichlet=1, Periodic=2)          # LBMPM_INLET_VELOCITY | _PRESSURE | _PERIODIC
+_OUTLETS = dict(Dirichlet=0, Convective=1, Periodic=2)      # LBMPM_OUTLET_PRESSURE | _CONVECTIVE | _NONE
+
+
+def periodic_pair(inlet, outlet):
+    """periodic z: inlet 'Periodic' with outlet 'Periodic' -- no open planes, all nz planes wrap like x and y, the mask is taken as given
+    and the velocity / density parameters of the open planes are not read.  True for the pair, False for neither; ValueError for one
+    without the other"""
+    if (inlet == "Periodic") != (outlet == "Periodic"):
+        raise ValueError("periodic z is BoundaryTypeInlet 'Periodic' together with BoundaryTypeOutlet 'Periodic', not inlet=%r with outlet=%r"
+                         % (inlet, outlet))
+    return inlet == "Periodic"
+
+
 def _f64(a):
     return np.ascontiguousarray(a, dtype=np.float64)
 
@@ -76,6 +90,10 @@ class RK3DCSFSolver(SlabTransportCalls, SlabAnalysisCalls):
         """slab = (z0, global_nz): this lattice is a slab of an undivided lattice of global_nz planes -- its planes 2 .. nz-3 are the planes
         z0 .. of that lattice, its two planes at either end images of the neighbouring slabs' edge planes (cut from the undivided lattice,
         wrapping around its ends, like the rest).
+        params: DEFAULT_PARAMS' keys.  inlet="Periodic" with outlet="Periodic" (both or neither, else ValueError) is periodic z: no open
+        planes, every plane wraps like x and y, the mask is taken as given (nz >= 4) and velocityZ*, density* are not read; self.periodic_z
+        says so.  Tracers then take neither dirichlet_inlet nor free_outlet (LbmpmError, LBMPM_ERR_INVALID), and clusters() / morphology()
+        still do not wrap z.
         tracers = dict(<the keyword arguments of configure_tracers>): the D3Q7 tracers, configured at construction.  On a slab this is the
         only way to them (lbmpm_rk3dcsf_tracer_configure_slab): their populations travel inside the population message, so every slab of
         the ring is given the same dict, before a transport is connected."""
@@ -103,12 +121,12 @@ class RK3DCSFSolver(SlabTransportCalls, SlabAnalysisCalls):
         if p["relax"] not in ("SRT", "MRT"):
             raise ValueError("RelaxationType must be 'SRT' or 'MRT'")
         cfg.relaxation = 1 if p["relax"] == "MRT" else 0
-        if p["inlet"] not in ("Neumann", "Dirichlet"):
-            raise ValueError("BoundaryTypeInlet must be 'Neumann' or 'Dirichlet'")
-        if p["outlet"] not in ("Dirichlet", "Convective"):
-            raise ValueError("BoundaryTypeOutlet must be 'Dirichlet' or 'Convective'")
-        cfg.inlet_type = 0 if p["inlet"] == "Neumann" else 1
-        cfg.outlet_type = 0 if p["outlet"] == "Dirichlet" else 1
+        self.periodic_z = periodic_pair(p["inlet"], p["outlet"])
+        if p["inlet"] not in _INLETS:
+            raise ValueError("BoundaryTypeInlet must be 'Neumann' or 'Dirichlet' (or 'Periodic', with BoundaryTypeOutlet 'Periodic')")
+        if p["outlet"] not in _OUTLETS:
+            raise ValueError("BoundaryTypeOutlet must be 'Dirichlet' or 'Convective' (or 'Periodic', with BoundaryTypeInlet 'Periodic')")
+        cfg.inlet_type, cfg.outlet_type = _INLETS[p["inlet"]], _OUTLETS[p["outlet"]]
         cfg.device = int(device)
         cfg.variant = int(p["variant"])        # 1: no bulk skip (cross-check)
         cfg.bulk_epsilon = float(p["bulk_epsilon"])      # 0: exact (2^-51); opt-in: cut a colour's tail below this fraction of the density
@@ -387,6 +405,12 @@ def _angles_valid(slab, a):
                               "within [0, 180] degrees" % (float(a[z, y, x]), z, y, x), _lib.ERR_INVALID)
 
 
+def _periodic_params(params):
+    """periodic_pair of the inlet / outlet a params dict (or None) asks for"""
+    p = params or {}
+    return periodic_pair(p.get("inlet", DEFAULT_PARAMS["inlet"]), p.get("outlet", DEFAULT_PARAMS["outlet"]))
+
+
 _TRACERS_AT_CONSTRUCTION = ("tracers on z-slabs are part of the slabs' population message, which is sized when the ring is set up: "
                             "give them to %s at construction (tracers=dict(...)), not afterwards")
 
@@ -402,6 +426,7 @@ class RK3DCSFCluster(StackedAnalysis):
         dom = np.ascontiguousarray(is_domain, dtype=np.uint8)
         self.shape = dom.shape
         self.nz, self.ny, self.nx = dom.shape
+        self.periodic_z = _periodic_params(params)       # (periodic z: a cut may fall anywhere, the ring's seam is one more face)
         self.cuts = list(cuts) if cuts is not None else slab_cuts(self.nz, nslabs)
         n = len(self.cuts) - 1
         devices = list(devices) if devices is not None else [0] * n
@@ -530,6 +555,7 @@ class RK3DCSFDistributed(GatheredAnalysis):
         self.shape = dom.shape
         self.nz = dom.shape[0]
         self.group = None
+        self.periodic_z = _periodic_params(params)
         # (default: equal shares of the fluid cells -- the same cuts on every rank, they hold the same mask)
         self.cuts = list(cuts) if cuts is not None else slab_cuts(self.nz, self.world, weights=(dom.reshape(self.nz, -1) == 1).sum(axis=1) + 1.0e-3)
         if len(self.cuts) != self.world + 1:
