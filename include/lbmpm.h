@@ -702,7 +702,8 @@ int64_t lbmpm_rk3d_device_bytes(const lbmpm_rk3d *ctx);
  * The tracers' dirichlet_inlet and free_outlet name planes that are not special any more: lbmpm_rk3dcsf_tracer_configure / _configure_slab
  * refuse them (LBMPM_ERR_INVALID); with both 0 the tracers are periodic in z as they always were.  The analyses keep their documented z
  * behaviour whatever the flow does: clusters, cluster properties and morphology do NOT wrap z -- a ganglion that sits across the seam counts
- * as two, touching the first and the last plane.
+ * as two, touching the first and the last plane (tests/test_rk3d_csf_periodic_observers_gpu.py: every observer against its restatement,
+ * rolled lattices, slabs and ranks; tests/test_rk3d_csf_periodic_runs_gpu.py: restart, the contact-angle map, the drivers).
  * ---------------------------------------------------------------------------------- */
 typedef struct lbmpm_rk3dcsf_config {
     int64_t nx, ny, nz;        /* xDomain, yDomain, zDomain (incl. the ghost planes 0 and nz-1); nz >= 8 (periodic z: nz >= 4) */

@@ -136,6 +136,62 @@ def free_lattice(grains=True):
     return dom, rR, rB
 
 
+# ------------------------------------------------------------------------------------------------ the ring box (observers, restart)
+# The 70 x 33 x 12 box of the analyses' tests (tests/test_integrals_gpu.py: rows of 64 + 6 cells, 2310 cells per plane = two chunks of the
+# reducer and a ragged one, 12 planes = no multiple of the 4-plane cluster tile) with a mask made for a ring: nothing repeats at the ends of
+# z, and what is special lies on the seam between plane 11 and plane 0.
+RING_SHAPE = (12, 33, 70)
+RING_PARAMS = dict(relax="MRT", theta=55.0, tauB=0.8, sigma=0.06, inlet="Periodic", outlet="Periodic")
+RING_TRACER = dict(num_tracers=1, diffusion_x=0.12, beta_interface=0.3, dirichlet_inlet=False, free_outlet=False)
+SEAM = "seam_ganglion"
+
+
+def ring_box(seed=29):
+    """the mask [12][33][70]: seeded blocks anywhere round the ring (some across the seam), a grain across the seam, a grain in the planes
+    10, 11 under fluid of plane 0 and one in the planes 0, 1 over fluid of plane 11, row y = 7 all solid in the planes 3 .. 8, plane 5 with
+    five fluid cells, and room for the ganglion of ring_red_cells"""
+    nz, ny, nx = RING_SHAPE
+    rng = np.random.default_rng(seed)
+    dom = np.ones(RING_SHAPE, dtype=np.uint8)
+    for _ in range(60):
+        z, y, x = rng.integers(0, nz), rng.integers(0, ny - 3), rng.integers(0, nx - 4)
+        for p in (z, (z + 1) % nz):
+            dom[p, y:y + 3, x:x + 4] = 0
+    dom[3:9, 7, :] = 0
+    dom[5] = 0
+    dom[5, 20, 30:33] = 1
+    dom[5, 3, 68:70] = 1
+    dom[[9, 10, 11, 0, 1, 2], 13:23, 29:45] = 1          # the ganglion's room
+    dom[[11, 0], 24:28, 8:14] = 0                        # the grain across the seam
+    dom[10:12, 2:5, 50:56] = 0; dom[0:2, 2:5, 50:56] = 1
+    dom[0:2, 28:31, 20:26] = 0; dom[10:12, 28:31, 20:26] = 1
+    return dom
+
+
+def ring_red_cells():
+    """the pattern of its own: one red ganglion across the seam, three planes thick on either side (9 .. 11 and 0 .. 2), whose footprints
+    in the planes 11 and 0 differ and overlap (x 34 .. 39, y 16 .. 19); blue everywhere else"""
+    red = np.zeros(RING_SHAPE, dtype=bool)
+    red[9:12, 14:20, 30:40] = True
+    red[0:3, 16:22, 34:44] = True
+    return red
+
+
+def ring_densities(name, dom):
+    """(rhoR, rhoB) of the pattern `name`: SEAM, or a pattern of tests/test_clusters_gpu.densities"""
+    if name != SEAM:
+        from test_clusters_gpu import densities
+        return densities(name, dom)
+    fl, red = dom == 1, ring_red_cells()
+    return np.where(fl & red, 1.0, 0.0), np.where(fl & ~red, 1.0, 0.0)
+
+
+def ring_concentration(dom):
+    nz, ny, nx = dom.shape
+    z, y, x = np.mgrid[0:nz, 0:ny, 0:nx]
+    return np.where(dom == 1, 0.3 + 0.2 * np.cos(2. * np.pi * (z / nz + x / nx)) + 0.05 * np.sin(2. * np.pi * y / ny), 0.0)
+
+
 def gap_lattice(nz, ny, gap, wall=2):
     """a gap `gap` cells wide between walls `wall` thick at both ends of x, red in its lower half, blue in the upper one: uniform along z"""
     nx = gap + 2 * wall

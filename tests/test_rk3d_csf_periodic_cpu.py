@@ -87,6 +87,96 @@ def test_the_analytic_two_layer_profile():
     assert PR.two_layer_errors(u(np.arange(32) + 0.5))[2] == 0.0
 
 
+# ------------------------------------------------------------------------------------------------ the ring box
+def ring_classes(name, dom=None):
+    """the class field (0 solid, 1 R, 2 B) of a prescribed sharp pattern on the ring box"""
+    dom = PR.ring_box() if dom is None else dom
+    rR, rB = PR.ring_densities(name, dom)
+    return np.where(dom == 1, np.where(rR > rB, 1, 2), 0).astype(np.uint8)
+
+
+def seam_rows(table, nz=12):
+    """the R rows of a cluster table that touch the first plane and not the last, and the other way round"""
+    red = table[table[:, 1] == 1]
+    return red[(red[:, 3] == 0) & (red[:, 4] < nz - 1)], red[(red[:, 3] > 0) & (red[:, 4] == nz - 1)]
+
+
+UPWARDS = ("RR_z", "BB_z", "RB_z", "RS_z", "BS_z", "sq_R_xz", "sq_R_yz", "sq_B_xz", "sq_B_yz", "cube_R", "cube_B")
+
+
+def test_the_ring_box_is_made_for_a_ring():
+    dom = PR.ring_box()
+    fl = dom == 1
+    assert dom.shape == (12, 33, 70) and dom.dtype == np.uint8
+    for a, b in ((0, 11), (0, 1), (11, 10), (1, 10)):
+        assert not np.array_equal(dom[a], dom[b]), (a, b)
+    assert not fl[[11, 0], 24:28, 8:14].any() and fl[[10, 1], 24:28, 8:14].all()          # a grain across the seam, and only there
+    assert int((fl[0] & ~fl[11]).sum()) >= 18 and int((fl[11] & ~fl[0]).sum()) >= 18       # fluid of either plane faces solid across the seam
+    assert int(fl[5].sum()) == 5 and not fl[3:9, 7].any()
+    assert all(int(fl[z].sum()) > 1500 for z in range(12) if z != 5)
+    red = PR.ring_red_cells()
+    assert fl[red].all()                                                                   # the ganglion lies in fluid
+    for half in (red[9:12], red[0:3]):
+        assert all(int(p.sum()) == 60 for p in half)                                       # three planes thick on either side
+    assert 0 < int((red[11] & red[0]).sum()) < 60 and not red[3:9].any()                   # the footprints differ and overlap
+    c = PR.ring_concentration(dom)
+    assert np.all(c[fl] > 0.04) and not np.array_equal(c[0], c[11])
+
+
+@pytest.mark.parametrize("conn", [6, 18])
+def test_the_seam_ganglion_counts_as_two(conn):
+    """z does not wrap in the labeller: the ganglion is one red row that starts at plane 0 and one that ends at plane 11, and the same
+    classes rolled by six planes -- the seam in the middle -- have fewer clusters.  An implementation that wrapped z would hand out
+    another table"""
+    from test_clusters_cpu import cpu_label
+    cls = ring_classes(PR.SEAM)
+    _, tab = cpu_label(cls, conn)
+    _, rolled = cpu_label(np.roll(cls, 6, axis=0), conn)
+    assert tab.shape[0] > rolled.shape[0], (tab.shape, rolled.shape)
+    low, high = seam_rows(tab)
+    assert low.shape[0] == 1 and high.shape[0] == 1 and int((tab[:, 1] == 1).sum()) == 2, tab
+    assert tuple(low[0, 2:]) == (180, 0, 2) and tuple(high[0, 2:]) == (180, 9, 11)
+    red = rolled[rolled[:, 1] == 1]
+    assert red.shape[0] == 1 and tuple(red[0, 2:]) == (360, 3, 8)                          # joined, were the seam no end
+    # the Python join of slab tables takes the stack as a chain: the cuts of the GPU tests give the undivided table
+    from test_clusters_cpu import by_slabs
+    for cuts in ([0, 6, 12], [0, 4, 8, 12]):
+        assert np.array_equal(by_slabs(cls, conn, cuts)[1], tab), cuts
+
+
+def test_the_seam_shows_in_the_plane_above_and_in_the_end_rows():
+    """for every prescribed pattern: morphology's row 11 with plane 0 as the plane above differs from the row with nothing above in
+    columns that reach upwards (a wrapping count would show); the integrals' rows 0 and 1, 10 and 11, and the change table's rows 0 and
+    3 differ by more than the comparison's bound (a leftover redirect of an open plane to its neighbour would show)"""
+    import change_ref
+    from test_clusters_gpu import SHARP
+    from test_integrals_gpu import restate
+    from test_morphology_cpu import C, cpu_morphology
+    dom = PR.ring_box()
+    up = [C[n] for n in UPWARDS]
+    flat = [c for c in range(28) if c not in up]
+    for name in SHARP + (PR.SEAM,):
+        rR, rB = PR.ring_densities(name, dom)
+        cls = ring_classes(name, dom)
+        alone, joined = cpu_morphology(cls, rR + rB), cpu_morphology(cls, rR + rB, above=cls[0])
+        assert np.array_equal(alone[:11], joined[:11]) and np.array_equal(alone[11, flat], joined[11, flat])
+        assert not np.array_equal(alone[11, up], joined[11, up]), name
+        zero = np.zeros(dom.shape)
+        now = dict(rhoR=rR, rhoB=rB, vx=zero, vy=zero, vz=zero, phi=np.where(dom == 1, (rR - rB) / np.maximum(rR + rB, 1e-300), 0.0))
+        T, A = restate(dom, now)
+        for a, b in ((0, 1), (10, 11)):
+            assert rows_differ(T, A, a, b, (2, 3)), (name, a, b)
+        T, A = change_ref.restate(dom, now, dict(now, phi=-now["phi"]))
+        assert rows_differ(T, A, 0, 3, (7,)), name
+
+
+def rows_differ(T, A, a, b, cols):
+    """the columns among `cols` in which the rows a and b of a restated table lie further apart than the two rows' summation bounds
+    (2 (n - 1) 2^-53 sum|term| each: tests/test_integrals_gpu.py) together"""
+    bound = lambda r: 2.0 * max(T[r, 0] - 1.0, 0.0) * 2.0 ** -53 * A[r]
+    return [c for c in cols if abs(T[a, c] - T[b, c]) > bound(a)[c] + bound(b)[c]]
+
+
 # ------------------------------------------------------------------------------------------------ the Python classes
 @pytest.fixture
 def seen(monkeypatch):

@@ -113,16 +113,22 @@ ROLL_STEPS = 12
 _FREE = {}
 
 
+def free_solver(k, variant):
+    """a solver on the 16^3 lattice of tests/periodic_ref.py rolled by k planes along z, three tracers, before the first step"""
+    dom, rR, rB = (np.roll(a, k, axis=0) for a in PR.free_lattice())
+    z, y, x = np.mgrid[0:16, 0:16, 0:16]
+    s = solver(dom, dict(PR.FREE_PARAMS, variant=variant), tracers=TRACERS)
+    s.set_macro(rR, rB)
+    for t in range(3):
+        conc = (0.2 + 0.1 * t + 0.1 * np.cos(2. * np.pi * ((z + 3 * t) / 16. + y / 16.)) * np.sin(2. * np.pi * x / 16.)) * (t < 2)
+        s.set_concentration(t, np.roll(np.where(PR.free_lattice()[0] == 1, conc, 0.0), k, axis=0))
+    return s
+
+
 def free_run(k, variant):
-    """the 16^3 lattice of tests/periodic_ref.py rolled by k planes along z, three tracers, after ROLL_STEPS steps: (fields, bulk_cells)"""
+    """... after ROLL_STEPS steps: (fields, bulk_cells)"""
     if (k, variant) not in _FREE:
-        dom, rR, rB = (np.roll(a, k, axis=0) for a in PR.free_lattice())
-        z, y, x = np.mgrid[0:16, 0:16, 0:16]
-        s = solver(dom, dict(PR.FREE_PARAMS, variant=variant), tracers=TRACERS)
-        s.set_macro(rR, rB)
-        for t in range(3):
-            conc = (0.2 + 0.1 * t + 0.1 * np.cos(2. * np.pi * ((z + 3 * t) / 16. + y / 16.)) * np.sin(2. * np.pi * x / 16.)) * (t < 2)
-            s.set_concentration(t, np.roll(np.where(PR.free_lattice()[0] == 1, conc, 0.0), k, axis=0))
+        s = free_solver(k, variant)
         s.step(ROLL_STEPS)
         _FREE[(k, variant)] = (fields_of(s), s.bulk_cells)
         s.close()
