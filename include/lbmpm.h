@@ -533,7 +533,11 @@ int lbmpm_rk3d_change(lbmpm_rk3d *ctx, int remark, int64_t *steps_between, doubl
  *               interface band.  phi_cut >= 0; at 0 the R cells are the integrals' CELLS_R.
  *   Neighbours  connectivity 6 (faces) or 18 (the D3Q19 links); anything else: LBMPM_ERR_UNSUPPORTED.  x and y wrap periodically as in
  *               the solvers; z does not, in either model (nor does the CSF ring's last-to-first face): clusters are read between the
- *               open planes.
+ *               open planes.  On a lattice that is periodic in z the seam between plane nz-1 and plane 0 is one more cut, which the
+ *               caller closes as it joins slabs: through lbmpm_*_clusters_faces of the lowest and the highest plane (the Python side:
+ *               clusters.close_seam, wrap_z=True -- a cluster across the seam becomes one row whose ZMAX may exceed nz-1, and every
+ *               row gets a winding: by how many periods the cluster is connected to its own image along z, 0 for a ganglion.  Windings
+ *               along x and y are not computed).  The table of this call is the open one either way.
  *   Cluster     a maximal set of cells of one class connected through neighbours of that class.  Its label is the global cell number
  *               (z_global * ny + y) * nx + x of its smallest cell, a uint32; 0xFFFFFFFF: in no cluster.  A lattice of 2^32 - 1 cells or
  *               more: LBMPM_ERR_UNSUPPORTED.  The label makes the result unique and independent of how the lattice is cut.
@@ -562,7 +566,9 @@ int lbmpm_rk3d_clusters_faces(lbmpm_rk3d *ctx, uint32_t *labels, uint8_t *classe
  *   Class byte    the values of LBMPM_MORPH_*: R or B exactly where the clusters put the cell into a cluster of that class, S where the
  *                 flow's loader says solid, N for every other fluid cell.  lbmpm_*_cluster_props_face hands out the classes of the
  *                 lowest and the highest own plane; `below` / `above` are the highest plane of the slab below and the lowest plane of
- *                 the slab above.  A byte > 3 in either: LBMPM_ERR_INVALID.  NULL: nothing is there -- z never wraps.
+ *                 the slab above.  A byte > 3 in either: LBMPM_ERR_INVALID.  NULL: nothing is there -- z never wraps of itself.  A
+ *                 caller that closes the seam of a lattice periodic in z passes the planes across it: a context that holds the
+ *                 whole lattice its own face planes (below = its highest, above = its lowest), the end slabs each other's.
  *   FACES_FLUID,  cell-centred: of the six face neighbours of every cell of the cluster (x +- 1 mod nx, y +- 1 mod ny, literally for a
  *   FACES_SOLID   small nx or ny: each direction counts once; z +- 1 from the own planes, `below` or `above`) those of the other phase,
  *                 and the S ones.  An R-B face counts once for the R cluster and once for the B cluster.
@@ -570,7 +576,8 @@ int lbmpm_rk3d_clusters_faces(lbmpm_rk3d *ctx, uint32_t *labels, uint8_t *classe
  *   SQUARES,      whose cells are all of the anchor's class, credited to the anchor's cluster: PAIRS over the three axes, SQUARES over
  *   CUBES         the three orientations.  Such an element is face-connected, so it lies in one cluster under either connectivity;
  *                 an element cut by a slab face is counted by the anchor's slab.  chi_6 of a cluster = CELLS - PAIRS + SQUARES - CUBES.
- *   SUM_Z         the sum of the global plane numbers of the cluster's cells (the centroid along z, the axis that does not wrap)
+ *   SUM_Z         the sum of the global plane numbers of the cluster's cells (the centroid along z, the axis that does not wrap; a
+ *                 caller that closes the seam adds nz per cell and period to the rows it joins: clusters.close_seam)
  *   MASS, MOM_a   fixed-point sums, added with integer atomics (no floating-point atomics: their order is not fixed).  Per cell
  *                 rho = rho_R + rho_B (one rounded addition, as in the morphology) and p_a = rho * u_a (one rounded product, as in the
  *                 integrals), each rounded to nearest-even to a multiple of its quantum: MASS in units of 2^-LBMPM_CP_MASS_BITS, MOM_a
@@ -606,7 +613,10 @@ int lbmpm_rk3d_cluster_props(lbmpm_rk3d *ctx, const uint8_t *below, const uint8_
  *   Elements    x and y wrap as in the solvers; z does not, in either model (as for the clusters).  An element is a set of cells
  *               anchored at its corner cell c = (x, y, z), the cell with the lowest x, y and z before any wrap; its other cells are at
  *               x + 1 mod nx, y + 1 mod ny and z + 1.  An element belongs to the plane of c.  Elements that would need plane nz do not
- *               exist.  There is no special case for a small nx or ny: one element per anchor cell and kind, literally.
+ *               exist -- unless the caller passes `above`, the plane over the highest own plane: the lowest plane of the slab above,
+ *               or, to close the seam of a lattice periodic in z, the lattice's own plane 0 (lbmpm_*_morphology_face of the context
+ *               itself, or of the lowest slab; wrap_z=True on the Python side).  There is no special case for a small nx or ny: one
+ *               element per anchor cell and kind, literally.
  *   Table       [own planes][LBMPM_MORPH_COLS] doubles, every count far below 2^53:
  *               CELLS_R, CELLS_B, CELLS_N   cells of each class in the plane
  *               RHO_R, RHO_B                sum of rho_R + rho_B over the plane's R cells, and over its B cells
@@ -701,9 +711,12 @@ int64_t lbmpm_rk3d_device_bytes(const lbmpm_rk3d *ctx);
  * ring there (tests/test_rk3d_csf_periodic_gpu.py: a lattice rolled along z gives the rolled fields bit for bit and the same bulk count).
  * The tracers' dirichlet_inlet and free_outlet name planes that are not special any more: lbmpm_rk3dcsf_tracer_configure / _configure_slab
  * refuse them (LBMPM_ERR_INVALID); with both 0 the tracers are periodic in z as they always were.  The analyses keep their documented z
- * behaviour whatever the flow does: clusters, cluster properties and morphology do NOT wrap z -- a ganglion that sits across the seam counts
- * as two, touching the first and the last plane (tests/test_rk3d_csf_periodic_observers_gpu.py: every observer against its restatement,
- * rolled lattices, slabs and ranks; tests/test_rk3d_csf_periodic_runs_gpu.py: restart, the contact-angle map, the drivers).
+ * behaviour whatever the flow does: of themselves clusters, cluster properties and morphology do NOT wrap z -- a ganglion that sits across
+ * the seam counts as two, touching the first and the last plane (tests/test_rk3d_csf_periodic_observers_gpu.py: every observer against its
+ * restatement, rolled lattices, slabs and ranks; tests/test_rk3d_csf_periodic_runs_gpu.py: restart, the contact-angle map, the drivers).
+ * The seam is closed by the caller, with the calls that join slabs and no other: the context's own face planes as `below` / `above` of
+ * lbmpm_rk3dcsf_cluster_props and `above` of lbmpm_rk3dcsf_morphology, and the labels of lbmpm_rk3dcsf_clusters_faces joined across the
+ * seam with a winding per cluster (the paragraphs of those functions; wrap_z=True of the Python classes; tests/test_rk3d_csf_seam_gpu.py).
  * ---------------------------------------------------------------------------------- */
 typedef struct lbmpm_rk3dcsf_config {
     int64_t nx, ny, nz;        /* xDomain, yDomain, zDomain (incl. the ghost planes 0 and nz-1); nz >= 8 (periodic z: nz >= 4) */

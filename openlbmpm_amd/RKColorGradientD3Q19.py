@@ -78,7 +78,18 @@ perturbation model are a ConfigError): periodic z -- no inlet, no outlet, every 
 drive and the saturation is conserved (the relative-permeability set-up; README).  The mask is taken as given: duct() keeps its four side
 walls, a voxel file gets its side walls and NO buffer planes (num_buffering_layers is not applied), the planes at the ends need not
 repeat.  NeumannType, velocityZ*, density* are not used.  The result file gets /BoundaryCondition/PeriodicZ = 1; IsCycle, checkpoints
-and restart_from= work unchanged.  clusters_every / morphology_every tables do not wrap z.
+and restart_from= work unchanged.  clusters_every / morphology_every tables by default do not wrap z: plane nz-1 and plane 0 are ends of
+the lattice to them, a ganglion across the seam is two rows, and what Clusters defines through open planes (percolation, trapped cells)
+has no meaning.
+
+analyses_wrap_z = True (--wrap-z of the command line; periodic z only, ConfigError otherwise): the clusters and morphology tasks close
+the seam (wrap_z=True of clusters() / morphology(); openlbmpm_amd/clusters.py: close_seam).  A cluster across the seam is one row whose
+zmax exceeds nz-1 (its planes zmin .. zmax counted on without a break, 0 <= zmin < nz; sum_z of the property table likewise), every row
+has a winding in /Clusters/WindingAtStep<step> [n] int64 -- 0: a ganglion; w > 0: the cluster is connected to its own image w periods
+further along z, it conducts round the ring and has zmin = 0, zmax = nz-1 -- and the logged percolation, trapped cells and ganglia are
+defined through the winding (with winding_R / winding_B, the largest of each phase).  The morphology table counts what reaches from plane
+nz-1 up into plane 0.  /Clusters/WrapZ = 1 and /Morphology/WrapZ = 1 mark the groups; without the flag neither they nor a Winding dataset
+exist and the file is what it was.  Windings along x and y are not computed.
 """
 import os
 
@@ -212,7 +223,7 @@ class RKColorGradient3D:
                  structure_path=None, initial_dir=None, record_pdf=False, restart_from=None, checkpoint_every=0, csf_bulk_epsilon=0.0,
                  csf_transport=None, integrals_every=0, clusters_every=0, clusters_connectivity=6, morphology_every=0,
                  morphology_phi_cut=0.0, clusters_props=False, steady_every=0, steady_tol=0.0, steady_phase_tol=None, contact_angle_solids=None,
-                 body_force=None):
+                 body_force=None, analyses_wrap_z=False):
         self.pathIni = pathIniFile
         self.par = config.read_rk3d(pathIniFile)
         # periodic z (3-D CSF only; BoundaryTypeInlet = BoundaryTypeOutlet = 'Periodic'): no open planes -- the mask is taken as given
@@ -249,6 +260,10 @@ class RKColorGradient3D:
         if self.steady_tol > 0 and self.steady_every <= 0:
             raise config.ConfigError("steady_tol = %g needs steady_every > 0: the cadence at which the criterion is looked at" % self.steady_tol)
         self.steady_step = None         # the step at which the criterion was met
+        # periodic z only, opt-in: the clusters and morphology tasks close the seam between plane nz-1 and plane 0 (wrap_z=True)
+        self.analyses_wrap_z = bool(analyses_wrap_z)
+        if self.analyses_wrap_z and not self.periodic_z:
+            raise config.ConfigError("analyses_wrap_z closes the seam of a run that is periodic in z: BoundaryTypeInlet = BoundaryTypeOutlet = 'Periodic'")
         self.gather_records = True
         self.records = 0
         self.physicalVX = self.physicalVY = self.physicalVZ = None
@@ -514,13 +529,16 @@ class RKColorGradient3D:
             return False
         self.steady_criteria, self.steady_step = [], None
         here, ckw = h.rank == 0, (dict(props=True) if self.clusters_props else {})
+        wrap = dict(wrap_z=True) if self.analyses_wrap_z else {}          # (absent by default: the perturbation model's handle is called as ever)
+        marked = lambda: [("WrapZ", np.array([1], dtype=np.int64))] if self.analyses_wrap_z else []
         return [
             self._integrals_task(h),
-            PeriodicTask(self, self.clusters_every, ("Clusters", "PhaseClusters"), here, lambda: h.clusters(connectivity=self.clusters_connectivity, **ckw),
-                         "clusters", "cluster_steps", datasets=(("TableAtStep%d", "table"), ("PropsAtStep%d", "props")), report=log("clusters"),
-                         closing=lambda: [("Columns", cluster_column_bytes())] + ([("PropColumns", prop_column_bytes())] if self.clusters_props else [])),
-            PeriodicTask(self, self.morphology_every, ("Morphology", "PhaseMorphology"), here, lambda: h.morphology(self.morphology_phi_cut),
-                         "morphology", "morphology_steps", report=log("morphology"), closing=lambda: [("Columns", morphology_column_bytes())]),
+            PeriodicTask(self, self.clusters_every, ("Clusters", "PhaseClusters"), here, lambda: h.clusters(connectivity=self.clusters_connectivity, **ckw, **wrap),
+                         "clusters", "cluster_steps", datasets=(("TableAtStep%d", "table"), ("PropsAtStep%d", "props"), ("WindingAtStep%d", "winding")),
+                         report=log("clusters"),
+                         closing=lambda: [("Columns", cluster_column_bytes())] + ([("PropColumns", prop_column_bytes())] if self.clusters_props else []) + marked()),
+            PeriodicTask(self, self.morphology_every, ("Morphology", "PhaseMorphology"), here, lambda: h.morphology(self.morphology_phi_cut, **wrap),
+                         "morphology", "morphology_steps", report=log("morphology"), closing=lambda: [("Columns", morphology_column_bytes())] + marked()),
             # the steady-state monitor: only multiples of its cadence, the first visit marks, its verdict ends the run before that step's record
             PeriodicTask(self, self.steady_every, ("Steady", "SteadyState"), here, h.change, "change", "steady_steps", report=steady, mark=h.mark_change,
                          before_record=True, only_multiples=True,

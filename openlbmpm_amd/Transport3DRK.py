@@ -28,7 +28,8 @@ and tracer -- mass balances, the breakthrough -flux_z at the outlet, the plume's
 [nz][nT][9], /TracerIntegrals/Steps and /TracerIntegrals/Columns of ConcentrationResults.h5.  Both counts of non-finite cells meet the
 nan_guard rule at that cadence (collective under torchrun; rank 0 writes), masses and extrema go to the log.  N = 0 writes no group and
 adds no stop; the records and checkpoints of a run do not depend on N.  The flow driver's other cadences (clusters_every,
-morphology_every, steady_every) are accepted by the constructor and not acted on: this driver runs the two integrals tasks only.
+morphology_every, steady_every, and analyses_wrap_z with them) are accepted by the constructor and not acted on: this driver runs the two
+integrals tasks only.
 """
 import numpy as np
 

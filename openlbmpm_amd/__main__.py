@@ -16,6 +16,8 @@
                                                   (/Clusters/PropsAtStep<step>); ganglia and mobile ganglia to the log
         [--morphology-every N]                    rk3d: cells, class pairs, squares and cubes per plane, counted on the device, every N steps (/Morphology
         [--morphology-phi-cut c]                  of the result file); interfacial area, wetted fraction, Euler characteristics, capillary pressure to the log
+        [--wrap-z]                                rk3d with periodic z: --clusters-every / --morphology-every close the seam between plane nz-1 and plane 0
+                                                  (a cluster across it is one row, /Clusters/WindingAtStep<step>; percolation = a cluster that winds)
         [--contact-angles FILE]                   rk3d with SurfaceTensionType = 'CSF', tr3d: mixed wettability -- a .npy of contact angles per solid voxel
                                                   (the lattice's shape, or the voxel file's; NaN = the ini's ContactAngle); /Wettability/ContactAngle
         [--body-force GX GY GZ]                   rk3d with SurfaceTensionType = 'CSF', tr3d: an acceleration in lattice units for both colours (gravity,
@@ -83,6 +85,11 @@ def parser():
                     help="rk3d: every N steps the phase morphology (cells, density sums, class pairs, squares and cubes per plane), counted on the device, "
                          "to /Morphology of the result file; interfacial area, wetted fraction, Euler characteristics and capillary pressure to the log; 0: off")
     ap.add_argument("--morphology-phi-cut", type=float, default=0.0, metavar="c", help="rk3d: cells with |phi| within c of 0 belong to neither phase")
+    ap.add_argument("--wrap-z", action="store_true",
+                    help="rk3d with periodic z (BoundaryTypeInlet = BoundaryTypeOutlet = 'Periodic'), with --clusters-every / --morphology-every: close the "
+                         "seam between plane nz-1 and plane 0 -- a cluster across it is one row (zmax may exceed nz-1), /Clusters/WindingAtStep<step> says "
+                         "by how many periods a cluster is connected to its own image (0: a ganglion), the morphology counts across the seam; "
+                         "/Clusters/WrapZ and /Morphology/WrapZ = 1")
     ap.add_argument("--steady-every", type=int, default=0, metavar="N",
                     help="rk3d: at every multiple of N steps the change of the velocity and the phase field since the multiple before (per plane: squared "
                          "changes by phase, cells that changed colour, largest changes), reduced on the device against a snapshot kept there, to /Steady "
@@ -122,7 +129,7 @@ def main(argv=None):
                                 clusters_every=a.clusters_every, clusters_connectivity=a.clusters_connectivity, clusters_props=a.clusters_props,
                                 morphology_every=a.morphology_every, morphology_phi_cut=a.morphology_phi_cut, steady_every=a.steady_every,
                                 steady_tol=a.steady_tol, steady_phase_tol=a.steady_phase_tol, contact_angle_solids=a.contact_angles,
-                                body_force=_body_force(a))
+                                body_force=_body_force(a), analyses_wrap_z=a.wrap_z)
         if a.steps is not None:
             sim.timeSteps = a.steps
         path = sim.runRKColorGradient3D()

@@ -13,6 +13,18 @@ import numpy as np
 from .integrals import fresh
 
 
+def ring_asked(self, wrap_z, whole=True):
+    """wrap_z of clusters() / morphology() as a bool; ValueError, before anything is launched, unless the object is periodic in z
+    (periodic_z: the 3-D CSF classes say so) and -- one context -- holds the whole lattice"""
+    if not wrap_z:
+        return False
+    if not getattr(self, "periodic_z", False):
+        raise ValueError("wrap_z=True closes the seam of a lattice that is periodic in z (3-D CSF, inlet = outlet = 'Periodic'): %s is not" % type(self).__name__)
+    if not whole:
+        raise ValueError("wrap_z=True on one slab of a cut lattice: the seam is closed where the slabs are joined (the cluster's or the distributed class)")
+    return True
+
+
 class SlabAnalysisCalls:
     """One context.  The class has the library in _L, its context in _h, the C prefix in _C_PREFIX ("lbmpm_rk3d" | "lbmpm_rk3dcsf"), the
     plane's extent in nx, ny, the number of its own planes in own_planes (a slab: without ghost or halo planes) and the planes of the
@@ -58,13 +70,26 @@ class SlabAnalysisCalls:
         from .clusters import props_table
         return props_table(self._L, self._C_PREFIX, self._h, count, self.ny, self.nx, below, above)
 
-    def clusters(self, phi_cut=0.0, connectivity=6, labels=False, props=False):
+    def clusters(self, phi_cut=0.0, connectivity=6, labels=False, props=False, wrap_z=False):
         """clusters.Clusters of the own planes: the connected cells of each phase of phi, labelled on the device (lbmpm_*_clusters).
-        props=True: with the property table (faces, elements, plane sum, mass and momentum per cluster), reduced on the device"""
-        from .clusters import Clusters
-        got = self.clusters_part(phi_cut, connectivity, labels, faces=False)
-        table = self.cluster_props_part(got["table"].shape[0]) if props else None
-        return Clusters(got["table"], self.nx, self.ny, self.lattice_nz, got.get("labels"), table)
+        props=True: with the property table (faces, elements, plane sum, mass and momentum per cluster), reduced on the device.
+        wrap_z=True (periodic z, the whole lattice in this context; else ValueError): the seam between plane nz - 1 and plane 0 is
+        closed -- the same launches, the property table reduced with the context's own face planes beside it, then clusters.close_seam
+        on the table and the two face planes: a cluster across the seam is one row, every row has its winding"""
+        from .clusters import Clusters, close_seam, relabel
+        if not ring_asked(self, wrap_z, self.own_planes == self.lattice_nz):
+            got = self.clusters_part(phi_cut, connectivity, labels, faces=False)
+            table = self.cluster_props_part(got["table"].shape[0]) if props else None
+            return Clusters(got["table"], self.nx, self.ny, self.lattice_nz, got.get("labels"), table)
+        got = self.clusters_part(phi_cut, connectivity, labels, faces=True)
+        opened = None
+        if props:
+            own = self.cluster_props_face()
+            opened = self.cluster_props_part(got["table"].shape[0], below=own[1], above=own[0])
+        table, winding, mapping, closed = close_seam(got["table"], got["face_labels"], got["face_classes"], self.nx, self.ny, self.lattice_nz,
+                                                     connectivity, opened)
+        return Clusters(table, self.nx, self.ny, self.lattice_nz, relabel(got["labels"], mapping) if labels else None, closed,
+                        winding=winding, wrap_z=True)
 
     def morphology_face(self, phi_cut=0.0):
         """[ny][nx] uint8: the classes of the lowest own plane -- what the slab below passes to morphology_part as `above`"""
@@ -77,10 +102,12 @@ class SlabAnalysisCalls:
         from .morphology import table
         return table(self._L, self._C_PREFIX, self._h, self.own_planes, self.ny, self.nx, phi_cut, above)
 
-    def morphology(self, phi_cut=0.0):
-        """morphology.Morphology of the own planes: cells, class pairs, squares and cubes, counted on the device (lbmpm_*_morphology)"""
+    def morphology(self, phi_cut=0.0, wrap_z=False):
+        """morphology.Morphology of the own planes: cells, class pairs, squares and cubes, counted on the device (lbmpm_*_morphology).
+        wrap_z=True (periodic z, the whole lattice in this context; else ValueError): plane 0 is the plane above plane nz - 1"""
         from .morphology import Morphology
-        return Morphology(self.morphology_part(phi_cut), self.nx, self.ny)
+        above = self.morphology_face(phi_cut) if ring_asked(self, wrap_z, self.own_planes == self.lattice_nz) else None
+        return Morphology(self.morphology_part(phi_cut, above), self.nx, self.ny)
 
 
 class StackedAnalysis:
@@ -104,21 +131,25 @@ class StackedAnalysis:
         t, steps = fresh(lambda: stacked(self.slabs, remark), self._refresh)
         return Change(t, self.nx, self.ny, steps)
 
-    def clusters(self, phi_cut=0.0, connectivity=6, labels=False, props=False):
+    def clusters(self, phi_cut=0.0, connectivity=6, labels=False, props=False, wrap_z=False):
         """clusters.Clusters of the whole lattice: the slabs' tables joined through their face planes.  props=True: with the property
-        table -- the slabs hand each other their class planes, every slab reduces its own rows, the rows are added"""
+        table -- the slabs hand each other their class planes, every slab reduces its own rows, the rows are added.  wrap_z=True
+        (periodic z; else ValueError): the stack is a ring -- the end slabs hand each other their planes too, and the seam is closed on
+        the joined table (clusters.close_seam)"""
         from .clusters import merged, stacked_props
+        ring = ring_asked(self, wrap_z)
 
         def take():
             parts = [s.clusters_part(phi_cut, connectivity, labels) for s in self.slabs]
-            return stacked_props(self.slabs, parts) if props else parts
-        return merged(fresh(take, self._refresh), self.nx, self.ny, self.nz, connectivity, labels)
+            return stacked_props(self.slabs, parts, ring) if props else parts
+        return merged(fresh(take, self._refresh), self.nx, self.ny, self.nz, connectivity, labels, ring)
 
-    def morphology(self, phi_cut=0.0):
+    def morphology(self, phi_cut=0.0, wrap_z=False):
         """morphology.Morphology of the whole lattice: every slab joins the lowest own plane of the slab over it on its device, the top
-        slab nothing -- z does not wrap here, whatever the flow does"""
+        slab nothing -- or, with wrap_z=True (periodic z; else ValueError), the lowest plane of the bottom slab"""
         from .morphology import Morphology, stacked
-        return Morphology(fresh(lambda: stacked(self.slabs, phi_cut), self._refresh), self.nx, self.ny)
+        ring = ring_asked(self, wrap_z)
+        return Morphology(fresh(lambda: stacked(self.slabs, phi_cut, ring), self._refresh), self.nx, self.ny)
 
 
 class GatheredAnalysis:
@@ -145,11 +176,13 @@ class GatheredAnalysis:
         t = self.gather(part)
         return None if t is None else Change(t, self.nx, self.ny, steps)
 
-    def clusters(self, phi_cut=0.0, connectivity=6, labels=False, props=False):
+    def clusters(self, phi_cut=0.0, connectivity=6, labels=False, props=False, wrap_z=False):
         """clusters.Clusters of the whole lattice: the ranks' tables and face planes, joined on rank 0 (with labels=True the label planes
         too).  props=True: with the property table -- one all_gather of 2 ny nx class bytes first, every rank reduces its own rows, rank
-        0 adds them"""
+        0 adds them.  wrap_z=True (periodic z; else ValueError on every rank): the ranks are a ring -- the same all_gather hands rank 0
+        the last rank's plane and the last rank rank 0's, and rank 0 closes the seam on the joined table (clusters.close_seam)"""
         from .clusters import faces_from_neighbours, gather_merged
+        ring = ring_asked(self, wrap_z)
 
         def take():
             part = self.slab.clusters_part(phi_cut, connectivity, labels)
@@ -158,15 +191,17 @@ class GatheredAnalysis:
             return part
         part = fresh(take, self._refresh)
         if props:
-            below, above = faces_from_neighbours(part.pop("props_face"), self.rank, self.world, self.group, self.device_index)
+            below, above = faces_from_neighbours(part.pop("props_face"), self.rank, self.world, self.group, self.device_index, ring)
             part["props"] = self.slab.cluster_props_part(part["table"].shape[0], below, above)
-        return gather_merged(part, self.rank, self.world, self.group, self.nx, self.ny, self.nz, connectivity, labels)
+        return gather_merged(part, self.rank, self.world, self.group, self.nx, self.ny, self.nz, connectivity, labels, ring)
 
-    def morphology(self, phi_cut=0.0):
+    def morphology(self, phi_cut=0.0, wrap_z=False):
         """morphology.Morphology of the whole lattice: every rank takes the lowest class plane of the rank above it (one all_gather of
-        [ny][nx] bytes) and joins on its device; the tables through gather()"""
+        [ny][nx] bytes) and joins on its device; the tables through gather().  wrap_z=True (periodic z; else ValueError on every rank):
+        the last rank takes rank 0's plane out of the same all_gather"""
         from .morphology import Morphology, face_from_above
+        ring = ring_asked(self, wrap_z)
         mine = fresh(lambda: self.slab.morphology_face(phi_cut), self._refresh)
-        above = face_from_above(mine, self.rank, self.world, self.group, self.device_index)
+        above = face_from_above(mine, self.rank, self.world, self.group, self.device_index, ring)
         t = self.gather(self.slab.morphology_part(phi_cut, above))
         return None if t is None else Morphology(t, self.nx, self.ny)

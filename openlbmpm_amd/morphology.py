@@ -3,7 +3,8 @@ definition) and the state variables that two-phase theory adds to saturation -- 
 areas, the Euler characteristic of each phase and a phase-averaged pressure difference: a Pc-S-a_nw sample without a field download.
 
 The library classifies every cell (S solid, R, B, N neither) and counts, per plane, the cells, the pairs along every axis by their
-classes and the 2 x 2 squares and 2 x 2 x 2 cubes of one phase, each anchored at its lowest corner; x and y wrap, z does not.  The
+classes and the 2 x 2 squares and 2 x 2 x 2 cubes of one phase, each anchored at its lowest corner; x and y wrap, z does not unless
+asked to (wrap_z=True on a lattice that is periodic in z: plane 0 is then the plane above plane nz - 1, through the same `above`).  The
 counts are integers and the two density sums are added in a fixed order, so a table is the same bit for bit however the lattice was
 cut into slabs: a slab passes the classes of its lowest plane (`face`) to the slab below it, which joins on its device.
 """
@@ -140,21 +141,22 @@ def table(L, prefix, handle, planes, ny, nx, phi_cut=0.0, above=None):
     return out
 
 
-def stacked(slabs, phi_cut):
-    """the slabs of one process, lowest first: every slab gets the face of the slab over it, the top one None; [nz][28]"""
-    faces = [s.morphology_face(phi_cut) for s in slabs[1:]] + [None]
+def stacked(slabs, phi_cut, ring=False):
+    """the slabs of one process, lowest first: every slab gets the face of the slab over it, the top one None (ring: the lowest slab's);
+    [nz][28]"""
+    faces = [s.morphology_face(phi_cut) for s in slabs[1:]] + [slabs[0].morphology_face(phi_cut) if ring else None]
     return np.concatenate([s.morphology_part(phi_cut, up) for s, up in zip(slabs, faces)], axis=0)
 
 
-def face_from_above(mine, rank, world, group, device):
-    """collective: every rank gives the face of its slab and takes that of rank + 1 (None on the last): one all_gather of [ny][nx]
-    bytes, through device memory under nccl, host memory under gloo"""
+def face_from_above(mine, rank, world, group, device, ring=False):
+    """collective: every rank gives the face of its slab and takes that of rank + 1 (None on the last; ring: rank 0's): one all_gather
+    of [ny][nx] bytes, through device memory under nccl, host memory under gloo; a world of one: none (ring: its own face)"""
     if world == 1:
-        return None
+        return np.asarray(mine) if ring else None
     import torch
     import torch.distributed as dist
     dev = torch.device("cuda", device) if dist.get_backend(group) == "nccl" else torch.device("cpu")
     t = torch.from_numpy(np.ascontiguousarray(mine, dtype=np.uint8)).to(dev)
     every = [torch.empty_like(t) for _ in range(world)]
     dist.all_gather(every, t, group=group)
-    return every[rank + 1].cpu().numpy() if rank + 1 < world else None
+    return every[(rank + 1) % world].cpu().numpy() if rank + 1 < world or ring else None

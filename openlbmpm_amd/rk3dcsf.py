@@ -92,8 +92,8 @@ class RK3DCSFSolver(SlabTransportCalls, SlabAnalysisCalls):
         wrapping around its ends, like the rest).
         params: DEFAULT_PARAMS' keys.  inlet="Periodic" with outlet="Periodic" (both or neither, else ValueError) is periodic z: no open
         planes, every plane wraps like x and y, the mask is taken as given (nz >= 4) and velocityZ*, density* are not read; self.periodic_z
-        says so.  Tracers then take neither dirichlet_inlet nor free_outlet (LbmpmError, LBMPM_ERR_INVALID), and clusters() / morphology()
-        still do not wrap z.
+        says so.  Tracers then take neither dirichlet_inlet nor free_outlet (LbmpmError, LBMPM_ERR_INVALID).  clusters() / morphology()
+        by default still take plane nz-1 and plane 0 as ends of the lattice; wrap_z=True closes the seam (analysis.py, clusters.close_seam).
         tracers = dict(<the keyword arguments of configure_tracers>): the D3Q7 tracers, configured at construction.  On a slab this is the
         only way to them (lbmpm_rk3dcsf_tracer_configure_slab): their populations travel inside the population message, so every slab of
         the ring is given the same dict, before a transport is connected."""
