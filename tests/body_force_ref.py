@@ -105,9 +105,13 @@ class BodyForceRef:
             v[self.fl] = v[self.fl] + 0.5 * Fb[a][self.fl] / rho[self.fl]
         return Fb
 
-    def step(self):
+    def step(self, hook=None):
+        """hook: called once, between the two halves -- after step_a() has put the force's half into u, before rk3dcsf_step_b: the
+        moment the solver's tracer sub-step reads rho_R, u and G (tests/tr3d_ref.py).  It reads; the recipe's bits do not depend on it"""
         fl = self.fl
         Fb = self.step_a()
+        if hook is not None:
+            hook()
         rR, rB = self._view("rhoR").copy(), self._view("rhoB").copy()
         u = [self._view(c).copy() for c in ("vx", "vy", "vz")]
         phi = self._view("phi").copy()
@@ -152,9 +156,9 @@ class BodyForceRef:
         self.steps += 1
         return self
 
-    def run(self, n):
+    def run(self, n, hook=None):
         for _ in range(int(n)):
-            self.step()
+            self.step(hook)
         return self
 
 

@@ -40,11 +40,16 @@ class PeriodicRef:
         par = {k: v for k, v in (params or {}).items() if k not in FLOW_KEYS}
         self.dom = np.ascontiguousarray(dom, dtype=np.uint8)
         self.fl = self.dom == 1
+        self.g_r, self.g_b = np.asarray(g_r, dtype=np.float64), np.asarray(g_b, dtype=np.float64)
         self.ref = R.BodyForceRef(swap(self.dom), swap(rhoR0), swap(rhoB0), par, tuple(g_r)[::-1], tuple(g_b)[::-1], crisp=crisp)
 
-    def run(self, n):
-        self.ref.run(n)
+    def run(self, n, hook=None):
+        """hook: BodyForceRef.step's, handed through; when it is called field() gives rhoR, vx .. Gz of that moment in the solver's axes"""
+        self.ref.run(n, hook)
         return self
+
+    def step(self, hook=None):
+        return self.run(1, hook)
 
     def step_a(self):
         self.ref.step_a()

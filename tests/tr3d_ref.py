@@ -40,7 +40,9 @@ def _shift(a, e):
 
 
 class Tracer3DRef:
-    def __init__(self, dom, conc0, tracer=None, pdf0=None):
+    def __init__(self, dom, conc0, tracer=None, pdf0=None, seam_wall=False):
+        """seam_wall = True: nothing is pulled across the seam between plane nz-1 and plane 0; the populations that would cross it bounce
+        back there (a negative control: a tracer step that forgot to wrap z)"""
         t = dict(DEFAULT_TRACER3D); t.update(tracer or {})
         self.t = t
         self.dom = np.asarray(dom) == 1
@@ -60,6 +62,8 @@ class Tracer3DRef:
         self.C = self._conc()
         # where the neighbour in direction i is fluid
         self.to_fluid = [self.dom & _shift(self.dom, -E[i]) for i in range(7)]
+        if seam_wall:
+            self.to_fluid[5][-1] = False; self.to_fluid[6][0] = False
 
     def _conc(self):
         c = np.zeros((self.nT,) + self.dom.shape)
@@ -111,27 +115,41 @@ class Tracer3DRef:
 
 
 class Coupled3DRef:
-    """oracle/rk3d_csf_oracle.c's flow with the restated tracer sub-step spliced between its two halves (after the wetting-corrected
-    colour gradient, before the CSF force); after_b = True: spliced after the second half instead (the negative control)"""
+    """A flow reference with the restated tracer sub-step spliced between the two halves of its step (after the wetting-corrected colour
+    gradient, before the CSF force); after_b = True: spliced after the second half instead (the negative control).
+    The flow is oracle/rk3d_csf_oracle.c's (rhoR0, rhoB0, flow_params), or `flow`: a tests/body_force_ref.BodyForceRef or a
+    tests/periodic_ref.PeriodicRef made by the caller -- anything with dom, field(name) in the solver's axes and step(hook), which calls
+    the hook between its halves with the body force's half in u.  The sub-step runs in the solver's axes either way.
+    alter: f(fields, self) -> fields, applied to [rhoR, vx, vy, vz, Gx, Gy, Gz] before the sub-step reads them (negative controls)"""
 
-    def __init__(self, dom, rhoR0, rhoB0, conc0, flow_params=None, tracer=None):
-        from oracle.rk3dcsf import RK3DCSFOracle
-        self.flow = RK3DCSFOracle(dom, rhoR0, rhoB0, flow_params)
-        self.tr = Tracer3DRef(dom, conc0, tracer)
+    def __init__(self, dom, rhoR0=None, rhoB0=None, conc0=None, flow_params=None, tracer=None, flow=None, alter=None, seam_wall=False):
+        if flow is None:
+            from oracle.rk3dcsf import RK3DCSFOracle
+            flow = RK3DCSFOracle(dom, rhoR0, rhoB0, flow_params)
+        self.flow = flow
+        self.tr = Tracer3DRef(dom, conc0, tracer, seam_wall=seam_wall)
+        self.alter = alter
         self.steps = 0
 
     def _fields(self):
-        return [self.flow.field(n) for n in ("rhoR", "vx", "vy", "vz", "Gx", "Gy", "Gz")]
+        f = [self.flow.field(n) for n in ("rhoR", "vx", "vy", "vz", "Gx", "Gy", "Gz")]
+        return self.alter(f, self) if self.alter else f
+
+    def _substep(self):
+        self.tr.substep(*self._fields())
 
     def run(self, n, after_b=False):
         f = self.flow
         for _ in range(int(n)):
-            f._L.rk3dcsf_step_a(C.byref(f._s))
-            if not after_b:
-                self.tr.substep(*self._fields())
-            f._L.rk3dcsf_step_b(C.byref(f._s))
+            if hasattr(f, "step"):
+                f.step(None if after_b else self._substep)
+            else:
+                f._L.rk3dcsf_step_a(C.byref(f._s))
+                if not after_b:
+                    self._substep()
+                f._L.rk3dcsf_step_b(C.byref(f._s))
             if after_b:
-                self.tr.substep(*self._fields())
+                self._substep()
             self.steps += 1
         return self
 
