@@ -927,6 +927,45 @@ enum { LBMPM_TRINT_CELLS = 0, LBMPM_TRINT_MASS, LBMPM_TRINT_FLUX_X, LBMPM_TRINT_
  * partials is allocated by the first call.  LBMPM_ERR_STATE before lbmpm_rk3dcsf_tracer_configure(_slab) and before a concentration or
  * populations were set.  One stream synchronisation, planes * num_tracers * 72 bytes copied */
 int lbmpm_rk3dcsf_tracer_integrals(lbmpm_rk3dcsf *ctx, double *out);
+/* Reaction at solid walls (not in the reference, which bounces every tracer population back unchanged): the linear surface reaction
+ * D dC/dn = k C_wall as a reactive bounce-back inside the pull of the tracer sub-step.  For a fluid cell x and a direction i in 1 .. 6
+ * whose source cell x - e_i is solid, the pull takes g_i = r g*_OPP[i](x) in the place of g*_OPP[i](x), with r = (1 - 3 k) / (1 + 3 k)
+ * and k >= 0 the surface rate of that tracer at that solid voxel in lattice units (a velocity: cells per step; the Damkoehler number of a
+ * pore of width H is k H / D).  It follows from the link's wall concentration C_w = (g_out + g_in) / (2 w) = 3 (g_out + g_in) and the
+ * flux into the wall g_out - g_in = k C_w; the wall sits half-way, where the scheme is second order.  k = 0 gives r = 1.0, an exact
+ * product: the fields stay bit-equal to a run without the call.  k = inf gives r = -1, the instantaneous reaction C_w = 0.  r is
+ * computed on the host in double by exactly that expression.  The first pull after the state was given takes the populations where they
+ * stand and has no wall event; the Inamuro inlet and the free outlet's plane copy stay as they are; a solid across a slab cut reacts like
+ * any other (the messages do not change).  A context without a wall reaction launches the kernels it launched before.
+ * rates: [num_classes][num_tracers], 1 <= num_classes <= 8; minerals: one class byte per cell of the context's lattice [nz][ny][nx] (a
+ * slab: with its ghost planes, cut like is_domain), read at the solid cells and ignored elsewhere, or NULL with num_classes == 1 (every
+ * solid is class 0).  While a map is set the context holds 4 bytes per fluid cell more (device_bytes), none otherwise.
+ * rates == NULL switches the reaction off and releases the map.  Whenever the context is idle, repeatedly, like
+ * lbmpm_rk3dcsf_set_body_force: the state, the step counter, the contact angles, the body force and the snapshot of lbmpm_rk3dcsf_change
+ * stay, and lbmpm_rk3dcsf_tracer_set_concentration / _set_pdf keep it; a restart in a new context gives it again.  The rate belongs to
+ * the pull: the observers (tracer_get_concentration, _get_pdf, _integrals, _wall_integrals) called after a change see the new rate's
+ * pull of the stored populations.  It is deliberately NOT a field of lbmpm_tracer3d_config, like the body force.
+ * LBMPM_ERR_STATE: before lbmpm_rk3dcsf_tracer_configure(_slab), between the stages of a step; LBMPM_ERR_INVALID, nothing changed: a rate
+ * that is negative or NaN, num_classes outside 1 .. 8, a class >= num_classes at a solid cell (the message names the first one), NULL
+ * minerals with more than one class */
+int lbmpm_rk3dcsf_tracer_set_wall_reaction(lbmpm_rk3dcsf *ctx, int num_classes, const double *rates, const uint8_t *minerals);
+/* the rates in force, rates_out [8][num_tracers] (classes beyond those given: zeros; all zeros without a wall reaction), and through
+ * num_classes_out (may be NULL) the number of classes given, 0 without one */
+int lbmpm_rk3dcsf_tracer_get_wall_reaction(const lbmpm_rk3dcsf *ctx, int *num_classes_out, double *rates_out);
+/* The uptake at the walls: for every plane z the context owns and every tracer, LBMPM_TRWALL_COLS doubles over the plane's fluid cells
+ * and their wall links ((cell, direction) pairs whose source cell is solid), with g_out = g*_OPP[i](x) the stored population that left for
+ * the wall and g_in = r g_out as the pull computes it.  Reduced like lbmpm_rk3dcsf_tracer_integrals: the same bits however the lattice is
+ * cut.  It reads the stored populations and the table of source cells alone -- the step accumulates nothing.
+ *   LINKS the wall links | UPTAKE sum of g_out - g_in: what the walls took in the last completed sub-step, so that
+ *   mass(step n - 1) - mass(step n) of lbmpm_rk3dcsf_tracer_integrals is the sum of UPTAKE after step n where nothing else adds or removes
+ *   tracer | C sum of 3 (g_out + g_in), the wall concentrations of the links (C / LINKS: their mean) | NONFINITE cells with a population
+ *   that is not finite among those read: such a cell counts here and in LINKS and contributes to nothing else
+ * Before the first step after the state was given no wall event has happened: UPTAKE, C and NONFINITE are 0.  Valid with tracers
+ * configured and a state given, with or without a wall reaction (r = 1: an UPTAKE of exactly 0). */
+enum { LBMPM_TRWALL_LINKS = 0, LBMPM_TRWALL_UPTAKE, LBMPM_TRWALL_C, LBMPM_TRWALL_NONFINITE };
+#define LBMPM_TRWALL_COLS 4
+/* out: host [own planes][num_tracers][LBMPM_TRWALL_COLS].  One stream synchronisation, planes * num_tracers * 32 bytes copied */
+int lbmpm_rk3dcsf_tracer_wall_integrals(lbmpm_rk3dcsf *ctx, double *out);
 
 /* ---- 3-D CSF slabs: the three face messages over a transport INSIDE the library (the perturbation model's transports above, "Transport
  * of the slab exchange": IPC landing areas filled by copy-engine transfers + stream value operations, or ncclSend / ncclRecv of a librccl

@@ -30,12 +30,20 @@ nan_guard rule at that cadence (collective under torchrun; rank 0 writes), masse
 adds no stop; the records and checkpoints of a run do not depend on N.  The flow driver's other cadences (clusters_every,
 morphology_every, steady_every, and analyses_wrap_z with them) are accepted by the constructor and not acted on: this driver runs the two
 integrals tasks only.
+
+wall_reaction= / [Reaction] WallReactionRate: the tracers' first-order reaction at solid walls (RK3DCSFSolver.set_wall_reaction;
+include/lbmpm.h) -- rates k >= 0 in lattice units, a number, one per tracer, or [classes][nT] with wall_minerals= / [Reaction]
+WallMineralFile, the class byte of every solid voxel (an array or a .npy in the lattice's shape, or the voxel file's).  Independent of
+[SystemType] Reaction.  ConcentrationResults.h5 gets /WallReaction/Rates [classes][nT] once, and with integrals_every the uptake table
+(integrals.TracerWallIntegrals: wall_links, uptake, wall_c, nonfinite per plane and tracer) as /TracerWallIntegrals/PlanesAtStep<step>
+[nz][nT][4], /Steps and /Columns, one more task at the tracers' cadence.  A checkpoint does not hold the rates: restart_from= applies
+them again.  Without the option the files are what they were.
 """
 import numpy as np
 
 from . import config, runloop
 from .RKColorGradientD3Q19 import RKColorGradient3D, _CSFSlab
-from .integrals import tracer_column_bytes
+from .integrals import tracer_column_bytes, tracer_wall_column_bytes
 from .results import RecordGuard, ResultFile
 from .runloop import PeriodicTask
 
@@ -51,6 +59,7 @@ class _CSFTracerSlab(_CSFSlab):
                        free_outlet=t["outlet_type"] == "Freeflow", reaction_rate=t["reaction_rate"], diffusion_j=tuple(t["diffJ3"]))
         _CSFSlab.__init__(self, dom, par, device, bulk_epsilon, distributed=distributed, transport=transport, tracers=tracers)
         self.tracer_integrals = self.solver.tracer_integrals
+        self.tracer_wall_integrals = self.solver.tracer_wall_integrals
 
     def get_state(self):
         st, info = _CSFSlab.get_state(self)
@@ -68,11 +77,64 @@ class _CSFTracerSlab(_CSFSlab):
 
 
 class Transport3DRK(RKColorGradient3D):
-    def __init__(self, pathIniFile, initial_concentration=None, **kw):
+    def __init__(self, pathIniFile, initial_concentration=None, wall_reaction=None, wall_minerals=None, **kw):
         RKColorGradient3D.__init__(self, pathIniFile, **kw)
         self.tr = config.read_transport3d(pathIniFile, periodic_z=self.periodic_z)      # (periodic z: no Dirichlet inlet, no Freeflow outlet)
         self.numTracers = self.tr["num_tracers"]
         self._initial_concentration = initial_concentration
+        # the reaction at solid walls: rates [classes][nT] (a number, [nT] or [classes][nT]) and the solid voxels' classes, an array or the
+        # path of a .npy file; None: the ini's [Reaction] WallReactionRate / WallMineralFile, if any
+        self.wall_reaction = self._wall_reaction_arg(wall_reaction) if wall_reaction is not None else self.tr["wall_reaction"]
+        self.wall_minerals = wall_minerals if wall_minerals is not None else (self.tr["wall_mineral_file"] if wall_reaction is None else None)
+        if self.wall_minerals is not None and self.wall_reaction is None:
+            raise config.ConfigError("wall_minerals without wall_reaction: the classes belong to the rates")
+        if self.wall_reaction is not None and len(self.wall_reaction) > 1 and self.wall_minerals is None:
+            raise config.ConfigError("wall_reaction gives %d classes: wall_minerals says which solid voxel is of which" % len(self.wall_reaction))
+        if self.wall_reaction is not None and self.par["tension_type"] != "CSF":
+            raise config.ConfigError("wall_reaction belongs to the D3Q7 tracers of SurfaceTensionType = 'CSF': the perturbation model carries no tracers")
+
+    def _wall_reaction_arg(self, rates):
+        a = np.asarray(rates, dtype=np.float64)
+        if a.ndim > 2 or (a.ndim == 2 and a.shape[1] != self.numTracers):
+            raise config.ConfigError("wall_reaction: a number, %d numbers (one per tracer) or [classes][%d], not shape %s" % (self.numTracers, self.numTracers, a.shape))
+        flat = np.full(self.numTracers, float(a)) if a.ndim == 0 else a.reshape(-1)
+        return config.wall_reaction_rates(flat.tolist(), self.numTracers)
+
+    def solid_minerals(self):
+        """wall_minerals on the lattice [nz][ny][nx] as class bytes (class 0 where the file does not reach: buffer planes, forced side
+        walls), or None; after initializeDomainBorder"""
+        import os
+        m = self.wall_minerals
+        if m is None:
+            return None
+        if isinstance(m, (str, os.PathLike)):
+            if not os.path.isfile(m):
+                raise config.ConfigError("wall minerals: file %s not found" % m)
+            m = np.load(m)
+        m = np.asarray(m)
+        if m.dtype.kind not in "ui" or m.size and (m.min() < 0 or m.max() > 7):
+            raise config.ConfigError("wall minerals: one class 0 .. 7 per voxel (an integer array)")
+        m = m.astype(np.uint8)
+        voxels = getattr(self, "_voxels", None) if self._domain is None else None
+        if voxels is not None:         # framed like the voxel file (geometry.voxel_domain): buffer planes below and above
+            if m.shape != np.shape(voxels):
+                raise config.ConfigError("wall minerals have shape %s, the voxel file %s" % (m.shape, np.shape(voxels)))
+            buf = np.zeros((self._image_buffer,) + m.shape[1:], dtype=np.uint8)
+            m = np.concatenate([buf, m, buf], axis=0)
+        if m.shape != self.isDomain.shape:
+            raise config.ConfigError("wall minerals have shape %s, the lattice %s" % (m.shape, self.isDomain.shape))
+        return np.ascontiguousarray(m)
+
+    def _apply_wall_reaction(self, solver, out):
+        """wall_reaction into the solver (every rank makes the same call with the undivided map) and the rates in force into
+        /WallReaction/Rates"""
+        from ._lib import LbmpmError
+        try:
+            solver.set_wall_reaction(np.array(self.wall_reaction, dtype=np.float64), self.solid_minerals())
+        except (ValueError, LbmpmError) as e:
+            raise config.ConfigError("wall_reaction: %s" % e)
+        if out is not None:
+            out.write("WallReaction", "Rates", np.array(solver.wall_reaction, dtype=np.float64))
 
     def initializeTransportDomain(self):
         fluid = self.isDomain == 1
@@ -109,9 +171,16 @@ class Transport3DRK(RKColorGradient3D):
         among them."""
         def report(step, t):
             self._tracer_guard.integrals(step, None if t is None else t.nonfinite, None if t is None else t.summary())
-        return [self._integrals_task(h, before_record=True),
-                PeriodicTask(self, self.integrals_every, ("TracerIntegrals", "PlaneIntegrals"), h.rank == 0, h.tracer_integrals, "tracer_integrals", file="conc",
-                             report=report, closing=lambda: [("Columns", tracer_column_bytes())], before_record=True, joined=True)]
+        def report_wall(step, t):
+            self._tracer_guard.integrals(step, None if t is None else t.nonfinite, None if t is None else t.summary())
+        tasks = [self._integrals_task(h, before_record=True),
+                 PeriodicTask(self, self.integrals_every, ("TracerIntegrals", "PlaneIntegrals"), h.rank == 0, h.tracer_integrals, "tracer_integrals", file="conc",
+                              report=report, closing=lambda: [("Columns", tracer_column_bytes())], before_record=True, joined=True)]
+        if self.wall_reaction is not None:       # (only a run with a wall reaction has the task and its group)
+            tasks.append(PeriodicTask(self, self.integrals_every, ("TracerWallIntegrals", "WallUptake"), h.rank == 0, h.tracer_wall_integrals,
+                                      "tracer_wall_integrals", file="conc", report=report_wall,
+                                      closing=lambda: [("Columns", tracer_wall_column_bytes())], before_record=True, joined=True))
+        return tasks
 
     def runTransport3DMPMCRK(self, progress=None):
         if self.par["tension_type"] != "CSF":
@@ -121,8 +190,11 @@ class Transport3DRK(RKColorGradient3D):
         done = self._start(h)
         tasks = self._tasks(h)
         flow = self._open_flow_file(h, tasks, h.rank == 0)
-        conc = ResultFile(self.output_dir, "ConcentrationResults", (("TransportMacro", "MacroData"),) + runloop.groups(tasks, "conc")) if h.rank == 0 else None
+        more = (("WallReaction", "SurfaceRates"),) if self.wall_reaction is not None else ()
+        conc = ResultFile(self.output_dir, "ConcentrationResults", (("TransportMacro", "MacroData"),) + runloop.groups(tasks, "conc") + more) if h.rank == 0 else None
         runloop.attach(tasks, conc, "conc")
+        if self.wall_reaction is not None:       # (after a restart_from too: a checkpoint does not hold the rates)
+            self._apply_wall_reaction(h.solver, conc)
         self.concentration_path = conc.path if conc else None
         # distributed: every rank checks its own planes, the verdict is collective (all ranks raise together, none is left in an exchange)
         guard = dict(nan_guard=getattr(self, "nan_guard", "raise"), collective=self._distributed(), device=self.device)

@@ -22,6 +22,9 @@
                                                   (the lattice's shape, or the voxel file's; NaN = the ini's ContactAngle); /Wettability/ContactAngle
         [--body-force GX GY GZ]                   rk3d with SurfaceTensionType = 'CSF', tr3d: an acceleration in lattice units for both colours (gravity,
         [--body-force-blue GX GY GZ]              force-driven flow), the second option: another one for blue; /BodyForce/Acceleration of the result file
+        [--wall-reaction K [K ...]]               tr3d: first-order reaction of the tracers at solid walls, D dC/dn = k C_wall -- one rate per tracer in lattice
+        [--wall-minerals FILE]                    units (inf: C_wall = 0), or classes x tracers with a .npy of class bytes per solid voxel; /WallReaction/Rates
+                                                  and, with --integrals-every, /TracerWallIntegrals of ConcentrationResults
         [--steady-every N]                        rk3d: the change of velocity and phase field between multiples of N steps, reduced on the device (/Steady of
         [--steady-tol t] [--steady-phase-tol p]   the result file); with a tolerance the run ends at the first multiple where the change is within it
 """
@@ -70,6 +73,14 @@ def parser():
                          "bodyForceX / Y / Z; /BodyForce/Acceleration of the result file")
     ap.add_argument("--body-force-blue", type=float, nargs=3, default=None, metavar=("GX", "GY", "GZ"),
                     help="... the blue fluid's acceleration where it differs (--body-force is then the red one's; alone: red has none)")
+    ap.add_argument("--wall-reaction", type=float, nargs="+", default=None, metavar="K",
+                    help="tr3d: the tracers react at solid walls, D dC/dn = k C_wall (a reactive bounce-back): one rate k >= 0 per tracer in lattice units "
+                         "(a velocity; Damkoehler number k H / D; inf: the instantaneous reaction), or classes x tracers values class by class with "
+                         "--wall-minerals.  The same as [Reaction] WallReactionRate; /WallReaction/Rates of ConcentrationResults and, with "
+                         "--integrals-every, the uptake per plane and tracer in /TracerWallIntegrals")
+    ap.add_argument("--wall-minerals", default=None, metavar="FILE",
+                    help="tr3d, with --wall-reaction: the mineral class 0 .. 7 of every solid voxel (.npy of integers in the shape of the lattice, or of the "
+                         "voxel file).  The same as [Reaction] WallMineralFile")
     ap.add_argument("--integrals-every", type=int, default=0, metavar="N",
                     help="rk3d, tr3d: every N steps the plane integrals (saturation, masses, fluxes, largest speed, non-finite cells), reduced on the device, "
                          "to /Integrals of the result file and the log; tr3d also the tracers' (cells, mass, flux_x, flux_y, flux_z, sum_c2, cmin, cmax, "
@@ -115,6 +126,10 @@ def main(argv=None):
     t0 = time.time()
     if a.model not in ("rk3d", "tr3d") and _body_force(a) is not None:
         raise SystemExit("--body-force belongs to rk3d (SurfaceTensionType = 'CSF') and tr3d: the 2-D solvers have no body force")
+    if a.model != "tr3d" and (a.wall_reaction is not None or a.wall_minerals is not None):
+        raise SystemExit({"rk3d": "--wall-reaction belongs to tr3d: rk3d runs the flow alone, there is no tracer to react",
+                          "tr": "--wall-reaction belongs to tr3d: the D2Q5 tracers of tr bounce back from solids unchanged"}
+                         .get(a.model, "--wall-reaction belongs to tr3d: the 2-D solvers carry no tracers that could react at a wall"))
     if a.model == "rk":
         from .RKD2Q9 import RKColorGradientLBM
         sim = RKColorGradientLBM(a.ini_dir, output_dir=a.out, device=a.device)
@@ -139,7 +154,8 @@ def main(argv=None):
     elif a.model == "tr3d":
         from .Transport3DRK import Transport3DRK
         sim = Transport3DRK(a.ini_dir, output_dir=a.out, device=_rank_device(a.device), csf_transport=a.csf_transport,
-                            integrals_every=a.integrals_every, contact_angle_solids=a.contact_angles, body_force=_body_force(a))
+                            integrals_every=a.integrals_every, contact_angle_solids=a.contact_angles, body_force=_body_force(a),
+                            wall_reaction=a.wall_reaction, wall_minerals=a.wall_minerals)
         if a.steps is not None:
             sim.timeSteps = a.steps
         path = " and ".join(str(f) for f in sim.runTransport3DMPMCRK())        # (under torchrun rank 0 writes both files)

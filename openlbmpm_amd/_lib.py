@@ -245,6 +245,9 @@ _SIGNATURES = {
     "lbmpm_rk3dcsf_tracer_get_concentration": (C.c_int, [C.c_void_p, C.c_int, F64P]),
     "lbmpm_rk3dcsf_tracer_get_pdf": (C.c_int, [C.c_void_p, C.c_int, F64P]),
     "lbmpm_rk3dcsf_tracer_set_pdf": (C.c_int, [C.c_void_p, C.c_int, F64P]),
+    "lbmpm_rk3dcsf_tracer_set_wall_reaction": (C.c_int, [C.c_void_p, C.c_int, F64P, U8P]),
+    "lbmpm_rk3dcsf_tracer_get_wall_reaction": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), F64P]),
+    "lbmpm_rk3dcsf_tracer_wall_integrals": (C.c_int, [C.c_void_p, F64P]),
     "lbmpm_rk3dcsf_ipc_init": (C.c_int, [C.c_void_p, C.c_void_p]),
     "lbmpm_rk3dcsf_ipc_connect": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "lbmpm_rk3dcsf_rccl_connect": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_char_p]),

@@ -267,13 +267,17 @@ def read_sc2d(ini_dir):
     return p
 
 
-def read_transport(ini_dir):
+def read_transport(ini_dir, wall_reaction=False):
     """transportsetup.ini -> dict (keys consumed by Transport2DRK.py:31-311; the file itself is not
     shipped with the reference).  Only the combinations its working loop runTransport2DMPMCRKNew
     can execute are accepted: multiphase flow system, D2Q5, MRT, Dirichlet (Inamuro) inlet or none,
-    free-flow outlet or none."""
+    free-flow outlet or none.  [Reaction] WallReactionRate / WallMineralFile belong to the 3-D tracers
+    (read_transport3d): a ConfigError here unless wall_reaction says the caller reads them."""
     c = Ini(os.path.join(ini_dir, "transportsetup.ini"))
     p = {}
+    if not wall_reaction and "Reaction" in c.cp and any(k in c.cp["Reaction"] for k in ("WallReactionRate", "WallMineralFile")):
+        raise ConfigError("[Reaction] WallReactionRate / WallMineralFile: the reaction at solid walls is part of the D3Q7 tracers of the 3-D CSF flow "
+                          "(tr3d, Transport3DRK); the D2Q5 tracers bounce back unchanged")
     if c.str("SystemType", "Option") != "MPMC":
         raise ConfigError("[SystemType] Option: only 'MPMC' (tracers in the two-phase flow) is part of the GPU path")
     p["reaction_rate"] = 0.0
@@ -334,8 +338,12 @@ def read_transport3d(ini_dir, periodic_z=False):
     diffJ3 is the rest weight of the reaction source on the D3Q7 lattice: the moving weights must agree with the 2-D model's,
     (1 - J0') / 6 = (1 - J0) / 4, so J0' = (3 J0 - 1) / 2 (the 2-D default J0 = 1/3 gives 0).
     periodic_z: the flow is periodic in z (read_rk3d: BoundaryTypeInlet = BoundaryTypeOutlet = 'Periodic') -- the planes nz-1 and 0 are
-    ordinary planes, so InletType = 'Dirichlet' and the OutletType the loop acts on, 'Freeflow', are a ConfigError."""
-    p = read_transport(ini_dir)
+    ordinary planes, so InletType = 'Dirichlet' and the OutletType the loop acts on, 'Freeflow', are a ConfigError.
+    [Reaction] WallReactionRate (read only when present, whatever [SystemType] Reaction says): the first-order reaction at solid walls,
+    k >= 0 in lattice units per tracer (inf: the instantaneous reaction) -- NumberTracers values, or classes x NumberTracers values class by
+    class with [Reaction] WallMineralFile, a .npy of class bytes per solid voxel: p["wall_reaction"] [classes][n] (None without the key),
+    p["wall_mineral_file"] (None without)."""
+    p = read_transport(ini_dir, wall_reaction=True)
     if periodic_z and (p["inlet_type"] == "Dirichlet" or p["outlet_type"] == "Freeflow"):
         raise ConfigError("[BoundaryCondition] InletType = %r, OutletType = %r on a flow that is periodic in z: the inlet and outlet planes they act on "
                           "are ordinary planes there (neither 'Dirichlet' nor 'Freeflow')" % (p["inlet_type"], p["outlet_type"]))
@@ -349,4 +357,29 @@ def read_transport3d(ini_dir, periodic_z=False):
     p["dXZ"], p["dZX"] = first("DiffusionXZ", p["dXY"]), first("DiffusionZX", p["dYX"])
     p["dYZ"], p["dZY"] = first("DiffusionYZ", 0.0), first("DiffusionZY", 0.0)
     p["diffJ3"] = [(3. * j - 1.) / 2. for j in p["diffJ"]]
+    p["wall_reaction"] = p["wall_mineral_file"] = None
+    rsec = c.cp["Reaction"] if "Reaction" in c.cp else {}
+    if "WallReactionRate" in rsec:
+        p["wall_reaction"] = wall_reaction_rates(c.floats("Reaction", "WallReactionRate"), n, "%s: [Reaction] WallReactionRate" % c.path)
+    if "WallMineralFile" in rsec:
+        if p["wall_reaction"] is None:
+            raise ConfigError("%s: [Reaction] WallMineralFile without WallReactionRate" % c.path)
+        p["wall_mineral_file"] = os.path.expanduser(c.str("Reaction", "WallMineralFile"))
+    if p["wall_reaction"] is not None and len(p["wall_reaction"]) > 1 and p["wall_mineral_file"] is None:
+        raise ConfigError("%s: [Reaction] WallReactionRate gives %d classes: WallMineralFile says which solid voxel is of which" % (c.path, len(p["wall_reaction"])))
     return p
+
+
+def wall_reaction_rates(values, n, what="wall_reaction"):
+    """a flat list of rates -> [classes][n] (n: the number of tracers): n values, or classes x n values class by class with 1 .. 8
+    classes; every rate >= 0 (inf: the instantaneous reaction).  ConfigError otherwise"""
+    import math
+    try:
+        v = [float(x) for x in values]
+    except (TypeError, ValueError):
+        raise ConfigError("%s: numbers, not %r" % (what, values))
+    if not v or len(v) % n or len(v) // n > 8:
+        raise ConfigError("%s needs %d values (one per tracer), or classes x %d with 1 .. 8 classes, not %d" % (what, n, n, len(v)))
+    if any(math.isnan(x) or x < 0. for x in v):
+        raise ConfigError("%s: a rate is >= 0 (inf: the instantaneous reaction), not %r" % (what, [x for x in v if math.isnan(x) or x < 0.][0]))
+    return [v[m * n:(m + 1) * n] for m in range(len(v) // n)]

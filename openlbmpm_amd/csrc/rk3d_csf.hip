@@ -1097,6 +1097,7 @@ __global__ __launch_bounds__(256) void csf3d_import(CsfDev p, double *f, const d
 #include "rk3d_tracer.h"
 #include "rk3d_integrals.h"
 #include "rk3d_tracer_integrals.h"
+#include "rk3d_tracer_wall.h"
 #include "rk3d_clusters.h"
 #include "rk3d_morphology.h"
 #include "rk3d_cluster_props.h"
@@ -1192,6 +1193,13 @@ struct lbmpm_rk3dcsf {
     double *gA = nullptr, *gB = nullptr, *trflow = nullptr;      // [ntr][7][FS] x 2, [4][FS]
     uint32_t *trsrc = nullptr;                                   // [6][FS] when the context has no table of source cells of its own
     double trB[4][9];
+    double *trwall = nullptr;      // lbmpm_rk3dcsf_tracer_wall_integrals: chunk partials + the table (rk3d_tracer_wall.h), allocated by the first call
+    // lbmpm_rk3dcsf_tracer_set_wall_reaction: the rates as given [class][tracer], r = (1 - 3 k) / (1 + 3 k) [tracer][class] (TrDev.r), the
+    // class words of the fluid cells while a mineral map is set (TrDev.wcls)
+    bool wall = false;
+    int wall_classes = 0;
+    double wall_k[8][4], wall_r[4][8];
+    uint32_t *wcls = nullptr;
     double *wang = nullptr;        // lbmpm_rk3dcsf_set_contact_angles: [3][nfluid] theta, cos, sin per fluid cell (CsfDev.wang), allocated by the first call
     double gacc[6] = {0., 0., 0., 0., 0., 0.};      // lbmpm_rk3dcsf_set_body_force: g_R, g_B (CsfDev.gacc)
     bool bf = false;               // ... one of them is not zero: the step launches the BF instances of the two collisions
@@ -1293,7 +1301,9 @@ TrDev make_trdev(const lbmpm_rk3dcsf *c)
     for (int a = 0; a < 4; ++a) {
         for (int b = 0; b < 9; ++b) t.B[a][b] = c->trB[a][b];
         t.beta[a] = k.beta_interface[a]; t.cin[a] = k.inlet_concentration[a]; t.j0[a] = k.diffusion_j[a];
+        for (int b = 0; b < 8; ++b) t.r[a][b] = c->wall ? c->wall_r[a][b] : 1.;
     }
+    t.wcls = c->wall ? c->wcls : nullptr;
     return t;
 }
 
@@ -1302,9 +1312,11 @@ int launch_tracers(lbmpm_rk3dcsf *c, const CsfDev &p, unsigned g)
 {
     const TrDev t = make_trdev(c);
     // (SLAB: a context with ghost planes; the undivided lattice keeps the instance without the ghost and global-plane tests)
-    lbmpm::dispatch([&](auto first, auto slab) {
-        lbmpm::dispatch_int<1, 4>([&](auto nt) { tr3d_step<decltype(first)::value, decltype(nt)::value, decltype(slab)::value><<<g, 256, 0, c->stream>>>(p, t); }, c->ntr);
-    }, c->tr_first, c->cfg.ghost_lo || c->cfg.ghost_hi);
+    // (WALL: a wall reaction is set; the first pull has no wall event and keeps the instance without)
+    lbmpm::dispatch([&](auto first, auto slab, auto wall) {
+        constexpr bool FIRST = decltype(first)::value, WALL = decltype(wall)::value && !FIRST;
+        lbmpm::dispatch_int<1, 4>([&](auto nt) { tr3d_step<FIRST, decltype(nt)::value, decltype(slab)::value, WALL><<<g, 256, 0, c->stream>>>(p, t); }, c->ntr);
+    }, c->tr_first, c->cfg.ghost_lo || c->cfg.ghost_hi, c->wall);
     LBMPM_HIP_TRY(hipGetLastError());
     std::swap(c->gA, c->gB);
     c->tr_first = false;
@@ -2447,8 +2459,9 @@ static int tracer_observe(lbmpm_rk3dcsf *c, int tracer, double *conc, double *pd
     double *const st = staged.get();
     const CsfDev p = make_dev(c);
     const TrDev t = make_trdev(c);
-    if (c->tr_first) tr3d_observe<true><<<blocks_of(c->N), 256, 0, c->stream>>>(p, t, tracer, pdf ? st + c->N : nullptr, st);
-    else tr3d_observe<false><<<blocks_of(c->N), 256, 0, c->stream>>>(p, t, tracer, pdf ? st + c->N : nullptr, st);
+    if (c->tr_first) tr3d_observe<true, false><<<blocks_of(c->N), 256, 0, c->stream>>>(p, t, tracer, pdf ? st + c->N : nullptr, st);
+    else if (c->wall) tr3d_observe<false, true><<<blocks_of(c->N), 256, 0, c->stream>>>(p, t, tracer, pdf ? st + c->N : nullptr, st);
+    else tr3d_observe<false, false><<<blocks_of(c->N), 256, 0, c->stream>>>(p, t, tracer, pdf ? st + c->N : nullptr, st);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e == hipSuccess && conc) e = hipMemcpy(conc, st, c->N * sizeof(double), hipMemcpyDeviceToHost);
@@ -2481,7 +2494,102 @@ extern "C" int lbmpm_rk3dcsf_tracer_integrals(lbmpm_rk3dcsf *c, double *out)
     { const int rc = integral_buffer<TracerCols>(c->mem, &c->trinteg, planes, plane_cells, nT, nullptr); if (rc) return rc; }
     const CsfDev p = make_dev(c);
     const TrDev t = make_trdev(c);
-    if (c->tr_first) LBMPM_HIP_TRY(tracer_integrals_run(TrIntLoader<true>{p, t}, planes, plane_cells, nT, c->trinteg, out, c->stream));
-    else LBMPM_HIP_TRY(tracer_integrals_run(TrIntLoader<false>{p, t}, planes, plane_cells, nT, c->trinteg, out, c->stream));
+    if (c->tr_first) LBMPM_HIP_TRY(tracer_integrals_run(TrIntLoader<true, false>{p, t}, planes, plane_cells, nT, c->trinteg, out, c->stream));
+    else if (c->wall) LBMPM_HIP_TRY(tracer_integrals_run(TrIntLoader<false, true>{p, t}, planes, plane_cells, nT, c->trinteg, out, c->stream));
+    else LBMPM_HIP_TRY(tracer_integrals_run(TrIntLoader<false, false>{p, t}, planes, plane_cells, nT, c->trinteg, out, c->stream));
+    return LBMPM_OK;
+}
+
+// Reaction at solid walls: see include/lbmpm.h.  The rates travel as kernel arguments (make_trdev); with a mineral map one class word per
+// fluid cell is built on the device from the uploaded class bytes (tr3d_setup_wall).  Everything is checked before anything changes.
+extern "C" int lbmpm_rk3dcsf_tracer_set_wall_reaction(lbmpm_rk3dcsf *c, int num_classes, const double *rates, const uint8_t *minerals)
+{
+    const char *who = "lbmpm_rk3dcsf_tracer_set_wall_reaction";
+    LBMPM_REQUIRE(c, "%s: null context", who);
+    { const int rc = tracer_ready(c, 0, who); if (rc) return rc; }
+    if (c->next_stage != 0) { set_error("%s: stage %d of a step begun with lbmpm_rk3dcsf_stage is next", who, c->next_stage); return LBMPM_ERR_STATE; }
+    LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
+    if (!rates) {
+        LBMPM_REQUIRE(!minerals, "%s: a mineral map without rates", who);
+        if (c->wcls) {           // no launch may still read the map
+            LBMPM_HIP_TRY(hipStreamSynchronize(c->stream));
+            c->mem.release(&c->wcls);
+        }
+        c->wall = false; c->wall_classes = 0;
+        return LBMPM_OK;
+    }
+    LBMPM_REQUIRE(num_classes >= 1 && num_classes <= 8, "%s: %d mineral classes, 1 .. 8 are built", who, num_classes);
+    LBMPM_REQUIRE(minerals || num_classes == 1, "%s: %d classes without a mineral map (NULL minerals: every solid is class 0, num_classes 1)", who, num_classes);
+    const int nT = c->ntr;
+    double k[8][4], r[4][8];
+    for (int m = 0; m < 8; ++m) for (int t = 0; t < 4; ++t) { k[m][t] = 0.; r[t][m] = 1.; }
+    for (int m = 0; m < num_classes; ++m)
+        for (int t = 0; t < nT; ++t) {
+            const double v = rates[(size_t)m * nT + t];
+            LBMPM_REQUIRE(v >= 0., "%s: the rate %g of tracer %d at mineral class %d: k >= 0 (inf: the instantaneous reaction)", who, v, t, m);      // (false for NaN)
+            k[m][t] = v + 0.;
+            r[t][m] = std::isinf(v) ? -1.0 : (1. - 3. * v) / (1. + 3. * v);
+        }
+    const size_t N = c->N, pl = (size_t)c->nx * c->ny;
+    if (minerals) {
+        std::vector<uint8_t> dom;
+        try { dom.resize(N); }
+        catch (const std::bad_alloc &) { set_error("%s: out of host memory", who); return LBMPM_ERR_NOMEM; }
+        LBMPM_HIP_TRY(hipMemcpy(dom.data(), c->dom, N, hipMemcpyDeviceToHost));
+        for (size_t n = 0; n < N; ++n)
+            if (dom[n] != 1 && (int)minerals[n] >= num_classes) {
+                const size_t z = n / pl, q = n - z * pl;
+                set_error("%s: mineral class %d at the solid cell (z, y, x) = (%zu, %zu, %zu), %d classes were given", who, (int)minerals[n], z, q / (size_t)c->nx, q % (size_t)c->nx, num_classes);
+                return LBMPM_ERR_INVALID;
+            }
+    }
+    LBMPM_HIP_TRY(hipStreamSynchronize(c->stream));
+    if (minerals) {
+        lbmpm::DeviceTemp<uint8_t> staged;
+        LBMPM_HIP_TRY(staged.alloc(N));
+        uint32_t *w = c->wcls;
+        if (!w) { const int rc = c->mem.alloc(&w, (size_t)c->nfluid, nullptr); if (rc) return rc; }
+        hipError_t e = hipMemcpy(staged.get(), minerals, N, hipMemcpyHostToDevice);
+        if (e == hipSuccess) {
+            tr3d_setup_wall<<<blocks_of((size_t)c->nfluid), 256, 0, c->stream>>>(make_dev(c), staged.get(), w);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) {
+            if (!c->wcls) c->mem.release(&w);
+            set_error("%s failed: %s", who, hipGetErrorString(e));
+            return LBMPM_ERR_HIP;
+        }
+        c->wcls = w;
+    } else if (c->wcls) {
+        c->mem.release(&c->wcls);
+    }
+    for (int m = 0; m < 8; ++m) for (int t = 0; t < 4; ++t) { c->wall_k[m][t] = k[m][t]; c->wall_r[t][m] = r[t][m]; }
+    c->wall = true; c->wall_classes = num_classes;
+    return LBMPM_OK;
+}
+
+extern "C" int lbmpm_rk3dcsf_tracer_get_wall_reaction(const lbmpm_rk3dcsf *c, int *num_classes_out, double *rates_out)
+{
+    LBMPM_REQUIRE(c && rates_out, "lbmpm_rk3dcsf_tracer_get_wall_reaction: null argument");
+    { const int rc = tracer_ready(c, 0, "lbmpm_rk3dcsf_tracer_get_wall_reaction"); if (rc) return rc; }
+    for (int m = 0; m < 8; ++m) for (int t = 0; t < c->ntr; ++t) rates_out[(size_t)m * c->ntr + t] = c->wall ? c->wall_k[m][t] : 0.;
+    if (num_classes_out) *num_classes_out = c->wall ? c->wall_classes : 0;
+    return LBMPM_OK;
+}
+
+// The uptake at the walls (rk3d_tracer_wall.h): out [own planes][num_tracers][LBMPM_TRWALL_COLS]; slabs included.
+extern "C" int lbmpm_rk3dcsf_tracer_wall_integrals(lbmpm_rk3dcsf *c, double *out)
+{
+    LBMPM_REQUIRE(c && out, "lbmpm_rk3dcsf_tracer_wall_integrals: null argument");
+    { const int rc = tracer_ready(c, 0, "lbmpm_rk3dcsf_tracer_wall_integrals"); if (rc) return rc; }
+    if (!c->tr_given) { set_error("lbmpm_rk3dcsf_tracer_wall_integrals before lbmpm_rk3dcsf_tracer_set_concentration / _set_pdf"); return LBMPM_ERR_STATE; }
+    LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
+    const unsigned planes = (unsigned)(c->nz - c->cfg.ghost_lo - c->cfg.ghost_hi), plane_cells = (unsigned)c->nx * (unsigned)c->ny, nT = (unsigned)c->ntr;
+    { const int rc = integral_buffer<TracerWallCols>(c->mem, &c->trwall, planes, plane_cells, nT, nullptr); if (rc) return rc; }
+    const CsfDev p = make_dev(c);
+    const TrDev t = make_trdev(c);
+    if (c->tr_first) LBMPM_HIP_TRY(tracer_wall_integrals_run(TrWallLoader<true>{p, t}, planes, plane_cells, nT, c->trwall, out, c->stream));
+    else LBMPM_HIP_TRY(tracer_wall_integrals_run(TrWallLoader<false>{p, t}, planes, plane_cells, nT, c->trwall, out, c->stream));
     return LBMPM_OK;
 }

@@ -15,6 +15,10 @@
 //   streaming      T:139-194   half-way bounce-back on solids; as a PULL of the post-collision populations, like the flow's
 //   inlet          T:682-698   Inamuro on plane nz-1: the population moving down is C_in - sum(others)
 //   concentration  T:78-90
+//   wall reaction  (not in the reference; lbmpm_rk3dcsf_tracer_set_wall_reaction, include/lbmpm.h) the linear surface reaction
+//                  D dC/dn = k C_wall as a reactive bounce-back: the population that comes back off a solid is r times the one that
+//                  left, r = (1 - 3 k) / (1 + 3 k) per tracer and mineral class of that solid.  Kernels with WALL = false are the ones
+//                  a context without a wall reaction launches
 // Stored: the post-collision populations, SoA [tracer][7][FS] over fluid cells like the flow's planes, two buffers.  tr3d_step pulls
 // (streaming + inlet + concentration: the end of sub-step k - 1) and collides with rhoR, u, G of flow step k (the start of sub-step k).
 // Slabs (a context with ghost planes, SLAB): the outlet and the inlet are planes of the UNDIVIDED lattice (z + zoff), the ghost planes'
@@ -33,14 +37,21 @@ struct TrDev {
     double crit, rate;
     double B[4][9];              // I - S^-1 of every tracer, row-major over (x, y, z)
     double beta[4], cin[4], j0[4];
+    // wall reaction: read by the WALL instances and by the uptake reduction (rk3d_tracer_wall.h) only
+    double r[4][8];              // [tracer][mineral class] (1 - 3 k) / (1 + 3 k); ones without a wall reaction
+    const uint32_t *wcls;        // [FS] nibble i - 1: the class of the solid at x - e_i (0 off a solid); null: every solid is class 0
 };
 
 constexpr int TQ = 7;
 constexpr double TW = 1. / 6.;
 
 // the populations of one tracer at fluid cell js as a completed sub-step leaves them: streamed (FIRST: taken where they stand), inlet plane
-template <bool FIRST>
-__device__ __forceinline__ void tr_pull(const CsfDev &p, const TrDev &t, int tr, unsigned js, const unsigned s[TQ], bool top, double g[TQ])
+// the class word of fluid cell js (WALL only; one load per cell, shared by its tracers)
+__device__ __forceinline__ uint32_t tr_wall_word(const TrDev &t, unsigned js) { return t.wcls ? t.wcls[js] : 0u; }
+__device__ __forceinline__ double tr_wall_r(const TrDev &t, int tr, uint32_t word, int i) { return t.r[tr][(word >> (4 * (i - 1))) & 7u]; }
+
+template <bool FIRST, bool WALL = false>
+__device__ __forceinline__ void tr_pull(const CsfDev &p, const TrDev &t, int tr, unsigned js, const unsigned s[TQ], bool top, double g[TQ], uint32_t word = 0u)
 {
     constexpr int OPP[Q] = CSF_OPP;
     const double *gt = t.gin + (size_t)tr * TQ * p.FS;
@@ -50,6 +61,7 @@ __device__ __forceinline__ void tr_pull(const CsfDev &p, const TrDev &t, int tr,
         size_t off = (size_t)i * p.FS + js;
         if (!FIRST) off = s[i] != SRC_WALL ? (size_t)i * p.FS + s[i] : (size_t)OPP[i] * p.FS + js;
         g[i] = gt[off];
+        if (!FIRST && WALL && s[i] == SRC_WALL) g[i] = tr_wall_r(t, tr, word, i) * g[i];      // (k = 0: r = 1.0, the product is exact)
     }
     if (!FIRST && top && t.inlet) {              // T:682-698
         const double sum = g[0] + g[1] + g[2] + g[3] + g[4] + g[5];
@@ -72,7 +84,7 @@ __device__ __forceinline__ void tr_sources(const CsfDev &p, const TrDev &t, unsi
     for (int i = 1; i < TQ; ++i) s[i] = FIRST ? js : t.src[(size_t)(i - 1) * p.FS + js];
 }
 
-template <bool FIRST, int NT, bool SLAB>
+template <bool FIRST, int NT, bool SLAB, bool WALL>
 __global__ __launch_bounds__(256) void tr3d_step(CsfDev p, TrDev t)
 {
     constexpr int CX[Q] = CSF_CX, CY[Q] = CSF_CY, CZ[Q] = CSF_CZ;
@@ -88,8 +100,9 @@ __global__ __launch_bounds__(256) void tr3d_step(CsfDev p, TrDev t)
     unsigned s[TQ];
     tr_sources<FIRST>(p, t, js, s);
     double g[NT][TQ], C[NT];
+    const uint32_t word = WALL ? tr_wall_word(t, js) : 0u;
 #pragma unroll
-    for (int tr = 0; tr < NT; ++tr) { tr_pull<FIRST>(p, t, tr, js, s, top, g[tr]); C[tr] = tr_sum(g[tr]); }
+    for (int tr = 0; tr < NT; ++tr) { tr_pull<FIRST, WALL>(p, t, tr, js, s, top, g[tr], word); C[tr] = tr_sum(g[tr]); }
     const double rhoR = t.flow[js], vx = t.flow[p.FS + js], vy = t.flow[2 * p.FS + js], vz = t.flow[3 * p.FS + js];
     const double gx = p.G[ns], gy = p.G[p.NS + ns], gz = p.G[2 * p.NS + ns];
     const double ind = rhoR > t.crit ? -(1. - 1.) : -(1. - 0.);
@@ -131,7 +144,7 @@ __global__ __launch_bounds__(256) void tr3d_step(CsfDev p, TrDev t)
 
 // what the reference's arrays hold after the last completed sub-step (the pull, the inlet plane, the sum), dense: out_g [N][7] (may be
 // null), out_c [N]; zeros off the fluid
-template <bool FIRST>
+template <bool FIRST, bool WALL>
 __global__ __launch_bounds__(256) void tr3d_observe(CsfDev p, TrDev t, int tr, double *out_g, double *out_c)
 {
     const unsigned n = blockIdx.x * 256u + threadIdx.x;
@@ -142,7 +155,7 @@ __global__ __launch_bounds__(256) void tr3d_observe(CsfDev p, TrDev t, int tr, d
         const unsigned j = p.cidx[n], pl = (unsigned)p.nx * (unsigned)p.ny;
         unsigned s[TQ];
         tr_sources<FIRST>(p, t, j, s);
-        tr_pull<FIRST>(p, t, tr, j, s, (int)(n / pl) + p.zoff == p.nzg - 1, g);      // (the inlet plane of the undivided lattice)
+        tr_pull<FIRST, WALL>(p, t, tr, j, s, (int)(n / pl) + p.zoff == p.nzg - 1, g, WALL ? tr_wall_word(t, j) : 0u);      // (the inlet plane of the undivided lattice)
         c = tr_sum(g);
     }
     if (out_g) {
@@ -177,4 +190,23 @@ __global__ __launch_bounds__(256) void tr3d_setup_src(CsfDev p, uint32_t *src)
 #pragma unroll
     for (int i = 1; i < TQ; ++i)
         src[(size_t)(i - 1) * p.FS + j] = ((m >> OPP[i]) & 1u) ? p.cidx[at(nb, -CX[i], -CY[i], -CZ[i])] : SRC_WALL;
+}
+
+// the class words of the wall reaction (TrDev::wcls) from a class byte per lattice cell: nibble i - 1 is the class of the solid the
+// direction i would be pulled from, 0 where that neighbour is fluid
+__global__ __launch_bounds__(256) void tr3d_setup_wall(CsfDev p, const uint8_t *cls, uint32_t *wcls)
+{
+    constexpr int CX[Q] = CSF_CX, CY[Q] = CSF_CY, CZ[Q] = CSF_CZ, OPP[Q] = CSF_OPP;
+    const unsigned j = blockIdx.x * 256u + threadIdx.x;
+    if (j >= p.NF) return;
+    const unsigned n = p.cells[j];
+    int x, y, z;
+    cell_of(p, n, x, y, z);
+    const Nb nb = make_nb(p, x, y, z);
+    const uint32_t m = p.meta[n];
+    uint32_t w = 0u;
+#pragma unroll
+    for (int i = 1; i < TQ; ++i)
+        if (!((m >> OPP[i]) & 1u)) w |= (uint32_t)(cls[at(nb, -CX[i], -CY[i], -CZ[i])] & 7u) << (4 * (i - 1));
+    wcls[j] = w;
 }

@@ -46,8 +46,8 @@ struct TracerCols {
 };
 
 // the populations of tracer `set` as tr3d_observe<FIRST> hands them out (streamed, the inlet plane of the undivided lattice applied; on a
-// slab the pulls out of the ghost planes); own planes only (plane 0 is lattice plane p.glo)
-template <bool FIRST>
+// slab the pulls out of the ghost planes; WALL: the wall reaction's bounce-back); own planes only (plane 0 is lattice plane p.glo)
+template <bool FIRST, bool WALL>
 struct TrIntLoader {
     CsfDev p;
     TrDev t;
@@ -59,7 +59,7 @@ struct TrIntLoader {
         const unsigned j = p.cidx[n];
         unsigned s[TQ];
         tr_sources<FIRST>(p, t, j, s);
-        tr_pull<FIRST>(p, t, (int)set, j, s, (int)z + p.zoff == p.nzg - 1, c.g);
+        tr_pull<FIRST, WALL>(p, t, (int)set, j, s, (int)z + p.zoff == p.nzg - 1, c.g, WALL ? tr_wall_word(t, j) : 0u);
         return true;
     }
 };

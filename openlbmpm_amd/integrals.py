@@ -1,6 +1,7 @@
 """Plane integrals of the 3-D solvers: the table of lbmpm_rk3d_integrals / lbmpm_rk3dcsf_integrals (include/lbmpm.h) and what a
 two-phase run is read through -- saturation, masses, fluxes, Darcy velocities, the largest speed, the count of non-finite cells; and
-the tracers' table of lbmpm_rk3dcsf_tracer_integrals (TracerIntegrals): mass balances, breakthrough, the moments of a plume along z.
+the tracers' table of lbmpm_rk3dcsf_tracer_integrals (TracerIntegrals): mass balances, breakthrough, the moments of a plume along z;
+and the table of lbmpm_rk3dcsf_tracer_wall_integrals (TracerWallIntegrals): what the tracers' wall reaction took up, per plane and tracer.
 
 The library reduces every plane on the device in a fixed order, so a table is the same bit for bit however the lattice was cut into
 slabs; `totals` keeps that: one loop over the planes in plane order, not a reduction whose order numpy may choose.
@@ -208,6 +209,63 @@ class TracerIntegrals:
         return out
 
 
+# the wall table's columns, in the order of LBMPM_TRWALL_* (csrc/rk3d_tracer_wall.h is the only other place that knows it)
+TRACER_WALL_COLUMNS = ("wall_links", "uptake", "wall_c", "nonfinite")
+_W = {c: i for i, c in enumerate(TRACER_WALL_COLUMNS)}
+
+
+class TracerWallIntegrals:
+    """planes: [nz][nT][4], one row per lattice plane and tracer over the plane's wall links -- a fluid cell and a direction whose source
+    cell is solid: their count, the sum of g_out - g_in (what the walls took out of the tracer in the last completed sub-step), the sum of
+    the links' wall concentrations 3 (g_out + g_in), and the cells with a population that is not finite among those read (they count in
+    the links and in nothing else).  The mass a run loses from step n - 1 to step n is uptake(k) after step n."""
+    COLUMNS = TRACER_WALL_COLUMNS
+
+    def __init__(self, planes, nx, ny):
+        a = np.ascontiguousarray(planes, dtype=np.float64)
+        if a.ndim != 3 or a.shape[2] != len(TRACER_WALL_COLUMNS):
+            raise TypeError("planes must have shape [nz][nT][%d]" % len(TRACER_WALL_COLUMNS))
+        self.planes, self.nx, self.ny = a, int(nx), int(ny)
+        self.nz, self.num_tracers = a.shape[0], a.shape[1]
+
+    def column(self, name, tracer):
+        """the profile of one column of one tracer along z"""
+        return self.planes[:, int(tracer), _W[name]]
+
+    def total(self, name, tracer):
+        """the planes added in plane order"""
+        t = 0.0
+        for v in self.column(name, tracer).tolist():
+            t += v
+        return t
+
+    def uptake(self, tracer):
+        """what the walls of the whole lattice took out of the tracer in the last completed sub-step"""
+        return self.total("uptake", tracer)
+
+    @property
+    def wall_links(self):
+        """wall links of the lattice (the same for every tracer)"""
+        return int(self.total("wall_links", 0))
+
+    def mean_wall_concentration(self, tracer):
+        """sum of the links' wall concentrations / links (all of them: a lattice with non-finite cells reports those in `nonfinite`)"""
+        n = self.total("wall_links", tracer)
+        return self.total("wall_c", tracer) / n if n else float("nan")
+
+    @property
+    def nonfinite(self):
+        """cells with a non-finite population at a wall, all tracers together"""
+        return int(sum(self.total("nonfinite", k) for k in range(self.num_tracers)))
+
+    def summary(self):
+        """the numbers a log line carries: uptake<k>, wallC<k> per tracer"""
+        out = {}
+        for k in range(self.num_tracers):
+            out["uptake%d" % k], out["wallC%d" % k] = self.uptake(k), self.mean_wall_concentration(k)
+        return out
+
+
 def _name_bytes(names):
     width = max(len(c) for c in names)
     return np.array([list(c.encode().ljust(width, b"\0")) for c in names], dtype=np.uint8)
@@ -221,6 +279,11 @@ def column_bytes():
 def tracer_column_bytes():
     """TRACER_COLUMNS the same way: /TracerIntegrals/Columns (column_names reads both)"""
     return _name_bytes(TRACER_COLUMNS)
+
+
+def tracer_wall_column_bytes():
+    """TRACER_WALL_COLUMNS the same way: /TracerWallIntegrals/Columns"""
+    return _name_bytes(TRACER_WALL_COLUMNS)
 
 
 def column_names(a):
@@ -257,4 +320,12 @@ def tracer_table(L, handle, planes, num_tracers):
     from ._lib import F64P, check
     out = np.empty((int(planes), int(num_tracers), len(TRACER_COLUMNS)), dtype=np.float64)
     check(L.lbmpm_rk3dcsf_tracer_integrals(handle, out.ctypes.data_as(F64P)), "lbmpm_rk3dcsf_tracer_integrals")
+    return out
+
+
+def tracer_wall_table(L, handle, planes, num_tracers):
+    """[planes][nT][4] of one context through lbmpm_rk3dcsf_tracer_wall_integrals"""
+    from ._lib import F64P, check
+    out = np.empty((int(planes), int(num_tracers), len(TRACER_WALL_COLUMNS)), dtype=np.float64)
+    check(L.lbmpm_rk3dcsf_tracer_wall_integrals(handle, out.ctypes.data_as(F64P)), "lbmpm_rk3dcsf_tracer_wall_integrals")
     return out

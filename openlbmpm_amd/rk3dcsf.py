@@ -83,6 +83,46 @@ def body_force_pair(g=None, red=None, blue=None):
     return three(g if red is None else red, "red"), three(g if blue is None else blue, "blue")
 
 
+def wall_rates(rates, num_tracers):
+    """the rates of set_wall_reaction as a float64 array [classes][nT]: a scalar (every tracer, one class), [nT] (one class) or
+    [classes][nT], 1 .. 8 classes.  ValueError: another shape.  (The values are the library's to check: k >= 0, inf allowed.)"""
+    nT = int(num_tracers)
+    a = np.asarray(rates, dtype=np.float64)
+    if a.ndim == 0:
+        a = np.full((1, nT), float(a))
+    elif a.ndim == 1:
+        a = a.reshape(1, -1)
+    if a.ndim != 2 or a.shape[1] != nT or not 1 <= a.shape[0] <= 8:
+        raise ValueError("wall reaction rates: a number, [%d] numbers (one per tracer) or [classes][%d] with 1 .. 8 classes, not shape %s"
+                         % (nT, nT, np.shape(rates)))
+    return np.ascontiguousarray(a)
+
+
+def _undivided_minerals(minerals, shape):
+    if minerals is None:
+        return None
+    m = np.asarray(minerals)
+    if m.shape != tuple(shape):
+        raise ValueError("minerals must have the shape of the lattice %s, not %s" % (tuple(shape), m.shape))
+    if m.dtype.kind not in "ui" or m.min() < 0 or m.max() > 255:
+        raise ValueError("minerals: one class byte (0 .. 7) per cell")
+    return np.ascontiguousarray(m, dtype=np.uint8)
+
+
+def _wall_valid(dom, rates, minerals):
+    """what lbmpm_rk3dcsf_tracer_set_wall_reaction checks, ahead of the calls: RK3DCSFCluster changes no slab when another would refuse"""
+    if not bool(np.all(rates >= 0.0)):
+        raise _lib.LbmpmError("set_wall_reaction: a rate that is negative or NaN", _lib.ERR_INVALID)
+    if minerals is None and rates.shape[0] != 1:
+        raise _lib.LbmpmError("set_wall_reaction: %d classes without a mineral map" % rates.shape[0], _lib.ERR_INVALID)
+    if minerals is not None:
+        bad = (np.asarray(dom) != 1) & (minerals >= rates.shape[0])
+        if bad.any():
+            z, y, x = [int(i[0]) for i in np.nonzero(bad)]
+            raise _lib.LbmpmError("set_wall_reaction: mineral class %d at the solid cell (z, y, x) = (%d, %d, %d), %d classes were given"
+                                  % (int(minerals[z, y, x]), z, y, x, rates.shape[0]), _lib.ERR_INVALID)
+
+
 class RK3DCSFSolver(SlabTransportCalls, SlabAnalysisCalls):
     _C_PREFIX, _NO_TRANSPORT = "lbmpm_rk3dcsf", "none"
 
@@ -301,6 +341,43 @@ class RK3DCSFSolver(SlabTransportCalls, SlabAnalysisCalls):
         check(self._L.lbmpm_rk3dcsf_tracer_set_pdf(self._h, int(t), ptr), "lbmpm_rk3dcsf_tracer_set_pdf")
         self._keep = []
 
+    def set_wall_reaction(self, rates, minerals=None):
+        """first-order reaction of the tracers at solid walls, D dC/dn = k C_wall: a population that bounces off a solid comes back times
+        r = (1 - 3 k) / (1 + 3 k) (include/lbmpm.h).  rates: k >= 0 in lattice units (a velocity; Damkoehler number k H / D; inf: C_wall
+        = 0) -- a number for every tracer, [nT] numbers, or [classes][nT] with minerals [nz][ny][nx] (a slab: with its ghost planes), the
+        class byte 0 .. classes-1 of every solid cell (ignored at fluid cells).  None: off.  Needs configured tracers; whenever the
+        solver is idle, repeatedly; the state, the step counter, the contact angles, the body force and the snapshot of change() stay,
+        set_concentration / set_tracer_pdf keep it, and the observers see the new rate's pull at once.  k = 0 leaves the fields bit-equal
+        to a run without the call.  ValueError: a wrong shape; LbmpmError: no tracers (LBMPM_ERR_STATE); a negative or NaN rate, a class
+        at a solid cell that is not below `classes` (LBMPM_ERR_INVALID) -- nothing changed"""
+        name = "lbmpm_rk3dcsf_tracer_set_wall_reaction"
+        if rates is None:
+            if minerals is not None:
+                raise ValueError("set_wall_reaction: a mineral map without rates")
+            check(self._L.lbmpm_rk3dcsf_tracer_set_wall_reaction(self._h, 0, None, None), name)
+            return
+        if not getattr(self, "num_tracers", 0):
+            raise _lib.LbmpmError("set_wall_reaction before configure_tracers", _lib.ERR_STATE)
+        a = wall_rates(rates, self.num_tracers)
+        m = _undivided_minerals(minerals, self.shape)
+        check(self._L.lbmpm_rk3dcsf_tracer_set_wall_reaction(self._h, a.shape[0], a.ctypes.data_as(F64P), None if m is None else m.ctypes.data_as(U8P)), name)
+
+    @property
+    def wall_reaction(self):
+        """the rates in force, [classes][nT]; None without a wall reaction"""
+        n = C.c_int(0)
+        out = np.zeros((8, max(1, getattr(self, "num_tracers", 0))), dtype=np.float64)
+        check(self._L.lbmpm_rk3dcsf_tracer_get_wall_reaction(self._h, C.byref(n), out.ctypes.data_as(F64P)), "lbmpm_rk3dcsf_tracer_get_wall_reaction")
+        return out[:n.value].copy() if n.value else None
+
+    def tracer_wall_integrals(self):
+        """integrals.TracerWallIntegrals of the own planes, [planes][nT][4]: wall links, uptake, summed wall concentration and the
+        non-finite count per plane and tracer (lbmpm_rk3dcsf_tracer_wall_integrals), reduced on the device from the stored populations;
+        valid with or without a wall reaction (without: an uptake of exactly 0)"""
+        from .integrals import TracerWallIntegrals, tracer_wall_table
+        n = max(1, getattr(self, "num_tracers", 0))          # (without tracers the library refuses before it writes)
+        return TracerWallIntegrals(tracer_wall_table(self._L, self._h, self.own_planes, n), self.nx, self.ny)
+
     def get(self, name):
         out = np.empty(self.shape + ((19,) if name in _PDF_FIELDS else ()), dtype=np.float64)
         check(self._L.lbmpm_rk3dcsf_get_field(self._h, FIELDS[name], out.ctypes.data_as(F64P)), "get_field(%s)" % name)
@@ -489,6 +566,33 @@ class RK3DCSFCluster(StackedAnalysis):
     def get_tracer_pdf(self, t):
         return np.concatenate([g.own(s.get_tracer_pdf(t)) for s, g in zip(self.slabs, self.geo)], axis=0)
 
+    def set_wall_reaction(self, rates, minerals=None):
+        """RK3DCSFSolver.set_wall_reaction with the undivided `minerals` [nz][ny][nx]; every slab takes its planes and the images of its
+        neighbours'.  Checked on every slab before any is changed"""
+        if rates is None:
+            if minerals is not None:
+                raise ValueError("set_wall_reaction: a mineral map without rates")
+            for s in self.slabs:
+                s.set_wall_reaction(None)
+            return
+        if not self.num_tracers:
+            raise _lib.LbmpmError("set_wall_reaction before configure_tracers", _lib.ERR_STATE)
+        a = wall_rates(rates, self.num_tracers)
+        cut = [g.cut(_undivided_minerals(minerals, self.shape)) for g in self.geo]
+        for s, m in zip(self.slabs, cut):
+            _wall_valid(s.is_domain, a, m)
+        for s, m in zip(self.slabs, cut):
+            s.set_wall_reaction(a, m)
+
+    @property
+    def wall_reaction(self):
+        return self.slabs[0].wall_reaction
+
+    def tracer_wall_integrals(self):
+        """the slabs' wall tables in plane order: bit-equal to the undivided lattice's"""
+        from .integrals import TracerWallIntegrals
+        return TracerWallIntegrals(np.concatenate([s.tracer_wall_integrals().planes for s in self.slabs], axis=0), self.nx, self.ny)
+
     def _exchange(self, msg):
         n = len(self.slabs)
         for k in range(n):                         # a ring: the last slab's high face is the first slab's low face
@@ -626,6 +730,21 @@ class RK3DCSFDistributed(GatheredAnalysis):
 
     def get_tracer_pdf(self, t):
         return np.ascontiguousarray(self.geo.own(self.slab.get_tracer_pdf(t)))
+
+    def set_wall_reaction(self, rates, minerals=None):
+        """RK3DCSFSolver.set_wall_reaction, the same call on every rank, with the undivided `minerals` [nz][ny][nx]; every rank takes
+        its planes and the images of its neighbours'.  Call it after sync(): the slab must be idle"""
+        self.slab.set_wall_reaction(rates, self.geo.cut(_undivided_minerals(minerals, self.shape)))
+
+    @property
+    def wall_reaction(self):
+        return self.slab.wall_reaction
+
+    def tracer_wall_integrals(self):
+        """collective: rank 0 returns the integrals.TracerWallIntegrals of the whole lattice ([nz][nT][4]), the others None"""
+        from .integrals import TracerWallIntegrals
+        t = self.gather(self.slab.tracer_wall_integrals().planes)
+        return None if t is None else TracerWallIntegrals(t, self.shape[2], self.shape[1])
 
     def _face_sizes(self):
         """doubles of the three messages (LBMPM_CSF_MSG_* order) this slab sends / expects through either face"""
