@@ -1307,16 +1307,25 @@ TrDev make_trdev(const lbmpm_rk3dcsf *c)
     return t;
 }
 
+// return f(first, wall): the instance of the tracers' pull that is valid now.  FIRST until the first sub-step; WALL while a wall reaction
+// is set -- the first pull has no wall event and keeps the instance without, so <true, true> is never asked for
+template <typename F>
+int with_pull(const lbmpm_rk3dcsf *c, F &&f)
+{
+    return lbmpm::dispatch([&](auto first, auto wall) { return f(first, std::bool_constant<decltype(wall)::value && !decltype(first)::value>{}); }, c->tr_first, c->wall);
+}
+
 // one launch for all tracers over every fluid cell (g: blocks8 of the fluid cells); swaps the tracers' buffers
 int launch_tracers(lbmpm_rk3dcsf *c, const CsfDev &p, unsigned g)
 {
     const TrDev t = make_trdev(c);
     // (SLAB: a context with ghost planes; the undivided lattice keeps the instance without the ghost and global-plane tests)
-    // (WALL: a wall reaction is set; the first pull has no wall event and keeps the instance without)
-    lbmpm::dispatch([&](auto first, auto slab, auto wall) {
-        constexpr bool FIRST = decltype(first)::value, WALL = decltype(wall)::value && !FIRST;
-        lbmpm::dispatch_int<1, 4>([&](auto nt) { tr3d_step<FIRST, decltype(nt)::value, decltype(slab)::value, WALL><<<g, 256, 0, c->stream>>>(p, t); }, c->ntr);
-    }, c->tr_first, c->cfg.ghost_lo || c->cfg.ghost_hi, c->wall);
+    with_pull(c, [&](auto first, auto wall) {
+        lbmpm::dispatch([&](auto slab) {
+            lbmpm::dispatch_int<1, 4>([&](auto nt) { tr3d_step<decltype(first)::value, decltype(nt)::value, decltype(slab)::value, decltype(wall)::value><<<g, 256, 0, c->stream>>>(p, t); }, c->ntr);
+        }, c->cfg.ghost_lo || c->cfg.ghost_hi);
+        return LBMPM_OK;
+    });
     LBMPM_HIP_TRY(hipGetLastError());
     std::swap(c->gA, c->gB);
     c->tr_first = false;
@@ -1771,108 +1780,107 @@ extern "C" int lbmpm_rk3dcsf_stage(lbmpm_rk3dcsf *c, int stage)
 }
 
 namespace {
-// A face message as runs of doubles inside the context's arrays: what this context SENDS through `face` (recv = false: its edge planes)
-// or where what comes through `face` lands (recv = true: its ghost planes).  The two sides list their runs in the same order.
+// A face message, described: what this context SENDS through `face` (recv = false: out of its edge planes) or where what comes through
+// `face` lands (recv = true: in its ghost planes).  The two sides list their parts in the same order; a face without ghost planes has none.
+//   populations   runs of doubles inside the context's arrays, behind them one flag byte per fluid cell of two planes (csf3d_face_flags)
+//   phi, n        the fluid cells of two planes / of one plane in three components: the receiver recomputes phi on the walls of its first
+//                 ghost plane itself (same inputs, same order), nobody reads the second one's walls or a wall's n
 struct Run { double *ptr; size_t count; };
-int face_runs(lbmpm_rk3dcsf *c, int msg, int face, bool recv, Run runs[MAX_RUNS])
+struct Stretch { unsigned j0, count; };          // the fluid cells j0 .. j0 + count - 1
+struct FaceMsg {
+    Run runs[MAX_RUNS];
+    int nruns = 0, ntr = 0;
+    double *base = nullptr;                      // phi, n: [ncomp][stride] indexed by lattice cell, through the context's table of cells
+    size_t stride = 0;
+    unsigned ncomp = 0;
+    const uint32_t *table = nullptr;
+    Stretch cells{0u, 0u}, flags{0u, 0u};
+    uint8_t *pure = nullptr;
+    bool empty() const { return nruns == 0 && ncomp == 0; }
+    size_t run_doubles() const { size_t t = 0; for (int k = 0; k < nruns; ++k) t += runs[k].count; return t; }
+    // a packed buffer: the runs in order (or [ncomp][cells]), the flag bytes behind them
+    size_t doubles() const { return run_doubles() + (size_t)ncomp * cells.count + ((size_t)flags.count + 7) / 8; }
+};
+FaceMsg face_msg(const lbmpm_rk3dcsf *c, int msg, int face, bool recv)
 {
-    const int g = face == 0 ? c->cfg.ghost_lo : c->cfg.ghost_hi;
-    if (g == 0) return 0;
+    FaceMsg m;
+    if ((face == 0 ? c->cfg.ghost_lo : c->cfg.ghost_hi) == 0) return m;
     const int lo = c->cfg.ghost_lo, top = c->nz - c->cfg.ghost_hi;       // own planes: lo .. top - 1
+    // the plane next to the face (sent) / the first ghost plane (received); the lower of the two planes on that side of the face
+    const int z1 = face == 0 ? (recv ? lo - 1 : lo) : (recv ? top : top - 1), z2 = (face == 0) == recv ? z1 - 1 : z1;
+    const auto planes = [&](int z, int n) { const unsigned j0 = c->pfirst[(size_t)z]; return Stretch{j0, c->pfirst[(size_t)(z + n)] - j0}; };
+    const Stretch one = planes(z1, 1), two = planes(z2, 2);
     if (msg == LBMPM_CSF_MSG_PDF) {
         // the populations that cross the face, of the plane next to it: moving down (c_z < 0) through the low face, up through the high one;
         // the receiver pulls them out of its first ghost plane.  Fluid cells of a plane are one stretch of every population plane.
         static const int DN[5] = {6, 12, 13, 16, 17}, UP[5] = {5, 11, 14, 15, 18};
-        const int z = face == 0 ? (recv ? lo - 1 : lo) : (recv ? top : top - 1);
         const int *dir = (face == 0) != recv ? DN : UP;      // sent through the low face: down; received through the low face: up
-        const size_t first = c->pfirst[(size_t)z], count = c->pfirst[(size_t)z + 1] - first;
         for (int col = 0; col < 2; ++col)
-            for (int a = 0; a < 5; ++a) runs[col * 5 + a] = Run{c->fA + ((size_t)col * Q + (size_t)dir[a]) * c->FS + first, count};
+            for (int a = 0; a < 5; ++a) m.runs[col * 5 + a] = Run{c->fA + ((size_t)col * Q + (size_t)dir[a]) * c->FS + one.j0, one.count};
         // behind them, per tracer, the one D3Q7 population that crosses the face (-z: 6, +z: 5), as tr3d_step has just written it: out of /
         // into the buffer the next tr3d_step reads (launch_tracers has swapped it when stage 2 returns)
-        for (int t = 0; t < c->ntr; ++t) runs[10 + t] = Run{c->gA + ((size_t)t * TQ + (size_t)dir[0]) * c->FS + first, count};
-        return 10 + c->ntr;
+        for (int t = 0; t < c->ntr; ++t) m.runs[10 + t] = Run{c->gA + ((size_t)t * TQ + (size_t)dir[0]) * c->FS + one.j0, one.count};
+        m.nruns = 10 + c->ntr; m.ntr = c->ntr;
+        m.flags = two; m.pure = c->pure;
+    } else {
+        const bool phi = msg == LBMPM_CSF_MSG_PHI;
+        m.base = phi ? c->phi : c->nh; m.stride = phi ? 0 : c->NS; m.ncomp = phi ? 1u : 3u;
+        m.cells = phi ? two : one; m.table = c->cells;
     }
-    return 0;                                    // (phi and n: cell_msg)
+    return m;
 }
 bool msg_ok(int msg, int face) { return msg >= 0 && msg <= 2 && (face == 0 || face == 1); }
-// n runs from `from` to `to` (either side a packed buffer when its runs are null: consecutive stretches of `buf`), one launch on `stream`
-int copy_runs(const Run *from, const Run *to, const double *buf_in, double *buf_out, const Run *shape, int n, hipStream_t stream)
+// do the two sides of a face describe the same message?
+int same_shape(const FaceMsg &out, const FaceMsg &in)
 {
+    if (out.empty() || in.empty()) { set_error("lbmpm_rk3dcsf_face_copy: the two contexts do not share that face"); return LBMPM_ERR_INVALID; }
+    if (out.ntr != in.ntr) { set_error("lbmpm_rk3dcsf_face_copy: the two contexts carry %d and %d tracers (lbmpm_rk3dcsf_tracer_configure_slab on every slab of the ring)", out.ntr, in.ntr); return LBMPM_ERR_INVALID; }
+    for (int k = 0; k < out.nruns; ++k)
+        if (out.runs[k].count != in.runs[k].count) { set_error("lbmpm_rk3dcsf_face_copy: the masks of the two sides of the face differ (%zu / %zu cells)", out.runs[k].count, in.runs[k].count); return LBMPM_ERR_INVALID; }
+    if (out.cells.count != in.cells.count) { set_error("lbmpm_rk3dcsf_face_copy: the masks of the two sides of the face differ (%u / %u cells)", out.cells.count, in.cells.count); return LBMPM_ERR_INVALID; }
+    if (out.flags.count != in.flags.count) { set_error("lbmpm_rk3dcsf_face_copy: the masks of the two sides of the face differ"); return LBMPM_ERR_INVALID; }
+    return LBMPM_OK;
+}
+// a message from `from` to `to` on `stream`; a side that is null is a packed buffer (buf_in / buf_out).  Populations: one launch for the
+// runs and one for the flags; phi, n: one launch.
+int face_transfer(const FaceMsg *from, const FaceMsg *to, const double *buf_in, double *buf_out, hipStream_t stream)
+{
+    const FaceMsg &m = from ? *from : *to;
     RunSet r;
     unsigned most = 0;
     size_t off = 0;
     for (int k = 0; k < MAX_RUNS; ++k) {
-        r.count[k] = k < n ? (unsigned)shape[k].count : 0u;
-        r.src[k] = k < n ? (from ? from[k].ptr : buf_in + off) : nullptr;
-        r.dst[k] = k < n ? (to ? to[k].ptr : buf_out + off) : nullptr;
-        if (k < n) { off += shape[k].count; most = most > r.count[k] ? most : r.count[k]; }
+        const bool on = k < m.nruns;
+        r.count[k] = on ? (unsigned)m.runs[k].count : 0u;
+        r.src[k] = on ? (from ? from->runs[k].ptr : buf_in + off) : nullptr;
+        r.dst[k] = on ? (to ? to->runs[k].ptr : buf_out + off) : nullptr;
+        off += r.count[k]; most = most > r.count[k] ? most : r.count[k];
     }
-    if (n == 0 || most == 0) return LBMPM_OK;
-    unsigned gx = (most + 2047u) / 2048u;            // eight doubles per thread
-    if (gx > 1024u) gx = 1024u;
-    csf3d_copy_runs<<<dim3(gx, (unsigned)n), 256, 0, stream>>>(r);
+    if (most) {
+        unsigned gx = (most + 2047u) / 2048u;            // eight doubles per thread
+        if (gx > 1024u) gx = 1024u;
+        csf3d_copy_runs<<<dim3(gx, (unsigned)m.nruns), 256, 0, stream>>>(r);
+        LBMPM_HIP_TRY(hipGetLastError());
+    }
+    if (m.cells.count) {
+        unsigned gx = (m.cells.count + 1023u) / 1024u;
+        if (gx > 1024u) gx = 1024u;
+        csf3d_copy_cells<<<dim3(gx, m.ncomp), 256, 0, stream>>>(from ? from->base : buf_in, from ? from->table : nullptr, from ? from->cells.j0 : 0u, from ? from->stride : 0,
+                                                                to ? to->base : buf_out, to ? to->table : nullptr, to ? to->cells.j0 : 0u, to ? to->stride : 0, m.cells.count);
+    }
+    if (const unsigned n = m.flags.count) {
+        if (!to) csf3d_face_flags_pack<<<blocks_of(n), 256, 0, stream>>>(from->pure, from->flags.j0, n, reinterpret_cast<uint8_t *>(buf_out + off));
+        else csf3d_face_flags<<<((to->flags.j0 + n - 1u) >> 8) - (to->flags.j0 >> 8) + 1u, 256, 0, stream>>>(
+            from ? nullptr : reinterpret_cast<const uint8_t *>(buf_in + off), from ? from->pure : nullptr, from ? from->flags.j0 : 0u, to->pure, to->flags.j0, n);
+    }
     LBMPM_HIP_TRY(hipGetLastError());
     return LBMPM_OK;
-}
-// the fluid cells of the two planes next to a face (sent) / beyond it (received), as a stretch of the cells' numbers: the flags of csf3d_face_flags
-void flag_cells(const lbmpm_rk3dcsf *c, int face, bool recv, unsigned &j0, unsigned &count)
-{
-    const int lo = c->cfg.ghost_lo, top = c->nz - c->cfg.ghost_hi;
-    const int z = face == 0 ? (recv ? 0 : lo) : (recv ? top : top - 2);
-    j0 = c->pfirst[(size_t)z]; count = c->pfirst[(size_t)z + 2] - j0;
-}
-// phi (two planes) and n (the plane next to the face / the first ghost plane) travel for fluid cells only: the receiver recomputes phi on
-// the walls of its first ghost plane itself (same inputs, same order), nobody reads the second one's walls or a wall's n
-struct CellMsg { double *base; size_t stride; unsigned ncomp, j0, count; };
-CellMsg cell_msg(const lbmpm_rk3dcsf *c, int msg, int face, bool recv)
-{
-    const int lo = c->cfg.ghost_lo, top = c->nz - c->cfg.ghost_hi;
-    CellMsg m;
-    if (msg == LBMPM_CSF_MSG_PHI) {
-        const int z = face == 0 ? (recv ? 0 : lo) : (recv ? top : top - 2);
-        m.base = c->phi; m.stride = 0; m.ncomp = 1;
-        m.j0 = c->pfirst[(size_t)z]; m.count = c->pfirst[(size_t)z + 2] - m.j0;
-    } else {
-        const int z = face == 0 ? (recv ? lo - 1 : lo) : (recv ? top : top - 1);
-        m.base = c->nh; m.stride = c->NS; m.ncomp = 3;
-        m.j0 = c->pfirst[(size_t)z]; m.count = c->pfirst[(size_t)z + 1] - m.j0;
-    }
-    return m;
-}
-int copy_cells(const CellMsg *from, const lbmpm_rk3dcsf *fc, const CellMsg *to, const lbmpm_rk3dcsf *tc, const double *buf_in, double *buf_out, hipStream_t stream)
-{
-    const CellMsg &shape = from ? *from : *to;
-    if (shape.count == 0) return LBMPM_OK;
-    unsigned gx = (shape.count + 1023u) / 1024u;
-    if (gx > 1024u) gx = 1024u;
-    csf3d_copy_cells<<<dim3(gx, shape.ncomp), 256, 0, stream>>>(from ? from->base : buf_in, from ? fc->cells : nullptr, from ? from->j0 : 0u, from ? from->stride : 0,
-                                                                 to ? to->base : buf_out, to ? tc->cells : nullptr, to ? to->j0 : 0u, to ? to->stride : 0, shape.count);
-    LBMPM_HIP_TRY(hipGetLastError());
-    return LBMPM_OK;
-}
-size_t flag_doubles(const lbmpm_rk3dcsf *c, int face, bool recv)
-{
-    unsigned j0, count;
-    flag_cells(c, face, recv, j0, count);
-    return ((size_t)count + 7) / 8;
 }
 }  // namespace
 
 static int64_t face_total(const lbmpm_rk3dcsf *c, int msg, int face, bool recv)
 {
-    if (!c || !msg_ok(msg, face)) return 0;
-    if (msg != LBMPM_CSF_MSG_PDF) {
-        if ((face == 0 ? c->cfg.ghost_lo : c->cfg.ghost_hi) == 0) return 0;
-        const CellMsg m = cell_msg(c, msg, face, recv);
-        return (int64_t)m.ncomp * m.count;
-    }
-    Run runs[MAX_RUNS];
-    const int n = face_runs(const_cast<lbmpm_rk3dcsf *>(c), msg, face, recv, runs);
-    int64_t t = 0;
-    for (int k = 0; k < n; ++k) t += (int64_t)runs[k].count;
-    if (n && msg == LBMPM_CSF_MSG_PDF) t += (int64_t)flag_doubles(c, face, recv);      // one byte per fluid cell of two planes behind the populations
-    return t;
+    return c && msg_ok(msg, face) ? (int64_t)face_msg(c, msg, face, recv).doubles() : 0;
 }
 extern "C" int64_t lbmpm_rk3dcsf_face_doubles(const lbmpm_rk3dcsf *c, int msg, int face) { return face_total(c, msg, face, false); }
 extern "C" int64_t lbmpm_rk3dcsf_face_doubles_in(const lbmpm_rk3dcsf *c, int msg, int face) { return face_total(c, msg, face, true); }
@@ -1881,60 +1889,23 @@ extern "C" int lbmpm_rk3dcsf_face_pack(lbmpm_rk3dcsf *c, int msg, int face, doub
 {
     LBMPM_REQUIRE(c && buf && msg_ok(msg, face), "lbmpm_rk3dcsf_face_pack: bad argument");
     LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
-    if ((face == 0 ? c->cfg.ghost_lo : c->cfg.ghost_hi) == 0) return LBMPM_OK;
-    if (msg != LBMPM_CSF_MSG_PDF) { const CellMsg m = cell_msg(c, msg, face, false); return copy_cells(&m, c, nullptr, nullptr, nullptr, buf, c->stream); }
-    Run runs[MAX_RUNS];
-    const int n = face_runs(c, msg, face, false, runs);
-    { const int rc = copy_runs(runs, nullptr, nullptr, buf, runs, n, c->stream); if (rc) return rc; }
-    for (int k = 0; k < n; ++k) buf += runs[k].count;
-    if (n && msg == LBMPM_CSF_MSG_PDF) {
-        unsigned j0, count;
-        flag_cells(c, face, false, j0, count);
-        if (count) csf3d_face_flags_pack<<<blocks_of(count), 256, 0, c->stream>>>(c->pure, j0, count, reinterpret_cast<uint8_t *>(buf));
-        LBMPM_HIP_TRY(hipGetLastError());
-    }
-    return LBMPM_OK;
+    const FaceMsg m = face_msg(c, msg, face, false);
+    return face_transfer(&m, nullptr, nullptr, buf, c->stream);
 }
 
 extern "C" int lbmpm_rk3dcsf_face_unpack(lbmpm_rk3dcsf *c, int msg, int face, const double *buf)
 {
     LBMPM_REQUIRE(c && buf && msg_ok(msg, face), "lbmpm_rk3dcsf_face_unpack: bad argument");
     LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
-    if ((face == 0 ? c->cfg.ghost_lo : c->cfg.ghost_hi) == 0) return LBMPM_OK;
-    if (msg != LBMPM_CSF_MSG_PDF) { const CellMsg m = cell_msg(c, msg, face, true); return copy_cells(nullptr, nullptr, &m, c, buf, nullptr, c->stream); }
-    Run runs[MAX_RUNS];
-    const int n = face_runs(c, msg, face, true, runs);
-    { const int rc = copy_runs(nullptr, runs, buf, nullptr, runs, n, c->stream); if (rc) return rc; }
-    for (int k = 0; k < n; ++k) buf += runs[k].count;
-    if (n && msg == LBMPM_CSF_MSG_PDF) {
-        unsigned j0, count;
-        flag_cells(c, face, true, j0, count);
-        if (count) csf3d_face_flags<<<((j0 + count - 1u) >> 8) - (j0 >> 8) + 1u, 256, 0, c->stream>>>(reinterpret_cast<const uint8_t *>(buf), nullptr, 0u, c->pure, j0, count);
-        LBMPM_HIP_TRY(hipGetLastError());
-    }
-    return LBMPM_OK;
+    const FaceMsg m = face_msg(c, msg, face, true);
+    return face_transfer(nullptr, &m, buf, nullptr, c->stream);
 }
 
 extern "C" int lbmpm_rk3dcsf_face_copy(lbmpm_rk3dcsf *src, int src_face, lbmpm_rk3dcsf *dst, int msg)
 {
     LBMPM_REQUIRE(src && dst && src != dst && msg_ok(msg, src_face), "lbmpm_rk3dcsf_face_copy: bad argument");
-    Run out[MAX_RUNS], in[MAX_RUNS];
-    int n = 0;
-    CellMsg cm_out{}, cm_in{};
-    if ((src_face == 0 ? src->cfg.ghost_lo : src->cfg.ghost_hi) == 0 || (src_face == 0 ? dst->cfg.ghost_hi : dst->cfg.ghost_lo) == 0) {
-        set_error("lbmpm_rk3dcsf_face_copy: the two contexts do not share that face"); return LBMPM_ERR_INVALID;
-    }
-    if (msg == LBMPM_CSF_MSG_PDF) {
-        if (src->ntr != dst->ntr) { set_error("lbmpm_rk3dcsf_face_copy: the two contexts carry %d and %d tracers (lbmpm_rk3dcsf_tracer_configure_slab on every slab of the ring)", src->ntr, dst->ntr); return LBMPM_ERR_INVALID; }
-        n = face_runs(src, msg, src_face, false, out);
-        const int m = face_runs(dst, msg, 1 - src_face, true, in);
-        if (n == 0 || n != m) { set_error("lbmpm_rk3dcsf_face_copy: the two contexts do not share that face"); return LBMPM_ERR_INVALID; }
-        for (int k = 0; k < n; ++k)
-            if (out[k].count != in[k].count) { set_error("lbmpm_rk3dcsf_face_copy: the masks of the two sides of the face differ (%zu / %zu cells)", out[k].count, in[k].count); return LBMPM_ERR_INVALID; }
-    } else {
-        cm_out = cell_msg(src, msg, src_face, false); cm_in = cell_msg(dst, msg, 1 - src_face, true);
-        if (cm_out.count != cm_in.count) { set_error("lbmpm_rk3dcsf_face_copy: the masks of the two sides of the face differ (%u / %u cells)", cm_out.count, cm_in.count); return LBMPM_ERR_INVALID; }
-    }
+    const FaceMsg out = face_msg(src, msg, src_face, false), in = face_msg(dst, msg, 1 - src_face, true);
+    { const int rc = same_shape(out, in); if (rc) return rc; }       // (before anything is queued: a refused call leaves both streams alone)
     // on the sender's stream, once the receiver's last stage (which may read the planes written here) has run; the receiver's stream then waits
     LBMPM_HIP_TRY(hipSetDevice(src->cfg.device));
     if (src->cfg.device != dst->cfg.device) {    // two GPUs of one process: the sender's kernels write the receiver's memory
@@ -1943,16 +1914,7 @@ extern "C" int lbmpm_rk3dcsf_face_copy(lbmpm_rk3dcsf *src, int src_face, lbmpm_r
         else if (e != hipSuccess) { set_error("lbmpm_rk3dcsf_face_copy: device %d cannot reach device %d (%s); use face_pack / face_unpack", src->cfg.device, dst->cfg.device, hipGetErrorString(e)); return LBMPM_ERR_UNSUPPORTED; }
     }
     LBMPM_HIP_TRY(hipStreamWaitEvent(src->stream, dst->ev_stage, 0));
-    if (msg == LBMPM_CSF_MSG_PDF) { const int rc = copy_runs(out, in, nullptr, nullptr, out, n, src->stream); if (rc) return rc; }
-    else { const int rc = copy_cells(&cm_out, src, &cm_in, dst, nullptr, nullptr, src->stream); if (rc) return rc; }
-    if (msg == LBMPM_CSF_MSG_PDF) {
-        unsigned sj0, scount, dj0, dcount;
-        flag_cells(src, src_face, false, sj0, scount);
-        flag_cells(dst, 1 - src_face, true, dj0, dcount);
-        if (scount != dcount) { set_error("lbmpm_rk3dcsf_face_copy: the masks of the two sides of the face differ"); return LBMPM_ERR_INVALID; }
-        if (scount) csf3d_face_flags<<<((dj0 + scount - 1u) >> 8) - (dj0 >> 8) + 1u, 256, 0, src->stream>>>(nullptr, src->pure, sj0, dst->pure, dj0, scount);
-        LBMPM_HIP_TRY(hipGetLastError());
-    }
+    { const int rc = face_transfer(&out, &in, nullptr, nullptr, src->stream); if (rc) return rc; }
     LBMPM_HIP_TRY(hipEventRecord(src->ev_sent[src_face], src->stream));
     LBMPM_HIP_TRY(hipSetDevice(dst->cfg.device));
     LBMPM_HIP_TRY(hipStreamWaitEvent(dst->stream, src->ev_sent[src_face], 0));
@@ -1981,8 +1943,7 @@ static int observe(lbmpm_rk3dcsf *c, bool rec, double *pdf)
     const CsfDev p = make_dev(c);
     double *rho = c->obs, *u = rho + 2 * c->N, *phi = u + 3 * c->N;
     const unsigned g = blocks_of(c->N);
-    if (c->first) { if (rec) csf3d_observe<true, true><<<g, 256, 0, c->stream>>>(p, pdf, rho, u, phi); else csf3d_observe<true, false><<<g, 256, 0, c->stream>>>(p, pdf, rho, u, phi); }
-    else { if (rec) csf3d_observe<false, true><<<g, 256, 0, c->stream>>>(p, pdf, rho, u, phi); else csf3d_observe<false, false><<<g, 256, 0, c->stream>>>(p, pdf, rho, u, phi); }
+    lbmpm::dispatch([&](auto first, auto r) { csf3d_observe<decltype(first)::value, decltype(r)::value><<<g, 256, 0, c->stream>>>(p, pdf, rho, u, phi); }, c->first, rec);
     LBMPM_HIP_TRY(hipGetLastError());
     LBMPM_HIP_TRY(hipStreamSynchronize(c->stream));
     return LBMPM_OK;
@@ -2459,9 +2420,10 @@ static int tracer_observe(lbmpm_rk3dcsf *c, int tracer, double *conc, double *pd
     double *const st = staged.get();
     const CsfDev p = make_dev(c);
     const TrDev t = make_trdev(c);
-    if (c->tr_first) tr3d_observe<true, false><<<blocks_of(c->N), 256, 0, c->stream>>>(p, t, tracer, pdf ? st + c->N : nullptr, st);
-    else if (c->wall) tr3d_observe<false, true><<<blocks_of(c->N), 256, 0, c->stream>>>(p, t, tracer, pdf ? st + c->N : nullptr, st);
-    else tr3d_observe<false, false><<<blocks_of(c->N), 256, 0, c->stream>>>(p, t, tracer, pdf ? st + c->N : nullptr, st);
+    with_pull(c, [&](auto first, auto wall) {
+        tr3d_observe<decltype(first)::value, decltype(wall)::value><<<blocks_of(c->N), 256, 0, c->stream>>>(p, t, tracer, pdf ? st + c->N : nullptr, st);
+        return LBMPM_OK;
+    });
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e == hipSuccess && conc) e = hipMemcpy(conc, st, c->N * sizeof(double), hipMemcpyDeviceToHost);
@@ -2490,14 +2452,15 @@ extern "C" int lbmpm_rk3dcsf_tracer_integrals(lbmpm_rk3dcsf *c, double *out)
     { const int rc = tracer_ready(c, 0, "lbmpm_rk3dcsf_tracer_integrals"); if (rc) return rc; }
     if (!c->tr_given) { set_error("lbmpm_rk3dcsf_tracer_integrals before lbmpm_rk3dcsf_tracer_set_concentration / _set_pdf"); return LBMPM_ERR_STATE; }
     LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
-    const unsigned planes = (unsigned)(c->nz - c->cfg.ghost_lo - c->cfg.ghost_hi), plane_cells = (unsigned)c->nx * (unsigned)c->ny, nT = (unsigned)c->ntr;
-    { const int rc = integral_buffer<TracerCols>(c->mem, &c->trinteg, planes, plane_cells, nT, nullptr); if (rc) return rc; }
+    const AnalysisView v = AnalysisModel<lbmpm_rk3dcsf>::view(c);
+    const unsigned nT = (unsigned)c->ntr;
+    { const int rc = integral_buffer<TracerCols>(c->mem, &c->trinteg, v.planes, v.plane_cells(), nT, nullptr); if (rc) return rc; }
     const CsfDev p = make_dev(c);
     const TrDev t = make_trdev(c);
-    if (c->tr_first) LBMPM_HIP_TRY(tracer_integrals_run(TrIntLoader<true, false>{p, t}, planes, plane_cells, nT, c->trinteg, out, c->stream));
-    else if (c->wall) LBMPM_HIP_TRY(tracer_integrals_run(TrIntLoader<false, true>{p, t}, planes, plane_cells, nT, c->trinteg, out, c->stream));
-    else LBMPM_HIP_TRY(tracer_integrals_run(TrIntLoader<false, false>{p, t}, planes, plane_cells, nT, c->trinteg, out, c->stream));
-    return LBMPM_OK;
+    return with_pull(c, [&](auto first, auto wall) -> int {
+        LBMPM_HIP_TRY(tracer_integrals_run(TrIntLoader<decltype(first)::value, decltype(wall)::value>{p, t}, v.planes, v.plane_cells(), nT, c->trinteg, out, c->stream));
+        return LBMPM_OK;
+    });
 }
 
 // Reaction at solid walls: see include/lbmpm.h.  The rates travel as kernel arguments (make_trdev); with a mineral map one class word per
@@ -2585,11 +2548,13 @@ extern "C" int lbmpm_rk3dcsf_tracer_wall_integrals(lbmpm_rk3dcsf *c, double *out
     { const int rc = tracer_ready(c, 0, "lbmpm_rk3dcsf_tracer_wall_integrals"); if (rc) return rc; }
     if (!c->tr_given) { set_error("lbmpm_rk3dcsf_tracer_wall_integrals before lbmpm_rk3dcsf_tracer_set_concentration / _set_pdf"); return LBMPM_ERR_STATE; }
     LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
-    const unsigned planes = (unsigned)(c->nz - c->cfg.ghost_lo - c->cfg.ghost_hi), plane_cells = (unsigned)c->nx * (unsigned)c->ny, nT = (unsigned)c->ntr;
-    { const int rc = integral_buffer<TracerWallCols>(c->mem, &c->trwall, planes, plane_cells, nT, nullptr); if (rc) return rc; }
+    const AnalysisView v = AnalysisModel<lbmpm_rk3dcsf>::view(c);
+    const unsigned nT = (unsigned)c->ntr;
+    { const int rc = integral_buffer<TracerWallCols>(c->mem, &c->trwall, v.planes, v.plane_cells(), nT, nullptr); if (rc) return rc; }
     const CsfDev p = make_dev(c);
     const TrDev t = make_trdev(c);
-    if (c->tr_first) LBMPM_HIP_TRY(tracer_wall_integrals_run(TrWallLoader<true>{p, t}, planes, plane_cells, nT, c->trwall, out, c->stream));
-    else LBMPM_HIP_TRY(tracer_wall_integrals_run(TrWallLoader<false>{p, t}, planes, plane_cells, nT, c->trwall, out, c->stream));
-    return LBMPM_OK;
+    return with_pull(c, [&](auto first, auto) -> int {       // (the uptake has no WALL instance of its own)
+        LBMPM_HIP_TRY(tracer_wall_integrals_run(TrWallLoader<decltype(first)::value>{p, t}, v.planes, v.plane_cells(), nT, c->trwall, out, c->stream));
+        return LBMPM_OK;
+    });
 }

@@ -492,7 +492,77 @@ _TRACERS_AT_CONSTRUCTION = ("tracers on z-slabs are part of the slabs' populatio
                             "give them to %s at construction (tracers=dict(...)), not afterwards")
 
 
-class RK3DCSFCluster(StackedAnalysis):
+class _SlabSetup:
+    """What RK3DCSFCluster and RK3DCSFDistributed share: how a set-up call with undivided arrays reaches the slabs, and how the slabs'
+    arrays come back.  self.slabs is the slabs this object holds, self._pairs() the (slab, _SlabGeometry) pairs -- all of them in a
+    cluster, this rank's one under torch.distributed.  A setter takes the undivided array [nz][ny][nx] and gives every slab its planes and the images of its
+    neighbours'; a getter returns the own planes of the pairs, stacked along z (Distributed: this rank's own planes, gather() stacks
+    them on rank 0).  Distributed: the same call with the same arrays on every rank, and the setters after sync() -- the slab must be idle."""
+
+    def set_macro(self, rhoR, rhoB, vx=None, vy=None, vz=None):
+        """the undivided arrays [nz][ny][nx]; every slab takes its planes"""
+        for s, g in self._pairs():
+            s.set_macro(*[g.cut(None if a is None else np.asarray(a, dtype=np.float64)) for a in (rhoR, rhoB, vx, vy, vz)])
+
+    def set_pdf(self, fR, fB, force=None):
+        for s, g in self._pairs():
+            s.set_pdf(g.cut(np.asarray(fR)), g.cut(np.asarray(fB)), None if force is None else tuple(g.cut(np.asarray(c)) for c in force))
+
+    def set_contact_angles(self, theta):
+        """the undivided array [nz][ny][nx], the same on every rank (RK3DCSFSolver.set_contact_angles; None: the scalar angle again);
+        every slab takes its planes and the images of its neighbours'.  Distributed: call it after sync(), the slab must be idle"""
+        theta = _undivided_angles(theta, self.shape)
+        for s, g in self._pairs():
+            s.set_contact_angles(g.cut(theta))
+
+    def set_body_force(self, g=None, *, red=None, blue=None):
+        """RK3DCSFSolver.set_body_force on every slab, the same call on every rank (the force is local to a cell: no message changes)"""
+        for s in self.slabs:
+            s.set_body_force(g, red=red, blue=blue)
+
+    def configure_tracers(self, *args, **kwargs):
+        """refused: on slabs the tracers change the size of the population message, so they are given at construction (tracers=)"""
+        raise _lib.LbmpmError(_TRACERS_AT_CONSTRUCTION % type(self).__name__, _lib.ERR_UNSUPPORTED)
+
+    def set_concentration(self, t, conc):
+        """the undivided array [nz][ny][nx]; every slab takes its planes (and the images of its neighbours')"""
+        for s, g in self._pairs():
+            s.set_concentration(t, g.cut(np.asarray(conc, dtype=np.float64)))
+
+    def set_tracer_pdf(self, t, pdf):
+        for s, g in self._pairs():
+            s.set_tracer_pdf(t, g.cut(np.asarray(pdf, dtype=np.float64)))
+
+    def set_wall_reaction(self, rates, minerals=None):
+        """RK3DCSFSolver.set_wall_reaction, the same call on every rank, with the undivided `minerals` [nz][ny][nx]; every slab takes
+        its planes and the images of its neighbours'.  Distributed: call it after sync(), the slab must be idle"""
+        m = _undivided_minerals(minerals, self.shape)
+        for s, g in self._pairs():
+            s.set_wall_reaction(rates, g.cut(m))
+
+    def _own(self, of):
+        return np.concatenate([g.own(of(s)) for s, g in self._pairs()], axis=0)
+
+    def get(self, name):
+        """the own planes of the slabs held (Distributed: this rank's)"""
+        return self._own(lambda s: s.get(name))
+
+    def get_concentration(self, t):
+        """the own planes of the slabs held (Distributed: this rank's; gather() stacks them on rank 0)"""
+        return self._own(lambda s: s.get_concentration(t))
+
+    def get_tracer_pdf(self, t):
+        return self._own(lambda s: s.get_tracer_pdf(t))
+
+    # (the same on every slab)
+    body_force = property(lambda self: self.slabs[0].body_force)
+    wall_reaction = property(lambda self: self.slabs[0].wall_reaction)
+    steps_done = property(lambda self: self.slabs[0].steps_done)
+    dominant_kernel = property(lambda self: self.slabs[0].dominant_kernel)
+    num_fluid_nodes = property(lambda self: sum(int((g.own(s.is_domain) == 1).sum()) for s, g in self._pairs()))
+
+
+class RK3DCSFCluster(_SlabSetup, StackedAnalysis):
     """The 3-D CSF model cut into slabs along z, every slab a context of its own (devices[k]; all on one GPU: a rehearsal of the
     decomposition, bit-equal to the undivided lattice).  One time step = three stages with a face message after each: phi (two planes),
     n (one plane), the populations crossing the face (lbmpm_rk3dcsf_stage / _face_copy).
@@ -516,77 +586,33 @@ class RK3DCSFCluster(StackedAnalysis):
         for s in self.slabs:
             s.close()
 
-    def set_macro(self, rhoR, rhoB, vx=None, vy=None, vz=None):
-        for s, g in zip(self.slabs, self.geo):
-            s.set_macro(*[g.cut(None if a is None else np.asarray(a, dtype=np.float64)) for a in (rhoR, rhoB, vx, vy, vz)])
-
-    def set_pdf(self, fR, fB, force=None):
-        for s, g in zip(self.slabs, self.geo):
-            s.set_pdf(g.cut(np.asarray(fR)), g.cut(np.asarray(fB)), None if force is None else tuple(g.cut(np.asarray(c)) for c in force))
+    def _pairs(self):
+        return list(zip(self.slabs, self.geo))
 
     def set_contact_angles(self, theta):
-        """the undivided array [nz][ny][nx] (RK3DCSFSolver.set_contact_angles; None: the scalar angle again); every slab takes its
-        planes and the images of its neighbours'.  Checked on every slab before any is changed"""
+        """_SlabSetup.set_contact_angles.  Checked on every slab before any is changed"""
         theta = _undivided_angles(theta, self.shape)
-        cut = [g.cut(theta) for g in self.geo]
         if theta is not None:
-            for s, a in zip(self.slabs, cut):
-                _angles_valid(s, a)
-        for s, a in zip(self.slabs, cut):
-            s.set_contact_angles(a)
+            for s, g in self._pairs():
+                _angles_valid(s, g.cut(theta))
+        super().set_contact_angles(theta)
 
     def set_body_force(self, g=None, *, red=None, blue=None):
-        """RK3DCSFSolver.set_body_force on every slab (the force is local to a cell: no message changes).  Checked before any slab is changed"""
+        """_SlabSetup.set_body_force.  Checked before any slab is changed"""
         if not (g is None and red is None and blue is None):
             if not np.all(np.isfinite(body_force_pair(g, red, blue))):
                 raise _lib.LbmpmError("set_body_force: an acceleration that is not finite", _lib.ERR_INVALID)
-        for s in self.slabs:
-            s.set_body_force(g, red=red, blue=blue)
-
-    @property
-    def body_force(self):
-        return self.slabs[0].body_force
-
-    def configure_tracers(self, *args, **kwargs):
-        """refused: on slabs the tracers change the size of the population message, so they are given at construction (tracers=)"""
-        raise _lib.LbmpmError(_TRACERS_AT_CONSTRUCTION % type(self).__name__, _lib.ERR_UNSUPPORTED)
-
-    def set_concentration(self, t, conc):
-        """the undivided array [nz][ny][nx]; every slab takes its planes (and the images of its neighbours')"""
-        for s, g in zip(self.slabs, self.geo):
-            s.set_concentration(t, g.cut(np.asarray(conc, dtype=np.float64)))
-
-    def set_tracer_pdf(self, t, pdf):
-        for s, g in zip(self.slabs, self.geo):
-            s.set_tracer_pdf(t, g.cut(np.asarray(pdf, dtype=np.float64)))
-
-    def get_concentration(self, t):
-        return np.concatenate([g.own(s.get_concentration(t)) for s, g in zip(self.slabs, self.geo)], axis=0)
-
-    def get_tracer_pdf(self, t):
-        return np.concatenate([g.own(s.get_tracer_pdf(t)) for s, g in zip(self.slabs, self.geo)], axis=0)
+        super().set_body_force(g, red=red, blue=blue)
 
     def set_wall_reaction(self, rates, minerals=None):
-        """RK3DCSFSolver.set_wall_reaction with the undivided `minerals` [nz][ny][nx]; every slab takes its planes and the images of its
-        neighbours'.  Checked on every slab before any is changed"""
-        if rates is None:
-            if minerals is not None:
-                raise ValueError("set_wall_reaction: a mineral map without rates")
-            for s in self.slabs:
-                s.set_wall_reaction(None)
-            return
-        if not self.num_tracers:
-            raise _lib.LbmpmError("set_wall_reaction before configure_tracers", _lib.ERR_STATE)
-        a = wall_rates(rates, self.num_tracers)
-        cut = [g.cut(_undivided_minerals(minerals, self.shape)) for g in self.geo]
-        for s, m in zip(self.slabs, cut):
-            _wall_valid(s.is_domain, a, m)
-        for s, m in zip(self.slabs, cut):
-            s.set_wall_reaction(a, m)
-
-    @property
-    def wall_reaction(self):
-        return self.slabs[0].wall_reaction
+        """_SlabSetup.set_wall_reaction.  Checked on every slab before any is changed"""
+        if rates is not None:
+            if not self.num_tracers:
+                raise _lib.LbmpmError("set_wall_reaction before configure_tracers", _lib.ERR_STATE)
+            a, m = wall_rates(rates, self.num_tracers), _undivided_minerals(minerals, self.shape)
+            for s, g in self._pairs():
+                _wall_valid(s.is_domain, a, g.cut(m))
+        super().set_wall_reaction(rates, minerals)
 
     def tracer_wall_integrals(self):
         """the slabs' wall tables in plane order: bit-equal to the undivided lattice's"""
@@ -613,28 +639,19 @@ class RK3DCSFCluster(StackedAnalysis):
         for s in self.slabs:
             s.sync()
 
-    def get(self, name):
-        return np.concatenate([g.own(s.get(name)) for s, g in zip(self.slabs, self.geo)], axis=0)
-
     def tracer_integrals(self):
         """the slabs' tracer tables in plane order: bit-equal to the undivided lattice's"""
         from .integrals import TracerIntegrals
         return TracerIntegrals(np.concatenate([s.tracer_integrals().planes for s in self.slabs], axis=0), self.nx, self.ny)
 
-    num_fluid_nodes = property(lambda self: int(self.is_fluid_total))
-    steps_done = property(lambda self: self.slabs[0].steps_done)
-    dominant_kernel = property(lambda self: self.slabs[0].dominant_kernel)
-
-    @property
-    def is_fluid_total(self):
-        return sum(int((g.own(s.is_domain) == 1).sum()) for s, g in zip(self.slabs, self.geo))
+    is_fluid_total = property(lambda self: self.num_fluid_nodes)
 
     @property
     def bulk_cells(self):
         return sum(s.bulk_cells for s in self.slabs)
 
 
-class RK3DCSFDistributed(GatheredAnalysis):
+class RK3DCSFDistributed(_SlabSetup, GatheredAnalysis):
     """One slab of the 3-D CSF model per rank of torch.distributed (launch: one process per GPU).  The face messages travel as device
     tensors under the nccl (= RCCL) backend and through host memory under gloo; three per step and face (phi, n, populations: 2 + 3 +
     10 doubles per cell of a plane, + 1 per tracer), batched per stage.  Opt-in (transport='ipc' | 'rccl' | 'auto'): the messages travel over a transport
@@ -700,45 +717,10 @@ class RK3DCSFDistributed(GatheredAnalysis):
         if self.world > 1 and want != "torch":
             self._connect(want)
 
-    def configure_tracers(self, *args, **kwargs):
-        """refused: on slabs the tracers change the size of the population message, so they are given at construction (tracers=)"""
-        raise _lib.LbmpmError(_TRACERS_AT_CONSTRUCTION % type(self).__name__, _lib.ERR_UNSUPPORTED)
+    slabs = property(lambda self: [self.slab])
 
-    def set_contact_angles(self, theta):
-        """the undivided array [nz][ny][nx], the same on every rank (RK3DCSFSolver.set_contact_angles; None: the scalar angle again);
-        every rank takes its planes and the images of its neighbours'.  Call it after sync(): the slab must be idle"""
-        self.slab.set_contact_angles(self.geo.cut(_undivided_angles(theta, self.shape)))
-
-    def set_body_force(self, g=None, *, red=None, blue=None):
-        """RK3DCSFSolver.set_body_force, the same call on every rank (the force is local to a cell: no message changes)"""
-        self.slab.set_body_force(g, red=red, blue=blue)
-
-    @property
-    def body_force(self):
-        return self.slab.body_force
-
-    def set_concentration(self, t, conc):
-        """the undivided array [nz][ny][nx]; every rank takes its planes (and the images of its neighbours')"""
-        self.slab.set_concentration(t, self.geo.cut(np.asarray(conc, dtype=np.float64)))
-
-    def set_tracer_pdf(self, t, pdf):
-        self.slab.set_tracer_pdf(t, self.geo.cut(np.asarray(pdf, dtype=np.float64)))
-
-    def get_concentration(self, t):
-        """this rank's own planes (gather() stacks them on rank 0)"""
-        return np.ascontiguousarray(self.geo.own(self.slab.get_concentration(t)))
-
-    def get_tracer_pdf(self, t):
-        return np.ascontiguousarray(self.geo.own(self.slab.get_tracer_pdf(t)))
-
-    def set_wall_reaction(self, rates, minerals=None):
-        """RK3DCSFSolver.set_wall_reaction, the same call on every rank, with the undivided `minerals` [nz][ny][nx]; every rank takes
-        its planes and the images of its neighbours'.  Call it after sync(): the slab must be idle"""
-        self.slab.set_wall_reaction(rates, self.geo.cut(_undivided_minerals(minerals, self.shape)))
-
-    @property
-    def wall_reaction(self):
-        return self.slab.wall_reaction
+    def _pairs(self):
+        return [(self.slab, self.geo)]
 
     def tracer_wall_integrals(self):
         """collective: rank 0 returns the integrals.TracerWallIntegrals of the whole lattice ([nz][nT][4]), the others None"""
@@ -825,14 +807,6 @@ class RK3DCSFDistributed(GatheredAnalysis):
             self._t_stage, self._t_msg, self._t_count = [0.0] * 3, [0.0] * 3, [0] * 3
         return out
 
-    def set_macro(self, rhoR, rhoB, vx=None, vy=None, vz=None):
-        """the undivided arrays [nz][ny][nx]; every rank takes its planes"""
-        self.slab.set_macro(*[self.geo.cut(None if a is None else np.asarray(a, dtype=np.float64)) for a in (rhoR, rhoB, vx, vy, vz)])
-
-    def set_pdf(self, fR, fB, force=None):
-        self.slab.set_pdf(self.geo.cut(np.asarray(fR)), self.geo.cut(np.asarray(fB)),
-                          None if force is None else tuple(self.geo.cut(np.asarray(c)) for c in force))
-
     def step(self, nsteps=1):
         if self.world == 1:
             return self.slab.step(nsteps)
@@ -851,10 +825,6 @@ class RK3DCSFDistributed(GatheredAnalysis):
         else:
             self.slab.sync()
 
-    def get(self, name):
-        """this rank's own planes"""
-        return np.ascontiguousarray(self.geo.own(self.slab.get(name)))
-
     def tracer_integrals(self):
         """collective: rank 0 returns the integrals.TracerIntegrals of the whole lattice ([nz][nT][9]: axis 0 is z, so gather() stacks the
         ranks' tables), the others None"""
@@ -871,7 +841,3 @@ class RK3DCSFDistributed(GatheredAnalysis):
     device_index = property(lambda self: self._dev.index)
     ny = property(lambda self: self.shape[1])
     nx = property(lambda self: self.shape[2])
-
-    num_fluid_nodes = property(lambda self: int((self.geo.own(self.slab.is_domain) == 1).sum()))
-    steps_done = property(lambda self: self.slab.steps_done)
-    dominant_kernel = property(lambda self: self.slab.dominant_kernel)

@@ -160,7 +160,13 @@ def test_refusals_of_connect_and_step():
     other_cut = _slab(dom, 0, 20)
     blocked = dom.copy(); blocked[15:17, 5:9, 5:9] = 0                         # another mask beyond the cut at plane 15
     other_mask = _slab(blocked, 0, 15)
-    assert other_mask.face_doubles_in(1, 1) != ring[1].face_doubles(1, 0)
+    for m in range(3):                                                         # face_copy refuses it for every message, nothing enqueued
+        assert other_mask.face_doubles_in(m, 1) != ring[1].face_doubles(m, 0)
+        assert status(ring[1].send_to, 0, other_mask, m) == ERR_INVALID
+    blocked2 = dom.copy(); blocked2[16:17, 5:9, 5:9] = 0                       # the edge plane's runs match, only the flag stretch differs
+    flags_only = _slab(blocked2, 0, 15)
+    assert flags_only.face_doubles_in(2, 1) == ring[1].face_doubles(2, 0) and flags_only.face_doubles_in(1, 1) != ring[1].face_doubles(1, 0)
+    assert status(ring[1].send_to, 0, flags_only, 0) == ERR_INVALID
     assert status(ring[1].ipc_connect, other_cut.ipc_init(), blobs[2]) == ERR_INVALID      # a slab of another cut
     assert status(ring[1].ipc_connect, other_mask.ipc_init(), blobs[2]) == ERR_INVALID     # other message sizes across the face
     assert status(ring[1].ipc_connect, b"\x17" * 256, blobs[2]) == ERR_INVALID             # not a blob
@@ -180,7 +186,7 @@ def test_refusals_of_connect_and_step():
     assert status(ring[1].transport_probe, 1) == ERR_STATE
     ring[1].transport_disconnect()
     assert ring[1].transport == "none"
-    for s in ring + [other_cut, other_mask, whole]:
+    for s in ring + [other_cut, other_mask, flags_only, whole]:
         s.close()
 
 
