@@ -4,6 +4,10 @@ against the vector's magnitude).  tests/test_param_points_cpu.py proves that at 
 every rate moves the oracle by >= 1000 x that tolerance, and that the oracle follows itself within a tenth of it: a kernel that ignores a
 config field, hard-codes its default or swaps two fields fails here by three orders of magnitude.
 
+The 2-D CSF step with tracers fused into it (table rk2d-tr) is its own instantiation of the fused tile: sixteen instances that pair every
+value of relaxation, wetting rule, tautype, inlet, outlet, tracer set (1, 2, 3 with the reaction, 4), tracer ends and launch path (tall
+lattice: rk2d_fused_tracer with both copies of node_finish; short lattice: the single launch) with every value of every other axis.
+
 At A also the paths that carry a parameter outside the step kernel: slabs (face pack / unpack), get_pdf and set_pdf of the 23-value
 storage (beta enters its records), the 3-D CSF slabs and the bulk kernel csf3d_collide_deep (the MRT rates a second time)."""
 import numpy as np
@@ -54,6 +58,77 @@ def test_rk2d_csf(point, inst):
         worst = max(worst, _hold("rk2d-csf", got, ref[n], "%s %s step %d" % (point, _id(inst), n)))
     s.close()
     _report("rk2d-csf", point, inst, worst)
+
+
+_FLOW_2D = ("fR", "fB", "rhoR", "rhoB", "phi", "vx", "vy", "Gx", "Gy", "Fx", "Fy", "K")
+
+
+def _tracer_solver(p):
+    """RK2DSolver with the tracers of p["tr"] on the lattice of the instance, started as the oracle of P.oracle_run("rk2d-tr", p) is"""
+    from openlbmpm_amd.rk2d import DEFAULT_PARAMS, RK2DSolver
+    dom, rR, rB = P.lattice_tr(p["lattice"])
+    conc = P.concentrations(dom, p["tracers"])
+    s = RK2DSolver(dom, {k: p[k] for k in DEFAULT_PARAMS}, diagnostics=True)
+    s.set_macro(rR, rB)
+    s.configure_tracers(**p["tr"])
+    for k in range(p["tracers"]):
+        s.set_tracer(k, conc[k])
+    return s, conc
+
+
+@pytest.mark.parametrize("point,inst", _cases("rk2d-tr"), ids=_id)
+def test_rk2d_tracers(point, inst):
+    """the CSF step with D2Q5 tracers fused into it -- rk2d_fused_tracer<MRT, SH> on the tall lattice, rk2d_fused<MRT, true, SH, 1> on the
+    short one (launch_fused_tracer) -- against oracle.tr.CoupledOracle: every tracer's concentration and the flow fields of the CSF table"""
+    p = P.params(P.RK2D_TR, point, inst)
+    assert P.tracer_launch(P.lattice_tr(p["lattice"])[0].shape[0])[3] == (p["lattice"] == "short")
+    ref = P.oracle_run("rk2d-tr", p, CHECKPOINTS)
+    s, _ = _tracer_solver(p)
+    worst = 0.0
+    for n in CHECKPOINTS:
+        s.step(n - s.steps_done)
+        got = {f: s.get_compact(f) for f in _FLOW_2D}
+        got.update({"C%d" % k: s.get_tracer(k, compact=True) for k in range(p["tracers"])})
+        assert all("C%d" % k in ref[n] for k in range(p["tracers"]))
+        worst = max(worst, _hold("rk2d-tr", got, ref[n], "%s %s step %d" % (point, _id(inst), n)))
+    s.close()
+    _report("rk2d-tr", point, inst, worst)
+
+
+@pytest.mark.parametrize("relax,lattice", [("SRT", "tall"), ("MRT", "short")])
+def test_rk2d_tracers_are_passive(relax, lattice):
+    """the flow part of the tracer kernel sees neither the number of tracers nor their parameters: one tracer at A and four at B leave
+    the same populations, bit for bit"""
+    t = P.RK2D_TR
+    out = []
+    for point, nT in (("A", 1), ("B", 4)):
+        p = P.params(t, "A", dict(t["base"], relax=relax, lattice=lattice, tracers=nT))
+        p["tr"] = P.tracer_kwargs(t["tracer"], point, nT, p["ends"])
+        s, _ = _tracer_solver(p)
+        s.step(P.STEPS)
+        out.append((s.get("fR"), s.get("fB")))
+        s.close()
+    for name, a, b in (("fR", out[0][0], out[1][0]), ("fB", out[0][1], out[1][1])):
+        rows = np.flatnonzero(np.any(a != b, axis=(1, 2)))
+        assert rows.size == 0, "%s differs between one tracer at A and four at B on the rows %s" % (name, rows.tolist())
+    assert np.all(np.isfinite(out[0][0])) and np.abs(out[0][0]).max() > 0
+
+
+@pytest.mark.parametrize("relax", ["SRT", "MRT"])
+def test_rk2d_tracers_keep_their_mass_between_closed_ends(relax):
+    """both ends off (the tracers' streaming wraps in y, walls bounce back), four tracers at A on the tall lattice: the summed concentration
+    of every tracer stays, to the 1e-11 of test_tracer_gpu.py::test_tracer_mass_conserved_without_open_boundaries"""
+    t = P.RK2D_TR
+    p = P.params(t, "A", dict(t["base"], relax=relax, tracers=4, ends=(False, False)))
+    s, conc = _tracer_solver(p)
+    s.step(P.STEPS)
+    for k in range(4):
+        c = s.get_tracer(k)
+        e = abs(c.sum() - conc[k].sum()) / conc[k].sum()
+        print("rk2d-tr %s: tracer %d keeps its mass to %.2e" % (relax, k, e))
+        assert np.isfinite(c).all() and e < 1e-11, (k, e)
+    assert np.abs(s.get_tracer(0) - conc[0]).max() > 1e-3        # (and moved)
+    s.close()
 
 
 def _pert_solver(p, **more):
