@@ -74,7 +74,8 @@ int lbmpm_hbm_stream_test(int device, int64_t bytes_per_buffer, int reps, double
 enum { LBMPM_RELAX_SRT = 0, LBMPM_RELAX_MRT = 1 };
 enum { LBMPM_INLET_VELOCITY = 0,      /* BoundaryTypeInlet 'Neumann'   */
        LBMPM_INLET_PRESSURE = 1,      /* BoundaryTypeInlet 'Dirichlet' */
-       LBMPM_INLET_PERIODIC = 2 };    /* rk3dcsf only, together with LBMPM_OUTLET_NONE: BoundaryTypeInlet 'Periodic' -- periodic z */
+       LBMPM_INLET_PERIODIC = 2 };    /* rk3dcsf and rk2d (CSF step), together with LBMPM_OUTLET_NONE: BoundaryTypeInlet 'Periodic' --
+                                         periodic z / periodic y */
 enum { LBMPM_OUTLET_PRESSURE = 0,     /* BoundaryTypeOutlet 'Dirichlet'  */
        LBMPM_OUTLET_CONVECTIVE = 1,   /* BoundaryTypeOutlet 'Convective' */
        LBMPM_OUTLET_NONE = 2,         /* sc2d: no boundary kernels at all, inlet included: fully periodic box
@@ -205,6 +206,28 @@ typedef struct lbmpm_rk2d_perturbation {
     double outlet_rho_b;           /*                      densityBL                           */
 } lbmpm_rk2d_perturbation;
 int lbmpm_rk2d_set_perturbation(lbmpm_rk2d *ctx, const lbmpm_rk2d_perturbation *par);
+/* Body force (gravity, force-driven flow) of the CSF step: lbmpm_rk2d_set_body_force gives each colour an acceleration g_R = (gx, gy), g_B in
+ * lattice units.  In every fluid node the step computes, the force density is F_b = rho_R g_R + rho_B g_B with the densities the node has
+ * after the step's boundary-row rules.  The velocity is u = ((sum e f_tot + F_csf / 2) + F_b / 2) / rho, evaluated in that order: the CSF
+ * force stays the one of the step before, F_b is the step's own, so nothing new is stored per node.  The Guo source (SRT :1743-1798, MRT
+ * :2027-2113 in moment space) takes F_csf + F_b in the place of F_csf.  LBMPM_RK_FX / _FY and the force that set_pdf / set_macro clear stay
+ * the CSF force alone; LBMPM_RK_VX / _VY / _REC_VX / _REC_VY and the tracers' flow carry the u above.  The force is not a configuration
+ * field: a context without one, between open rows, launches the kernels it always launched (rk2d_fused, rk2d_fused_tracer, rk2d_collide_stream);
+ * with one the step is rk2d_forced / rk2d_forced_tracer / rk2d_collide_stream_forced, in both schedules and with tracers.
+ * NULL, NULL switches the force off.  Whenever the context is idle, repeatedly; the state and the step counter stay, set_macro / set_pdf keep
+ * it.  LBMPM_ERR_INVALID (nothing changed): one pointer NULL, a value not finite.  LBMPM_ERR_UNSUPPORTED: the perturbation operator, in
+ * either order of the two calls.
+ * Periodic y (force-driven flow without open rows): inlet_type LBMPM_INLET_PERIODIC together with outlet_type LBMPM_OUTLET_NONE; one
+ * without the other is LBMPM_ERR_INVALID.  All ny rows are then ordinary rows that wrap like x: no ghost row copies another, no Zou-He or
+ * convective rule runs, inlet_velocity_y, inlet_rho_* and outlet_rho_total are not read, and the mask is taken as given.  The REC_* fields
+ * read the pulled state with no row rule.  Colour mass is conserved to rounding and a body force is the only drive.  The step is the forced
+ * family with the boundary rows compiled out (accelerations of zero add exact zeros), in both schedules.  The tracers' dirichlet_inlet and
+ * free_outlet name rows that are not special any more: lbmpm_rk2d_tracer_configure refuses them (LBMPM_ERR_INVALID); with both 0 the
+ * tracers wrap in y as they always did.  lbmpm_rk2d_set_perturbation refuses such a context (LBMPM_ERR_UNSUPPORTED).
+ * (tests/test_rk2d_force_gpu.py; the reference recipe around the oracle: tests/body_force_2d_ref.py.) */
+int lbmpm_rk2d_set_body_force(lbmpm_rk2d *ctx, const double *accel_r, const double *accel_b);     /* [2] each */
+/* the accelerations in force; zeros without a body force */
+int lbmpm_rk2d_get_body_force(const lbmpm_rk2d *ctx, double *accel_r, double *accel_b);
 int lbmpm_rk2d_tracer_configure(lbmpm_rk2d *ctx, const lbmpm_tracer_config *cfg);
 /* dense [ny][nx] concentration; g = C w (Transport2DRK.py:399-470); before the first step */
 int lbmpm_rk2d_tracer_set_concentration(lbmpm_rk2d *ctx, int tracer, const double *conc);

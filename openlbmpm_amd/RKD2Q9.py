@@ -15,7 +15,9 @@ import numpy as np
 from . import config
 from .geometry import simple_geometry, image_domain, initial_densities_rk
 from .results import RecordGuard, ResultFile
-from .rk2d import RK2DSolver
+from .rk2d import RK2DSolver, body_force_arg
+
+_FLOW_GROUPS = (("FluidMacro", "MacroData"), ("FluidPDF", "MicroData"), ("FluidVelocity", "MacroVelocity"))
 
 
 def load_structure_image(path):
@@ -26,12 +28,27 @@ def load_structure_image(path):
 
 
 class RKColorGradientLBM:
-    def __init__(self, pathIniFile, output_dir=None, image=None, device=0, initial_dir=None):
+    def __init__(self, pathIniFile, output_dir=None, image=None, device=0, initial_dir=None, body_force=None):
+        """body_force = (gx, gy) for both colours | dict(red=(gx, gy), blue=(gx, gy)): an acceleration per colour in lattice units for
+        the CSF loop (RK2DSolver.set_body_force; the model: include/lbmpm.h) -- gravity, or the drive of a flow between open rows at
+        equal pressure or on a lattice periodic in y.  The keyword (and --body-force of the command line) is the only way in: the
+        reference reads [BodyForce] and never uses it, so a reference set-up with isBodyForce = 'yes' stays refused (config.read_rk2d)
+        rather than gaining a force here.  The result file gets /BodyForce/Acceleration [2][2] once: red, blue as the solver holds them.
+        [BoundaryCondition] BoundaryTypeInlet = 'Periodic' with BoundaryTypeOutlet = 'Periodic' (CSF only): periodic y -- no open rows,
+        the lattice taken as given (an image gets its side walls and no buffer rows), VelocityY*, density* not used; the result file
+        gets /BoundaryCondition/PeriodicY = 1.  Without either the file is what it was."""
         self.pathIni = pathIniFile
         self.initial_dir = initial_dir or os.path.expanduser("~/LBMInitial")
         self.fluidPDFR = self.fluidPDFB = None
         self.physicalVX = self.physicalVY = None
         self.par = config.read_rk2d(pathIniFile)
+        self.periodic_y = self.par["periodic_y"]
+        try:
+            self.body_force = body_force_arg(body_force)
+        except (KeyError, ValueError, TypeError) as e:
+            raise config.ConfigError("body_force = (gx, gy) or dict(red=(gx, gy), blue=(gx, gy)): %s" % e)
+        if self.body_force is not None and self.par["tension_type"] != "CSF":
+            raise config.ConfigError("body_force belongs to SurfaceTensionType = 'CSF': the perturbation model's solver has no force term")
         self.output_dir = output_dir or os.path.expanduser("~/LBMResults")
         self.device = device
         self.nan_guard = "raise"              # 'raise' | 'warn' | 'off': finiteness check of every record (results.RecordGuard)
@@ -48,7 +65,7 @@ class RKColorGradientLBM:
             img = self._image
             if img is None:
                 img = load_structure_image(os.path.expanduser("~/StructureImage/structure.png"))
-            self.isDomain = image_domain(img, p["nbuf"], p["ratio"])
+            self.isDomain = image_domain(img, 0 if self.periodic_y else p["nbuf"], p["ratio"])     # (a ring: side walls, no buffer rows)
         else:
             self.isDomain = simple_geometry(p["nx"], p["ny"])
         self.yDomain, self.xDomain = self.isDomain.shape
@@ -122,11 +139,9 @@ class RKColorGradientLBM:
         self.initializeDomainCondition()
         keys = ("sigma", "theta", "wetting", "beta", "delta", "tauR", "tauB", "tautype", "relax", "inlet", "outlet",
                 "vyR", "vyB", "rhoBH", "rhoRH", "rhoBL", "rhoRL")
-        solver = RK2DSolver(self.isDomain, {k: p[k] for k in keys}, device=self.device)
+        solver = RK2DSolver(self.isDomain, self._solver_params(keys), device=self.device, periodic_y=self.periodic_y)
         self._upload_initial_state(solver)
-        out = ResultFile(self.output_dir, "SimulationResultsRK",
-                         (("FluidMacro", "MacroData"), ("FluidPDF", "MicroData"), ("FluidVelocity", "MacroVelocity")))
-        self.result_path = out.path
+        out = self._open_flow_file(solver)
         self._guard = RecordGuard("rk2d", int((self.isDomain == 1).sum()), self.nan_guard)
         done = 0
         while done < self.timeSteps:
@@ -143,6 +158,23 @@ class RKColorGradientLBM:
         solver.sync()
         self.solver = solver
         return self.result_path
+
+    def _solver_params(self, keys):
+        """the ini's values for RK2DSolver; a periodic run's BoundaryTypeInlet / Outlet = 'Periodic' become the solver's periodic_y=True"""
+        return {k: self.par[k] for k in keys if not (self.periodic_y and k in ("inlet", "outlet"))}
+
+    def _open_flow_file(self, solver):
+        """SimulationResultsRK; the body force goes into the solver and, once, into the file, and a periodic run says so there"""
+        more = ((("BodyForce", "Acceleration"),) if self.body_force is not None else ()) + \
+            ((("BoundaryCondition", "OpenRows"),) if self.periodic_y else ())
+        out = ResultFile(self.output_dir, "SimulationResultsRK", _FLOW_GROUPS + more)
+        self.result_path = out.path
+        if self.periodic_y:
+            out.write("BoundaryCondition", "PeriodicY", np.array([1], dtype=np.int64))     # (only a periodic run has the group)
+        if self.body_force is not None:
+            solver.set_body_force(**self.body_force)
+            out.write("BodyForce", "Acceleration", np.array(solver.body_force, dtype=np.float64))
+        return out
 
     # -- the perturbation loop (RKD2Q9.py:978-1223), kernel by kernel on the kernel-level layer
     def runRKColorGradient2DPerturbation(self, progress=None, initial_pdf=None):

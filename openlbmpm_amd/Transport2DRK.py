@@ -25,13 +25,14 @@ from .rk2d import RK2DSolver
 
 
 class Transport2DRK(RKColorGradientLBM):
-    def __init__(self, pathIniFile, output_dir=None, image=None, device=0, initial_dir=None, inlet_concentration_from_ini=False):
+    def __init__(self, pathIniFile, output_dir=None, image=None, device=0, initial_dir=None, inlet_concentration_from_ini=False, body_force=None):
         """`inlet_concentration_from_ini`: the reference reads [BoundaryCondition] ConcentrationInlet (:162-167) and then
         hands the inlet kernel a hard-coded array [1.0] (:1161-1162, one entry: with one tracer the inlet value is 1.0
         whatever the file says; the kernel indexes it by tracer, so more than one tracer reads past its end).  Default:
         what the reference computes where it is defined (tracer 0 -> 1.0), the file's values for the others; True: the
         file's values for all."""
-        RKColorGradientLBM.__init__(self, pathIniFile, output_dir=output_dir, image=image, device=device, initial_dir=initial_dir)
+        RKColorGradientLBM.__init__(self, pathIniFile, output_dir=output_dir, image=image, device=device, initial_dir=initial_dir,
+                                    body_force=body_force)        # (body_force, periodic y: RKColorGradientLBM; the tracers ride the forced u)
         self.tr = config.read_transport(pathIniFile)
         self.numTracers = self.tr["num_tracers"]
         t = self.tr
@@ -41,6 +42,13 @@ class Transport2DRK(RKColorGradientLBM):
                 warnings.warn("ConcentrationInlet[0] = %g is ignored as in the reference (Transport2DRK.py:1161 uses 1.0); "
                               "pass inlet_concentration_from_ini=True to use it" % self.inletConcentration[0])
             self.inletConcentration[0] = 1.0
+        if self.periodic_y:
+            # the rows the tracers' inlet and outlet rules name are ordinary rows on a ring (lbmpm_rk2d_tracer_configure refuses them)
+            if t["inlet_type"] == "Dirichlet" or t["outlet_type"] == "Freeflow":
+                raise config.ConfigError("periodic y: the tracers wrap with the flow -- InletType 'Dirichlet' / OutletType 'Freeflow' of transportsetup.ini "
+                                         "name rows that are not special any more (got %r / %r); any other spelling runs without them"
+                                         % (t["inlet_type"], t["outlet_type"]))
+            return
         if t["outlet_type"] != "Freeflow":
             warnings.warn("OutletType = '%s': the loop applies its free-flow rows only for the spelling 'Freeflow' "
                           "(Transport2DRK.py:1363); running without a tracer outlet rule, as the reference would" % t["outlet_type"])
@@ -93,7 +101,7 @@ class Transport2DRK(RKColorGradientLBM):
         self.initializeTransportDomain()
         keys = ("sigma", "theta", "wetting", "beta", "delta", "tauR", "tauB", "tautype", "relax", "inlet", "outlet",
                 "vyR", "vyB", "rhoBH", "rhoRH", "rhoBL", "rhoRL")
-        solver = RK2DSolver(self.isDomain, {k: p[k] for k in keys}, device=self.device)
+        solver = RK2DSolver(self.isDomain, self._solver_params(keys), device=self.device, periodic_y=self.periodic_y)
         self._upload_initial_state(solver)
         n = self.numTracers
         solver.configure_tracers(diffX=tuple(t["diffX"]), diffY=tuple(t["diffY"]), dXY=t["dXY"], dYX=t["dYX"],
@@ -102,10 +110,9 @@ class Transport2DRK(RKColorGradientLBM):
                                  diffJ=tuple(t["diffJ"]))
         for k in range(n):
             solver.set_tracer(k, self.tracerConc[k])
-        flow = ResultFile(self.output_dir, "SimulationResultsRK",
-                          (("FluidMacro", "MacroData"), ("FluidPDF", "MicroData"), ("FluidVelocity", "MacroVelocity")))
+        flow = self._open_flow_file(solver)
         conc = ResultFile(self.output_dir, "ConcentrationResults", (("TransportMacro", "MacroData"),))
-        self.result_path, self.concentration_path = flow.path, conc.path
+        self.concentration_path = conc.path
         self._guard = RecordGuard("rk2d+tracers", int((self.isDomain == 1).sum()), self.nan_guard)
         tracer_guard = RecordGuard("tracers", int((self.isDomain == 1).sum()), self.nan_guard)
         done = 0

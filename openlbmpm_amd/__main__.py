@@ -21,7 +21,8 @@
         [--contact-angles FILE]                   rk3d with SurfaceTensionType = 'CSF', tr3d: mixed wettability -- a .npy of contact angles per solid voxel
                                                   (the lattice's shape, or the voxel file's; NaN = the ini's ContactAngle); /Wettability/ContactAngle
         [--body-force GX GY GZ]                   rk3d with SurfaceTensionType = 'CSF', tr3d: an acceleration in lattice units for both colours (gravity,
-        [--body-force-blue GX GY GZ]              force-driven flow), the second option: another one for blue; /BodyForce/Acceleration of the result file
+        [--body-force-blue GX GY GZ]              force-driven flow), the second option: another one for blue; /BodyForce/Acceleration of the result file;
+                                                  rk with SurfaceTensionType = 'CSF', tr: the same with GX GY
         [--wall-reaction K [K ...]]               tr3d: first-order reaction of the tracers at solid walls, D dC/dn = k C_wall -- one rate per tracer in lattice
         [--wall-minerals FILE]                    units (inf: C_wall = 0), or classes x tracers with a .npy of class bytes per solid voxel; /WallReaction/Rates
                                                   and, with --integrals-every, /TracerWallIntegrals of ConcentrationResults
@@ -67,11 +68,12 @@ def parser():
                     help="rk3d with SurfaceTensionType = 'CSF', tr3d: contact angles in degrees per solid voxel (.npy in the shape of the lattice, or of the "
                          "voxel file; NaN: the ini's ContactAngle) -- every fluid cell next to solid takes the Cassie average over its solid neighbours; "
                          "the angles in force go to /Wettability/ContactAngle of the result file.  The same as [SurfaceTension] ContactAngleFile")
-    ap.add_argument("--body-force", type=float, nargs=3, default=None, metavar=("GX", "GY", "GZ"),
-                    help="rk3d with SurfaceTensionType = 'CSF', tr3d: an acceleration in lattice units on both colours (force density rho_R g + rho_B g): "
-                         "gravity, or the drive of a flow between open planes at equal pressure.  The same as [BodyForce] isBodyForce = 'yes' with "
-                         "bodyForceX / Y / Z; /BodyForce/Acceleration of the result file")
-    ap.add_argument("--body-force-blue", type=float, nargs=3, default=None, metavar=("GX", "GY", "GZ"),
+    ap.add_argument("--body-force", type=float, nargs="+", default=None, metavar="G",
+                    help="rk3d with SurfaceTensionType = 'CSF', tr3d: GX GY GZ; rk with SurfaceTensionType = 'CSF', tr: GX GY -- an acceleration in lattice "
+                         "units on both colours (force density rho_R g + rho_B g): gravity, or the drive of a flow between open ends at equal pressure or "
+                         "on a periodic lattice.  rk3d, tr3d: the same as [BodyForce] isBodyForce = 'yes' with bodyForceX / Y / Z (the 2-D ini keeps "
+                         "refusing that section: the reference reads it and never uses it); /BodyForce/Acceleration of the result file")
+    ap.add_argument("--body-force-blue", type=float, nargs="+", default=None, metavar="G",
                     help="... the blue fluid's acceleration where it differs (--body-force is then the red one's; alone: red has none)")
     ap.add_argument("--wall-reaction", type=float, nargs="+", default=None, metavar="K",
                     help="tr3d: the tracers react at solid walls, D dC/dn = k C_wall (a reactive bounce-back): one rate k >= 0 per tracer in lattice units "
@@ -113,26 +115,30 @@ def parser():
 
 
 def _body_force(a):
-    """--body-force / --body-force-blue as the drivers' body_force=, or None"""
+    """--body-force / --body-force-blue as the drivers' body_force=, or None: three components for the 3-D models, two for rk and tr"""
     if a.body_force is None and a.body_force_blue is None:
         return None
+    n = 3 if a.model in ("rk3d", "tr3d") else 2
+    for opt, v in (("--body-force", a.body_force), ("--body-force-blue", a.body_force_blue)):
+        if v is not None and len(v) != n:
+            raise SystemExit("%s of %s takes %s, not %d values" % (opt, a.model, "GX GY GZ" if n == 3 else "GX GY", len(v)))
     if a.body_force_blue is None:
         return tuple(a.body_force)
-    return dict(red=tuple(a.body_force or (0.0, 0.0, 0.0)), blue=tuple(a.body_force_blue))
+    return dict(red=tuple(a.body_force or (0.0,) * n), blue=tuple(a.body_force_blue))
 
 
 def main(argv=None):
     a = parser().parse_args(argv)
     t0 = time.time()
-    if a.model not in ("rk3d", "tr3d") and _body_force(a) is not None:
-        raise SystemExit("--body-force belongs to rk3d (SurfaceTensionType = 'CSF') and tr3d: the 2-D solvers have no body force")
+    if a.model == "sc" and _body_force(a) is not None:
+        raise SystemExit("--body-force belongs to the colour-gradient CSF models (rk, tr, rk3d, tr3d): the Shan-Chen solvers have no body force")
     if a.model != "tr3d" and (a.wall_reaction is not None or a.wall_minerals is not None):
         raise SystemExit({"rk3d": "--wall-reaction belongs to tr3d: rk3d runs the flow alone, there is no tracer to react",
                           "tr": "--wall-reaction belongs to tr3d: the D2Q5 tracers of tr bounce back from solids unchanged"}
                          .get(a.model, "--wall-reaction belongs to tr3d: the 2-D solvers carry no tracers that could react at a wall"))
     if a.model == "rk":
         from .RKD2Q9 import RKColorGradientLBM
-        sim = RKColorGradientLBM(a.ini_dir, output_dir=a.out, device=a.device)
+        sim = RKColorGradientLBM(a.ini_dir, output_dir=a.out, device=a.device, body_force=_body_force(a))
         if a.steps is not None:
             sim.timeSteps = a.steps
         path = sim.runRKColorGradient2D()
@@ -162,7 +168,7 @@ def main(argv=None):
         steps, nodes = sim.timeSteps, sim.voidSpace
     elif a.model == "tr":
         from .Transport2DRK import Transport2DRK
-        sim = Transport2DRK(a.ini_dir, output_dir=a.out, device=a.device)
+        sim = Transport2DRK(a.ini_dir, output_dir=a.out, device=a.device, body_force=_body_force(a))
         if a.steps is not None:
             sim.timeSteps = a.steps
         path = " and ".join(sim.runTransport2DMPMCRKNew())

@@ -133,6 +133,8 @@ _SIGNATURES = {
     "lbmpm_rk2d_device_bytes": (C.c_int64, [C.c_void_p]),
     "lbmpm_rk2d_tracer_configure": (C.c_int, [C.c_void_p, C.POINTER(TracerConfig)]),
     "lbmpm_rk2d_set_perturbation": (C.c_int, [C.c_void_p, C.POINTER(RK2DPerturbation)]),
+    "lbmpm_rk2d_set_body_force": (C.c_int, [C.c_void_p, F64P, F64P]),
+    "lbmpm_rk2d_get_body_force": (C.c_int, [C.c_void_p, F64P, F64P]),
     "lbmpm_rk2d_tracer_set_concentration": (C.c_int, [C.c_void_p, C.c_int, F64P]),
     "lbmpm_rk2d_tracer_get_concentration": (C.c_int, [C.c_void_p, C.c_int, F64P]),
     "lbmpm_sc2d_create": (C.c_int, [C.POINTER(SC2DConfig), U8P, C.POINTER(C.c_void_p)]),

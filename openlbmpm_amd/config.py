@@ -108,6 +108,13 @@ def read_rk2d(ini_dir):
     p["rhoRL"] = c.float("BoundaryCondition", "densityRL", default=1.0)
     p["cycle"] = c.str("CyclesSetup", "IsCycle", default="'no'") == "yes"
     p["last_step"] = c.int("CyclesSetup", "LastStep", default=0)
+    # periodic y (CSF only): BoundaryTypeInlet = 'Periodic' with BoundaryTypeOutlet = 'Periodic' -- no open rows, the lattice taken as given
+    p["periodic_y"] = p["inlet"] == "Periodic" or p["outlet"] == "Periodic"
+    if p["periodic_y"]:
+        if p["inlet"] != p["outlet"]:
+            raise ConfigError("periodic y: BoundaryTypeInlet = 'Periodic' together with BoundaryTypeOutlet = 'Periodic', not %r with %r" % (p["inlet"], p["outlet"]))
+        if p["tension_type"] == "Perturbation":
+            raise ConfigError("BoundaryTypeInlet / BoundaryTypeOutlet = 'Periodic' belong to SurfaceTensionType = 'CSF': the perturbation model keeps its open rows")
     if p["tension_type"] == "Perturbation":
         # the perturbation driver does not go through RK2DSolver's checks; a misspelt value must not pick a physics path silently
         # (the reference's own outlet switch is if / elif without else: any other value would run with NO outlet rule, RKD2Q9.py:1064-1088)

@@ -32,6 +32,11 @@ struct PertDev {
     double *pd;        // [4][plane] rhoR, rhoB, vx, vy of the last step (nullptr = off)
 };
 
+// accelerations of the body force (lbmpm_rk2d_set_body_force; rk2d_forced), lattice units per colour: an argument of their own for the same reason
+struct ForceDev {
+    double gRx, gRy, gBx, gBy;
+};
+
 struct RKDev {
     int nx, ny, pitch;
     size_t plane;
@@ -354,17 +359,20 @@ __device__ __forceinline__ void unit_normal(int wetting, double gx, double gy, d
 // ---------------------------------------------------------------- kernels (split schedule)
 constexpr int BX = 64, BY = 4;
 
-// K1: phase field of the post-streaming, post-BC state (calPhaseFieldPhi A:1348)
-__global__ __launch_bounds__(BX *BY) void rk2d_phase_field(RKDev p)
+// K1: phase field of the post-streaming, post-BC state (calPhaseFieldPhi A:1348).  BC = false: periodic y, no row is special
+template <bool BC>
+__device__ __forceinline__ void phase_field_node(RKDev p)
 {
     const int x = blockIdx.x * BX + threadIdx.x, y = blockIdx.y * BY + threadIdx.y;
     if (x >= p.nx || y >= p.ny) return;
     const size_t idx = (size_t)y * p.pitch + x;
     if (!(p.flags[idx] & 1)) return;
     double fR[9], fB[9], rR, rB;
-    node_state<true>(p, x, y, fR, fB, rR, rB);
+    node_state<BC>(p, x, y, fR, fB, rR, rB);
     p.phi[idx] = (rR - rB) / (rR + rB);
 }
+__global__ __launch_bounds__(BX *BY) void rk2d_phase_field(RKDev p) { phase_field_node<true>(p); }
+__global__ __launch_bounds__(BX *BY) void rk2d_phase_field_ring(RKDev p) { phase_field_node<false>(p); }
 
 // K2: colour gradient with wetting correction
 //   calColorValueOnSolid A:1560-1581 (evaluated on the fly for solid neighbours),
@@ -410,8 +418,10 @@ __global__ __launch_bounds__(BX *BY) void rk2d_gradient(RKDev p)
 
 // K3: everything else of the step (dominant kernel): stream+BC, u, curvature + CSF force,
 // collision + forcing, recolouring, store post-collision populations.
-template <bool MRT>
-__global__ __launch_bounds__(BX *BY) void rk2d_collide_stream(RKDev p)
+// FORCE: the body force F_b = rho_R g_R + rho_B g_B of this step -- its half in u behind the lagged CSF force's, the whole of it beside the CSF
+// force in the Guo source; p.F stays the CSF force alone.  BC = false: periodic y.
+template <bool MRT, bool FORCE, bool BC>
+__device__ __forceinline__ void collide_stream_node(RKDev p, ForceDev g)
 {
     constexpr double W[9] = LBMPM_D2Q9_W;
     constexpr int EX[9] = LBMPM_D2Q9_EX, EY[9] = LBMPM_D2Q9_EY;
@@ -420,14 +430,21 @@ __global__ __launch_bounds__(BX *BY) void rk2d_collide_stream(RKDev p)
     const size_t idx = (size_t)y * p.pitch + x;
     if (!(p.flags[idx] & 1)) return;
     double fR[9], fB[9], rR, rB;
-    node_state<true>(p, x, y, fR, fB, rR, rB);
+    node_state<BC>(p, x, y, fR, fB, rR, rB);
     double fT[9];
 #pragma unroll
     for (int i = 0; i < 9; ++i) fT[i] = fR[i] + fB[i];          // calTotalFluidPDF A:1414
     // calPhysicalVelocityRKGPU2DNew1 A:2634-2654 (force of the PREVIOUS step)
     const double rs = rB + rR;
-    const double vx = (fT[1] - fT[3] + fT[5] - fT[6] - fT[7] + fT[8] + 0.5 * p.F[idx]) / rs;
-    const double vy = (fT[2] - fT[4] + fT[5] + fT[6] - fT[7] - fT[8] + 0.5 * p.F[p.plane + idx]) / rs;
+    double vx, vy, Fbx = 0., Fby = 0.;
+    if constexpr (FORCE) {
+        Fbx = rR * g.gRx + rB * g.gBx; Fby = rR * g.gRy + rB * g.gBy;
+        vx = ((fT[1] - fT[3] + fT[5] - fT[6] - fT[7] + fT[8] + 0.5 * p.F[idx]) + 0.5 * Fbx) / rs;
+        vy = ((fT[2] - fT[4] + fT[5] + fT[6] - fT[7] - fT[8] + 0.5 * p.F[p.plane + idx]) + 0.5 * Fby) / rs;
+    } else {
+        vx = (fT[1] - fT[3] + fT[5] - fT[6] - fT[7] + fT[8] + 0.5 * p.F[idx]) / rs;
+        vy = (fT[2] - fT[4] + fT[5] + fT[6] - fT[7] - fT[8] + 0.5 * p.F[p.plane + idx]) / rs;
+    }
     const double phi = (rR - rB) / (rR + rB);
     // calForceTermInColorGradient[New]2D A:1686-1736 / A:2499-2551
     const double gx = p.G[idx], gy = p.G[p.plane + idx];
@@ -453,10 +470,14 @@ __global__ __launch_bounds__(BX *BY) void rk2d_collide_stream(RKDev p)
     p.F[idx] = Fx;
     p.F[p.plane + idx] = Fy;
     if (p.diag) { p.diag[idx] = vx; p.diag[p.plane + idx] = vy; p.diag[2 * p.plane + idx] = K; }
-    collide<MRT>(p, fT, rR, rB, phi, vx, vy, Fx, Fy);
+    collide<MRT>(p, fT, rR, rB, phi, vx, vy, FORCE ? Fx + Fbx : Fx, FORCE ? Fy + Fby : Fy);
     recolor(p.beta, fT, rR, rB, gx, gy, fR, fB);
     lbmpm_dev::store_pairs<true>(p.fout, p.plane, idx, fR, fB);
 }
+template <bool MRT>
+__global__ __launch_bounds__(BX *BY) void rk2d_collide_stream(RKDev p) { collide_stream_node<MRT, false, true>(p, ForceDev{}); }
+template <bool MRT, bool BC>
+__global__ __launch_bounds__(BX *BY) void rk2d_collide_stream_forced(RKDev p, ForceDev g) { collide_stream_node<MRT, true, BC>(p, g); }
 
 // ---------------------------------------------------------------- fused schedule
 // One kernel per time step.  A workgroup owns a TW x TH tile and recomputes the phase
@@ -590,8 +611,10 @@ __device__ unsigned long long rk2d_ph[256 * 16];
 #else
 #define RK2D_BC true
 #endif
-template <bool MRT, bool TRACER, typename SH, int TR>
-__device__ __forceinline__ void rk2d_fused_tile(const RKDev &p, int tiles_x, int t, double *s_phi, double *s_ux, double *s_uy, double *s_gx, double *s_gy,
+// FORCE: the body force of this step (collide_stream_node above; g is read by the forced instances only).  BC: the boundary rows; false on
+// a lattice periodic in y, where every row is an ordinary row that wraps like x.
+template <bool MRT, bool TRACER, typename SH, int TR, bool FORCE = false, bool BC = RK2D_BC>
+__device__ __forceinline__ void rk2d_fused_tile(const RKDev &p, const ForceDev &g, int tiles_x, int t, double *s_phi, double *s_ux, double *s_uy, double *s_gx, double *s_gy,
                                                 uint16_t *s_list, int *s_cnt, uint8_t *s_fluid)
 {
     constexpr int TW = SH::TW, TH = SH::TH, NT = SH::NT, H = SH::H, TY = SH::TY, THREADS = SH::THREADS;
@@ -648,7 +671,7 @@ __device__ __forceinline__ void rk2d_fused_tile(const RKDev &p, int tiles_x, int
         const bool inside = (x < p.nx) && (y < p.ny);
         // nodes beyond the lattice edge of a partial tile are periodic images of real nodes and serve as halo for the valid part of the tile
         const int xw = inside ? x : wrapm(x, p.nx), yw = inside ? y : wrapm(y, p.ny);
-        const int ys = node_source_row<RK2D_BC>(p, yw);
+        const int ys = node_source_row<BC>(p, yw);
         {
             const size_t idx = (size_t)yw * p.pitch + xw;
             sn[0] = asm_ldu8(p.solidnbr, (unsigned)idx);
@@ -680,7 +703,7 @@ __device__ __forceinline__ void rk2d_fused_tile(const RKDev &p, int tiles_x, int
             if (hdo) {
                 LBMPM_TAKEN;                       // (a lane of this wave is here: openlbmpm_amd/inflight.py drops hipcc's all-lanes-off branch)
                 hx = wrapm(tx0 - H + hrx, p.nx); hy = wrapm(ty0 - H + hry, p.ny);
-                hys = node_source_row<RK2D_BC>(p, hy);
+                hys = node_source_row<BC>(p, hy);
                 hsn = asm_ldu8(p.solidnbr, (unsigned)hys * (unsigned)p.pitch + (unsigned)hx);
                 pull_issue_asm(p, hx, hys, hq);
             }
@@ -700,7 +723,7 @@ __device__ __forceinline__ void rk2d_fused_tile(const RKDev &p, int tiles_x, int
                 for (int i = 0; i < 9; ++i) { fR[i] = q[i].x; fB[i] = q[i].y; }
                 const unsigned psn = first ? 0u : (ys == yw ? sn[0] : (unsigned)p.solidnbr[(size_t)ys * p.pitch + xw]);
                 pull_patch(p, xw, ys, psn, fR, fB);
-                node_finish<RK2D_BC, TR>(p, yw, ys, fR, fB, rR[0], rB[0]);
+                node_finish<BC, TR>(p, yw, ys, fR, fB, rR[0], rB[0]);
 #pragma unroll
                 for (int i = 0; i < 9; ++i) fT[0][i] = fR[i] + fB[i];
                 s_phi[ri] = (rR[0] - rB[0]) / (rR[0] + rB[0]);
@@ -715,7 +738,7 @@ __device__ __forceinline__ void rk2d_fused_tile(const RKDev &p, int tiles_x, int
             for (int i = 0; i < 9; ++i) { hR[i] = hq[i].x; hB[i] = hq[i].y; }
             pull_patch(p, hx, hys, first ? 0u : hsn, hR, hB);
             double a, c;
-            node_finish<RK2D_BC, TR>(p, hy, hys, hR, hB, a, c);
+            node_finish<BC, TR>(p, hy, hys, hR, hB, a, c);
             s_phi[hry * RW + hrx] = (a - c) / (a + c);
         }
     } else {
@@ -739,7 +762,7 @@ __device__ __forceinline__ void rk2d_fused_tile(const RKDev &p, int tiles_x, int
         hdo = s_fluid[hry * RW + hrx] && (need3 || !(hrx == 0 || hrx == RW - 1 || hry == 0 || hry == RH - 1));
         if (hdo) {
             hx = wrapm(tx0 - H + hrx, p.nx); hy = wrapm(ty0 - H + hry, p.ny);
-            hys = node_source_row<RK2D_BC>(p, hy);
+            hys = node_source_row<BC>(p, hy);
             pull_node(p, hx, hys, hR, hB);
         }
     }
@@ -760,7 +783,7 @@ __device__ __forceinline__ void rk2d_fused_tile(const RKDev &p, int tiles_x, int
             sn[m] = p.solidnbr[idx];
             Fpx[m] = __builtin_nontemporal_load(p.F + idx);          // read once, by its own node
             Fpy[m] = __builtin_nontemporal_load(p.F + p.plane + idx);
-            node_state<RK2D_BC, TR>(p, xw, yw, fR, fB, rR[m], rB[m]);
+            node_state<BC, TR>(p, xw, yw, fR, fB, rR[m], rB[m]);
 #pragma unroll
             for (int i = 0; i < 9; ++i) fT[m][i] = fR[i] + fB[i];
             s_phi[ri] = (rR[m] - rB[m]) / (rR[m] + rB[m]);
@@ -768,7 +791,7 @@ __device__ __forceinline__ void rk2d_fused_tile(const RKDev &p, int tiles_x, int
     }
     if (hdo) {
         double a, c;
-        node_finish<RK2D_BC, TR>(p, hy, hys, hR, hB, a, c);
+        node_finish<BC, TR>(p, hy, hys, hR, hB, a, c);
         s_phi[hry * RW + hrx] = (a - c) / (a + c);
     }
     }
@@ -780,7 +803,7 @@ __device__ __forceinline__ void rk2d_fused_tile(const RKDev &p, int tiles_x, int
         if (!need3 && (rx == 0 || rx == RW - 1 || ry == 0 || ry == RH - 1)) continue;
         const int x = wrapm(tx0 - H + rx, p.nx), y = wrapm(ty0 - H + ry, p.ny);
         double fR[9], fB[9], a, c;
-        node_state<RK2D_BC, TR>(p, x, y, fR, fB, a, c);
+        node_state<BC, TR>(p, x, y, fR, fB, a, c);
         s_phi[ri] = (a - c) / (a + c);
     }
     PH2(1)
@@ -897,8 +920,15 @@ __device__ __forceinline__ void rk2d_fused_tile(const RKDev &p, int tiles_x, int
         Fx = sgn * p.sigma * K * gx[m]; Fy = sgn * p.sigma * K * gy[m];
         const double rs = rB[m] + rR[m];
         double *f = fT[m];
-        const double vx = (f[1] - f[3] + f[5] - f[6] - f[7] + f[8] + 0.5 * Fpx[m]) / rs;
-        const double vy = (f[2] - f[4] + f[5] + f[6] - f[7] - f[8] + 0.5 * Fpy[m]) / rs;
+        double vx, vy, Fbx = 0., Fby = 0.;
+        if constexpr (FORCE) {          // u = ((sum e f + F_csf / 2) + F_b / 2) / rho, F_b = rho_R g_R + rho_B g_B of this step
+            Fbx = rR[m] * g.gRx + rB[m] * g.gBx; Fby = rR[m] * g.gRy + rB[m] * g.gBy;
+            vx = ((f[1] - f[3] + f[5] - f[6] - f[7] + f[8] + 0.5 * Fpx[m]) + 0.5 * Fbx) / rs;
+            vy = ((f[2] - f[4] + f[5] + f[6] - f[7] - f[8] + 0.5 * Fpy[m]) + 0.5 * Fby) / rs;
+        } else {
+            vx = (f[1] - f[3] + f[5] - f[6] - f[7] + f[8] + 0.5 * Fpx[m]) / rs;
+            vy = (f[2] - f[4] + f[5] + f[6] - f[7] - f[8] + 0.5 * Fpy[m]) / rs;
+        }
         const double phi = (rR[m] - rB[m]) / (rR[m] + rB[m]);
         if (p.diag) {
             p.diag[idx] = vx; p.diag[p.plane + idx] = vy; p.diag[2 * p.plane + idx] = K;
@@ -911,7 +941,7 @@ __device__ __forceinline__ void rk2d_fused_tile(const RKDev &p, int tiles_x, int
 #if defined(LBMPM_DEV) && defined(LBMPM_PHASES2D)
         ph_acc[8] += __builtin_readcyclecounter() - tr_t0;
 #endif
-        collide<MRT>(p, f, rR[m], rB[m], phi, vx, vy, Fx, Fy);
+        collide<MRT>(p, f, rR[m], rB[m], phi, vx, vy, FORCE ? Fx + Fbx : Fx, FORCE ? Fy + Fby : Fy);
         recolor(p.beta, f, rR[m], rB[m], gx[m], gy[m], fR, fB);
         }
         __builtin_nontemporal_store(Fx, p.F + idx);
@@ -946,7 +976,7 @@ __global__ __launch_bounds__(SH::THREADS) __attribute__((amdgpu_waves_per_eu(4, 
     __shared__ uint8_t s_fluid[SH::RH * SH::RW];
     // XCD-aware tile assignment: workgroup b runs on XCD b % 8 (observed dispatch order);
     // give every XCD a contiguous band of tiles so halo rows are shared inside one L2.
-    rk2d_fused_tile<MRT, TRACER, SH, TR>(p, tiles_x, tile0 + xcd_tile(blockIdx.x, gridDim.x, tiles_x), s_phi, s_ux, s_uy, s_gx, s_gy, s_list, &s_cnt, s_fluid);
+    rk2d_fused_tile<MRT, TRACER, SH, TR>(p, ForceDev{}, tiles_x, tile0 + xcd_tile(blockIdx.x, gridDim.x, tiles_x), s_phi, s_ux, s_uy, s_gx, s_gy, s_list, &s_cnt, s_fluid);
 }
 
 // The tracer step as ONE launch: tiles below lo_end and from hi_begin on (the tile rows whose region holds a lattice row a boundary rule
@@ -965,8 +995,43 @@ __global__ __launch_bounds__(SH::THREADS) __attribute__((amdgpu_waves_per_eu(4, 
     __shared__ int s_cnt;
     __shared__ uint8_t s_fluid[SH::RH * SH::RW];
     const int t = xcd_tile(blockIdx.x, gridDim.x, tiles_x);
-    if (t < lo_end || t >= hi_begin) rk2d_fused_tile<MRT, true, SH, 1>(p, tiles_x, t, s_phi, s_ux, s_uy, s_gx, s_gy, s_list, &s_cnt, s_fluid);
-    else rk2d_fused_tile<MRT, true, SH, 0>(p, tiles_x, t, s_phi, s_ux, s_uy, s_gx, s_gy, s_list, &s_cnt, s_fluid);
+    if (t < lo_end || t >= hi_begin) rk2d_fused_tile<MRT, true, SH, 1>(p, ForceDev{}, tiles_x, t, s_phi, s_ux, s_uy, s_gx, s_gy, s_list, &s_cnt, s_fluid);
+    else rk2d_fused_tile<MRT, true, SH, 0>(p, ForceDev{}, tiles_x, t, s_phi, s_ux, s_uy, s_gx, s_gy, s_list, &s_cnt, s_fluid);
+}
+
+// The step with a body force and / or on a lattice periodic in y (lbmpm_rk2d_set_body_force; LBMPM_INLET_PERIODIC): the same tile with FORCE
+// on -- accelerations of zero add exact zeros, so a ring without a force runs these too -- and the boundary rows a template switch.  Kernels
+// of their own names: the unforced open-row instances above keep their text and their launches.  BC = false knows no TR order (no row rule
+// runs), BC = true with tracers is the re-summing copy TR = 1, as rk2d_fused<., true, ., 1>.
+template <bool MRT, bool TRACER, typename SH, bool BC>
+__global__ __launch_bounds__(SH::THREADS) __attribute__((amdgpu_waves_per_eu(4, 4))) void rk2d_forced(RKDev p, ForceDev g, int tiles_x)
+{
+    __shared__ double s_phi[SH::RH * SH::RW];
+    __shared__ double s_ux[SH::RH * SH::RW];
+    __shared__ double s_uy[SH::RH * SH::RW];
+    __shared__ double s_gx[SH::RH * SH::RW];
+    __shared__ double s_gy[SH::RH * SH::RW];
+    __shared__ uint16_t s_list[(SH::TW + 2) * (SH::TH + 2)];
+    __shared__ int s_cnt;
+    __shared__ uint8_t s_fluid[SH::RH * SH::RW];
+    rk2d_fused_tile<MRT, TRACER, SH, (TRACER && BC) ? 1 : 0, true, BC && RK2D_BC>(p, g, tiles_x, xcd_tile(blockIdx.x, gridDim.x, tiles_x), s_phi, s_ux, s_uy, s_gx, s_gy,
+                                                                                  s_list, &s_cnt, s_fluid);
+}
+// rk2d_fused_tracer with the force: open rows only (a ring has no rows that re-sum)
+template <bool MRT, typename SH>
+__global__ __launch_bounds__(SH::THREADS) __attribute__((amdgpu_waves_per_eu(4, 4))) void rk2d_forced_tracer(RKDev p, ForceDev g, int tiles_x, int lo_end, int hi_begin)
+{
+    __shared__ double s_phi[SH::RH * SH::RW];
+    __shared__ double s_ux[SH::RH * SH::RW];
+    __shared__ double s_uy[SH::RH * SH::RW];
+    __shared__ double s_gx[SH::RH * SH::RW];
+    __shared__ double s_gy[SH::RH * SH::RW];
+    __shared__ uint16_t s_list[(SH::TW + 2) * (SH::TH + 2)];
+    __shared__ int s_cnt;
+    __shared__ uint8_t s_fluid[SH::RH * SH::RW];
+    const int t = xcd_tile(blockIdx.x, gridDim.x, tiles_x);
+    if (t < lo_end || t >= hi_begin) rk2d_fused_tile<MRT, true, SH, 1, true>(p, g, tiles_x, t, s_phi, s_ux, s_uy, s_gx, s_gy, s_list, &s_cnt, s_fluid);
+    else rk2d_fused_tile<MRT, true, SH, 0, true>(p, g, tiles_x, t, s_phi, s_ux, s_uy, s_gx, s_gy, s_list, &s_cnt, s_fluid);
 }
 
 // ---------------------------------------------------------------- perturbation operator, fused
@@ -1244,8 +1309,8 @@ __global__ __launch_bounds__(BX *BY) void rk2dp_stored(RKDev p, double *out)
 // Observation kernels: populations/densities as the reference's device arrays hold them
 // after the last completed step (WITH_BC=false), or as resultInHDF5 records them at the
 // start of the next step (WITH_BC=true: + velocity, RKD2Q9.py:1382-1393).
-template <bool WITH_BC>
-__global__ __launch_bounds__(BX *BY) void rk2d_observe(RKDev p, double *out /*[22][plane]*/)
+template <bool WITH_BC, bool FORCE>
+__device__ __forceinline__ void observe_node(RKDev p, ForceDev g, double *out /*[22][plane]*/)
 {
     const int x = blockIdx.x * BX + threadIdx.x, y = blockIdx.y * BY + threadIdx.y;
     if (x >= p.nx || y >= p.ny) return;
@@ -1261,9 +1326,19 @@ __global__ __launch_bounds__(BX *BY) void rk2d_observe(RKDev p, double *out /*[2
 #pragma unroll
     for (int i = 0; i < 9; ++i) fT[i] = fR[i] + fB[i];
     const double rs = rB + rR;
-    out[20 * p.plane + idx] = (fT[1] - fT[3] + fT[5] - fT[6] - fT[7] + fT[8] + 0.5 * p.F[idx]) / rs;
-    out[21 * p.plane + idx] = (fT[2] - fT[4] + fT[5] + fT[6] - fT[7] - fT[8] + 0.5 * p.F[p.plane + idx]) / rs;
+    if constexpr (FORCE) {
+        out[20 * p.plane + idx] = ((fT[1] - fT[3] + fT[5] - fT[6] - fT[7] + fT[8] + 0.5 * p.F[idx]) + 0.5 * (rR * g.gRx + rB * g.gBx)) / rs;
+        out[21 * p.plane + idx] = ((fT[2] - fT[4] + fT[5] + fT[6] - fT[7] - fT[8] + 0.5 * p.F[p.plane + idx]) + 0.5 * (rR * g.gRy + rB * g.gBy)) / rs;
+    } else {
+        out[20 * p.plane + idx] = (fT[1] - fT[3] + fT[5] - fT[6] - fT[7] + fT[8] + 0.5 * p.F[idx]) / rs;
+        out[21 * p.plane + idx] = (fT[2] - fT[4] + fT[5] + fT[6] - fT[7] - fT[8] + 0.5 * p.F[p.plane + idx]) / rs;
+    }
 }
+template <bool WITH_BC>
+__global__ __launch_bounds__(BX *BY) void rk2d_observe(RKDev p, double *out) { observe_node<WITH_BC, false>(p, ForceDev{}, out); }
+// the REC_* fields under a body force (its half in the recorded velocity) and on a ring (WITH_BC = false: the pulled state, no row rule)
+template <bool WITH_BC>
+__global__ __launch_bounds__(BX *BY) void rk2d_observe_forced(RKDev p, ForceDev g, double *out) { observe_node<WITH_BC, true>(p, g, out); }
 
 // Tracer concentration as the reference's deviceTracerConc holds it after the last completed step
 // (streamed + inlet-corrected populations, calConcentrationGPU T:78-90)
@@ -1350,6 +1425,9 @@ struct lbmpm_rk2d {
     int model = 0;            // 0 CSF (the create-time model), 1 perturbation operator (lbmpm_rk2d_set_perturbation)
     lbmpm_rk2d_perturbation pert{};
     double *pd = nullptr;     // perturbation model: rhoR, rhoB, vx, vy of the last step (diagnostics)
+    bool force_on = false;    // lbmpm_rk2d_set_body_force: the step runs the forced kernels (a ring always does, with zeros)
+    double accR[2] = {0., 0.}, accB[2] = {0., 0.};
+    bool ring() const { return cfg.inlet_type == LBMPM_INLET_PERIODIC; }     // periodic y (with LBMPM_OUTLET_NONE: lbmpm_rk2d_create)
     int shape = 0;            // fused tile shape (LBMPM_RK2D_SHAPE, tuning only)
     bool streamed = false;    // false: fA holds the initial (already "post-streaming") state
     bool diag_valid = false;
@@ -1430,11 +1508,61 @@ void launch_fused_tracer(lbmpm_rk2d *c, const RKDev &p)
     else rk2d_fused_tracer<false, SH><<<g, b, 0, c->stream>>>(p, tiles_x, tiles_x * n_lo, tiles_x * (tiles_y - n_hi));
 }
 
+ForceDev make_force(const lbmpm_rk2d *c)
+{
+    ForceDev g;
+    g.gRx = c->accR[0]; g.gRy = c->accR[1]; g.gBx = c->accB[0]; g.gBy = c->accB[1];
+    return g;
+}
+
+// The fused step under a body force and / or on a ring: between open rows the launches of launch_fused_shape / launch_fused_tracer with
+// the forced kernels; on a ring one launch of rk2d_forced<., ., ., false> whatever the lattice's height (no tile row re-sums).
+template <typename SH>
+void launch_forced_shape(lbmpm_rk2d *c, const RKDev &p, const ForceDev &f)
+{
+    const int tiles_x = (c->nx + SH::TW - 1) / SH::TW, tiles_y = (c->ny + SH::TH - 1) / SH::TH;
+    const dim3 g(tiles_x * tiles_y), b(SH::THREADS);
+    const bool mrt = c->cfg.relaxation == LBMPM_RELAX_MRT;
+    if (c->ring()) {
+        if (c->ntr > 0) {
+            if (mrt) rk2d_forced<true, true, SH, false><<<g, b, 0, c->stream>>>(p, f, tiles_x);
+            else rk2d_forced<false, true, SH, false><<<g, b, 0, c->stream>>>(p, f, tiles_x);
+        } else {
+            if (mrt) rk2d_forced<true, false, SH, false><<<g, b, 0, c->stream>>>(p, f, tiles_x);
+            else rk2d_forced<false, false, SH, false><<<g, b, 0, c->stream>>>(p, f, tiles_x);
+        }
+        return;
+    }
+    if (c->ntr == 0) {
+        if (mrt) rk2d_forced<true, false, SH, true><<<g, b, 0, c->stream>>>(p, f, tiles_x);
+        else rk2d_forced<false, false, SH, true><<<g, b, 0, c->stream>>>(p, f, tiles_x);
+        return;
+    }
+    constexpr int H = 3;           // (n_lo, n_hi: launch_fused_tracer)
+    int n_lo = 0, n_hi = 0;
+    for (int ty = 0; ty < tiles_y; ++ty) {
+        if (ty * SH::TH - H <= 1) n_lo = ty + 1;
+        if (ty * SH::TH + SH::TH - 1 + H >= c->ny - 2 && n_hi == 0) n_hi = tiles_y - ty;
+    }
+    if (n_lo + n_hi >= tiles_y) {
+        if (mrt) rk2d_forced<true, true, SH, true><<<g, b, 0, c->stream>>>(p, f, tiles_x);
+        else rk2d_forced<false, true, SH, true><<<g, b, 0, c->stream>>>(p, f, tiles_x);
+        return;
+    }
+    if (mrt) rk2d_forced_tracer<true, SH><<<g, b, 0, c->stream>>>(p, f, tiles_x, tiles_x * n_lo, tiles_x * (tiles_y - n_hi));
+    else rk2d_forced_tracer<false, SH><<<g, b, 0, c->stream>>>(p, f, tiles_x, tiles_x * n_lo, tiles_x * (tiles_y - n_hi));
+}
+
 int launch_step(lbmpm_rk2d *c, bool diag, bool timed)
 {
     RKDev p = make_dev(c);
     if (!diag) p.diag = nullptr;
     hipEvent_t e0 = nullptr, e1 = nullptr;
+    const bool forced = c->model == 0 && (c->force_on || c->ring());
+    if (forced && c->cfg.variant == 0 && !(c->shape == 0 || c->shape == 3)) {       // (development builds only: the product has shape 0)
+        set_error("the forced / periodic step exists in the tile shapes 0 (64 x 8) and 3 (64 x 4) only (got shape %d)", c->shape);
+        return LBMPM_ERR_UNSUPPORTED;
+    }
     if (c->model == 1) {
         const PertDev q = make_pert(c, diag);
         const bool ev = timed && c->pool.take(&e0, &e1);
@@ -1446,7 +1574,10 @@ int launch_step(lbmpm_rk2d *c, bool diag, bool timed)
     } else if (c->cfg.variant == 0) {
         const bool ev = timed && c->pool.take(&e0, &e1);
         if (ev) LBMPM_HIP_TRY(hipEventRecord(e0, c->stream));
-        if (c->ntr > 0) {
+        if (forced) {
+            if (c->shape == 3) launch_forced_shape<FusedShape<4, 1>>(c, p, make_force(c));
+            else launch_forced_shape<FusedShape<8, 1>>(c, p, make_force(c));
+        } else if (c->ntr > 0) {
             // registers are capped at 128 (amdgpu_waves_per_eu on the kernel): two 64 x 8 blocks share a CU
             if (c->shape == 3) launch_fused_tracer<FusedShape<4, 1>>(c, p);
 #if defined(LBMPM_DEV) && defined(LBMPM_TRACER_TALL)
@@ -1465,11 +1596,22 @@ int launch_step(lbmpm_rk2d *c, bool diag, bool timed)
         if (ev) LBMPM_HIP_TRY(hipEventRecord(e1, c->stream));
     } else {
         const dim3 g = grid_of(c), b(BX, BY);
-        rk2d_phase_field<<<g, b, 0, c->stream>>>(p);
-        rk2d_gradient<<<g, b, 0, c->stream>>>(p);
+        const bool ring = c->ring(), mrt = c->cfg.relaxation == LBMPM_RELAX_MRT;
+        if (ring) rk2d_phase_field_ring<<<g, b, 0, c->stream>>>(p);
+        else rk2d_phase_field<<<g, b, 0, c->stream>>>(p);
+        rk2d_gradient<<<g, b, 0, c->stream>>>(p);         // (no row rule of its own: it reads the phase field, wrapped)
         const bool ev = timed && c->pool.take(&e0, &e1);
         if (ev) LBMPM_HIP_TRY(hipEventRecord(e0, c->stream));
-        if (c->cfg.relaxation == LBMPM_RELAX_MRT) rk2d_collide_stream<true><<<g, b, 0, c->stream>>>(p);
+        if (forced) {
+            const ForceDev f = make_force(c);
+            if (ring) {
+                if (mrt) rk2d_collide_stream_forced<true, false><<<g, b, 0, c->stream>>>(p, f);
+                else rk2d_collide_stream_forced<false, false><<<g, b, 0, c->stream>>>(p, f);
+            } else {
+                if (mrt) rk2d_collide_stream_forced<true, true><<<g, b, 0, c->stream>>>(p, f);
+                else rk2d_collide_stream_forced<false, true><<<g, b, 0, c->stream>>>(p, f);
+            }
+        } else if (mrt) rk2d_collide_stream<true><<<g, b, 0, c->stream>>>(p);
         else rk2d_collide_stream<false><<<g, b, 0, c->stream>>>(p);
         if (ev) LBMPM_HIP_TRY(hipEventRecord(e1, c->stream));
     }
@@ -1506,8 +1648,10 @@ extern "C" int lbmpm_rk2d_create(const lbmpm_rk2d_config *cfg, const uint8_t *is
     LBMPM_REQUIRE(cfg->wetting_type == 1 || cfg->wetting_type == 2, "WettingType must be 1 or 2 (got %d)", cfg->wetting_type);
     LBMPM_REQUIRE(cfg->tau_type == 1 || cfg->tau_type == 2, "TauType must be 1 or 2 (got %d)", cfg->tau_type);
     LBMPM_REQUIRE(cfg->relaxation == LBMPM_RELAX_SRT || cfg->relaxation == LBMPM_RELAX_MRT, "bad relaxation %d", cfg->relaxation);
-    LBMPM_REQUIRE(cfg->inlet_type == 0 || cfg->inlet_type == 1, "bad inlet_type %d", cfg->inlet_type);
-    LBMPM_REQUIRE(cfg->outlet_type == 0 || cfg->outlet_type == 1, "bad outlet_type %d", cfg->outlet_type);
+    LBMPM_REQUIRE((cfg->inlet_type == LBMPM_INLET_PERIODIC) == (cfg->outlet_type == LBMPM_OUTLET_NONE),
+                  "periodic y is LBMPM_INLET_PERIODIC together with LBMPM_OUTLET_NONE (got inlet_type %d, outlet_type %d)", cfg->inlet_type, cfg->outlet_type);
+    LBMPM_REQUIRE(cfg->inlet_type == 0 || cfg->inlet_type == 1 || cfg->inlet_type == LBMPM_INLET_PERIODIC, "bad inlet_type %d", cfg->inlet_type);
+    LBMPM_REQUIRE(cfg->outlet_type == 0 || cfg->outlet_type == 1 || cfg->outlet_type == LBMPM_OUTLET_NONE, "bad outlet_type %d", cfg->outlet_type);
     LBMPM_REQUIRE(cfg->tau_r > 0.5 && cfg->tau_b > 0.5, "TauR/TauB must exceed 0.5");
     LBMPM_REQUIRE(cfg->variant == 0 || cfg->variant == 1, "variant must be 0 (fused) or 1 (split), got %d", cfg->variant);
     LBMPM_HIP_TRY(hipSetDevice(cfg->device));
@@ -1738,7 +1882,9 @@ extern "C" int lbmpm_rk2d_get_field(lbmpm_rk2d *c, int field, double *out)
         if (!c->obs) { const int rc = c->mem.alloc(&c->obs, 22 * c->plane, c->stream); if (rc) return rc; }
         RKDev p = make_dev(c);
         const dim3 g = grid_of(c), b(BX, BY);
-        if (rec) rk2d_observe<true><<<g, b, 0, c->stream>>>(p, c->obs);
+        if (rec && c->ring()) rk2d_observe_forced<false><<<g, b, 0, c->stream>>>(p, make_force(c), c->obs);
+        else if (rec && c->force_on) rk2d_observe_forced<true><<<g, b, 0, c->stream>>>(p, make_force(c), c->obs);
+        else if (rec) rk2d_observe<true><<<g, b, 0, c->stream>>>(p, c->obs);
         else rk2d_observe<false><<<g, b, 0, c->stream>>>(p, c->obs);
         LBMPM_HIP_TRY(hipGetLastError());
         LBMPM_HIP_TRY(hipStreamSynchronize(c->stream));
@@ -1803,6 +1949,10 @@ extern "C" int lbmpm_rk2d_set_perturbation(lbmpm_rk2d *c, const lbmpm_rk2d_pertu
 {
     LBMPM_REQUIRE(c && par, "lbmpm_rk2d_set_perturbation: null argument");
     LBMPM_REQUIRE(c->cfg.variant == 0 && c->ntr == 0, "the perturbation operator runs as the fused schedule, without tracers");
+    if (c->ring() || c->force_on) {
+        set_error("the perturbation operator has neither a body force nor periodic y (both belong to the CSF step)");
+        return LBMPM_ERR_UNSUPPORTED;
+    }
     // only the parameters the configured inlet / outlet kernels use are checked (the kernel-level loop runs an ini whose unused ones are odd)
     LBMPM_REQUIRE(std::isfinite(par->ak_r) && std::isfinite(par->ak_b) && std::isfinite(par->solid_phi), "lbmpm_rk2d_set_perturbation: A_k and solidPhi must be finite");
     LBMPM_REQUIRE(c->cfg.outlet_type != LBMPM_OUTLET_PRESSURE || (par->outlet_rho_r > 0. && par->outlet_rho_b > 0.),
@@ -1831,12 +1981,41 @@ extern "C" int lbmpm_rk2d_set_perturbation(lbmpm_rk2d *c, const lbmpm_rk2d_pertu
     return LBMPM_OK;
 }
 
+extern "C" int lbmpm_rk2d_set_body_force(lbmpm_rk2d *c, const double *accel_r, const double *accel_b)
+{
+    LBMPM_REQUIRE(c, "lbmpm_rk2d_set_body_force: null context");
+    LBMPM_REQUIRE((accel_r == nullptr) == (accel_b == nullptr), "lbmpm_rk2d_set_body_force: both accelerations or neither (NULL, NULL switches the force off)");
+    if (c->model == 1) {
+        set_error("the perturbation operator has no body force (it belongs to the CSF step)");
+        return LBMPM_ERR_UNSUPPORTED;
+    }
+    if (!accel_r) {
+        c->force_on = false;
+        c->accR[0] = c->accR[1] = c->accB[0] = c->accB[1] = 0.;
+        return LBMPM_OK;
+    }
+    LBMPM_REQUIRE(std::isfinite(accel_r[0]) && std::isfinite(accel_r[1]) && std::isfinite(accel_b[0]) && std::isfinite(accel_b[1]),
+                  "lbmpm_rk2d_set_body_force: an acceleration is not finite");
+    c->accR[0] = accel_r[0]; c->accR[1] = accel_r[1]; c->accB[0] = accel_b[0]; c->accB[1] = accel_b[1];
+    c->force_on = true;
+    return LBMPM_OK;
+}
+
+extern "C" int lbmpm_rk2d_get_body_force(const lbmpm_rk2d *c, double *accel_r, double *accel_b)
+{
+    LBMPM_REQUIRE(c && accel_r && accel_b, "lbmpm_rk2d_get_body_force: null argument");
+    accel_r[0] = c->accR[0]; accel_r[1] = c->accR[1]; accel_b[0] = c->accB[0]; accel_b[1] = c->accB[1];
+    return LBMPM_OK;
+}
+
 extern "C" int lbmpm_rk2d_tracer_configure(lbmpm_rk2d *c, const lbmpm_tracer_config *t)
 {
     LBMPM_REQUIRE(c && t, "lbmpm_rk2d_tracer_configure: null argument");
     LBMPM_REQUIRE(t->num_tracers >= 1 && t->num_tracers <= 4, "NumberTracers must be 1..4 (got %d)", t->num_tracers);
     LBMPM_REQUIRE(c->cfg.variant == 0, "tracer transport is fused into the default (fused) schedule only");
     LBMPM_REQUIRE(c->model == 0, "tracer transport rides on the CSF step (Transport2DRK.py); the perturbation operator has no tracer loop in the reference");
+    LBMPM_REQUIRE(!(c->ring() && (t->dirichlet_inlet || t->free_outlet)),
+                  "dirichlet_inlet / free_outlet name the rows ny-1 and 0, which are ordinary rows on a lattice periodic in y: set both to 0");
     LBMPM_HIP_TRY(hipSetDevice(c->cfg.device));
     // D2Q5 moment matrix and collision matrix -M^-1 S^-1 (Transport2DRK.py:316-347)
     const double M[25] = {1, 1, 1, 1, 1,   0, 1, -1, 0, 0,   0, 0, 0, 1, -1,   4, -1, -1, -1, -1,   0, 1, 1, -1, -1};

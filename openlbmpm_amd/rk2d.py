@@ -24,9 +24,40 @@ def _f64(a):
     return np.ascontiguousarray(a, dtype=np.float64)
 
 
+def body_force_pair(g=None, red=None, blue=None):
+    """the arguments of set_body_force as ((gx, gy) of red, (gx, gy) of blue): g for both colours, red / blue in its place for one; a
+    colour nobody names is zero.  ValueError: not two numbers"""
+    def two(v, what):
+        if v is None:
+            return (0.0, 0.0)
+        a = np.asarray(v, dtype=np.float64)
+        if a.shape != (2,):
+            raise ValueError("body force %s = (gx, gy), not %r" % (what, v))
+        return tuple(float(x) for x in a)
+    return two(g if red is None else red, "red"), two(g if blue is None else blue, "blue")
+
+
+def body_force_arg(body_force):
+    """the drivers' body_force= keyword -- (gx, gy) for both colours or dict(red=, blue=) -- as the keyword arguments of set_body_force;
+    None stays None (no force)"""
+    if body_force is None:
+        return None
+    if isinstance(body_force, dict):
+        unknown = set(body_force) - {"red", "blue"}
+        if unknown:
+            raise KeyError("unknown body_force entries: %s" % sorted(unknown))
+        gr, gb = body_force_pair(None, body_force.get("red"), body_force.get("blue"))
+    else:
+        gr, gb = body_force_pair(body_force)
+    return dict(red=gr, blue=gb)
+
+
 class RK2DSolver:
-    def __init__(self, is_domain, params=None, device=0, variant=0, diagnostics=False, perturbation=None):
-        """perturbation = dict(AkR=, AkB=, solidPhi=): the step of SurfaceTensionType 'Perturbation' (RKD2Q9.py:978-1223) as one fused
+    def __init__(self, is_domain, params=None, device=0, variant=0, diagnostics=False, perturbation=None, periodic_y=False):
+        """periodic_y = True: the CSF step on a lattice periodic in y (LBMPM_INLET_PERIODIC with LBMPM_OUTLET_NONE, include/lbmpm.h) -- every
+        row wraps like x, no boundary-row rule runs, params["inlet"], ["outlet"], vyR, vyB, rho*H, rho*L are not read, the mask is taken as
+        given.  A keyword, not a value of params["inlet"] / ["outlet"]: those name the kinds of open rows and keep refusing anything else.
+        perturbation = dict(AkR=, AkB=, solidPhi=): the step of SurfaceTensionType 'Perturbation' (RKD2Q9.py:978-1223) as one fused
         launch instead of the CSF step (lbmpm_rk2d_set_perturbation): inlet 'Neumann' (vyR / vyB per colour) or 'Dirichlet' (rhoRH /
         rhoBH), outlet 'Dirichlet' (rhoRL / rhoBL per colour) or 'Convective', tauR, tauB, beta, relax of `params`; raises LbmpmError
         (unsupported) for solid nodes in the boundary rows."""
@@ -52,11 +83,14 @@ class RK2DSolver:
             raise ValueError("RelaxationType must be 'SRT' or 'MRT'")
         cfg.relaxation = 1 if p["relax"] == "MRT" else 0
         if p["inlet"] not in ("Neumann", "Dirichlet"):
-            raise ValueError("BoundaryTypeInlet must be 'Neumann' or 'Dirichlet'")
+            raise ValueError("BoundaryTypeInlet must be 'Neumann' or 'Dirichlet' (a lattice periodic in y: periodic_y=True)")
         if p["outlet"] not in ("Dirichlet", "Convective"):
-            raise ValueError("BoundaryTypeOutlet must be 'Dirichlet' or 'Convective'")
-        cfg.inlet_type = 0 if p["inlet"] == "Neumann" else 1
-        cfg.outlet_type = 0 if p["outlet"] == "Dirichlet" else 1
+            raise ValueError("BoundaryTypeOutlet must be 'Dirichlet' or 'Convective' (a lattice periodic in y: periodic_y=True)")
+        self.periodic_y = bool(periodic_y)
+        if self.periodic_y and perturbation is not None:
+            raise ValueError("the perturbation model has no periodic y (it belongs to the CSF step)")
+        cfg.inlet_type = 2 if self.periodic_y else (0 if p["inlet"] == "Neumann" else 1)
+        cfg.outlet_type = 2 if self.periodic_y else (0 if p["outlet"] == "Dirichlet" else 1)
         cfg.inlet_velocity_y = p["vyB"] + p["vyR"]
         cfg.inlet_rho_r = p["rhoRH"]; cfg.inlet_rho_b = p["rhoBH"]
         cfg.outlet_rho_total = p["rhoBL"] + p["rhoRL"]
@@ -114,6 +148,26 @@ class RK2DSolver:
 
     def enable_diagnostics(self, on=True):
         check(self._L.lbmpm_rk2d_enable_diagnostics(self._h, 1 if on else 0), "enable_diagnostics")
+
+    def set_body_force(self, g=None, *, red=None, blue=None):
+        """an acceleration per colour in lattice units (gravity, force-driven flow): g = (gx, gy) for both colours, red= / blue= in its
+        place for one; all None: no body force, the step launches the kernels it launched before.  The force density of a node is
+        rho_R g_R + rho_B g_B; half of it enters u, the Guo source takes it beside the CSF force (include/lbmpm.h).  get("Fx"), get("Fy")
+        stay the CSF force alone; get("vx"), get("rec_vx") ... and the tracers' flow carry the forced u.  Whenever the solver is idle,
+        repeatedly; the state and the step counter stay, set_macro / set_pdf keep it.  ValueError: not two numbers; LbmpmError: a value
+        that is not finite (LBMPM_ERR_INVALID), the perturbation model (LBMPM_ERR_UNSUPPORTED)"""
+        if g is None and red is None and blue is None:
+            check(self._L.lbmpm_rk2d_set_body_force(self._h, None, None), "lbmpm_rk2d_set_body_force")
+            return
+        gr, gb = body_force_pair(g, red, blue)
+        check(self._L.lbmpm_rk2d_set_body_force(self._h, (C.c_double * 2)(*gr), (C.c_double * 2)(*gb)), "lbmpm_rk2d_set_body_force")
+
+    @property
+    def body_force(self):
+        """((gx, gy) of red, (gx, gy) of blue) in force; zeros without a body force"""
+        gr, gb = (C.c_double * 2)(), (C.c_double * 2)()
+        check(self._L.lbmpm_rk2d_get_body_force(self._h, gr, gb), "lbmpm_rk2d_get_body_force")
+        return tuple(gr), tuple(gb)
 
     def set_stream(self, hip_stream_handle):
         check(self._L.lbmpm_rk2d_set_stream(self._h, C.c_void_p(hip_stream_handle)), "set_stream")
